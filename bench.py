@@ -29,6 +29,11 @@ leaf through the net, `secondary.cfg3_eval_cache_in_search_only` / `--eval-cache
 with repeats inside one search shared only.)
 A "step" (ttt) = one complete iteration: all 65,536 games played to the end.
 
+`--dump-outputs DIR` writes, untimed and after the timed steps, what the timed path computed as DIR/<name>.npy
+(float32 / float64, at most 64 MB): for reversi the boards every slot holds after the last step and every finished
+game's example rows, for ttt the same of the last iteration, for net the last forward's logits and values.  The inputs
+are seeded, so two builds run with the same arguments can be compared array for array.
+
 N > 1: one rank per GPU (torch.distributed, backend nccl = RCCL), games sharded
 by global id (weak scaling: 4096 per GPU), no data-path collective except ONE
 all-gather of the example blocks at the end of the timed region.
@@ -397,12 +402,62 @@ def cpu_baseline_ttt(sims):
             "sample": f"{cores} threads x {per} complete TTT games ({sims} sims/move, uniform priors) in {dt:.1f} s"}
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET = 64 << 20   # bytes of .npy payload per run
+
+
+def bit_cells(own, opp, n_bits):
+    """side-to-move bitboards (uint64) -> cells float32 [n, n_bits]: +1 own stone, -1 opponent stone, 0 empty"""
+    import numpy as np
+    sh = np.arange(n_bits, dtype=np.uint64)
+    a = (np.asarray(own, np.uint64)[:, None] >> sh) & np.uint64(1)
+    b = (np.asarray(opp, np.uint64)[:, None] >> sh) & np.uint64(1)
+    return a.astype(np.float32) - b.astype(np.float32)
+
+
+def examples_arrays(ex, n_bits):
+    """Examples rows as dump arrays (every array has one row per example)"""
+    import numpy as np
+    return {"ex_state": bit_cells(ex.own, ex.opp, n_bits), "ex_pi": ex.pi.astype(np.float32),
+            "ex_z": ex.z.astype(np.float32), "ex_mover": ex.mover.astype(np.float32), "ex_act": ex.act.astype(np.float32),
+            "ex_game": ex.game.astype(np.float64), "ex_ply": ex.ply.astype(np.float64)}
+
+
+def write_dump(path, arrays):
+    """arrays {name: ndarray} -> path/<name>.npy as float32 / float64.  Arrays sharing a leading dimension longer than
+    the budget allows are cut to the same fixed, seeded sample of rows (sorted, so row order is kept); returns a note
+    for the JSON line."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float64))
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = DUMP_BUDGET - 4096 * len(arrays)   # room for the .npy headers
+    sampled = {}
+    if total > budget:
+        big = {}
+        for k, v in arrays.items():
+            big.setdefault(v.shape[0], []).append(k)
+        n, keys = max(big.items(), key=lambda kv: sum(arrays[k].nbytes for k in kv[1]))
+        rest = total - sum(arrays[k].nbytes for k in keys)
+        keep = int(n * (budget - rest) / sum(arrays[k].nbytes for k in keys))
+        assert keep > 0, f"--dump-outputs: {total} bytes do not fit {budget}"
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        for k in keys:
+            arrays[k] = arrays[k][idx]
+            sampled[k] = f"{keep} of {n} rows (numpy default_rng(0).choice, sorted)"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    note(f"outputs written to {path}: {', '.join(sorted(arrays))}")
+    return {"dir": path, "arrays": {k: list(v.shape) for k, v in arrays.items()}, **({"sampled": sampled} if sampled else {})}
+
+
 # ------------------------------------------------------------------ the three workloads
 class Ctx:
     pass
 
 
-def run_net(ctx, B, K, W, fp8):
+def run_net(ctx, B, K, W, fp8, dump_dir=None):
     """BASELINE cfg 5: net forward only on a batch of fixture-F1 positions"""
     import numpy as np
     import torch
@@ -428,12 +483,14 @@ def run_net(ctx, B, K, W, fp8):
     ctx.barrier()
     t0 = time.perf_counter()
     for _ in range(K):
-        net.forward(own, opp, fp8=fp8)
+        lg, v = net.forward(own, opp, fp8=fp8)
     ctx.barrier()
     dt = time.perf_counter() - t0
     L.bz_profile_enable(0)
     launches, timed, ms = _lib.profile_read()["tower"]
     assert launches == timed == K, (launches, timed, K)
+    dumped = write_dump(dump_dir, {"logits": lg.float().cpu().numpy(), "value": v.float().cpu().numpy()}) \
+        if dump_dir and ctx.rank == 0 else None
     avg_ms = ms / timed
     peak = 2 * MFMA_PEAK_TFLOPS if fp8 else MFMA_PEAK_TFLOPS
     ach = B * NET_FLOP_PER_POS / (avg_ms * 1e-3) / 1e12
@@ -446,7 +503,8 @@ def run_net(ctx, B, K, W, fp8):
                        "positions": "fixture F1 positions tiled to the batch"},
             "roofline": {"bound": "mfma", "kernel": "f8::k_tower_fp8" if fp8 else "k_tower_bf16", "achieved": ach,
                          "peak": peak, "unit": "TFLOP/s", "frac": ach / peak, "traffic": tr, "traffic_source": tr_src, "launches": launches,
-                         "avg_launch_ms": avg_ms, "flop_per_launch": B * NET_FLOP_PER_POS}}
+                         "avg_launch_ms": avg_ms, "flop_per_launch": B * NET_FLOP_PER_POS},
+            **({"dump_outputs": dumped} if dumped else {})}
 
 
 def run_train(ctx, batch, K, W):
@@ -557,8 +615,9 @@ def run_env(ctx, n, K, W):
                                  "and I/O) at 4 cycles per wave64 instruction; profiles/r05_env_isa.txt has the histogram"}}
 
 
-def run_ttt(ctx, B, sims, K, W, ttt_lanes=0):
+def run_ttt(ctx, B, sims, K, W, ttt_lanes=0, dump_dir=None):
     """BASELINE cfg 2: TTT, uniform priors, the whole search of a move is one fused tree kernel"""
+    import numpy as np
     from betazero_amd import _lib
     from betazero_amd.engine import SelfPlayEngine
     L = _lib.lib()
@@ -586,6 +645,11 @@ def run_ttt(ctx, B, sims, K, W, ttt_lanes=0):
     L.bz_profile_enable(0)
     eng.status()  # raises on engine error flags
     cnt = eng.counters()
+    dumped = None
+    if dump_dir and ctx.rank == 0:  # the last iteration's games: final boards and every example row
+        own, opp, tm, st = eng.positions()
+        dumped = write_dump(dump_dir, {"final_board": bit_cells(own, opp, 9), "final_to_move": tm.astype(np.float32),
+                                       **examples_arrays(eng.examples(), 9)})
     launches, timed, ms = _lib.profile_read()["search_fused"]
     assert launches == timed
     avg_ms = ms / max(timed, 1)
@@ -598,6 +662,7 @@ def run_ttt(ctx, B, sims, K, W, ttt_lanes=0):
             "config": {"workload": f"ttt3x3_{B}games_{sims}sims_uniform_tree_only", "games_per_gpu": B,
                        "sims_per_move": sims, "step": "one complete self-play iteration of all games",
                        "ttt_lanes": ttt_lanes if ttt_lanes else 4},
+            **({"dump_outputs": dumped} if dumped else {}),
             "roofline": {"bound": "hbm", "kernel": "k_search_fused_ttt<%s, uniform>" % (ttt_lanes if ttt_lanes > 0 else 4) if ttt_lanes >= 0
                          else "k_search_fused<TicTacToe> (generic)", "achieved": ach, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": tr, "traffic_source": tr_src, "launches": launches,
@@ -605,7 +670,8 @@ def run_ttt(ctx, B, sims, K, W, ttt_lanes=0):
             "sims_per_s": cnt["n_sims"] * ctx.world / dt, "counters": cnt}
 
 
-def run_reversi(ctx, args, B, sims, K, W):
+def run_reversi(ctx, args, B, sims, K, W, dump_dir=None):
+    import numpy as np
     import torch
     import torch.distributed as dist
     from betazero_amd import _lib
@@ -726,6 +792,16 @@ def run_reversi(ctx, args, B, sims, K, W):
         dist.all_gather_object(ranks, mine)
     if ctx.rank != 0:
         return None
+    dumped = None
+    if dump_dir:  # untimed: the boards the last step left in every slot, and every finished game's example rows
+        sp.join()
+        torch.cuda.synchronize(ctx.dev)
+        pos = [e.positions() for e in engs]
+        own, opp = np.concatenate([p_[0] for p_ in pos]), np.concatenate([p_[1] for p_ in pos])
+        dumped = write_dump(dump_dir, {"board": bit_cells(own, opp, 64),
+                                       "to_move": np.concatenate([p_[2] for p_ in pos]).astype(np.float32),
+                                       "slot_state": np.concatenate([p_[3] for p_ in pos]).astype(np.float32),
+                                       **examples_arrays(sp.examples(), 64)})
     out = {"metric": "selfplay_games_per_s", "value": games / dt, "unit": "games/s", "n_gpus": ctx.world, "steps": K,
            "warmup": W, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "data": "synthetic", "dtype": prec,
@@ -817,6 +893,8 @@ def run_reversi(ctx, args, B, sims, K, W):
     out["net_evals_per_s"] = cnt["n_net_leaves"] * ctx.world / dt
     out["net_tflops_e2e"] = cnt["n_net_leaves"] * ctx.world * NET_FLOP_PER_POS / dt / 1e12
     out["counters"] = cnt
+    if dumped:
+        out["dump_outputs"] = dumped
     return out
 
 
@@ -886,7 +964,17 @@ def main():
                          "the device-side all_reduces, ranks.per_rank, pooled -- so that the multi-GPU branch can be run on a one-GPU box")
     ap.add_argument("--ttt-lanes", type=int, default=0, choices=[-1, 0, 1, 2, 4, 8],
                     help="--workload ttt: lanes per game of the fused search (bz_engine_cfg.ttt_lanes; 0 = default, -1 = generic kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (reversi: the boards its last step left "
+                         "and the finished games' example rows; ttt: the last iteration's; net: the last forward's logits "
+                         "and values) as DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded sample of rows beyond)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("reversi", "ttt", "net"):
+        ap.error("--dump-outputs covers --workload reversi, ttt and net")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     claim_stdout()
     if args.eval_cache == "off":
         args.no_eval_cache = True
@@ -911,16 +999,18 @@ def main():
     ctx.world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     ctx.backend = os.environ.get("BZ_DIST_BACKEND", "nccl")  # "gloo": rehearsal of the N>1 path on one GPU / on CPU
-    n_dev = torch.cuda.device_count()
-    if n_dev == 0:
-        if os.environ.get("BZ_BENCH_REHEARSAL") != "1" or ctx.world < 2:
-            sys.exit("bench.py: no GPU visible (the engine has no CPU path; BZ_BENCH_REHEARSAL=1 with --gpus >= 2 "
-                     "rehearses the multi-rank plumbing only)")
+    if os.environ.get("BZ_BENCH_REHEARSAL") == "1" and ctx.world >= 2:
+        # decided before anything asks for a device: counting them opens the GPU, and N rehearsal ranks on a GPU box
+        # would be N processes holding its card
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")
         rehearsal(args, ctx.rank, ctx.world)
         dist.destroy_process_group()
         return
+    n_dev = torch.cuda.device_count()
+    if n_dev == 0:
+        sys.exit("bench.py: no GPU visible (the engine has no CPU path; BZ_BENCH_REHEARSAL=1 with --gpus >= 2 "
+                 "rehearses the multi-rank plumbing only)")
     if local >= n_dev:
         if ctx.backend == "nccl":
             sys.exit(f"bench.py: --gpus {ctx.world} but only {n_dev} GPU(s) visible: RCCL needs one device per rank "
@@ -950,7 +1040,7 @@ def main():
 
     if args.workload == "net":  # BASELINE cfg 5: leaf-eval batch 8192, fp8 e4m3 net, MFMA-utilisation run
         out = run_net(ctx, args.games or 8192, args.steps if args.steps is not None else 1000,
-                      args.warmup if args.warmup is not None else 50, (args.precision or "fp8") == "fp8")
+                      args.warmup if args.warmup is not None else 50, (args.precision or "fp8") == "fp8", args.dump_outputs)
     elif args.workload == "train":
         out = run_train(ctx, args.games or 1024, args.steps if args.steps is not None else 200,
                         args.warmup if args.warmup is not None else 20)
@@ -960,7 +1050,7 @@ def main():
     elif args.workload == "ttt":
         sims = args.sims or 50
         out = run_ttt(ctx, args.games or 65536, sims, args.steps if args.steps is not None else 20,
-                      args.warmup if args.warmup is not None else 2, args.ttt_lanes)
+                      args.warmup if args.warmup is not None else 2, args.ttt_lanes, args.dump_outputs)
         if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_ttt(sims)
     else:
@@ -970,7 +1060,7 @@ def main():
             assert games % ctx.world == 0, "--scaling strong: --games must divide by the number of ranks"
             games //= ctx.world
         out = run_reversi(ctx, args, games, sims, args.steps if args.steps is not None else 8,
-                          args.warmup if args.warmup is not None else 1)
+                          args.warmup if args.warmup is not None else 1, args.dump_outputs)
         if out is not None:
             out["scaling"] = args.scaling
         if ctx.rank == 0 and ctx.world == 1:

@@ -25,6 +25,10 @@ Fixtures:
   F12 off_domain.json           cells and players outside {-1, 0, +1}: the reference treats any
                                 non-zero cell as occupied (tic_tac_toe_board.py:20-21,
                                 reversi_board.py:26) and plays `player` against `-player`
+  F13 dropin.json               what the reference's own loops and players produce over its own boards
+                                under fixed `random` seeds: ReversiTerminal transcripts (4/6/8), TTT
+                                OptimalPlayer games, a Reversi OptimalPlayer-vs-RandomPlayer opening,
+                                the states / actions of its collect_game_data loop
 
 Run:  python oracle/gen_golden.py
 """
@@ -586,8 +590,86 @@ def gen_f9():
     print("F9", rev.shape, game.shape, ttt.shape)
 
 
+# ---------------------------------------------------------------- F13: the reference's loops over its own boards
+def gen_f13():
+    """the expectations of tests/test_dropin_with_reference.py, recorded from the reference's unmodified code:
+    reversi   ReversiTerminal(RandomPlayer(1), RandomPlayer(-1), size).play() stdout, random.seed(100 + size)
+              (reversi_terminal.py:16-38), sizes 4 / 6 / 8;
+              OptimalPlayer(1, max_depth=2) vs RandomPlayer(-1) on 6x6, 12 turns, random.seed(7) (reversi_players.py);
+    ttt       OptimalPlayer(1) vs OptimalPlayer(-1), random.seed(0..2) (players.py:30-70): moves, is_game_over, board;
+              12 games of SL/generate_training_games.py's collect_game_data loop (tic_tac_toe.py:13-34 + :12-23),
+              random.seed(2024): states and actions."""
+    import contextlib
+    import io
+    rpath = os.path.join(REF, "src/reversi")
+    saved, saved_path = sys.modules.pop("players", None), list(sys.path)
+    # its `players` is a directory without __init__.py: the tic-tac-toe players.py must be off the path to let it through
+    sys.path[:] = [rpath] + [q for q in sys.path if q != os.path.join(REF, "src/tic_tac_toe")]
+    try:
+        rt = _load_by_path("ref_reversi_terminal", os.path.join(rpath, "game_logic", "reversi_terminal.py"))
+    finally:
+        sys.path[:] = saved_path
+        sys.modules.pop("players", None)
+        if saved is not None:
+            sys.modules["players"] = saved
+    out = {"reversi_terminal": {}}
+    for size in (4, 6, 8):
+        random.seed(100 + size)
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            rt.ReversiTerminal(rt.RandomPlayer(1), rt.RandomPlayer(-1), size=size).play()
+        out["reversi_terminal"][str(size)] = {"seed": 100 + size, "stdout": buf.getvalue()}
+    rp = _load_by_path("ref_reversi_players", os.path.join(REF, "src/reversi/players/reversi_players.py"))
+    random.seed(7)
+    b, cur, moves = ReversiBoard(size=6), 1, []
+    pl = {1: rp.OptimalPlayer(1, max_depth=2), -1: rp.RandomPlayer(-1)}
+    for _ in range(12):
+        if b.generate_possible_moves(cur):
+            mv = pl[cur].get_move(b)
+            moves.append([int(v) for v in mv])
+            b = b.make_move(*mv, cur)
+        cur = -cur
+    out["reversi_optimal_vs_random"] = {"seed": 7, "size": 6, "turns": 12, "moves": moves,
+                                        "board": np.asarray(b.board).tolist()}
+    tp = _load_by_path("ref_ttt_players", os.path.join(REF, "src/tic_tac_toe/players.py"))
+    out["ttt_optimal_games"] = []
+    for seed in range(3):
+        random.seed(seed)
+        b, cur, moves = TicTacToeBoard(), 1, []
+        p = {1: tp.OptimalPlayer(1), -1: tp.OptimalPlayer(-1)}
+        while not b.is_game_over()[0]:
+            mv = p[cur].get_move(b)
+            moves.append([int(v) for v in mv])
+            b = b.make_move(*mv, cur)
+            cur = -cur
+        over, w = b.is_game_over()
+        out["ttt_optimal_games"].append({"seed": seed, "moves": moves, "game_over": [bool(over), int(w)],
+                                         "board": np.asarray(b.board).tolist()})
+    random.seed(2024)
+    p1, p2 = tp.OptimalPlayer(1), tp.OptimalPlayer(-1)
+    states, actions = [], []
+    for _ in range(12):
+        b, cur, positions = TicTacToeBoard(), 1, []
+        while True:
+            positions.append(b.board)
+            r, c = (p1 if cur == 1 else p2).get_move(b)
+            b = b.make_move(r, c, cur)
+            if b.is_game_over()[0]:
+                positions.append(b.board)
+                break
+            cur = -cur
+        pos = np.stack(positions).astype(np.int64)
+        pos = pos * ((-1) ** np.arange(len(pos)))[:, None, None]
+        states.extend(pos[:-1]); actions.extend(-pos[1:] - pos[:-1])
+    out["ttt_collect_game_data"] = {"seed": 2024, "games": 12, "states": np.array(states).tolist(),
+                                    "actions": np.array(actions).tolist()}
+    with open(os.path.join(OUT, "dropin.json"), "w") as f:
+        json.dump(out, f)
+    print("F13", {k: len(v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f7", "f8", "f9", "f10", "f11", "f12"]
+    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f7", "f8", "f9", "f10", "f11", "f12", "f13"]
     if "f1" in which: gen_f1()
     if "f2" in which: gen_f2()
     if "f3" in which: gen_f3()
@@ -599,3 +681,4 @@ if __name__ == "__main__":
     if "f10" in which: gen_f10()
     if "f11" in which: gen_f11()
     if "f12" in which: gen_f12()
+    if "f13" in which: gen_f13()
