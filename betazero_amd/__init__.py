@@ -7,8 +7,16 @@ and raises when no HIP device is present -- there is no CPU fallback."""
 from .reversi import ReversiBoard, ReversiHeadless  # noqa: F401
 from .tic_tac_toe import TicTacToeBoard, TicTacToeHeadless, process_game_positions  # noqa: F401
 from .players import (Player, ReversiPlayer, RandomPlayer, ReversiRandomPlayer, MCTSPlayer,  # noqa: F401
-                      OptimalPlayer, ReversiOptimalPlayer, NetPlayer)
+                      OptimalPlayer, ReversiOptimalPlayer, NetPlayer, AIPlayer)
 
 __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadless", "process_game_positions",
            "Player", "ReversiPlayer", "RandomPlayer", "ReversiRandomPlayer", "MCTSPlayer",
-           "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer"]
+           "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
+           "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model"]
+
+
+def __getattr__(name):  # the MLP names load torch: only when asked for
+    if name in ("TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model"):
+        from . import mlp
+        return getattr(mlp, name)
+    raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

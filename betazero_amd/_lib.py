@@ -7,11 +7,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # BZ_HIP_SO: load a diagnostic variant built by betazero_amd.build.build_variant() instead of the
 # product library (needs BZ_ALLOW_EXPERIMENT=1 as well: such builds may time but not compute)
 SO = os.environ.get("BZ_HIP_SO") or os.path.join(HERE, "libbz_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 BZ_OK, BZ_EINVAL, BZ_EILLEGAL_MOVE, BZ_EHIP, BZ_ENOMEM, BZ_ENOGPU, BZ_ESTATE = range(7)
 GAME_TTT, GAME_REVERSI, GAME_REVERSI6, GAME_REVERSI4 = 0, 1, 2, 3
-EVAL_UNIFORM, EVAL_HASH, EVAL_NET_F32, EVAL_NET_BF16, EVAL_EXTERNAL, EVAL_NET_FP8 = range(6)
+EVAL_UNIFORM, EVAL_HASH, EVAL_NET_F32, EVAL_NET_BF16, EVAL_EXTERNAL, EVAL_NET_FP8, EVAL_MLP_F32, EVAL_MLP_BF16 = range(8)
 ST_RUNNING, ST_TERMINAL, ST_ILLEGAL, ST_MUST_PASS = range(4)
 PASS_ACTION = 64
 ENGINE_REUSE_SUBTREE = 1
@@ -56,6 +56,10 @@ class TrainAdam(C.Structure):         # bz_train_adam
                 ("p", TrainTensors), ("m", TrainTensors), ("v", TrainTensors)]
 
 
+class MlpAdam(C.Structure):          # bz_mlp_adam (host)
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", i32)]
+
+
 class TrainPartials(C.Structure):     # bz_train_partials
     _fields_ = [(n, vp) for n in ("tower", "tower_b", "stem", "heads", "heads_w")] + [("splits", i32)]
 
@@ -90,11 +94,23 @@ _SIGS = {
     "bz_net_forward_f32": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "bz_net_forward_bf16": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "bz_net_forward_fp8": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "bz_mlp_param_count": (i64, [i32]),
+    "bz_mlp_workspace_bytes": (i64, [i32, i32]),
+    "bz_mlp_create": (i32, [i32, i32, vp, vp, i64, vp, C.POINTER(vp)]),
+    "bz_mlp_destroy": (i32, [vp]),
+    "bz_mlp_update": (i32, [vp, vp, vp]),
+    "bz_mlp_forward_f32": (i32, [vp, vp, vp, i32, vp, vp]),
+    "bz_mlp_forward_bf16": (i32, [vp, vp, vp, i32, vp, vp]),
+    "bz_mlp_forward_states_f32": (i32, [vp, vp, i32, vp, vp]),
+    "bz_mlp_forward_states_bf16": (i32, [vp, vp, i32, vp, vp]),
+    "bz_mlp_train_workspace_bytes": (i64, [i32, i32]),
+    "bz_mlp_train_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(MlpAdam), vp, i64, vp, vp, vp, vp]),
     "bz_engine_workspace_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_create": (i32, [C.POINTER(EngineCfg), vp, i64, C.POINTER(vp)]),
     "bz_engine_destroy": (i32, [vp]),
     "bz_engine_get_layout": (i32, [vp, C.POINTER(EngineLayout)]),
     "bz_engine_set_net": (i32, [vp, vp]),
+    "bz_engine_set_mlp": (i32, [vp, vp]),
     "bz_engine_debug_set_search_seq": (i32, [vp, C.c_uint32]),
     "bz_engine_reset_games": (i32, [vp, vp]),
     "bz_engine_set_roots": (i32, [vp, vp, vp, vp, vp]),

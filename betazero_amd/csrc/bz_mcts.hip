@@ -1383,6 +1383,7 @@ struct bz_engine {
     bz_engine_layout lay;
     EngineDev dev;
     bz_net* net;
+    bz_mlp* mlp;  // BZ_EVAL_MLP_* (bz_engine_set_mlp)
     int64_t bytes;
     int pack_parity;  // which NEVAL buffer the last root_begin / select packed into
     int ttt_gw;       // lanes per game of the TTT-specialised fused search (cfg.ttt_lanes; 0 = the generic any-game kernel)
@@ -1409,6 +1410,7 @@ struct Offsets {
     int ecache, tt_buckets;
 };
 inline bool net_eval(int ek) { return ek == BZ_EVAL_NET_F32 || ek == BZ_EVAL_NET_BF16 || ek == BZ_EVAL_NET_FP8; }
+inline bool mlp_eval(int ek) { return ek == BZ_EVAL_MLP_F32 || ek == BZ_EVAL_MLP_BF16; }
 
 // nodes a game's arena holds: a fresh tree grows by one node per simulation; with subtree reuse a kept
 // subtree + sims new nodes must fit
@@ -1416,7 +1418,8 @@ inline int64_t nodes_per_game(const bz_engine_cfg& c) { return ((c.flags & BZ_EN
 
 bool cfg_ok(const bz_engine_cfg* c) {
     if (!(c && c->game >= BZ_GAME_TTT && c->game <= BZ_GAME_REVERSI4 && c->n_games > 0 && c->sims >= 1 &&
-          c->eval_kind >= 0 && c->eval_kind <= BZ_EVAL_NET_FP8 && c->rounds >= 1 &&
+          c->eval_kind >= 0 && c->eval_kind <= BZ_EVAL_MLP_BF16 && (!mlp_eval(c->eval_kind) || c->game == BZ_GAME_TTT) &&
+          c->rounds >= 1 &&
           c->t_max >= 1 && c->dirichlet_eps >= 0.0f && c->dirichlet_eps <= 1.0f &&
           (c->dirichlet_eps == 0.0f || (c->dirichlet_alpha > 0.0f && c->dirichlet_alpha <= 1.0f)) &&
           (c->ttt_lanes == -1 || c->ttt_lanes == 0 || c->ttt_lanes == 1 || c->ttt_lanes == 2 || c->ttt_lanes == 4 ||
@@ -1511,7 +1514,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "bz_engine_create: workspace must be 256-byte aligned");
     bz_engine* e = new (std::nothrow) bz_engine();
     if (!e) { set_error("out of host memory"); return BZ_ENOMEM; }
-    e->cfg = *cfg; e->net = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
+    e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -1532,7 +1535,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     d.leaf_kind = at<uint8_t>(ws, o.leaf_kind);
     d.leaf_own = at<u64>(ws, o.leaf_own); d.leaf_opp = at<u64>(ws, o.leaf_opp);
     d.c_own = at<u64>(ws, o.c_own); d.c_opp = at<u64>(ws, o.c_opp);
-    d.compact = net_eval(cfg->eval_kind) ? 1 : 0;
+    d.compact = (net_eval(cfg->eval_kind) || mlp_eval(cfg->eval_kind)) ? 1 : 0;
     d.ecache = o.ecache; d.tt_buckets = o.tt_buckets; d.tt = at<u64>(ws, o.tt); d.node_v = at<float>(ws, o.node_v); d.node_v_alt = at<float>(ws, o.node_v_alt);
     if (o.ecache) {  // generation 0 = never written
         hipError_t ce = hipMemset(d.tt, 0, (size_t)cfg->n_games * o.tt_buckets * 16 * 8);
@@ -1582,6 +1585,12 @@ BZ_EXPORT int32_t bz_engine_get_layout(const bz_engine* e, bz_engine_layout* out
 BZ_EXPORT int32_t bz_engine_set_net(bz_engine* e, bz_net* net) {
     BZ_REQUIRE(e, "bz_engine_set_net: null engine");
     e->net = net;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp) {
+    BZ_REQUIRE(e, "bz_engine_set_mlp: null engine");
+    e->mlp = mlp;
     return BZ_OK;
 }
 
@@ -1663,6 +1672,11 @@ BZ_EXPORT int32_t bz_engine_evaluate(bz_engine* e, void* stream) {
         return BZ_OK;
     }
     if (ek == BZ_EVAL_EXTERNAL) return BZ_OK;
+    if (mlp_eval(ek)) {  // (cfg_ok: tic-tac-toe only) the packed leaves, value 0 -- the reference's net has no value head
+        BZ_REQUIRE(e->mlp, "bz_engine_evaluate: eval_kind needs an MLP (bz_engine_set_mlp)");
+        return bz_mlp_forward_dev(e->mlp, ek == BZ_EVAL_MLP_BF16 ? 1 : 0, e->dev.c_own, e->dev.c_opp, nullptr, e->dev.B,
+                                  e->dev.flags + FLAG_NEVAL + e->pack_parity, e->dev.logits, e->dev.value, stream);
+    }
     BZ_REQUIRE(e->net, "bz_engine_evaluate: eval_kind needs a net (bz_engine_set_net)");
     // the net works on 8x8 planes; the reference's 6x6 / 4x4 boards live in their top-left corner (bit = 8*row+col for
     // every size), cells outside are never stones and never legal, so the same net serves them

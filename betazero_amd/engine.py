@@ -16,7 +16,9 @@ _GAMES = {"ttt": GAME_TTT, "tic_tac_toe": GAME_TTT, "reversi": GAME_REVERSI, "re
           GAME_REVERSI6: GAME_REVERSI6, GAME_REVERSI4: GAME_REVERSI4}
 _SIZES = {GAME_TTT: 3, GAME_REVERSI: 8, GAME_REVERSI6: 6, GAME_REVERSI4: 4}
 _EVALS = {"uniform": EVAL_UNIFORM, "hash": EVAL_HASH, "net_f32": EVAL_NET_F32, "net_bf16": EVAL_NET_BF16,
-          "external": EVAL_EXTERNAL, "net_fp8": EVAL_NET_FP8}
+          "external": EVAL_EXTERNAL, "net_fp8": EVAL_NET_FP8,
+          # the reference's tic-tac-toe MLP (betazero_amd.mlp.DeviceMLP as `net`): policy logits, value 0
+          "mlp_f32": _lib.EVAL_MLP_F32, "mlp_bf16": _lib.EVAL_MLP_BF16}
 
 
 def _u64(t):
@@ -123,6 +125,8 @@ class SelfPlayEngine:
         "n_cache_hits_prev" from the previous search) says how often it fired.  Ignored for the synthetic / external
         evaluators and with reuse_subtree."""
         check_sims(sims, reuse_subtree)
+        if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
+            raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
         L = _lib.lib()
         self.game = _GAMES[game]
@@ -148,7 +152,13 @@ class SelfPlayEngine:
         self.size = _SIZES[self.game]
         self.net = net
         if net is not None:
-            _lib.check(L.bz_engine_set_net(self.h, net.h))
+            from .mlp import DeviceMLP
+            if isinstance(net, DeviceMLP):
+                if net.max_batch < n_games:
+                    raise ValueError(f"DeviceMLP max_batch {net.max_batch} < n_games {n_games}")
+                _lib.check(L.bz_engine_set_mlp(self.h, net.h))
+            else:
+                _lib.check(L.bz_engine_set_net(self.h, net.h))
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -698,9 +708,10 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     With a net evaluator the games run as two pipelines on two HIP streams (PipelinedSelfPlay: the shape bench.py
     measures); `pipelines` overrides.  The rows do not depend on it."""
     if evaluator is None:
-        evaluator = "net_bf16" if net is not None else "uniform"
+        from .mlp import DeviceMLP
+        evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
     if pipelines is None:
-        pipelines = 2 if (evaluator.startswith("net_") and n_games >= 2) else 1
+        pipelines = 2 if (evaluator.startswith(("net_", "mlp_")) and n_games >= 2) else 1
     sp = PipelinedSelfPlay(game, n_games, sims, evaluator, net, pipelines, game_id_base=game_id_base,
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,

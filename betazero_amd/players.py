@@ -111,11 +111,43 @@ class NetPlayer(ReversiPlayer):
         return int(best) // 8, int(best) % 8
 
 
+class AIPlayer(Player):
+    """The reference's AIPlayer (src/tic_tac_toe/players.py:76-104) on the device MLP: AIPlayer(path_to_model, symbol)
+    loads the reference's checkpoint (mlp.load_reference_model: weights_only=True, never a pickle's code); path_to_model
+    may also be a TicTacToeNet or a DeviceMLP.  get_move runs one forward of symbol * board and plays the best LEGAL move
+    in descending-logit order; ties go to the lowest cell (torch.sort leaves their order unspecified).  Unlike the
+    reference it prints nothing (its three debug print lines, :100-102); the logits of the last call are in last_logits.
+    precision: "f32" (parity) or "bf16" (MFMA)."""
+
+    def __init__(self, path_to_model, symbol, precision="f32", device="cuda:0"):
+        import torch.nn as nn
+        from .mlp import DeviceMLP, load_reference_model
+        if precision not in ("f32", "bf16"):
+            raise ValueError("AIPlayer: precision is 'f32' or 'bf16'")
+        if isinstance(path_to_model, DeviceMLP):
+            self.net = path_to_model
+        else:
+            mod = path_to_model if isinstance(path_to_model, nn.Module) else load_reference_model(path_to_model)
+            self.net = DeviceMLP.from_module(mod, max_batch=16, device=device)
+        self.symbol, self.precision = symbol, precision
+        self.last_logits = None
+
+    def get_move(self, board):
+        x = self.symbol * np.asarray(board.board, dtype=np.float32).reshape(1, 9)
+        lg = self.net.forward_states(x, bf16=self.precision == "bf16")[0].cpu().numpy()
+        self.last_logits = lg
+        moves = board.generate_possible_moves()
+        idx = np.array([3 * r + c for r, c in moves])
+        best = int(idx[np.argmax(lg[idx])])  # moves are row-major: the first maximum is the lowest cell
+        return best // 3, best % 3
+
+
 class MCTSPlayer(Player):
     """get_move(board) -> (row, col) by one GPU search (PUCT, `sims` simulations)
     from `board` with `symbol` to move; plays argmax visit count (ties -> lowest
     action).  Works for TicTacToeBoard and 8x8 ReversiBoard; evaluator "net_bf16"
-    / "net_f32" need a betazero_amd.net.DeviceNet (Reversi, any of the reference's board sizes)."""
+    / "net_f32" need a betazero_amd.net.DeviceNet (Reversi, any of the reference's board sizes); "mlp_f32" (the default
+    with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0)."""
 
     def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0"):
         from .engine import check_sims
@@ -126,7 +158,9 @@ class MCTSPlayer(Player):
         self.eval_fn = evaluator if callable(evaluator) else None
         if self.eval_fn is not None:
             evaluator = "external"
-        self.evaluator = evaluator or ("net_bf16" if net is not None else "uniform")
+        from .mlp import DeviceMLP
+        self._mlp = isinstance(net, DeviceMLP)
+        self.evaluator = evaluator or (("mlp_f32" if self._mlp else "net_bf16") if net is not None else "uniform")
         self._eng = {}
         self.last_visits = None
 
@@ -144,6 +178,8 @@ class MCTSPlayer(Player):
         game = {8: "reversi", 6: "reversi6", 4: "reversi4"}[board.size] if hasattr(board, "size") else "ttt"
         if game == "ttt" and self.evaluator.startswith("net"):
             raise ValueError("the conv net evaluators serve the Reversi boards; use evaluator='uniform' or 'hash' for tic-tac-toe")
+        if game != "ttt" and (self._mlp or self.evaluator.startswith("mlp")):
+            raise ValueError("the MLP (DeviceMLP, evaluators 'mlp_f32' / 'mlp_bf16') serves tic-tac-toe, not Reversi")
         own, opp = board.bits(self.symbol)
         eng = self._engine(game)
         eng.set_roots([own], [opp], [self.symbol])

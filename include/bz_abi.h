@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define BZ_ABI_VERSION 6
+#define BZ_ABI_VERSION 7
 
 enum { BZ_OK = 0, BZ_EINVAL = 1, BZ_EILLEGAL_MOVE = 2, BZ_EHIP = 3, BZ_ENOMEM = 4, BZ_ENOGPU = 5,
        BZ_ESTATE = 6 };
@@ -46,7 +46,11 @@ enum { BZ_GAME_TTT = 0, BZ_GAME_REVERSI = 1, BZ_GAME_REVERSI6 = 2, BZ_GAME_REVER
  * (tree-kernel parity runs), the conv net in exact-fp32 parity mode, the conv
  * net on bf16 MFMA (the product path), or caller-filled logits/value. */
 enum { BZ_EVAL_UNIFORM = 0, BZ_EVAL_HASH = 1, BZ_EVAL_NET_F32 = 2, BZ_EVAL_NET_BF16 = 3,
-       BZ_EVAL_EXTERNAL = 4, BZ_EVAL_NET_FP8 = 5 };
+       BZ_EVAL_EXTERNAL = 4, BZ_EVAL_NET_FP8 = 5,
+       /* the reference's tic-tac-toe policy MLP (bz_mlp below, set by bz_engine_set_mlp), BZ_GAME_TTT only:
+        * the f32 parity forward or the bf16 MFMA forward.  The net has no value head: value = 0 for every
+        * evaluated leaf (terminal leaves keep the rules' value). */
+       BZ_EVAL_MLP_F32 = 6, BZ_EVAL_MLP_BF16 = 7 };
 #define BZ_PASS_ACTION 64
 
 int32_t bz_abi_version(void);
@@ -188,6 +192,52 @@ int32_t bz_net_forward_fp8(bz_net* net, const uint64_t* own, const uint64_t* opp
                            float* logits, float* value, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* The reference's tic-tac-toe policy MLP, TicTacToeNet                       */
+/*   src/tic_tac_toe/SL/neural_networks.py: Linear(9,H)-ReLU-Linear(H,H)-     */
+/*   ReLU-Linear(H,H)-ReLU-Linear(H,9), logits only; H = 256 shipped.         */
+/* Played by AIPlayer.get_move (players.py:76-104), trained by SL/train.py.   */
+/* ------------------------------------------------------------------------ */
+typedef struct bz_mlp bz_mlp;
+/* H: a multiple of 32 in 32..512.  Flat fp32 parameter vector in torch's order:
+ *  fc1.w[H][9] fc1.b[H] fc2.w[H][H] fc2.b[H] fc3.w[H][H] fc3.b[H] fc4.w[9][H] fc4.b[9]
+ * Both return -1 (bz_last_error) for an H out of range / max_batch < 1. */
+int64_t bz_mlp_param_count(int32_t H);
+int64_t bz_mlp_workspace_bytes(int32_t H, int32_t max_batch);
+/* params_host: host pointer.  Repacks + uploads the weights into the workspace (synchronises the stream once). */
+int32_t bz_mlp_create(int32_t H, int32_t max_batch, const float* params_host, void* workspace, int64_t workspace_bytes,
+                      void* stream, bz_mlp** out);
+int32_t bz_mlp_destroy(bz_mlp* mlp);
+/* replace the weights (same H); drains the device first, like bz_net_update */
+int32_t bz_mlp_update(bz_mlp* mlp, const float* params_host, void* stream);
+/* own/opp: device u64[n], side to move canonical, cell i = bit i (row-major), input x_i = own_i - opp_i;
+ * _states: device f32 x[n][9] as the reference feeds it (symbol * board).  logits: device f32[n][9].  n <= max_batch.
+ * _f32: fp32 parity mode, one fmaf chain per output over k = 0, 1, ..., K-1 from 0, then + bias -- a row's logits do
+ *       not depend on the batch it is in or on the run.
+ * _bf16: bf16 weights and activations, fp32 accumulation, on v_mfma_f32_16x16x32_bf16. */
+int32_t bz_mlp_forward_f32(bz_mlp* mlp, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, void* stream);
+int32_t bz_mlp_forward_bf16(bz_mlp* mlp, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, void* stream);
+int32_t bz_mlp_forward_states_f32(bz_mlp* mlp, const float* x, int32_t n, float* logits, void* stream);
+int32_t bz_mlp_forward_states_bf16(bz_mlp* mlp, const float* x, int32_t n, float* logits, void* stream);
+/* One supervised step of SL/train.py: loss = sum_r w_r CE(logits_r, target_r) / sum_r w_r (w_r = 1 when row_w is null:
+ * torch's CrossEntropyLoss mean), then torch.optim.Adam (no weight decay) with the bias corrections of step `step`.
+ * Two launches.  Everything is a caller-owned DEVICE buffer except `adam` (host):
+ *   params/m/v: fp32 [bz_mlp_param_count] (torch order; params must hold the weights the mlp was created / updated
+ *     with -- the step keeps both in step); grad (optional): the batch gradient;
+ *   x f32 [n][9], target i32 [n] (0..8 = the reference's action.argmax(1)), row_w f32 [n] (optional; 0 = row ignored,
+ *     so a short last batch needs no second shape); loss f32 [1] (optional); logits f32 [n][9] (optional, forward output);
+ *   ws: bz_mlp_train_workspace_bytes(H, n) bytes, 256-byte aligned.
+ * err (u32, sticky: the step ORs into it, the caller clears it): 1 = a target outside 0..8 on a row of non-zero weight,
+ * 2 = a non-finite loss, 4 = the row weights sum to <= 0.  While *err != 0 the step changes no parameter or moment. */
+typedef struct bz_mlp_adam {
+    float lr, beta1, beta2, eps;  /* SL/train.py: 1e-4, 0.9, 0.999, 1e-8 */
+    int32_t step;                 /* 1 for the first step */
+} bz_mlp_adam;
+int64_t bz_mlp_train_workspace_bytes(int32_t H, int32_t max_batch);
+int32_t bz_mlp_train_step(bz_mlp* mlp, float* params, float* m, float* v, float* grad, const float* x,
+                          const int32_t* target, const float* row_w, int32_t n, const bz_mlp_adam* adam,
+                          void* ws, int64_t ws_bytes, float* loss, float* logits, uint32_t* err, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Batched MCTS self-play engine.  The plug-in point it fills is             */
 /*   Player.get_move(board)  src/tic_tac_toe/players.py:6-9,                 */
 /*   ReversiPlayer.get_move  src/reversi/players/reversi_players.py:5-8      */
@@ -228,7 +278,7 @@ typedef struct bz_engine_cfg {
 /* keep the chosen child's subtree as the next search's tree; searches then go through the
  * step kernels for every evaluator */
 #define BZ_ENGINE_REUSE_SUBTREE 1u
-/* Evaluation cache (net evaluators; ignored with the synthetic / external evaluators and with BZ_ENGINE_REUSE_SUBTREE):
+/* Evaluation cache (conv net evaluators; ignored with the synthetic / external / MLP evaluators and with BZ_ENGINE_REUSE_SUBTREE):
  * a leaf whose position was already evaluated earlier in the SAME search -- reached by another move order -- takes that
  * node's priors and value instead of an evaluator row.  The evaluator is a function of the position alone
  * (players.py:84-98: canonical planes in, logits out), so every result (visit counts, W, P, pi, moves) is bit for
@@ -275,6 +325,9 @@ int32_t bz_engine_create(const bz_engine_cfg* cfg, void* workspace, int64_t work
 int32_t bz_engine_destroy(bz_engine* e);
 int32_t bz_engine_get_layout(const bz_engine* e, bz_engine_layout* out);
 int32_t bz_engine_set_net(bz_engine* e, bz_net* net);
+/* the MLP of BZ_EVAL_MLP_F32 / BZ_EVAL_MLP_BF16 (engines of BZ_GAME_TTT; those eval kinds with any other game are
+ * refused with BZ_EINVAL by bz_engine_workspace_bytes / bz_engine_create).  Its max_batch must be >= n_games. */
+int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp);
 /* test hook: set the count of searches begun so far (0 .. 2^19 - 3) -- the evaluation cache stamps its entries with it, cycling
  * through 1 .. 2^19 - 2; a test starts just below the wrap with this.  Nothing is carried over the jump. */
 int32_t bz_engine_debug_set_search_seq(bz_engine* e, uint32_t seq);
