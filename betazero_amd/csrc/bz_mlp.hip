@@ -116,7 +116,7 @@ __device__ __forceinline__ void f32_layer(const float* __restrict__ wT, const fl
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             float y = acc[r] + bj;
-            out[j * R + r] = relu ? fmaxf(y, 0.0f) : y;
+            out[j * R + r] = relu && y < 0.0f ? 0.0f : y;  // torch's ReLU: a NaN passes (fmaxf would make it 0)
         }
     }
 }

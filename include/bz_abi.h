@@ -227,7 +227,10 @@ int32_t bz_mlp_forward_states_bf16(bz_mlp* mlp, const float* x, int32_t n, float
  *     so a short last batch needs no second shape); loss f32 [1] (optional); logits f32 [n][9] (optional, forward output);
  *   ws: bz_mlp_train_workspace_bytes(H, n) bytes, 256-byte aligned.
  * err (u32, sticky: the step ORs into it, the caller clears it): 1 = a target outside 0..8 on a row of non-zero weight,
- * 2 = a non-finite loss, 4 = the row weights sum to <= 0.  While *err != 0 the step changes no parameter or moment. */
+ * 2 = a non-finite loss, 4 = the row weights sum to <= 0.  While *err != 0 the step changes no parameter or moment.
+ * The betas are float32; Adam is torch's formula at those betas: 1 - beta is taken in fp32 from the float beta (exact),
+ * the bias corrections 1 - beta^step in double from it.  (torch.optim.Adam takes 1 - beta in double from the Python
+ * float: at beta2 = 0.999 its v differs from this one by 1.3e-5 relative; the parameters do not measurably.) */
 typedef struct bz_mlp_adam {
     float lr, beta1, beta2, eps;  /* SL/train.py: 1e-4, 0.9, 0.999, 1e-8 */
     int32_t step;                 /* 1 for the first step */

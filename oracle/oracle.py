@@ -81,6 +81,8 @@ def lib():
         L.orc_mcts_search.restype = i32
         L.orc_mcts_search.argtypes = [i32, u64, u64, i32, i32, i32, C.c_float, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_mlp_forward_f32.restype = i32
+        L.orc_mlp_forward_f32.argtypes = [i32, C.c_void_p, C.c_void_p, i32, C.c_void_p]
         L.orc_selfplay_game.restype = i32
         L.orc_selfplay_game.argtypes = [C.POINTER(SpCfg), C.c_void_p, u64, i32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(i32), C.POINTER(i32),
@@ -173,6 +175,27 @@ class Net:
             lib().orc_net_destroy(self.h)
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- tic-tac-toe MLP
+def ttt_states(own, opp):
+    """side-to-move bitboards (cell i = bit i) -> fp32 inputs [n][9], x_i = own_i - opp_i"""
+    own = np.asarray(own, dtype=np.uint64).reshape(-1, 1)
+    opp = np.asarray(opp, dtype=np.uint64).reshape(-1, 1)
+    cells = np.arange(9, dtype=np.uint64)
+    return (((own >> cells) & 1).astype(np.int64) - ((opp >> cells) & 1).astype(np.int64)).astype(np.float32)
+
+
+def mlp_forward_f32(H, params, x):
+    """TicTacToeNet forward in the fp32 parity order (bz_oracle.c orc_mlp_forward_f32).  params: flat fp32 vector in torch's
+    order (TicTacToeNet.flat_params()); x: [n][9] fp32 -> logits [n][9] fp32"""
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    assert params.size == 2 * H * H + 21 * H + 9, (params.size, H)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 9)
+    lg = np.zeros((x.shape[0], 9), np.float32)
+    if lib().orc_mlp_forward_f32(H, params.ctypes.data, x.ctypes.data, x.shape[0], lg.ctypes.data):
+        raise ValueError("orc_mlp_forward_f32: bad arguments")
+    return lg
 
 
 # ---------------------------------------------------------------- mcts / self-play

@@ -82,7 +82,7 @@ def _bf16_emulation(m, x):
         a = r(torch.relu(y)) if i < 3 else y
     return a
 
-@pytest.mark.parametrize("H", [32, 64, 256, 512])
+@pytest.mark.parametrize("H", list(range(32, 513, 32)))
 def test_forward_hidden_sizes(H):
     from betazero_amd.mlp import DeviceMLP, TicTacToeNet
     torch.manual_seed(H)

@@ -175,3 +175,30 @@ def test_python_refuses_mlp_evaluator_on_reversi():
     from betazero_amd.engine import SelfPlayEngine
     with pytest.raises(ValueError, match="tic-tac-toe"):
         SelfPlayEngine("reversi", 4, 8, "mlp_f32")
+
+
+# ---------------------------------------------------------------- the C oracle's MLP (tests/test_gpu_mlp_numerics.py's yardstick)
+def test_oracle_mlp_forward_matches_reference_logits():
+    from oracle import oracle as orc
+    m, z = _fixture_module()
+    lg = orc.mlp_forward_f32(256, m.flat_params(), z["states"])
+    assert lg.shape == (4520, 9) and lg.dtype == np.float32
+    assert np.abs(lg - z["logits"]).max() <= 1e-5
+    # the bitboard helper gives the same inputs as the reference's symbol * board
+    tm = z["to_move"]
+    own = np.where(tm == 1, z["x_bits"], z["o_bits"]).astype(np.uint64)
+    opp = np.where(tm == 1, z["o_bits"], z["x_bits"]).astype(np.uint64)
+    assert np.array_equal(orc.ttt_states(own, opp), z["states"])
+
+
+@pytest.mark.parametrize("H", [32, 96, 512])
+def test_oracle_mlp_forward_matches_fp64_torch(H):
+    from oracle import oracle as orc
+    torch.manual_seed(100 + H)
+    m = TicTacToeNet(9, H, 9).eval()
+    g = torch.Generator().manual_seed(H)
+    x = torch.cat([torch.randint(-1, 2, (150, 9), generator=g).float(), torch.randn(50, 9, generator=g)])
+    with torch.no_grad():
+        ref = m.double()(x.double()).numpy()
+    lg = orc.mlp_forward_f32(H, m.float().flat_params(), x.numpy())
+    assert np.abs(lg - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max())
