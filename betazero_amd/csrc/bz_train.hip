@@ -74,8 +74,13 @@ __device__ __forceinline__ void store_tile(const char* buf, __bf16* dst, int pos
 // ---- the training epilogues.  Lane (r, h) register 4q + i of unit u holds channel 32 wt + 8q + 4h + i of board
 // cell (row u, column r & 7) of position r >> 3 (row-tile units).  Its ReLU bits for (q, u) are nibble 8q + u of a
 // 128-bit word per lane: word q, bits 4u .. 4u + 3.
-//   FWD: + bias (+ skip) -> ReLU -> bf16 -> LDS, and the bits (value > 0) into `bits`
+//   FWD: + bias (+ skip) -> ReLU -> bf16 -> LDS, and the bits (stored value > 0) into `bits`
 //   BWD: (+ skip) -> x bits -> bf16 -> LDS   (no bias, no clamp; use_bits == false: the gradient leaves unmasked)
+// The ReLU is torch's on the fp32 value: a NaN passes (and its bit is clear: NaN > 0 is false, as in torch's
+// threshold_backward), +-0 and negatives become +0 -- for finite values the same bits as a clamp after the rounding.  It is
+// IEEE maximum(v, +0), one v_maximum3_f32 on gfx950 (maximum propagates a NaN and orders -0 below +0; fmaxf would drop the NaN).
+// bf16 bits b > 0 as a value: 0x0001 .. 0x7f80 (positive finite or +inf; not +-0, not negative, not NaN)
+__device__ __forceinline__ unsigned bf16_pos(short b) { return (unsigned)(unsigned short)b - 1u < 0x7f80u ? 1u : 0u; }
 template <class G, bool BWD>
 __device__ __forceinline__ void epilogue_train(f32x16 (&acc)[G::MW][G::NU], char* out, bool second, const Bias<G>& bias,
                                                int wt0, int r, int h, unsigned (&bits)[4], bool use_bits) {
@@ -102,14 +107,14 @@ __device__ __forceinline__ void epilogue_train(f32x16 (&acc)[G::MW][G::NU], char
                     const unsigned nib = use_bits ? (word >> (4 * u)) & 0xFu : 0xFu;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = (nib >> i) & 1u ? v[i] : 0.0f;
+                } else {
+                    v = __builtin_elementwise_maximum(v, (f32x4)(0.0f));
                 }
                 f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
                 s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
                 s16x2 hi = __builtin_bit_cast(s16x2, __builtin_convertvector(vhi, bf16x2));
                 if (!BWD) {
-                    lo = __builtin_elementwise_max(lo, (s16x2)(0));
-                    hi = __builtin_elementwise_max(hi, (s16x2)(0));
-                    const unsigned nib = (lo[0] != 0 ? 1u : 0u) | (lo[1] != 0 ? 2u : 0u) | (hi[0] != 0 ? 4u : 0u) | (hi[1] != 0 ? 8u : 0u);
+                    const unsigned nib = bf16_pos(lo[0]) | bf16_pos(lo[1]) << 1 | bf16_pos(hi[0]) << 2 | bf16_pos(hi[1]) << 3;
                     word |= nib << (4 * u);
                 }
                 *reinterpret_cast<uint2*>(out + off) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
@@ -150,14 +155,14 @@ __device__ __forceinline__ void epilogue_train16(f32x16 (&acc)[G::MW][G::NU], ch
                         const unsigned nib = use_bits ? (word >> (4 * u)) & 0xFu : 0xFu;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = (nib >> i) & 1u ? v[i] : 0.0f;
+                    } else {
+                        v = __builtin_elementwise_maximum(v, (f32x4)(0.0f));
                     }
                     f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
                     s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
                     s16x2 hi = __builtin_bit_cast(s16x2, __builtin_convertvector(vhi, bf16x2));
                     if (!BWD) {
-                        lo = __builtin_elementwise_max(lo, (s16x2)(0));
-                        hi = __builtin_elementwise_max(hi, (s16x2)(0));
-                        const unsigned nib = (lo[0] != 0 ? 1u : 0u) | (lo[1] != 0 ? 2u : 0u) | (hi[0] != 0 ? 4u : 0u) | (hi[1] != 0 ? 8u : 0u);
+                        const unsigned nib = bf16_pos(lo[0]) | bf16_pos(lo[1]) << 1 | bf16_pos(hi[0]) << 2 | bf16_pos(hi[1]) << 3;
                         word |= nib << (4 * u);
                     }
                     *reinterpret_cast<uint2*>(out + off) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));

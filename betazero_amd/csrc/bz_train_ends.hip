@@ -27,10 +27,17 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+// the low / high bf16 of a word > 0 as a value (bits 0x0001 .. 0x7f80): torch's ReLU backward passes the gradient only there
+// (not at +-0, and not at a NaN, which the forward's ReLU lets through)
+__device__ __forceinline__ bool bf_pos_lo(unsigned w) { return (w & 0xffffu) - 1u < 0x7f80u; }
+__device__ __forceinline__ bool bf_pos_hi(unsigned w) { return (w >> 16) - 1u < 0x7f80u; }
 __device__ __forceinline__ unsigned pack2(float a, float b) {  // two floats -> two bf16 (round to nearest even), a in the low half
     f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
+// torch's ReLU: a NaN passes (fmaxf(y, 0) would turn it into 0 and hide it from the loss); +-0 and negatives become +0.
+// IEEE maximum (v_maximum3_f32 on gfx950): NaN-propagating, -0 ordered below +0
+__device__ __forceinline__ float relu(float y) { return __builtin_elementwise_maximum(y, 0.0f); }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
@@ -116,7 +123,7 @@ __global__ __launch_bounds__(256) void k_train_stem(const bz_train_batch* __rest
         }
         u32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = pack2(fmaxf(acc[2 * j], 0.0f), fmaxf(acc[2 * j + 1], 0.0f));
+        for (int j = 0; j < 4; ++j) o[j] = pack2(relu(acc[2 * j]), relu(acc[2 * j + 1]));
         *reinterpret_cast<u32x4*>(act0 + ((size_t)p * 64 + (row & 63)) * C + 8 * cg) = o;
     }
 }
@@ -156,7 +163,7 @@ __global__ __launch_bounds__(256) void k_train_stem_wgrad(const bz_train_batch* 
                 const int cl = it * CPW + sub, cell = c0 + cl;
                 const size_t at = ((size_t)p * 64 + cell) * PAIRS + pair;
                 const unsigned a = act0[at], g = g0[at];
-                const float glo = (a & 0x7fffu) ? bf_lo(g) : 0.0f, ghi = (a & 0x7fff0000u) ? bf_hi(g) : 0.0f;   // act0 >= 0: "> 0" = "not (+-)0"
+                const float glo = bf_pos_lo(a) ? bf_lo(g) : 0.0f, ghi = bf_pos_hi(a) ? bf_hi(g) : 0.0f;
                 const unsigned m = nb[64 * wv + cl];
 #pragma unroll
                 for (int k = 0; k < 18; ++k) {
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
                     d2 = fmaf(lo, hwS[2 * C + c], d2); d2 = fmaf(hi, hwS[2 * C + c + 1], d2);
                 }
             }
-            hvv[0] = fmaxf(d0, 0.0f); hvv[1] = fmaxf(d1, 0.0f); hvv[2] = fmaxf(d2, 0.0f);
+            hvv[0] = relu(d0); hvv[1] = relu(d1); hvv[2] = relu(d2);
 #pragma unroll
             for (int j = 0; j < 3; ++j) { hvS[64 * j + lane] = hvv[j]; A.hv[(size_t)pos * 192 + 64 * j + lane] = hvv[j]; }
         }
@@ -329,7 +336,7 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
             float t = v1b;
 #pragma unroll 8
             for (int cell = 0; cell < 64; ++cell) t = fmaf(V1t[cell * 65 + lane], hvS[128 + cell], t);
-            const float v1h = fmaxf(t, 0.0f);                       // (lanes >= VH: weights and bias are zero -> 0)
+            const float v1h = relu(t);                              // (lanes >= VH: weights and bias are zero -> 0)
             const float v = tanhf(wave_sum(v2w * v1h) + v2b);
             const float diff = v - zf;
             const float dpre2 = 2.0f * diff * A.inv_n * (1.0f - v * v);
@@ -377,8 +384,7 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
                 const int c = 8 * k + 2 * e;
                 const float glo = fmaf(dp[0], hwS[c], fmaf(dp[1], hwS[C + c], dp[2] * hwS[2 * C + c]));
                 const float ghi = fmaf(dp[0], hwS[c + 1], fmaf(dp[1], hwS[C + c + 1], dp[2] * hwS[2 * C + c + 1]));
-                // x is a stored ReLU output: bf16 >= 0, so "> 0" is "not the bit pattern of +0" (and of -0, which a kernel may have stored)
-                o[e] = pack2((xv[e] & 0x7fffu) ? glo : 0.0f, (xv[e] & 0x7fff0000u) ? ghi : 0.0f);
+                o[e] = pack2(bf_pos_lo(xv[e]) ? glo : 0.0f, bf_pos_hi(xv[e]) ? ghi : 0.0f);
             }
             *at = o;
         }
