@@ -36,12 +36,14 @@ class ArenaResult:
 
 
 def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=None, c_puct=1.5, seed=0, size=8,
-               device="cuda:0", max_plies=200, opening_plies=0):
+               device="cuda:0", max_plies=200, opening_plies=0, leaves_per_step=1):
     """MCTS (`sims` simulations, `evaluator`) vs minimax for n_games concurrent games; the MCTS side plays X
     (moves first) in the even-numbered games and O in the odd ones.  game: "ttt" | "reversi" (size 8, 6 or 4).
     Both players are deterministic, so without help there are only two distinct games (one per colour):
     `opening_plies` > 0 plays that many uniformly random legal moves (seeded) before the players take over, which
-    makes the B games B different tests."""
+    makes the B games B different tests.  leaves_per_step: K walks per tree step of the MCTS side."""
+    from .engine import check_leaves_per_step
+    check_leaves_per_step(leaves_per_step)
     if game != "ttt" and not 0 <= int(opponent_depth) <= 8:
         raise ValueError(f"play_arena: opponent_depth must be in 0..8 (got {opponent_depth}): the minimax kernel keeps an "
                          "explicit stack of that depth")
@@ -51,7 +53,7 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     ttt = game == "ttt"
     B = n_games
     ename = "ttt" if ttt else {8: "reversi", 6: "reversi6", 4: "reversi4"}[size]
-    eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device)
+    eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device, leaves_per_step=leaves_per_step)
     rng = np.random.default_rng(seed)
     st = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
     if ttt:

@@ -37,6 +37,9 @@ struct ProfScope {
 
 // bz_net.hip: which parameter upload the net's weights are from (changes with every bz_net_create / bz_net_update)
 uint64_t bz_net_epoch(const bz_net* net);
+// bz_net.hip / bz_mlp.hip: the rows one forward can take (a leaf-parallel engine needs K x n_games)
+int32_t bz_net_max_batch(const bz_net* net);
+int32_t bz_mlp_max_batch(const bz_mlp* mlp);
 // bz_net.hip: forward over the first *n_dev (device counter, <= max_n) positions; n_dev may be null
 int32_t bz_net_forward_dev(bz_net* net, int bf16, const uint64_t* own, const uint64_t* opp, int32_t max_n,
                            const uint32_t* n_dev, float* logits, float* value, void* stream);

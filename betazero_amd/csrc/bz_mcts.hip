@@ -18,7 +18,8 @@
 // leaves that need the net are packed through a double-buffered device-side counter.
 // Synthetic evaluators run the whole search in one launch (k_search_fused; k_search_fused_ttt for tic-tac-toe at
 // sims <= 120: root edges in registers, child header packed into the edge word, path in LDS).  Opt-in: Dirichlet root
-// noise (k_root_noise) and subtree reuse (two arenas, dev_reroot) -- DESIGN.md 3.9, 3.10.
+// noise (k_root_noise) and subtree reuse (two arenas, dev_reroot) -- DESIGN.md 3.9, 3.10; leaf-parallel search with virtual
+// loss (K walks per game per step, k_leaf_step) -- DESIGN.md 3.12.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -60,9 +61,15 @@ constexpr u32 kTerm = 1u << 8;
 // READY = nothing to expand or back up, select at once (a root whose subtree was kept from the previous move);
 // COPY = the leaf's position was evaluated earlier in this search (evaluation cache): its priors and value are copied
 // from that node instead of going through the evaluator again
-enum { LEAF_NONE = 0, LEAF_EVAL = 1, LEAF_TERMINAL = 2, LEAF_READY = 3, LEAF_COPY = 4 };
+// COLLIDE (leaf-parallel search) = the walk stopped at a node an earlier walk of the same step created and
+// that is not expanded yet: it takes that node's value and uses no evaluator row
+enum { LEAF_NONE = 0, LEAF_EVAL = 1, LEAF_TERMINAL = 2, LEAF_READY = 3, LEAF_COPY = 4, LEAF_COLLIDE = 5 };
 enum { CNT_SIMS, CNT_PATH_NODES, CNT_CHILD_SCORED, CNT_EDGES_BACKED, CNT_EXPANDED, CNT_CHILD_WRITTEN,
        CNT_ENV_STEPS, CNT_NET_LEAVES, CNT_CACHE_HITS, CNT_CACHE_HITS_PREV, CNT_N };
+// counters[10] (n_collisions, leaf-parallel search only) is not one of the per-wave slots (their layout, and so the
+// workspace, stays what it is at K = 1): k_leaf_step adds a wave's collisions straight into it, one atomic per wave that
+// has any -- they are rare
+constexpr int kCntCollisions = 10;
 constexpr int kCntWords = 24;  // u64 words of the counters block: CNT_N work counters, then (diagnostic builds) stamps at 16..23
 // NEVAL[2]: packed-leaf counters, double-buffered by simulation parity (the tree step that
 // packs into one buffer zeroes the other, so no extra reset launch is needed)
@@ -87,6 +94,11 @@ struct __attribute__((aligned(64))) GameHot {
 constexpr u32 kSrcPrev = 1u << 31;
 static_assert(sizeof(GameHot) == 64, "layout");
 
+// leaf-parallel search (K > 1): what walk j of game g left for the next tree step, at [g][j].
+// slot: the evaluator row of an EVAL leaf; v: an expanded leaf's value (what a later walk colliding with its node backs up)
+struct __attribute__((aligned(16))) LeafRec { u64 legal; u32 node, info, slot, depth, kind; float v; };
+static_assert(sizeof(LeafRec) == 32, "layout");
+
 struct EngineDev {
     int B, ncap, ecap, sims, na, t_max, rounds, temp_moves, openings, maxd, stagger;
     int compact;  // net evaluators: leaves needing evaluation are packed (c_own/c_opp/logits/value by slot)
@@ -97,7 +109,9 @@ struct EngineDev {
     Node* nodes; Edge* edges;
     u64 *g_own, *g_opp; int8_t* g_to_move; uint8_t* g_state; int32_t *g_moves, *g_nex, *g_round, *g_passes;
     struct GameHot* hot;  // [B]
-    PathEnt* path;        // [B][maxd], game-major
+    PathEnt* path;        // [B][K][maxd], game-major
+    int K;                // leaves per step (BZ_ENGINE_LEAVES_*): 1 = k_tree_step, > 1 = k_leaf_step
+    LeafRec* lrec;        // [B][K] (K > 1 only)
     uint8_t* leaf_kind; u64 *leaf_own, *leaf_opp, *c_own, *c_opp;
     float *logits, *value;
     u64 *ex_own, *ex_opp; float* ex_pi; int8_t *ex_z, *ex_mover; uint8_t* ex_act; int32_t* ex_len; int8_t* ex_winner;
@@ -403,7 +417,7 @@ __device__ __forceinline__ bool tt_lookup_insert(const EngineDev& E, int g, int 
 
 // M2: PUCT walk from the root; creates the child node behind the chosen unexpanded edge (env step:
 // apply + legal + terminal).  All lanes of the group return the same values.
-template <class G, class Sink>
+template <class G, class Sink, bool kLeafPar = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
                                            Sink& sink, LeafPos& lp, Stamps& st) {
@@ -444,6 +458,8 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             else if (lead) atomicOr(&E.flags[FLAG_ERR], ERR_DEPTH);
             depth++;
             if (e_term(bestw0)) { kind = LEAF_TERMINAL; leaf = child; tval = (float)e_val(bestw0); break; }
+            // leaf-parallel: a non-terminal child without edges was created by an earlier walk of this step
+            if (kLeafPar && e_nch(bestw0) == 0) { kind = LEAF_COLLIDE; leaf = child; tval = 0.0f; break; }
             // children's visits of X == visits of the edge into X minus the creating one
             e0 = e_edge0(bestw3); n = e_nch(bestw0); sumN = e_N(bestw0) - 1u;
             // X's position is needed only if the walk ends by extending X: the load goes out beside X's edge load
@@ -478,7 +494,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
         else if (lead) atomicOr(&E.flags[FLAG_ERR], ERR_DEPTH);
         depth++;
         leaf = id; kind = term ? LEAF_TERMINAL : LEAF_EVAL; tval = (float)tv;
-        if (E.ecache && !term) {  // evaluated before in this search? (wave-uniform branch: a kernel argument)
+        if (!kLeafPar && E.ecache && !term) {  // evaluated before in this search? (wave-uniform branch: a kernel argument; no cache with K > 1)
             u32 src = 0, src_e0 = 0;
             if (tt_lookup_insert<kGW>(E, g, sub, cown, copp, root.tt_gen, root.prev_nodes, id, src, src_e0)) { kind = LEAF_COPY; lp.src = src; lp.src_e0 = src_e0; }
         }
@@ -791,11 +807,19 @@ __global__ void __launch_bounds__(256) k_root_begin(EngineDev E, u32 tt_gen, int
         E.hot[g].n_nodes = 1; E.hot[g].n_edges = 0; E.hot[g].leaf_node = 0; E.hot[g].depth = 0;
         E.hot[g].root_base = 0;
     }
-    E.leaf_own[g] = E.g_own[g]; E.leaf_opp[g] = E.g_opp[g];
-    E.leaf_kind[g] = kind;
+    const size_t r0 = (size_t)g * E.K;  // leaf rows g*K + j (K = 1: row g)
+    E.leaf_own[r0] = E.g_own[g]; E.leaf_opp[r0] = E.g_opp[g];
+    E.leaf_kind[r0] = kind;
+    u32 slot = 0;
     if (E.compact && kind == LEAF_EVAL) {
-        u32 slot = atomicAdd(&E.flags[FLAG_NEVAL + 1], 1u);
+        slot = atomicAdd(&E.flags[FLAG_NEVAL + 1], 1u);
         E.hot[g].leaf_slot = slot; E.c_own[slot] = E.g_own[g]; E.c_opp[slot] = E.g_opp[g];
+    }
+    if (E.K > 1) {  // leaf-parallel: the root is walk 0's leaf, the other walks have none
+        LeafRec r; r.legal = E.hot[g].leaf_legal; r.node = 0; r.info = E.hot[g].leaf_info; r.slot = slot; r.depth = 0;
+        r.kind = kind; r.v = 0.0f;
+        E.lrec[r0] = r;
+        for (int j = 1; j < E.K; ++j) { E.lrec[r0 + j].kind = LEAF_NONE; E.leaf_kind[r0 + j] = LEAF_NONE; }
     }
     if (g == 0) E.flags[FLAG_NEVAL] = 0;
 }
@@ -824,14 +848,17 @@ __global__ void __launch_bounds__(64) k_root_noise(EngineDev E) {
 }
 
 // synthetic evaluators as a separate step (used by the step-by-step API)
+// (over the K*B leaf rows: grid-stride, the grid covers B)
 template <class G>
 __global__ void __launch_bounds__(256) k_eval_synth(EngineDev E, int eval_kind) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.leaf_kind[g] != LEAF_EVAL) return;
-    u64 h = hash_pos(E.leaf_own[g], E.leaf_opp[g]);
-    float* row = E.logits + (size_t)g * G::NA;
-    for (int a = 0; a < G::NA; ++a) row[a] = eval_kind == BZ_EVAL_HASH ? hash_logit(h, a) : 0.0f;
-    E.value[g] = eval_kind == BZ_EVAL_HASH ? hash_value(h) : 0.0f;
+    const int rows = E.B * E.K;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < rows; g += gridDim.x * blockDim.x) {
+        if (E.leaf_kind[g] != LEAF_EVAL) continue;
+        u64 h = hash_pos(E.leaf_own[g], E.leaf_opp[g]);
+        float* row = E.logits + (size_t)g * G::NA;
+        for (int a = 0; a < G::NA; ++a) row[a] = eval_kind == BZ_EVAL_HASH ? hash_logit(h, a) : 0.0f;
+        E.value[g] = eval_kind == BZ_EVAL_HASH ? hash_value(h) : 0.0f;
+    }
 }
 
 // One tree step for every game (16 lanes per game): [expand + backup of the previous leaf] and/or
@@ -956,6 +983,167 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
         }
     }
     st.mark(5);
+    cnt_flush<G::GW>(E, c);
+    st.mark(6);
+    st.flush(E.counters);
+}
+
+// Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
+// in k_tree_step.  One launch: [expand the pending leaves of the previous step in ascending j, each followed by the backup
+// of its path] then [K' = min(K, sims - sim_idx) walks in ascending j, each leaving a virtual loss (N += 1, W -= 1) on its
+// path before the next one starts].  Expanding leaf j and backing up path j before leaf j + 1 gives the bits of "expand all,
+// then back up all": an expansion writes only new edges and the header of its own node.  K paths overlap, so unlike
+// k_tree_step's pure-store backup every backup and virtual loss is a read-modify-write of the edge's {w0, W}, fenced per path.
+template <class G>
+__global__ void __launch_bounds__(256) k_leaf_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
+    constexpr int kGW = G::GW;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int g = t / kGW, sub = t % kGW;
+    const int K = E.K;
+    Cnt c = {};
+    Stamps st; st.start();
+    __shared__ u32 s_need, s_base;
+    if (threadIdx.x == 0) s_need = 0;
+    __syncthreads();
+    u32 eval_mask = 0, my_rank = 0;  // lead lane: the walks whose leaf needs an evaluator row; their first rank in the workgroup
+    u32 n_coll = 0;                  // lead lane: walks that collided
+    if (g < E.B) {
+        Edge* const edges = E.edges + (size_t)g * E.ecap;
+        LeafRec* const lr = E.lrec + (size_t)g * K;
+        const size_t r0 = (size_t)g * K;
+        // this game's rows, as per-lane pointers: the kernel-argument bases are not kept live across the walks
+        int maxd = E.maxd;
+        pin(maxd);  // (a VGPR: SGPRs are the scarce register file of this kernel)
+        PathEnt* const path_g = E.path + r0 * maxd;
+        u64* const lown = E.leaf_own + r0;
+        u64* const lopp = E.leaf_opp + r0;
+        uint8_t* const lkind = E.leaf_kind + r0;
+        const GameHot hot = E.hot[g];
+        const int state = E.g_state[g];
+        const bool active = state == 0 && lr[0].kind != LEAF_NONE;  // (a live game always has walk 0's leaf or a READY root)
+        u32 ne = hot.n_edges, nn = hot.n_nodes;
+        int root_n = (int)hot.root_n;
+        if (do_expand) {
+            for (int j = 0; j < K; ++j) {
+                const LeafRec L = lr[j];
+                if (L.kind != LEAF_EVAL && L.kind != LEAF_TERMINAL && L.kind != LEAF_COLLIDE) continue;
+                float v;
+                const u32 e0 = ne; int n = 0;
+                if (L.kind == LEAF_EVAL) {
+                    const u32 row = E.compact ? L.slot : (u32)(r0 + j);
+                    LogitSrc ls; ls.kind = BZ_EVAL_EXTERNAL; ls.h = 0; ls.row = E.logits + (size_t)row * G::NA;
+                    v = E.value[row];
+                    if (sub == 0 && !(v >= -3.0e38f && v <= 3.0e38f)) atomicOr(&E.flags[FLAG_ERR], ERR_EVAL_NONFINITE);
+                    n = dev_expand<G>(E, g, sub, L.node, L.legal, L.info, ls, ne, c, st);
+                    if (sub == 0) { c.v[CNT_NET_LEAVES]++; lr[j].v = v; }
+                    if (L.node == 0) root_n = n;
+                } else if (L.kind == LEAF_COLLIDE) {  // the value of the node an earlier walk of the step created, expanded above
+                    group_fence();
+                    v = 0.0f;  // (stays 0 without a source: a node left without edges by ERR_EDGE_OVERFLOW)
+                    for (int i = 0; i < j; ++i) {
+                        const LeafRec S = lr[i];
+                        if (S.kind == LEAF_EVAL && S.node == L.node) v = S.v;
+                    }
+                } else {
+                    v = (float)((int)((L.info >> 9) & 3u) - 1);
+                }
+                group_fence();  // this game's earlier expansions and backups -> the loads below
+                const PathEnt* path = path_g + (size_t)j * maxd;
+                const int depth = (int)L.depth, dmax = depth < maxd ? depth : maxd;
+                for (int d = sub; d < dmax; d += kGW) {  // val = -v at the leaf's edge; W = (W + 1) + val; N stays
+                    const PathEnt pe = path[d];
+                    const float val = ((dmax - 1 - d) & 1) ? v : -v;
+                    uint2 w = *reinterpret_cast<const uint2*>(edges + pe.eidx);
+                    if (d == depth - 1 && n > 0) {
+                        w.x |= (u32)n << kNchShift;
+                        edges[pe.eidx].w3 = L.node | (e0 << kChildBits);
+                    }
+                    w.y = __float_as_uint((__uint_as_float(w.y) + 1.0f) + val);
+                    *reinterpret_cast<uint2*>(edges + pe.eidx) = w;
+                }
+                if (sub == 0) c.v[CNT_EDGES_BACKED] += (u32)dmax;
+            }
+            if (sub == 0) { E.hot[g].n_edges = ne; E.hot[g].root_n = (u32)root_n; }
+        }
+        st.mark(2);
+        if (do_select) {
+            int kp = E.sims - (int)sim_idx < K ? E.sims - (int)sim_idx : K;
+            pin(kp);
+            const u32 sum0 = sim_idx + (E.reuse ? hot.root_base : 0u);  // the root's visits when walk 0 starts
+            const u64 rown = E.g_own[g], ropp = E.g_opp[g];
+            const int rtm = E.g_to_move[g];
+            for (int j = 0; j < K; ++j) {
+                u32 kind_out = LEAF_NONE;
+                if (active && j < kp) {
+                    group_fence();  // edges and virtual losses written above are read by this walk
+                    u32 leaf2; int k2, depth; float tv;
+                    LeafPos lpos; lpos.own = 0; lpos.opp = 0; lpos.legal = 0; lpos.info = 0; lpos.src = 0; lpos.src_e0 = 0;
+                    RootRef root; root.own = rown; root.opp = ropp; root.tm = rtm; root.n = root_n;
+                    root.sumN = sum0 + (u32)j;  // walks started so far, pending ones included
+                    root.has_pre = false; root.pre.w0 = 0; root.pre.W = 0.0f; root.pre.P = 0.0f; root.pre.w3 = 0;
+                    root.tt_gen = 0; root.prev_nodes = 0;
+                    PathEnt* path = path_g + (size_t)j * maxd;
+                    PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
+                    dev_select<G, PathHbm<kGW>, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st);
+                    sink.flush(sub, depth);
+                    group_fence();  // the walk's child-creation stores and deep path entries -> the virtual loss below
+                    // virtual loss: N += 1, W -= 1 on every path edge, from the words the walk saw (nothing else wrote them since)
+                    const int dmax = depth < maxd ? depth : maxd;
+                    if (sub < dmax)
+                        *reinterpret_cast<uint2*>(edges + sink.mine.eidx) = make_uint2(sink.mine.w0 + 1u, __float_as_uint(sink.mine.W - 1.0f));
+                    for (int d = sub + kGW; d < dmax; d += kGW) {
+                        const PathEnt pe = path[d];
+                        *reinterpret_cast<uint2*>(edges + pe.eidx) = make_uint2(pe.w0 + 1u, __float_as_uint(pe.W - 1.0f));
+                    }
+                    if (sub == 0) {
+                        LeafRec R; R.legal = 0; R.node = leaf2; R.info = 0; R.slot = 0; R.depth = (u32)depth; R.kind = (u32)k2; R.v = 0.0f;
+                        if (k2 == LEAF_EVAL) {
+                            R.legal = lpos.legal; R.info = lpos.info;
+                            lown[j] = lpos.own; lopp[j] = lpos.opp;
+                            if (E.compact) eval_mask |= 1u << j;
+                        } else if (k2 == LEAF_COLLIDE) {  // (the walk that created the node is found at expansion)
+                            n_coll++;
+                        } else {  // terminal leaf: the backup needs its value only
+                            R.info = (u32)((int)tv + 1) << 9;
+                        }
+                        lr[j] = R;
+                    }
+                    kind_out = (u32)k2;
+                } else if (sub == 0) {
+                    lr[j].kind = LEAF_NONE;
+                }
+                if (sub == 0) lkind[j] = (uint8_t)kind_out;
+            }
+            if (sub == 0) E.hot[g].n_nodes = nn;
+            if (sub == 0 && eval_mask) my_rank = atomicAdd(&s_need, (u32)__popc(eval_mask));
+            // the packed-leaf counters alternate step by step (computed here, not kept live across the walks)
+            if (t == 0) E.flags[FLAG_NEVAL + ((sim_idx / (u32)K + 1u) & 1u)] = 0;  // the buffer the NEXT select packs into
+        } else if (t == 0) {  // expand-only step (end of a search / step API): nothing is packed any more
+            E.flags[FLAG_NEVAL] = 0; E.flags[FLAG_NEVAL + 1] = 0;
+        }
+    }
+    if (do_select && E.compact) {  // (kernel arguments: the whole grid takes this branch or none of it)
+        __syncthreads();
+        if (threadIdx.x == 0) s_base = s_need ? atomicAdd(&E.flags[FLAG_NEVAL + ((sim_idx / (u32)E.K) & 1u)], s_need) : 0u;
+        __syncthreads();
+        if (eval_mask) {  // (lead lanes only)
+            u32 slot = s_base + my_rank;
+            LeafRec* const lr = E.lrec + (size_t)g * K;
+            for (u32 m = eval_mask; m; m &= m - 1u) {
+                const int j = __builtin_ctz(m);
+                const size_t r = (size_t)g * K + j;
+                lr[j].slot = slot; E.c_own[slot] = E.leaf_own[r]; E.c_opp[slot] = E.leaf_opp[r];
+                ++slot;
+            }
+        }
+    }
+    st.mark(5);
+    {
+        u32 x = n_coll;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+        if ((threadIdx.x & 63) == 0 && x) atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntCollisions, (unsigned long long)x);
+    }
     cnt_flush<G::GW>(E, c);
     st.mark(6);
     st.flush(E.counters);
@@ -1403,7 +1591,7 @@ struct Carver {
 
 struct Offsets {
     int64_t nodes, edges, nodes_alt, edges_alt, g_reuse, g_own, g_opp, g_to_move, g_state, g_moves, g_nex, g_round, g_passes, hot,
-        path, leaf_kind, leaf_own, leaf_opp, c_own, c_opp, logits, value, ex_own, ex_opp, ex_pi, ex_z, ex_mover,
+        path, lrec, leaf_kind, leaf_own, leaf_opp, c_own, c_opp, logits, value, ex_own, ex_opp, ex_pi, ex_z, ex_mover,
         ex_act, ex_len, ex_winner, ex_meta, root_N, root_W, root_P, counters, cnt_slots, flags, pack_off, tt, node_v, node_v_alt, total;
     int n_cnt_slots;
     int ncap, ecap, na, maxd;
@@ -1415,8 +1603,12 @@ inline bool mlp_eval(int ek) { return ek == BZ_EVAL_MLP_F32 || ek == BZ_EVAL_MLP
 // nodes a game's arena holds: a fresh tree grows by one node per simulation; with subtree reuse a kept
 // subtree + sims new nodes must fit
 inline int64_t nodes_per_game(const bz_engine_cfg& c) { return ((c.flags & BZ_ENGINE_REUSE_SUBTREE) ? 4 : 1) * ((int64_t)c.sims + 2); }
+// leaves per step: flag bits 8..12 hold K - 1
+inline int leaves_per_step(const bz_engine_cfg& c) { return (int)((c.flags & BZ_ENGINE_LEAVES_MASK) >> BZ_ENGINE_LEAVES_SHIFT) + 1; }
+constexpr uint32_t kFlagBits = (1u << 13) - 1u;  // flag bits 0..12; the leaves-per-step field is the highest
 
 bool cfg_ok(const bz_engine_cfg* c) {
+    if (c && (c->flags & ~kFlagBits)) return false;  // bits above the leaves-per-step field are reserved
     if (!(c && c->game >= BZ_GAME_TTT && c->game <= BZ_GAME_REVERSI4 && c->n_games > 0 && c->sims >= 1 &&
           c->eval_kind >= 0 && c->eval_kind <= BZ_EVAL_MLP_BF16 && (!mlp_eval(c->eval_kind) || c->game == BZ_GAME_TTT) &&
           c->rounds >= 1 &&
@@ -1438,12 +1630,14 @@ Offsets carve(const bz_engine_cfg& c) {
     o.ncap = (int)nodes_per_game(c);
     o.ecap = o.ncap * (ttt ? TicTacToe::MAXCH : Reversi::MAXCH);
     int64_t B = c.n_games, R = c.rounds, T = c.t_max;
+    const int64_t K = leaves_per_step(c);
     Carver k;
     o.nodes = k.take(B * o.ncap * (int64_t)sizeof(Node));
     o.edges = k.take(B * o.ecap * (int64_t)sizeof(Edge));
     // evaluation cache: net evaluators only (a synthetic evaluation costs less than the lookup), not with subtree reuse
     // (a kept subtree's nodes are not in the new search's table).  2 = with carry-over: a second arena, like subtree reuse
-    o.ecache = ((c.flags & BZ_ENGINE_EVAL_CACHE) && net_eval(c.eval_kind) && !reuse) ? ((c.flags & BZ_ENGINE_EVAL_CACHE_CARRY) ? 2 : 1) : 0;
+    // (and not with leaf-parallel search: K > 1)
+    o.ecache = ((c.flags & BZ_ENGINE_EVAL_CACHE) && net_eval(c.eval_kind) && !reuse && K == 1) ? ((c.flags & BZ_ENGINE_EVAL_CACHE_CARRY) ? 2 : 1) : 0;
     const bool two = reuse || o.ecache == 2;
     o.nodes_alt = k.take(two ? B * o.ncap * (int64_t)sizeof(Node) : 0);
     o.edges_alt = k.take(two ? B * o.ecap * (int64_t)sizeof(Edge) : 0);
@@ -1451,10 +1645,12 @@ Offsets carve(const bz_engine_cfg& c) {
     o.g_own = k.take(B * 8); o.g_opp = k.take(B * 8); o.g_to_move = k.take(B); o.g_state = k.take(B);
     o.g_moves = k.take(B * 4); o.g_nex = k.take(B * 4); o.g_round = k.take(B * 4); o.g_passes = k.take(B * 4);
     o.hot = k.take(B * (int64_t)sizeof(GameHot));
-    o.path = k.take((int64_t)o.maxd * B * (int64_t)sizeof(PathEnt));
-    o.leaf_kind = k.take(B); o.leaf_own = k.take(B * 8); o.leaf_opp = k.take(B * 8);
-    o.c_own = k.take(B * 8); o.c_opp = k.take(B * 8);
-    o.logits = k.take(B * o.na * 4); o.value = k.take(B * 4);
+    // leaf-parallel search: K paths and K leaf records per game, K*B leaf / evaluator rows (row g*K + j = walk j of game g)
+    o.path = k.take((int64_t)o.maxd * K * B * (int64_t)sizeof(PathEnt));
+    o.lrec = k.take(K > 1 ? K * B * (int64_t)sizeof(LeafRec) : 0);
+    o.leaf_kind = k.take(K * B); o.leaf_own = k.take(K * B * 8); o.leaf_opp = k.take(K * B * 8);
+    o.c_own = k.take(K * B * 8); o.c_opp = k.take(K * B * 8);
+    o.logits = k.take(K * B * o.na * 4); o.value = k.take(K * B * 4);
     o.ex_own = k.take(R * B * T * 8); o.ex_opp = k.take(R * B * T * 8); o.ex_pi = k.take(R * B * T * o.na * 4);
     o.ex_z = k.take(R * B * T); o.ex_mover = k.take(R * B * T); o.ex_act = k.take(R * B * T);
     o.ex_len = k.take(R * B * 4); o.ex_winner = k.take(R * B);
@@ -1499,14 +1695,17 @@ inline dim3 grid_lane(int B, int) { return grid_of(B); }
 #define BZ_DISPATCH_G(e, KERNEL, stream, ...) BZ_DISPATCH_IMPL(e, KERNEL, grid_groups, stream, __VA_ARGS__)
 
 const char* kBadCfg = "bad config (note: sims <= 8189, or <= 2045 with BZ_ENGINE_REUSE_SUBTREE -- the packed edge record, bz_abi.h)";
+const char* kBadFlags = "bad config: cfg.flags has bits set above bit 12 (the leaves-per-step field BZ_ENGINE_LEAVES_MASK ends there)";
 
 BZ_EXPORT int64_t bz_engine_workspace_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_workspace_bytes: %s", kBadFlags); return -1; }
     if (!cfg_ok(cfg)) { set_error("bz_engine_workspace_bytes: %s", kBadCfg); return -1; }
     return carve(*cfg).total;
 }
 
 BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t bytes, bz_engine** out) {
     BZ_REQUIRE(ws && out, "bz_engine_create: null pointer");
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_create: %s", kBadFlags); return BZ_EINVAL; }
     if (!cfg_ok(cfg)) { set_error("bz_engine_create: %s", kBadCfg); return BZ_EINVAL; }
     if (bz_device_count() <= 0) { set_error("bz_engine_create: no HIP device (the engine has no CPU path)"); return BZ_ENOGPU; }
     Offsets o = carve(*cfg);
@@ -1532,6 +1731,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     d.g_state = at<uint8_t>(ws, o.g_state); d.g_moves = at<int32_t>(ws, o.g_moves); d.g_nex = at<int32_t>(ws, o.g_nex);
     d.g_round = at<int32_t>(ws, o.g_round); d.g_passes = at<int32_t>(ws, o.g_passes);
     d.hot = at<GameHot>(ws, o.hot); d.path = at<PathEnt>(ws, o.path);
+    d.K = leaves_per_step(*cfg); d.lrec = at<LeafRec>(ws, o.lrec);
     d.leaf_kind = at<uint8_t>(ws, o.leaf_kind);
     d.leaf_own = at<u64>(ws, o.leaf_own); d.leaf_opp = at<u64>(ws, o.leaf_opp);
     d.c_own = at<u64>(ws, o.c_own); d.c_opp = at<u64>(ws, o.c_opp);
@@ -1584,12 +1784,16 @@ BZ_EXPORT int32_t bz_engine_get_layout(const bz_engine* e, bz_engine_layout* out
 
 BZ_EXPORT int32_t bz_engine_set_net(bz_engine* e, bz_net* net) {
     BZ_REQUIRE(e, "bz_engine_set_net: null engine");
+    BZ_REQUIRE(e->dev.K == 1 || !net || (int64_t)bz_net_max_batch(net) >= (int64_t)e->dev.K * e->dev.B,
+               "bz_engine_set_net: the net's max_batch is below leaves_per_step x n_games (the evaluator rows of one step)");
     e->net = net;
     return BZ_OK;
 }
 
 BZ_EXPORT int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp) {
     BZ_REQUIRE(e, "bz_engine_set_mlp: null engine");
+    BZ_REQUIRE(e->dev.K == 1 || !mlp || (int64_t)bz_mlp_max_batch(mlp) >= (int64_t)e->dev.K * e->dev.B,
+               "bz_engine_set_mlp: the MLP's max_batch is below leaves_per_step x n_games (the evaluator rows of one step)");
     e->mlp = mlp;
     return BZ_OK;
 }
@@ -1653,14 +1857,22 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
 
 static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t sim_idx, void* stream) {
     ProfScope ps(do_select ? BZ_PROF_SELECT : BZ_PROF_EXPAND_BACKUP, stream);
+    if (e->dev.K > 1) {  // leaf-parallel: sim_idx is a multiple of K, the packed-leaf buffers alternate per step
+        BZ_DISPATCH_G(e, k_leaf_step, stream, e->dev, do_expand, do_select, sim_idx);
+        if (do_select) e->pack_parity = (int)((sim_idx / (uint32_t)e->dev.K) & 1u);
+        return BZ_OK;
+    }
     BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
     if (do_select) e->pack_parity = (int)(sim_idx & 1u);
     return BZ_OK;
 }
 
-/* sim_index = number of simulations already completed in this search (the root's visit sum) */
+/* sim_index = number of simulations already completed in this search (the root's visit sum); with K leaves per step
+ * 0, K, 2K, ...: the step starts the next min(K, sims - sim_index) walks */
 BZ_EXPORT int32_t bz_engine_select(bz_engine* e, uint32_t sim_index, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    BZ_REQUIRE(e->dev.K == 1 || (sim_index % (uint32_t)e->dev.K == 0 && sim_index < (uint32_t)e->cfg.sims),
+               "bz_engine_select: sim_index must be a multiple of leaves_per_step below sims");
     return tree_step(e, 0, 1, sim_index, stream);
 }
 
@@ -1674,7 +1886,7 @@ BZ_EXPORT int32_t bz_engine_evaluate(bz_engine* e, void* stream) {
     if (ek == BZ_EVAL_EXTERNAL) return BZ_OK;
     if (mlp_eval(ek)) {  // (cfg_ok: tic-tac-toe only) the packed leaves, value 0 -- the reference's net has no value head
         BZ_REQUIRE(e->mlp, "bz_engine_evaluate: eval_kind needs an MLP (bz_engine_set_mlp)");
-        return bz_mlp_forward_dev(e->mlp, ek == BZ_EVAL_MLP_BF16 ? 1 : 0, e->dev.c_own, e->dev.c_opp, nullptr, e->dev.B,
+        return bz_mlp_forward_dev(e->mlp, ek == BZ_EVAL_MLP_BF16 ? 1 : 0, e->dev.c_own, e->dev.c_opp, nullptr, e->dev.B * e->dev.K,
                                   e->dev.flags + FLAG_NEVAL + e->pack_parity, e->dev.logits, e->dev.value, stream);
     }
     BZ_REQUIRE(e->net, "bz_engine_evaluate: eval_kind needs a net (bz_engine_set_net)");
@@ -1682,7 +1894,7 @@ BZ_EXPORT int32_t bz_engine_evaluate(bz_engine* e, void* stream) {
     // every size), cells outside are never stones and never legal, so the same net serves them
     BZ_REQUIRE(e->cfg.game != BZ_GAME_TTT, "bz_engine_evaluate: the conv net serves the Reversi boards, not tic-tac-toe");
     // leaves were packed by select: evaluate only the first flags[NEVAL] slots (device-side count)
-    return bz_net_forward_dev(e->net, ek == BZ_EVAL_NET_BF16 ? 1 : (ek == BZ_EVAL_NET_FP8 ? 2 : 0), e->dev.c_own, e->dev.c_opp, e->dev.B,
+    return bz_net_forward_dev(e->net, ek == BZ_EVAL_NET_BF16 ? 1 : (ek == BZ_EVAL_NET_FP8 ? 2 : 0), e->dev.c_own, e->dev.c_opp, e->dev.B * e->dev.K,
                               e->dev.flags + FLAG_NEVAL + e->pack_parity, e->dev.logits, e->dev.value, stream);
 }
 
@@ -1705,7 +1917,7 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     int ek = e->cfg.eval_kind;
     const bool noise = e->dev.dir_eps > 0.0f;
-    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise) {
+    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -1735,7 +1947,8 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
         if ((rc = tree_step(e, 1, 0, 0, stream)) != BZ_OK) return rc;
         if ((rc = bz_engine_root_noise(e, stream)) != BZ_OK) return rc;
     }
-    for (int s = 0; s < e->cfg.sims; ++s) {  // expand+backup of leaf s-1 (s = 0: the root) fused with select s
+    // expand+backup of the previous step's leaves (s = 0: the root) fused with the select of walks s .. s + K - 1
+    for (int s = 0; s < e->cfg.sims; s += e->dev.K) {
         if ((rc = tree_step(e, (noise && s == 0) ? 0 : 1, 1, (uint32_t)s, stream)) != BZ_OK) return rc;
         if ((rc = bz_engine_evaluate(e, stream)) != BZ_OK) return rc;
     }
@@ -1857,9 +2070,11 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
     for (int i = 0; i < n; ++i) {
         BZ_REQUIRE(engines[i], "bz_engines_step: null engine");
         BZ_REQUIRE(engines[i]->cfg.sims == engines[0]->cfg.sims, "bz_engines_step: the engines must search the same number of simulations");
+        BZ_REQUIRE(engines[i]->dev.K == engines[0]->dev.K, "bz_engines_step: the engines must take the same leaves per step");
         const int ek = engines[i]->cfg.eval_kind;
         BZ_REQUIRE(ek != BZ_EVAL_EXTERNAL, "bz_engines_step: BZ_EVAL_EXTERNAL callers drive the step API");
-        if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !engines[i]->dev.reuse && !(engines[i]->dev.dir_eps > 0.0f)) stepwise = false;
+        if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !engines[i]->dev.reuse && !(engines[i]->dev.dir_eps > 0.0f) &&
+            engines[i]->dev.K == 1) stepwise = false;
     }
     int32_t rc;
     if (!stepwise) {  // a fused search is one launch per engine: nothing to interleave
@@ -1876,16 +2091,19 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
             if ((rc = bz_engine_root_noise(e, streams[i])) != BZ_OK) return rc;
         }
     }
-    const int sims = engines[0]->cfg.sims, q = run_ahead_sims > 0 ? (run_ahead_sims >= 2 ? run_ahead_sims / 2 : 1) : 0;
-    for (int s = 0; s < sims; ++s) {
+    // (K > 1: one step = K simulations; the run-ahead bound counts steps of q / K, at least one)
+    const int sims = engines[0]->cfg.sims, K = engines[0]->dev.K;
+    const int q0 = run_ahead_sims > 0 ? (run_ahead_sims >= 2 ? run_ahead_sims / 2 : 1) : 0;
+    const int q = q0 ? (q0 / K > 0 ? q0 / K : 1) : 0;
+    for (int s = 0, step = 0; s < sims; s += K, ++step) {
         for (int i = 0; i < n; ++i) {
             bz_engine* e = engines[i];
             if ((rc = tree_step(e, (e->dev.dir_eps > 0.0f && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
         }
-        if (q && (s + 1) % q == 0)
+        if (q && (step + 1) % q == 0)
             for (int i = 0; i < n; ++i)
-                if ((rc = ahead_mark(engines[i], (s + 1) / q - 1, (hipStream_t)streams[i])) != BZ_OK) return rc;
+                if ((rc = ahead_mark(engines[i], (step + 1) / q - 1, (hipStream_t)streams[i])) != BZ_OK) return rc;
     }
     for (int i = 0; i < n; ++i) {
         if ((rc = tree_step(engines[i], 1, 0, 0, streams[i])) != BZ_OK) return rc;

@@ -322,6 +322,8 @@ BZ_EXPORT int32_t bz_mlp_update(bz_mlp* m, const float* params_host, void* strea
     return upload(m, params_host, (hipStream_t)stream);
 }
 
+int32_t bz_mlp_max_batch(const bz_mlp* m) { return m ? m->max_batch : 0; }
+
 int32_t bz_mlp_forward_dev(bz_mlp* m, int bf16, const uint64_t* own, const uint64_t* opp, const float* x, int32_t max_n,
                            const uint32_t* n_dev, float* logits, float* value, void* stream) {
     BZ_REQUIRE(m && logits && (x || (own && opp)), "bz_mlp_forward: null pointer");

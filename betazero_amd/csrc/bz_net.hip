@@ -1132,6 +1132,7 @@ static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp,
 }
 
 uint64_t bz_net_epoch(const bz_net* n) { return n ? n->epoch : 0; }
+int32_t bz_net_max_batch(const bz_net* n) { return n ? n->max_batch : 0; }
 
 int32_t bz_net_forward_dev(bz_net* n, int bf16 /* 0 f32, 1 bf16, 2 fp8 */, const uint64_t* own, const uint64_t* opp, int32_t max_n,
                            const uint32_t* n_dev, float* logits, float* value, void* stream) {

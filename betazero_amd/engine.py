@@ -113,18 +113,35 @@ def check_sims(sims, reuse_subtree=False):
                          "(BZ_ENGINE_MAX_SIMS / BZ_ENGINE_MAX_SIMS_REUSE in include/bz_abi.h)")
 
 
+MAX_LEAVES_PER_STEP = 32  # the 5-bit BZ_ENGINE_LEAVES_* field of cfg.flags (include/bz_abi.h)
+
+
+def check_leaves_per_step(leaves_per_step):
+    """leaf-parallel search: K walks per game per tree step, an int in 1..32 (bool refused)"""
+    k = leaves_per_step
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_LEAVES_PER_STEP:
+        raise ValueError(f"leaves_per_step must be an int in 1..{MAX_LEAVES_PER_STEP} (got {k!r})")
+    return int(k)
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
-                 dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True):
+                 dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
+                 leaves_per_step=1):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
         is re-created node for node by the new search), "search" only from the same search, False none.  Every result is bit
         for bit what it is without the cache (the net is a function of the position); counters()["n_cache_hits"] (of which
         "n_cache_hits_prev" from the previous search) says how often it fired.  Ignored for the synthetic / external
-        evaluators and with reuse_subtree."""
+        evaluators, with reuse_subtree and with leaves_per_step > 1.
+
+        leaves_per_step = K (BZ_ENGINE_LEAVES_*): every tree step runs K PUCT walks per game with virtual
+        loss, and the evaluator takes up to K x n_games rows per launch; 1 (the default) is the one-walk engine, unchanged.
+        counters()["n_collisions"] (K > 1 only) counts the walks that stopped at a node another walk of the same step created."""
         check_sims(sims, reuse_subtree)
+        self.K = check_leaves_per_step(leaves_per_step)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -136,7 +153,8 @@ class SelfPlayEngine:
         self.cfg = EngineCfg(self.game, n_games, sims, _EVALS[evaluator], c_puct, temp_moves, openings, rounds, t_max,
                              stagger, seed, game_id_base, n_games if game_id_stride is None else game_id_stride,
                              (_lib.ENGINE_REUSE_SUBTREE if reuse_subtree else 0) | (_lib.ENGINE_EVAL_CACHE if eval_cache else 0) |
-                             (_lib.ENGINE_EVAL_CACHE_CARRY if eval_cache in (True, "carry") else 0),
+                             (_lib.ENGINE_EVAL_CACHE_CARRY if eval_cache in (True, "carry") else 0) |
+                             ((self.K - 1) << _lib.ENGINE_LEAVES_SHIFT),
                              dirichlet_alpha, dirichlet_eps, ttt_lanes)
         nbytes = L.bz_engine_workspace_bytes(C.byref(self.cfg))
         if nbytes < 0:
@@ -154,8 +172,9 @@ class SelfPlayEngine:
         if net is not None:
             from .mlp import DeviceMLP
             if isinstance(net, DeviceMLP):
-                if net.max_batch < n_games:
-                    raise ValueError(f"DeviceMLP max_batch {net.max_batch} < n_games {n_games}")
+                if net.max_batch < n_games * self.K:
+                    raise ValueError(f"DeviceMLP max_batch {net.max_batch} < n_games {n_games}" +
+                                     (f" x leaves_per_step {self.K}" if self.K > 1 else ""))
                 _lib.check(L.bz_engine_set_mlp(self.h, net.h))
             else:
                 _lib.check(L.bz_engine_set_net(self.h, net.h))
@@ -192,9 +211,10 @@ class SelfPlayEngine:
 
     def search_external(self, eval_fn):
         """One full search with a caller-supplied evaluator (engine built with evaluator="external"): eval_fn(own, opp,
-        kind) gets the leaf positions as int64 CUDA tensors [B] (uint64 bit patterns, side-to-move canonical -- the input
-        convention of the reference's AIPlayer, players.py:85) and kind (uint8 [B], 1 = needs evaluation) and returns
-        (logits [B, NA] float32, value [B] float32) CUDA tensors; legality masking and the softmax happen in the expansion.
+        kind) gets the leaf positions as int64 CUDA tensors [K*B] (uint64 bit patterns, side-to-move canonical -- the input
+        convention of the reference's AIPlayer, players.py:85) and kind (uint8 [K*B], 1 = needs evaluation; row g*K + j =
+        walk j of game g, K = leaves_per_step) and returns (logits [K*B, NA] float32, value [K*B] float32) CUDA tensors;
+        legality masking and the softmax happen in the expansion.
         Any torch module can sit here -- e.g. an MLP over the 9 tic-tac-toe cells like the reference's TicTacToeNet."""
         lb = self.leaf_buffers()
 
@@ -204,7 +224,7 @@ class SelfPlayEngine:
             lb["value"].copy_(v.to(torch.float32).reshape(lb["value"].shape))
         self.root_begin(); fill(); self.expand_backup()
         self.root_noise()  # (no-op unless dirichlet_eps > 0) same place as in bz_engine_search
-        for s in range(self.sims):
+        for s in range(0, self.sims, self.K):  # one step = min(K, sims - s) walks per game
             self.select(s); fill(); self.expand_backup()
 
     def root_begin(self):
@@ -250,17 +270,22 @@ class SelfPlayEngine:
         return N, W, P
 
     def counters(self):
+        """the work counters by name (_lib.COUNTER_NAMES); "n_collisions" only for leaves_per_step > 1"""
         self._call(_lib.lib().bz_engine_sum_counters)
         c = self._view(self.lay.counters, torch.int64, (24,)).cpu().numpy()
-        return dict(zip(_lib.COUNTER_NAMES, (int(v) for v in c[:len(_lib.COUNTER_NAMES)])))
+        # n_collisions (counters[10]) only for a leaf-parallel engine: at K = 1 it is 0 by definition, and the dict stays
+        # what it was before leaves_per_step existed
+        names = _lib.COUNTER_NAMES if self.K > 1 else _lib.COUNTER_NAMES[:_lib.COUNTER_NAMES.index("n_collisions")]
+        return dict(zip(names, (int(v) for v in c[:len(names)])))
 
-    # leaf buffers for BZ_EVAL_EXTERNAL callers (torch tensors aliasing the workspace)
+    # leaf buffers for BZ_EVAL_EXTERNAL callers (torch tensors aliasing the workspace): K*B rows, row g*K + j = walk j of game g
     def leaf_buffers(self):
-        return {"own": self._view(self.lay.leaf_own, torch.int64, (self.B,)),
-                "opp": self._view(self.lay.leaf_opp, torch.int64, (self.B,)),
-                "kind": self._view(self.lay.leaf_kind, torch.uint8, (self.B,)),
-                "logits": self._view(self.lay.logits, torch.float32, (self.B, self.na)),
-                "value": self._view(self.lay.value, torch.float32, (self.B,))}
+        R = self.B * self.K
+        return {"own": self._view(self.lay.leaf_own, torch.int64, (R,)),
+                "opp": self._view(self.lay.leaf_opp, torch.int64, (R,)),
+                "kind": self._view(self.lay.leaf_kind, torch.uint8, (R,)),
+                "logits": self._view(self.lay.logits, torch.float32, (R, self.na)),
+                "value": self._view(self.lay.value, torch.float32, (R,))}
 
     def positions(self):
         return (_u64(self._view(self.lay.g_own, torch.int64, (self.B,))),
@@ -578,8 +603,9 @@ class PipelinedSelfPlay:
     host, and everything that hands data out (status, counters, pack_examples, examples ...) joins first."""
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
-                 game_id_stride=None, device="cuda:0", run_ahead=16, **engine_kwargs):
+                 game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, **engine_kwargs):
         assert 1 <= pipelines <= n_games
+        check_leaves_per_step(leaves_per_step)
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
         self.run_ahead = run_ahead
@@ -589,7 +615,8 @@ class PipelinedSelfPlay:
         assert len(self.streams) == pipelines
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
-                                       game_id_stride=stride, device=device, **engine_kwargs) for i in range(pipelines)]
+                                       game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, **engine_kwargs)
+                        for i in range(pipelines)]
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
 
@@ -701,12 +728,13 @@ class PipelinedSelfPlay:
 
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
-              reuse_subtree=False, pipelines=None):
+              reuse_subtree=False, pipelines=None, leaves_per_step=1):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
     With a net evaluator the games run as two pipelines on two HIP streams (PipelinedSelfPlay: the shape bench.py
-    measures); `pipelines` overrides.  The rows do not depend on it."""
+    measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine."""
+    check_leaves_per_step(leaves_per_step)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -715,7 +743,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     sp = PipelinedSelfPlay(game, n_games, sims, evaluator, net, pipelines, game_id_base=game_id_base,
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
-                           dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree)
+                           dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

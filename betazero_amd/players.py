@@ -149,9 +149,10 @@ class MCTSPlayer(Player):
     / "net_f32" need a betazero_amd.net.DeviceNet (Reversi, any of the reference's board sizes); "mlp_f32" (the default
     with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0)."""
 
-    def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0"):
-        from .engine import check_sims
+    def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1):
+        from .engine import check_leaves_per_step, check_sims
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
+        self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step (DESIGN.md 3.12)
         self.symbol, self.sims, self.net, self.c_puct, self.device = symbol, sims, net, c_puct, device
         # evaluator: "uniform" | "hash" | "net_bf16" | "net_f32" | "net_fp8", or a callable (own, opp, kind) -> (logits, value)
         # on CUDA tensors (SelfPlayEngine.search_external): any torch module, e.g. an MLP for tic-tac-toe
@@ -168,7 +169,7 @@ class MCTSPlayer(Player):
         from .engine import SelfPlayEngine
         if game not in self._eng:
             self._eng[game] = SelfPlayEngine(game, 1, self.sims, self.evaluator, self.net, self.c_puct,
-                                             device=self.device)
+                                             device=self.device, leaves_per_step=self.leaves_per_step)
         return self._eng[game]
 
     def get_move(self, board):

@@ -281,7 +281,8 @@ typedef struct bz_engine_cfg {
 /* keep the chosen child's subtree as the next search's tree; searches then go through the
  * step kernels for every evaluator */
 #define BZ_ENGINE_REUSE_SUBTREE 1u
-/* Evaluation cache (conv net evaluators; ignored with the synthetic / external / MLP evaluators and with BZ_ENGINE_REUSE_SUBTREE):
+/* Evaluation cache (conv net evaluators; ignored with the synthetic / external / MLP evaluators, with BZ_ENGINE_REUSE_SUBTREE
+ * and with more than one leaf per step, BZ_ENGINE_LEAVES_*):
  * a leaf whose position was already evaluated earlier in the SAME search -- reached by another move order -- takes that
  * node's priors and value instead of an evaluator row.  The evaluator is a function of the position alone
  * (players.py:84-98: canonical planes in, logits out), so every result (visit counts, W, P, pi, moves) is bit for
@@ -298,6 +299,16 @@ typedef struct bz_engine_cfg {
  * those without any cache.  counters[9] = the part of counters[8] that came from the previous search.  Nothing is carried
  * over a change of weights: a search that follows bz_net_update / bz_engine_set_net starts with the in-search cache only. */
 #define BZ_ENGINE_EVAL_CACHE_CARRY 4u
+/* Leaf-parallel search: bits 8..12 of flags hold K - 1, K = leaves per step per game (1..32; 0 in the
+ * field = K = 1 = the one-walk-per-step engine, unchanged).  With K > 1 every tree step runs K' = min(K, sims - done) PUCT
+ * walks per game, each leaving a virtual loss (N += 1, W -= 1) on its path for the next, and the evaluator takes up to
+ * K x n_games rows per launch.  A walk that reaches a node an earlier walk of the same step created (not expanded yet)
+ * stops there and backs up that node's value: counters[10] (n_collisions).  The evaluation cache is ignored with K > 1;
+ * the synthetic evaluators then run through the step kernels.  Bits above 12 are refused (BZ_EINVAL).
+ * Workspace with K > 1: the select paths [B][K][MAXD], a 32-byte record per leaf [B][K] (node, header, legal mask, evaluator
+ * row, depth, kind) and K x B leaf / evaluator rows (bz_engine_layout). */
+#define BZ_ENGINE_LEAVES_SHIFT 8
+#define BZ_ENGINE_LEAVES_MASK (31u << BZ_ENGINE_LEAVES_SHIFT)
 
 /* offsets (bytes, from the workspace base) of the caller-visible arrays */
 typedef struct bz_engine_layout {
@@ -308,12 +319,14 @@ typedef struct bz_engine_layout {
     int64_t ex_len;           /* i32 [rounds][B]  rows valid (-1 = game not finished) */
     int64_t ex_winner;        /* i8  [rounds][B]  absolute winner                    */
     int64_t root_N, root_W, root_P; /* u32/f32/f32 [B][NA] filled by bz_engine_root_stats */
-    int64_t leaf_own, leaf_opp;     /* u64 [B]   positions awaiting evaluation       */
-    int64_t leaf_kind;              /* u8  [B]   1 = needs (logits,value)             */
-    int64_t logits, value;          /* f32 [B][NA], f32 [B]  evaluator outputs        */
+    /* leaf rows: K x B with K leaves per step (BZ_ENGINE_LEAVES_*), row g*K + j = walk j of game g (K = 1: row g).
+     * Net / MLP evaluators read the leaves packed by slot instead; logits / value then hold the packed rows. */
+    int64_t leaf_own, leaf_opp;     /* u64 [K*B]   positions awaiting evaluation     */
+    int64_t leaf_kind;              /* u8  [K*B]   1 = needs (logits,value)           */
+    int64_t logits, value;          /* f32 [K*B][NA], f32 [K*B]  evaluator outputs    */
     int64_t g_own, g_opp;           /* u64 [B] current positions                      */
     int64_t g_to_move, g_state;     /* i8 / u8 [B]  (state: 0 active, 1 finished)     */
-    int64_t counters;               /* u64 [24] work counters: 0..8 used */
+    int64_t counters;               /* u64 [24] work counters: 0..10 used */
     int32_t na, t_max;
     /* The example arrays ex_own .. ex_winner are consecutive in the workspace and are followed by
      * a 256-byte header (ex_meta: u64 magic, game_id_base, game_id_stride, B, rounds, t_max, NA,
@@ -329,7 +342,8 @@ int32_t bz_engine_destroy(bz_engine* e);
 int32_t bz_engine_get_layout(const bz_engine* e, bz_engine_layout* out);
 int32_t bz_engine_set_net(bz_engine* e, bz_net* net);
 /* the MLP of BZ_EVAL_MLP_F32 / BZ_EVAL_MLP_BF16 (engines of BZ_GAME_TTT; those eval kinds with any other game are
- * refused with BZ_EINVAL by bz_engine_workspace_bytes / bz_engine_create).  Its max_batch must be >= n_games. */
+ * refused with BZ_EINVAL by bz_engine_workspace_bytes / bz_engine_create).  Its max_batch must be >= n_games; with K > 1
+ * leaves per step bz_engine_set_mlp (and bz_engine_set_net for a net) refuse a max_batch below K x n_games. */
 int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp);
 /* test hook: set the count of searches begun so far (0 .. 2^19 - 3) -- the evaluation cache stamps its entries with it, cycling
  * through 1 .. 2^19 - 2; a test starts just below the wrap with this.  Nothing is carried over the jump. */
@@ -344,7 +358,8 @@ int32_t bz_engine_set_roots(bz_engine* e, const uint64_t* own, const uint64_t* o
 int32_t bz_engine_search(bz_engine* e, void* stream);
 /* the search, step by step (BZ_EVAL_EXTERNAL callers fill logits/value between) */
 int32_t bz_engine_root_begin(bz_engine* e, void* stream);   /* roots -> leaf buffers       */
-/* sim_index = simulations already completed in this search (0, 1, 2, ...) */
+/* sim_index = simulations already completed in this search (0, 1, 2, ...); with K leaves per step 0, K, 2K, ...:
+ * the call starts the next min(K, sims - sim_index) walks of every active slot */
 int32_t bz_engine_select(bz_engine* e, uint32_t sim_index, void* stream); /* M2: PUCT walk + env step */
 int32_t bz_engine_evaluate(bz_engine* e, void* stream);     /* run cfg.eval_kind on leaves */
 int32_t bz_engine_expand_backup(bz_engine* e, void* stream);/* M3 + M4                     */
