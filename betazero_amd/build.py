@@ -69,11 +69,19 @@ def build(force=False, verbose=False):
     return _compile(SO, (), verbose)
 
 
+# the diagnostic options the kernel sources read; csrc/bz_common.h refuses them without -DBZ_EXPERIMENT
+VARIANT_FLAGS = ("BZ_EXP_STAMPS", "BZ_EXP_STAMPS_TAPS", "BZ_EXP_TREE_STAMPS", "BZ_EXP_TT_WEAK_HASH")
+
+
 def build_variant(name, extra_flags, force=False, verbose=False):
     """a diagnostic variant (e.g. name="stamps", extra_flags=["-DBZ_EXP_STAMPS"]) in its own file;
     load it with BZ_HIP_SO=<path> BZ_ALLOW_EXPERIMENT=1"""
     assert name and name != "so"
-    extra = ["-DBZ_EXPERIMENT"] + list(extra_flags)
+    extra_flags = list(extra_flags)
+    for f in extra_flags:  # a flag no source reads would build the product under a variant's name
+        if f.startswith("-DBZ_EXP_") and f[2:].split("=")[0] not in VARIANT_FLAGS:
+            raise ValueError(f"unknown diagnostic flag {f}: the sources read {', '.join(VARIANT_FLAGS)}")
+    extra = ["-DBZ_EXPERIMENT"] + extra_flags
     so = variant_path(name)
     if not force and not stale(so, extra):
         return so

@@ -8,6 +8,12 @@
 
 #define BZ_EXPORT extern "C" __attribute__((visibility("default")))
 
+// The diagnostic variants (in-kernel stamps, a weak TT hash for a test) are never the product library
+#if (defined(BZ_EXP_STAMPS) || defined(BZ_EXP_STAMPS_TAPS) || defined(BZ_EXP_TREE_STAMPS) || defined(BZ_EXP_TT_WEAK_HASH)) && \
+    !defined(BZ_EXPERIMENT)
+#error "BZ_EXP_* are diagnostic options: build them through betazero_amd.build.build_variant()"
+#endif
+
 namespace bz {
 void set_error(const char* fmt, ...);
 inline int32_t hip_fail(hipError_t e, const char* what) {

@@ -65,11 +65,9 @@ template <int C_, int P_ = 512 / C_, bool M16_ = false> struct Tw {
     static_assert(MW * PW * 4 == MT * P && PW >= 1, "the (M-tile, position) units must split evenly over 4 waves");
     static constexpr int NG = MT / MW;                 // wave groups along M
     static constexpr int NU = 2 * PW;                  // 32-cell units per M-tile of a wave
-#ifdef BZ_EXP_NO_ROWT  // diagnostic A/B (position-major units for every shape: no skipped MFMAs)
-    static constexpr bool ROWT = false;
-#else
-    static constexpr bool ROWT = PW == 4;              // units are board rows across the wave's four positions
-#endif
+    // units are board rows across the wave's four positions: -10.2 % per launch against position-major units at C = 128
+    // (profiles/r02_ab_tower_rowt.txt)
+    static constexpr bool ROWT = PW == 4;
     static constexpr int KS = KC < 8 ? KC : 8;         // k-steps per weight-prefetch chunk (register set)
     // activation-fragment buffers: fetched NBUF - 1 k-steps ahead (3 buffers and 3 weight sets were A/B'd on the
     // row-tile kernel: no change -- neither LDS nor L2 latency is what the K-loop waits for)
@@ -124,26 +122,6 @@ template <int C_, int P_ = 512 / C_, bool M16_ = false> struct Tw {
 };
 
 // Diagnostic build only (tools/exp_stamps.sh -> a separate libbz_hip.stamps.so, never the product .so)
-#if defined(BZ_EXP_STAMPS_TAPS) && !defined(BZ_EXP_STAMPS)
-#error "BZ_EXP_STAMPS_TAPS needs BZ_EXP_STAMPS"
-#endif
-#if defined(BZ_EXP_STAMPS) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_STAMPS is a diagnostic variant: build it through betazero_amd.build.build_variant()"
-#endif
-#if (defined(BZ_EXP_NOPS) || defined(BZ_EXP_NOP1) || defined(BZ_EXP_NO_ROWT) || defined(BZ_EXP_NO_LAYER_BARRIER) || defined(BZ_EXP_MFMA16) || defined(BZ_EXP_MFMA_AMAJOR) || defined(BZ_EXP_EPILOGUE_HALF)) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_NOPS is a diagnostic variant: build it through betazero_amd.build.build_variant()"
-#endif
-// weight-fragment loads of the bf16 tower.  Diagnostic option BZ_EXP_WEIGHTS_NT: non-temporal loads, to see whether the
-// 3.5 MB of fragments can pass through each XCD's 4-MB L2 without evicting the tree that the next tree step walks
-#ifdef BZ_EXP_WEIGHTS_NT
-#ifndef BZ_EXPERIMENT
-#error "BZ_EXP_WEIGHTS_NT is a diagnostic variant: build it through betazero_amd.build.build_variant()"
-#endif
-typedef unsigned bz_u32x4 __attribute__((ext_vector_type(4)));
-#define BZ_WLOAD(p) __builtin_nontemporal_load(reinterpret_cast<const bz_u32x4*>(p))
-#else
-#define BZ_WLOAD(p) (*(p))
-#endif
 #ifdef BZ_EXP_STAMPS
 // (one copy per translation unit; bz_debug_read in bz_net.hip reads the inference kernels' copy)
 static __device__ unsigned long long g_dbg[8 * 4096];
@@ -191,42 +169,13 @@ __device__ __forceinline__ void load_b(bf16x8 (&b)[G::NU], const char* in, const
     }
 }
 template <class G, int TAP>
-__device__ __forceinline__ void mfma_units(f32x16 (&acc)[G::MW][G::NU], const bf16x8 (&a)[G::MW], const bf16x8 (&b)[G::NU],
-                                           [[maybe_unused]] int kpar = 0) {
+__device__ __forceinline__ void mfma_units(f32x16 (&acc)[G::MW][G::NU], const bf16x8 (&a)[G::MW], const bf16x8 (&b)[G::NU]) {
     constexpr int dy = TAP / 3 - 1;
 #pragma unroll
     for (int mt = 0; mt < G::MW; ++mt)
 #pragma unroll
         for (int u = G::unit_lo(dy); u < G::unit_hi(dy); ++u)
-        {
-#ifdef BZ_EXP_MFMA16
-            // TIMING ONLY (the results are wrong): the same operand registers, LDS and weight traffic, but the matrix
-            // work of a 32x32x16 MFMA issued as TWO v_mfma_f32_16x16x32_bf16 (same MACs, 2 x 16 cycles instead of 32),
-            // accumulating into the quarters of the same 16 registers (even k-steps: quarters 0, 1; odd: 2, 3) -- what a
-            // kernel built on the 16x16x32 shape with a 32 co x (2 x 16 cells) wave tile would issue per 1-KB weight
-            // fragment.  tools/exp_ab_mfma16.sh: does the chip hold a higher clock on that shape (MI355X_MICROARCH.md,
-            // DVFS item 7)?
-            {
-                f32x16& c = acc[mt][u];
-                f32x4 q0 = kpar ? f32x4{c[8], c[9], c[10], c[11]} : f32x4{c[0], c[1], c[2], c[3]};
-                f32x4 q1 = kpar ? f32x4{c[12], c[13], c[14], c[15]} : f32x4{c[4], c[5], c[6], c[7]};
-                q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b[u], q0, 0, 0, 0);
-                q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[u], a[mt], q1, 0, 0, 0);  // (operands swapped: the compiler merges two identical products into one)
-                if (kpar) { c[8] = q0[0]; c[9] = q0[1]; c[10] = q0[2]; c[11] = q0[3]; c[12] = q1[0]; c[13] = q1[1]; c[14] = q1[2]; c[15] = q1[3]; }
-                else { c[0] = q0[0]; c[1] = q0[1]; c[2] = q0[2]; c[3] = q0[3]; c[4] = q1[0]; c[5] = q1[1]; c[6] = q1[2]; c[7] = q1[3]; }
-            }
-#else
             acc[mt][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt], b[u], acc[mt][u], 0, 0, 0);
-#endif
-#ifdef BZ_EXP_NOPS  // diagnostic duty sweep (tools/exp_duty_sweep.sh): BZ_EXP_NOPS x 8 idle issue cycles behind every MFMA
-#pragma unroll
-            for (int z = 0; z < BZ_EXP_NOPS; ++z) asm volatile("s_nop 7");
-#endif
-#ifdef BZ_EXP_NOP1  // finer steps: BZ_EXP_NOP1 x 1 idle issue cycle
-#pragma unroll
-            for (int z = 0; z < BZ_EXP_NOP1; ++z) asm volatile("s_nop 0");
-#endif
-        }
 }
 
 // One weight chunk CC = KS k-steps of up to 8 MFMAs (a whole conv tap at C <= 128, half a tap at C = 256); the tap is a
@@ -234,7 +183,8 @@ __device__ __forceinline__ void mfma_units(f32x16 (&acc)[G::MW][G::NU], const bf
 // DEPTH; the set freed by the previous chunk is filled for the chunk DEPTH - 1 ahead (coalesced 1 KB loads; the fragment
 // stream is linear over chunks, taps and layers).  Activation fragments are double-buffered: the ds_read_b128
 // of k-step k+1 are issued between the MFMAs of k-step k.  `in` points at the wave's first position; boff addresses
-// this chunk's tap and is replaced by the next chunk's on exit.
+// this chunk's tap and is replaced by the next chunk's on exit.  (Non-temporal weight loads, to keep the tree in the L2:
+// rejected, profiles/r03_ab_weights_nontemporal.txt.)
 template <class G> struct WSets { bf16x8 s[G::DEPTH][G::KS][G::MW]; };  // the weight-fragment register sets
 
 template <int S, int CC, class G>
@@ -248,7 +198,7 @@ __device__ __forceinline__ void chunk_step(f32x16 (&acc)[G::MW][G::NU], WSets<G>
 #pragma unroll
     for (int kc = 0; kc < G::KS; ++kc)
 #pragma unroll
-        for (int mt = 0; mt < G::MW; ++mt) nxt[kc][mt] = __builtin_bit_cast(bf16x8, BZ_WLOAD(&ap[(kc * G::MT + mt) * 64 + (unsigned)(32 * h + r)]));
+        for (int mt = 0; mt < G::MW; ++mt) nxt[kc][mt] = __builtin_bit_cast(bf16x8, ap[(kc * G::MT + mt) * 64 + (unsigned)(32 * h + r)]);
     ap += G::KS * G::MT * 64;
     static_assert(G::ROWT, "compile-time taps are for row-tile units");
     int boff_n[2] = {boff[0], boff[1]};
@@ -259,7 +209,7 @@ __device__ __forceinline__ void chunk_step(f32x16 (&acc)[G::MW][G::NU], WSets<G>
     for (int k = 0; k < G::KS; ++k) {
         if (k + D < G::KS) load_b<G, TAP>(B[(base + k + D) % NB], in, boff, kc0 + k + D);
         else if constexpr (!last) load_b<G, TAP_N>(B[(base + k + D) % NB], in, boff_n, kc0_n + k + D - G::KS);  // next chunk
-        mfma_units<G, TAP>(acc, use[k], B[(base + k) % NB], k & 1);
+        mfma_units<G, TAP>(acc, use[k], B[(base + k) % NB]);
     }
     constexpr int NA = G::unit_hi(TAP / 3 - 1) - G::unit_lo(TAP / 3 - 1);
 #pragma unroll
@@ -267,11 +217,7 @@ __device__ __forceinline__ void chunk_step(f32x16 (&acc)[G::MW][G::NU], WSets<G>
         if (G::MW == 1) {
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
-#ifdef BZ_EXP_MFMA16
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // the unit's 2 half-size MFMAs
-#else
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-#endif
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 DS read
             }
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // 1 VMEM read (weight prefetch)
@@ -301,7 +247,7 @@ __device__ __forceinline__ void chunk_step_pm(f32x16 (&acc)[G::MW][G::NU], WSets
 #pragma unroll
     for (int kc = 0; kc < G::KS; ++kc)
 #pragma unroll
-        for (int mt = 0; mt < G::MW; ++mt) nxt[kc][mt] = __builtin_bit_cast(bf16x8, BZ_WLOAD(&ap[(kc * G::MT + mt) * 64 + (unsigned)(32 * h + r)]));
+        for (int mt = 0; mt < G::MW; ++mt) nxt[kc][mt] = __builtin_bit_cast(bf16x8, ap[(kc * G::MT + mt) * 64 + (unsigned)(32 * h + r)]);
     ap += G::KS * G::MT * 64;
     int boff_n[2];
     tap_off_pm<G>(tap_n, r, h, boff_n);
@@ -337,7 +283,7 @@ template <int S0, int CC, class G>
 __device__ __forceinline__ void run_chunks(f32x16 (&acc)[G::MW][G::NU], WSets<G>& WS, const uint4*& ap, const char* in,
                                            int (&boff)[2], int r, int h, bf16x8 (&B)[G::NBUF][G::NU]) {
     if constexpr (CC < G::NCH) {  // the register-set index and the tap must be compile-time constants
-#ifdef BZ_EXP_STAMPS_TAPS  // per-tap cycles of workgroup 0, wave 0 (each stamp drains the LDS queue: it perturbs the layer totals)
+#ifdef BZ_EXP_STAMPS_TAPS  // (with BZ_EXP_STAMPS) per-tap cycles of workgroup 0, wave 0 (each stamp drains the LDS queue: it perturbs the layer totals)
         unsigned long long c0, c1;
         BZ_STAMP(c0);
 #endif
@@ -445,23 +391,13 @@ __device__ __forceinline__ void mfma16_quarter(f32x16& c, const bf16x8& a, const
 template <class G, int TAP, int HALF>
 __device__ __forceinline__ void mfma_units16(f32x16 (&acc)[G::MW][G::NU], const bf16x8 (&a)[2], const bf16x8 (&b)[G::NU]) {
     constexpr int dy = TAP / 3 - 1;
-#ifdef BZ_EXP_MFMA_AMAJOR
-    // diagnostic A/B (tools/exp_ab_mfma_order.sh): the same MFMAs, channel-half-major -- consecutive MFMAs then share the
-    // WEIGHT operand and change the activation operand, instead of sharing the activations and alternating the weights.
-    // Every accumulator quarter sees the same sequence of products: outputs are bit-identical.  The kernel is power-bound
-    // (1320 W at 2.0 GHz on random data against 985 W at 2.4 GHz on zero weights, profiles/r01_power_clock_rocm_smi.txt), so
-    // the question is whether one issue order costs less energy per MFMA than the other.
-#pragma unroll
-    for (int u = G::unit_lo(dy); u < G::unit_hi(dy); ++u) mfma16_quarter<HALF>(acc[0][u], a[0], b[u]);
-#pragma unroll
-    for (int u = G::unit_lo(dy); u < G::unit_hi(dy); ++u) mfma16_quarter<2 + HALF>(acc[0][u], a[1], b[u]);
-#else
+    // unit-major: consecutive MFMAs share the activation operand (1 % cheaper on this power-bound kernel than sharing the
+    // weight operand, same products: profiles/r05_ab_tower_mfma_order.txt)
 #pragma unroll
     for (int u = G::unit_lo(dy); u < G::unit_hi(dy); ++u) {
         mfma16_quarter<HALF>(acc[0][u], a[0], b[u]);      // a = 0: quarter b
         mfma16_quarter<2 + HALF>(acc[0][u], a[1], b[u]);  // a = 1: quarter 2 + b
     }
-#endif
 }
 // one conv tap: 2 KQ sub-steps; the register set freed by the previous tap is filled for the next one
 template <int S, int TAP, class G>
@@ -474,7 +410,7 @@ __device__ __forceinline__ void tap_step16(f32x16 (&acc)[G::MW][G::NU], WSets16<
 #pragma unroll
     for (int kq = 0; kq < G::KQ; ++kq)
 #pragma unroll
-        for (int a = 0; a < 2; ++a) nxt[kq][a] = __builtin_bit_cast(bf16x8, BZ_WLOAD(&ap[(kq * G::MT * 2 + a) * 64 + (unsigned)lane]));
+        for (int a = 0; a < 2; ++a) nxt[kq][a] = __builtin_bit_cast(bf16x8, ap[(kq * G::MT * 2 + a) * 64 + (unsigned)lane]);
     ap += G::KQ * G::MT * 2 * 64;
     int boff_n[G::KQ];
 #pragma unroll
@@ -518,6 +454,7 @@ __device__ __forceinline__ void load_bias16(Bias<G>& b, const float* __restrict_
     b.q[0][2] = b.q[0][3] = (f32x4)(0.0f);
 }
 // +bias (+skip) -> ReLU -> bf16 -> LDS for the 16x16 quarters.  `out` points at the wave's first position.
+// (Hiding half of it behind the MFMAs is worth 3.8 % at most: not built, profiles/r05_ab_epilogue_bound.txt.)
 template <class G>
 __device__ __forceinline__ void epilogue16(f32x16 (&acc)[G::MW][G::NU], char* out, bool second, const Bias<G>& bias, int wt,
                                            int lane) {
@@ -530,13 +467,8 @@ __device__ __forceinline__ void epilogue16(f32x16 (&acc)[G::MW][G::NU], char* ou
     for (int a = 0; a < 2; ++a) {
         const int slot = G::pos16(4 * wt + 2 * a + (g >> 1), x);
         const f32x4 bq = bias.q[0][a];
-#ifdef BZ_EXP_EPILOGUE_HALF  // TIMING ONLY (results are wrong): what hiding half of the epilogue behind MFMAs could gain at most
-        constexpr int kB0 = 1;
-#else
-        constexpr int kB0 = 0;
-#endif
 #pragma unroll
-        for (int b = kB0; b < 2; ++b)
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int par = 0; par < 2; ++par)
 #pragma unroll
@@ -630,9 +562,7 @@ __device__ __forceinline__ void conv_layer(const char* in, char* out, bool secon
     BZ_STAMP(t1);
     ep(acc, out, second, bias, G::wt0(w), r, h);
     BZ_STAMP(t2);
-#ifndef BZ_EXP_NO_LAYER_BARRIER  // TIMING ONLY (results are wrong without it): the ceiling of any scheme that relaxes the
-    __syncthreads();             // per-layer barrier (per-row ready counters, ...) -- tools/exp_ab_barrier.sh, DESIGN.md 5
-#endif
+    __syncthreads();  // relaxing this barrier is worth 0.1 % at most (profiles/r03_ab_tower_barrier.txt)
     BZ_STAMP(t3);
     tacc[0] += t1 - t0; tacc[1] += t2 - t1; tacc[2] += t3 - t2;
 }

@@ -51,17 +51,8 @@ __device__ __forceinline__ void load_tile(char* buf, const __bf16* src, int pos0
         *reinterpret_cast<uint4*>(buf + p * G::TILE + G::cell_off(p, c, k)) = s[i];
     }
 }
-#if defined(BZ_EXP_COPY_AFTER_BARRIER) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_COPY_AFTER_BARRIER is a diagnostic variant (the round-4 placement of the copy-out, for A/B): build it through betazero_amd.build.build_variant()"
-#endif
-#if defined(BZ_EXP_NO_TRAIN_STORES) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_NO_TRAIN_STORES is a diagnostic variant (timing only: the kernels then store nothing): build it through betazero_amd.build.build_variant()"
-#endif
 template <class G>
 __device__ __forceinline__ void store_tile(const char* buf, __bf16* dst, int pos0, int tid) {
-#ifdef BZ_EXP_NO_TRAIN_STORES
-    return;
-#endif
     constexpr int ZC = G::CELL / 16, N = G::P * 64 * ZC;
     uint4* d = reinterpret_cast<uint4*>(dst) + (size_t)pos0 * 64 * ZC;
 #pragma unroll 4
@@ -175,17 +166,12 @@ __device__ __forceinline__ void epilogue_train16(f32x16 (&acc)[G::MW][G::NU], ch
 // The copy-out of a layer's result (LDS tile -> HBM, what the weight gradients read) rides in the NEXT layer's epilogue on the
 // row-tile shapes: the tile is that layer's input, complete since the barrier and never written by its epilogue.  Issued
 // right behind a layer's own barrier the 16 stores per lane sit in front of the next K-loop's weight loads (vmcnt retires in
-// order); in the epilogue they have ~1.5 us without a vector-memory wait to land.  Same-box A/B (tools/exp_train_stores.sh,
-// profiles/r04_exp_train_stores.txt): -1.5 % (128 channels) .. -3.4 / -6.5 % (64 channels x 8 positions, forward / backward);
+// order); in the epilogue they have ~1.5 us without a vector-memory wait to land.  Same-box A/B
+// (profiles/r04_exp_train_stores.txt): -1.5 % (128 channels) .. -3.4 / -6.5 % (64 channels x 8 positions, forward / backward);
 // the half-tile shape measured +3 % on backward and keeps the copy behind the barrier.  The copy-out itself costs 10-20 % of
 // these kernels wherever it is issued (the same A/B against a build that stores nothing): 64 KB per workgroup and layer
 // through the CU's 64-B/clk path to L2, in step across all workgroups.
-template <class G> constexpr bool kCopyInEpilogue =
-#ifdef BZ_EXP_COPY_AFTER_BARRIER
-    false;
-#else
-    G::ROWT;
-#endif
+template <class G> constexpr bool kCopyInEpilogue = G::ROWT;
 // (Rejected, code removed: a layer's result stored to HBM from its own epilogue, straight from the registers that go to LDS --
 // no copy pass at all, but 8 bytes per lane and store, 32-byte runs per cell: 10 % slower, profiles/r04_exp_epilogue_stores.txt;
 // and the copy pass dealt to the next K-loop's sub-steps: 5 % slower, profiles/r04_exp_kloop_copy.txt.)
@@ -456,21 +442,6 @@ __device__ __forceinline__ void wg_stash(const u32x4 (&ra)[G::NLA], const u32x4 
     }
 }
 
-// diagnostic A/B: how far the k-step loop of the weight-gradient kernel is unrolled (tools/exp_wgrad_bounds.sh)
-#if (defined(BZ_EXP_WGRAD_NO_LDS_READS) || defined(BZ_EXP_WGRAD_NO_MFMA)) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_WGRAD_NO_LDS_READS / _NO_MFMA are diagnostic variants (timing only): build them through betazero_amd.build.build_variant()"
-#endif
-#if defined(BZ_EXP_WGRAD_NO_FETCH) && !defined(BZ_EXPERIMENT)
-#error "BZ_EXP_WGRAD_NO_FETCH is a diagnostic variant: build it through betazero_amd.build.build_variant()"
-#endif
-#ifdef BZ_EXP_WGRAD_UNROLL
-#ifndef BZ_EXPERIMENT
-#error "BZ_EXP_WGRAD_UNROLL is a diagnostic variant: build it through betazero_amd.build.build_variant()"
-#endif
-#define BZ_WGRAD_KK_UNROLL BZ_EXP_WGRAD_UNROLL
-#else
-#define BZ_WGRAD_KK_UNROLL 1
-#endif
 // the stages of one workgroup for the taps [T0, T1) of one wave (all waves run the same number of stages and barriers)
 template <int C, int T0, int T1>
 __device__ __forceinline__ void wgrad_wave(const WgradArgs& T, char* smem, int tid, int lane, int mt, int nt0, int l, int split, int half,
@@ -505,12 +476,10 @@ __device__ __forceinline__ void wgrad_wave(const WgradArgs& T, char* smem, int t
 #pragma unroll 1
     for (int s = s_begin; s < s_end; ++s) {
         const char* st = smem + ((s - s_begin) & 1) * G::STAGE;
-#ifndef BZ_EXP_WGRAD_NO_FETCH  // (diagnostic, timing only: every stage computes on the first stage's data -- what the kernel costs without its input stream)
         wg_fetch<G>(ra, rg, A, Gr, s + 1 < s_end ? s + 1 : s, half, tid);  // (the last stage re-reads itself: no branch around the registers)
-#endif
 #pragma unroll 1
         for (int p = 0; p < G::P2; ++p) {
-#pragma unroll BZ_WGRAD_KK_UNROLL
+#pragma unroll 1
             for (int kk = 0; kk < 4; ++kk) {  // k-step = board rows 2 kk (k half 0) and 2 kk + 1 (k half 1)
                 const int y = 2 * kk + hh;
                 bf16x8 bf[G::NTW];
@@ -522,17 +491,9 @@ __device__ __forceinline__ void wgrad_wave(const WgradArgs& T, char* smem, int t
 #pragma unroll
                 for (int t = T0; t < T1; ++t) {  // tap t = 3 (dy + 1) + (dx + 1): the activations one row / one column over
                     const int i0 = 9 * (y + t / 3) + (q + t % 3 - 1) + 1, i1 = i0 + 4;
-#ifdef BZ_EXP_WGRAD_NO_LDS_READS   // (timing only: every tap multiplies the gradient fragment with itself -- the loop without its activation reads)
-                    const bf16x8 af = bf[t & 1];
-#else
                     const bf16x8 af = tr_pair(st, G::a_off(p, i0, mt) + inner, G::a_off(p, i1, mt) + inner);
-#endif
-#ifdef BZ_EXP_WGRAD_NO_MFMA        // (timing only: the reads alone, folded into one accumulator so that they stay)
-                    acc[t - T0][0][0] += (float)af[0] + (float)af[7];
-#else
 #pragma unroll
                     for (int nt = 0; nt < G::NTW; ++nt) acc[t - T0][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf[nt], acc[t - T0][nt], 0, 0, 0);
-#endif
                 }
                 if (do_bias) {   // (behind the taps: the adds issue while the last MFMAs run, and nothing waits early for bf)
                     constexpr int JW = 8 / G::MT;

@@ -13,10 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def _resources(src, tmp_path):
+def _resources(src, tmp_path, extra=()):
     out = tmp_path / (os.path.basename(src) + ".s")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
-                           "-S", "-o", str(out), os.path.join(ROOT, "betazero_amd", "csrc", src)],
+                           "-S", *extra, "-o", str(out), os.path.join(ROOT, "betazero_amd", "csrc", src)],
                           stderr=subprocess.DEVNULL)
     res = {}
     txt = out.read_text()
@@ -108,3 +108,23 @@ def test_training_end_kernels_do_not_spill(tmp_path):
         k = _find(res, *parts)
         assert k["vspill"] == 0 and k["sspill"] == 0 and k["scratch"] == 0 and k["vgpr"] <= 512, (parts, k)
     assert _find(res, "k_train_headsILi128E")["vgpr"] <= 256
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@pytest.mark.parametrize("src, flags", [("bz_net.hip", ["-DBZ_EXP_STAMPS", "-DBZ_EXP_STAMPS_TAPS"]),
+                                        ("bz_train.hip", ["-DBZ_EXP_STAMPS", "-DBZ_EXP_STAMPS_TAPS"]),
+                                        ("bz_mcts.hip", ["-DBZ_EXP_TREE_STAMPS", "-DBZ_EXP_TT_WEAK_HASH"])])
+def test_diagnostic_variants_compile(src, flags, tmp_path):
+    """the variants build.build_variant makes (in-kernel clock stamps, the weak TT hash of a GPU test) in every source that
+    reads their flags (bz_train.hip through bz_tower.h): the product build never compiles these paths, so nothing else
+    notices when one stops compiling.  The stamps must really be there."""
+    _resources(src, tmp_path, ["-DBZ_EXPERIMENT"] + flags)
+    assert "s_memtime" in _resources.asm
+
+
+def test_build_variant_refuses_unknown_flags():
+    """a flag that no source reads (e.g. a retired A/B option) would build the product library under a variant's name"""
+    from betazero_amd import build
+    for flag in ("-DBZ_EXP_NO_ROWT", "-DBZ_EXP_NOPS=2"):
+        with pytest.raises(ValueError, match="BZ_EXP_STAMPS, BZ_EXP_STAMPS_TAPS, BZ_EXP_TREE_STAMPS, BZ_EXP_TT_WEAK_HASH"):
+            build.build_variant("retired", ["-DBZ_EXP_STAMPS", flag])

@@ -28,7 +28,7 @@ clk = d[:, 4] / d[:, 5] * 100e6
 print("in-kernel clock GHz: mean %.3f min %.3f max %.3f" % (clk.mean() / 1e9, clk.min() / 1e9, clk.max() / 1e9))
 # MFMA floor of the K-loop: 9 taps x 8 k-steps x 8 units x 32 cycles; the row-tile units skip one unit in 6 of the 9 taps
 # (fp8: 2 k-steps of K = 64 per tap, 64 cycles per MFMA; two workgroups per CU share each SIMD)
-units = 72 if os.environ.get("NO_ROWT") == "1" else 6 * 7 + 3 * 8
+units = 6 * 7 + 3 * 8
 floor = units * 2 * 64 if FP8 else units * 8 * 32
 print("per layer: kloop %.0f (MFMA floor %d)  epilogue %.0f  barrier %.0f" % (d[:, 0].mean() / 12, floor, d[:, 1].mean() / 12, d[:, 2].mean() / 12))
 t0 = d[:, 7]; print("WG start spread (us): ", np.percentile((t0 - t0.min()) / 100, [0, 25, 50, 75, 100]))
