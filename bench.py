@@ -6,9 +6,13 @@ Default workload = BASELINE config 3: Reversi 8x8, 4096 concurrent games per GPU
 (MFMA), tau=1 for moves < 8 + 12 fixed two-ply openings.  `--workload ttt` runs
 BASELINE config 2 (65,536 TTT games, 50 sims, uniform priors, tree kernels only),
 `--workload net` config 5 (net forward only, batch 8192, fp8), `--workload env` the
-batched board-env step kernel alone.  The default run also measures configs 2 and 5
-and the env step briefly after the headline measurement and attaches them as
-`secondary` (driver-timed evidence for their rooflines; not part of `value`).
+batched board-env step kernel alone.
+
+A plain run does only what its headline needs: set-up, warm-up, the timed steps,
+`--dump-outputs` and the JSON line.  `--full` adds everything else, after the
+headline measurement: configs 2 and 5, the env step, the training step and the
+headline workload's variants, attached as `secondary` (driver-timed evidence for
+their rooflines; not part of `value`), and the CPU baselines (`cpu_baseline`).
 
 A "step" (reversi) = one move for every concurrent game: root expansion + 800 x
 (select -> net -> expand/backup) + move choice / example row / env step.  The
@@ -934,8 +938,11 @@ def main():
                          "env = the batched board-env step kernel alone, train = the training step of the benchmark net")
     ap.add_argument("--games", type=int, default=None, help="concurrent games per GPU (default: BASELINE config)")
     ap.add_argument("--sims", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg-2 / cfg-5 runs after the headline one")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the secondary runs and the CPU baselines (off by default: "
+                         "a plain run sets up, warms up, times the steps, dumps its outputs if asked and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary runs after the headline one")
     ap.add_argument("--no-kernel-timers", action="store_true",
                     help="leave the in-library HIP-event timers off (A/B of their cost on `value`)")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp8"],
@@ -1051,7 +1058,7 @@ def main():
         sims = args.sims or 50
         out = run_ttt(ctx, args.games or 65536, sims, args.steps if args.steps is not None else 20,
                       args.warmup if args.warmup is not None else 2, args.ttt_lanes, args.dump_outputs)
-        if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+        if ctx.rank == 0 and ctx.world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_ttt(sims)
     else:
         sims = args.sims or 800
@@ -1063,7 +1070,7 @@ def main():
                           args.warmup if args.warmup is not None else 1, args.dump_outputs)
         if out is not None:
             out["scaling"] = args.scaling
-        if ctx.rank == 0 and ctx.world == 1:
+        if ctx.rank == 0 and ctx.world == 1 and args.full:
             if not args.no_secondary:  # cfg 2 and cfg 5 in the same driver-timed process (a few seconds)
                 sec = {}
                 a_fp8 = argparse.Namespace(**{**vars(args), "precision": "fp8", "mode": "steady"})

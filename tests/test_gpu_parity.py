@@ -2030,6 +2030,26 @@ def test_bench_two_ranks_end_to_end_on_one_gpu_gloo():
         assert r2.returncode != 0 and "GPU(s) visible" in (r2.stderr + r2.stdout)
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """a plain `python bench.py` run prints its headline line and runs nothing else: the secondary runs and the CPU
+    baselines belong to `--full`"""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BZ_DIST_BACKEND", "BZ_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--games", "256", "--sims", "32", "--steps", "4",
+           "--warmup", "1"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "selfplay_games_per_s" and out["value"] > 0 and (out["steps"], out["warmup"]) == (4, 1)
+    assert "secondary" not in out and "cpu_baseline" not in out
+    assert "secondary" not in r.stderr and "cpu baseline" not in r.stderr   # (bench.note: one progress line per leg)
+
+
 @pytest.mark.parametrize("launcher", ["torchrun", "self"])
 def test_bench_multi_gpu_branch_runs_under_rccl_at_world_size_1(launcher):
     """bench.py's N > 1 branch on the REAL backend ("nccl" = RCCL), as far as one GPU allows: `--force-collective` makes a
