@@ -124,6 +124,10 @@ _SIGS = {
     "bz_engine_root_noise": (i32, [vp, vp]),
     "bz_engine_root_stats": (i32, [vp, vp]),
     "bz_engine_play": (i32, [vp, i32, vp]),
+    "bz_engine_gumbel_bytes": (i64, [C.POINTER(EngineCfg), i32]),
+    "bz_engine_set_gumbel": (i32, [vp, i32, C.c_float, C.c_float, C.c_float, vp, i64, vp]),
+    "bz_gumbel_considered_visits": (i32, [i32, i32, vp]),
+    "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),
     "bz_mcts_expand_backup": (i32, [vp, vp]),

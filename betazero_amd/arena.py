@@ -36,14 +36,17 @@ class ArenaResult:
 
 
 def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=None, c_puct=1.5, seed=0, size=8,
-               device="cuda:0", max_plies=200, opening_plies=0, leaves_per_step=1):
+               device="cuda:0", max_plies=200, opening_plies=0, leaves_per_step=1, gumbel=None):
     """MCTS (`sims` simulations, `evaluator`) vs minimax for n_games concurrent games; the MCTS side plays X
     (moves first) in the even-numbered games and O in the odd ones.  game: "ttt" | "reversi" (size 8, 6 or 4).
     Both players are deterministic, so without help there are only two distinct games (one per colour):
     `opening_plies` > 0 plays that many uniformly random legal moves (seeded) before the players take over, which
-    makes the B games B different tests.  leaves_per_step: K walks per tree step of the MCTS side."""
-    from .engine import check_leaves_per_step
+    makes the B games B different tests.  leaves_per_step: K walks per tree step of the MCTS side.
+    gumbel (True or an engine.GumbelConfig): the MCTS side searches with Gumbel root search and plays its move
+    (SelfPlayEngine.root_policy; no Gumbel noise), DESIGN.md 3.13."""
+    from .engine import check_gumbel, check_leaves_per_step
     check_leaves_per_step(leaves_per_step)
+    gumbel = check_gumbel(gumbel, leaves_per_step=leaves_per_step)
     if game != "ttt" and not 0 <= int(opponent_depth) <= 8:
         raise ValueError(f"play_arena: opponent_depth must be in 0..8 (got {opponent_depth}): the minimax kernel keeps an "
                          "explicit stack of that depth")
@@ -53,7 +56,7 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     ttt = game == "ttt"
     B = n_games
     ename = "ttt" if ttt else {8: "reversi", 6: "reversi6", 4: "reversi4"}[size]
-    eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device, leaves_per_step=leaves_per_step)
+    eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel)
     rng = np.random.default_rng(seed)
     st = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
     if ttt:
@@ -108,9 +111,12 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
             with torch.cuda.device(dev):
                 _lib.check(L.bz_engine_set_roots(eng.h, o64.data_ptr(), p64.data_ptr(), roots_tm.data_ptr(), st()))
             eng.search()
-            eng._call(L.bz_engine_root_stats)
-            N = eng._view(eng.lay.root_N, torch.int32, (B, eng.na))
-            pick = N.argmax(1).to(torch.uint8)  # first maximum = lowest action (MCTSPlayer's rule)
+            if gumbel is not None:  # the Gumbel move (idle slots: -1, masked out below)
+                pick = eng.root_policy_dev()[1].to(torch.uint8)
+            else:
+                eng._call(L.bz_engine_root_stats)
+                N = eng._view(eng.lay.root_N, torch.int32, (B, eng.na))
+                pick = N.argmax(1).to(torch.uint8)  # first maximum = lowest action (MCTSPlayer's rule)
             eng.status()
             action = torch.where(mcts_turn, pick, action)
         if bool(mm_turn.any()):

@@ -125,6 +125,14 @@ struct EngineDev {
     int ecache, tt_buckets; u64* tt; float *node_v, *node_v_alt;
 };
 
+// Gumbel root search (m = 0: off), set by bz_engine_set_gumbel in the caller's buffer: the considered-visit
+// table T [m][sims] (row n_c - 1), every root edge's base = g + logf(P~) [B][MAXCH] and the root's value v_root [B].  A kernel
+// argument of the Gumbel kernels only: EngineDev, and with it every other kernel's code, stays what it is.
+struct GumbelDev {
+    int m; float scale, mvi, vs;
+    const uint16_t* T; float *base, *vroot;
+};
+
 struct Cnt { u32 v[CNT_N]; };
 
 // Diagnostic build only (betazero_amd.build.build_variant("treestamps", ["-DBZ_EXP_TREE_STAMPS"]), tools/exp_tree_stamps.py):
@@ -410,12 +418,86 @@ __device__ __forceinline__ bool tt_lookup_insert(const EngineDev& E, int g, int 
     return found;
 }
 
+// ---- Gumbel root search.  Every expression is one binary32 operation in the written order; sums run
+// over the root's edges in ascending order.  These helpers are serial loops over the root's <= 34 edges: in the tree step
+// every lane of the game's group runs the same loop on the same (broadcast) loads, so all lanes agree without exchanges.
+constexpr float kFltMin = 1.17549435e-38f;  // 2^-126
+__device__ __forceinline__ float gumbel_pfloor(float P) { return P > kFltMin ? P : kFltMin; }
+// what sigma(completed Q) needs from the root's current statistics: cq_i = N_i > 0 ? W_i / N_i : vmix,
+// sigma_i = s * ((cq_i - lo) / d)
+struct GumbelStats { float vmix, lo, d, s; u32 nmax; };
+__device__ __forceinline__ float gumbel_cq(const Edge& e, float vmix) {
+    const u32 N = e_N(e.w0);
+    return N > 0 ? fdiv(e.W, (float)N) : vmix;
+}
+__device__ __forceinline__ float gumbel_sigma(const GumbelStats& st, float cq) { return st.s * fdiv(cq - st.lo, st.d); }
+__device__ __forceinline__ GumbelStats gumbel_stats(const GumbelDev& Gm, const Edge* ed, int n, float v_root) {
+    u32 S = 0, nmax = 0;
+    float sp = 0.0f, spq = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const Edge e = ed[i];
+        const u32 N = e_N(e.w0);
+        S += N;
+        nmax = N > nmax ? N : nmax;
+        if (N > 0) {
+            const float q = fdiv(e.W, (float)N), pf = gumbel_pfloor(e.P);
+            sp = sp + pf;
+            const float t = pf * q;
+            spq = spq + t;
+        }
+    }
+    const float wq = sp > 0.0f ? fdiv(spq, sp) : 0.0f;
+    GumbelStats st;
+    if (S == 0) {
+        st.vmix = v_root;
+    } else {
+        const float t = (float)S * wq;
+        const float a = v_root + t;
+        const float b = (float)S + 1.0f;
+        st.vmix = fdiv(a, b);
+    }
+    float lo = 0.0f, hi = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const float cq = gumbel_cq(ed[i], st.vmix);
+        lo = (i == 0 || cq < lo) ? cq : lo;
+        hi = (i == 0 || cq > hi) ? cq : hi;
+    }
+    float d = hi - lo;
+    st.d = d < 1e-8f ? 1e-8f : d;
+    st.lo = lo;
+    float s = Gm.mvi + (float)nmax;
+    st.s = s * Gm.vs;
+    st.nmax = nmax;
+    return st;
+}
+// the root edge a walk takes at the root's visit sum k: among the edges with N == T[n_c][k], the first maximum of base + sigma
+// (one exists by construction of T; edge 0 stands in if the statistics were ever not those of this search)
+template <class G>
+__device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const GumbelDev& Gm, int g, const Edge* ed, int n, u32 k) {
+    if (n <= 0) return 0;  // (a root without edges: nothing to choose, as in the PUCT loop)
+    const int nc = n < Gm.m ? n : Gm.m;
+    const u32 kk = k < (u32)E.sims ? k : (u32)E.sims - 1u;
+    const u32 cv = Gm.T[(size_t)(nc - 1) * E.sims + kk];
+    const GumbelStats st = gumbel_stats(Gm, ed, n, Gm.vroot[g]);
+    const float* base = Gm.base + (size_t)g * G::MAXCH;
+    int best = -1;
+    float bests = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const Edge e = ed[i];
+        if (e_N(e.w0) != cv) continue;
+        const float sc = base[i] + gumbel_sigma(st, gumbel_cq(e, st.vmix));
+        if (best < 0 || sc > bests) { best = i; bests = sc; }
+    }
+    return best < 0 ? 0 : best;
+}
+
 // M2: PUCT walk from the root; creates the child node behind the chosen unexpanded edge (env step:
 // apply + legal + terminal).  All lanes of the group return the same values.
-template <class G, class Sink, bool kLeafPar = false>
+// kGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead; every deeper level is PUCT.
+template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
-                                           Sink& sink, LeafPos& lp, Stamps& st) {
+                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr) {
     constexpr int kGW = G::GW;
     Node* nodes = E.nodes + (size_t)g * E.ncap;
     Edge* edges = E.edges + (size_t)g * E.ecap;
@@ -429,6 +511,11 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
         const float sq = fsqrt((float)(sumN > 1u ? sumN : 1u));
         const Edge* ed = edges + e0;
         float bests = -__builtin_inff(), bestW = 0.0f; int best = 0; u32 bestw0 = 0, bestw3 = 0;
+        if (kGumbel && depth == 0) {  // (the root's edges start at index 0; sumN = the root's visit sum = sim_index)
+            best = gumbel_root_pick<G>(E, *gm, g, ed, n, sumN);
+            const Edge e = ed[best];
+            bestw0 = e.w0; bestw3 = e.w3; bestW = e.W;
+        } else
         for (int base = 0; base < n; base += kGW) {
             Cand cd; cd.i = base + sub; cd.sc = -__builtin_inff(); cd.W = 0.0f; cd.w0 = 0; cd.w3 = 0;
             if (cd.i < n) {
@@ -860,8 +947,10 @@ __global__ void __launch_bounds__(256) k_eval_synth(EngineDev E, int eval_kind) 
 // that consume them, so they go out back to back and complete in ONE memory round trip
 template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" : "+v"(x)); }
 
-template <class G>
-__global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
+// The body of k_tree_step and of k_gumbel_step (kGumbel: the Gumbel root rule at depth 0 of the walk and v_root stored
+// with the root's expansion); with kGumbel = false it is k_tree_step's code exactly.
+template <class G, bool kGumbel>
+__device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -905,13 +994,17 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
                 if (sub == 0) {
                     E.hot[g].n_edges = ne; c.v[CNT_NET_LEAVES]++; if (leaf == 0) E.hot[g].root_n = (u32)n;
                     if (E.ecache) E.node_v[(size_t)g * E.ncap + leaf] = v;  // what a later repeat of this position copies
+                    if (kGumbel && leaf == 0) Gm.vroot[g] = v;
                 }
                 if (leaf == 0) { root_n = n; pre_ok = false; }  // the root's edges did not exist when re0 was fetched
             } else if (kind == LEAF_COPY) {  // ---- round trip 2: the first evaluation's edges and value (evaluation cache)
                 const bool from_prev = (hot.copy_src & kSrcPrev) != 0u;
                 v = (from_prev ? E.node_v_alt : E.node_v)[(size_t)g * E.ncap + (hot.copy_src & ~kSrcPrev)];
                 n = dev_expand_copy<G>(E, g, sub, leaf, nlegal, ninfo, hot.copy_e0, from_prev, ne, c);
-                if (sub == 0) { E.hot[g].n_edges = ne; E.node_v[(size_t)g * E.ncap + leaf] = v; }
+                if (sub == 0) {
+                    E.hot[g].n_edges = ne; E.node_v[(size_t)g * E.ncap + leaf] = v;
+                    if (kGumbel && leaf == 0) Gm.vroot[g] = v;
+                }
             } else {
                 v = (float)((int)((ninfo >> 9) & 3u) - 1);
             }
@@ -941,7 +1034,7 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
                 RootRef root; root.own = rown; root.opp = ropp; root.tm = rtm; root.n = root_n;
                 root.sumN = sim_idx + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
                 PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
-                dev_select<G>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st);  // ---- one round trip per level
+                dev_select<G, PathHbm<kGW>, false, kGumbel>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm);  // ---- one round trip per level
                 sink.flush(sub, depth);
                 if (sub == 0) {
                     E.hot[g].n_nodes = nn; E.hot[g].leaf_node = leaf2; E.hot[g].depth = (u32)depth;
@@ -976,6 +1069,19 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
     cnt_flush<G::GW>(E, c);
     st.mark(6);
     st.flush(E.counters);
+}
+
+template <class G>
+__global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false>(E, none, do_expand, do_select, sim_idx);
+}
+
+// The tree step of a Gumbel search: k_tree_step with the Gumbel root rule.  The root's statistics are read
+// afresh after this step's backup (the group fence before the walk) by a serial loop over its edges.
+template <class G>
+__global__ void __launch_bounds__(256) k_gumbel_step(EngineDev E, GumbelDev Gm, int do_expand, int do_select, u32 sim_idx) {
+    tree_step_body<G, true>(E, Gm, do_expand, do_select, sim_idx);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -1395,22 +1501,12 @@ __global__ void __launch_bounds__(256) k_root_stats(EngineDev E) {
     }
 }
 
-// M5 + the reference's turn loop: pi, move choice, example row, env step,
-// pass rule (reversi_terminal.py:31-35), terminal handling, z back-fill.
+// M5's move choice, shared by k_play and k_root_policy: pi = N / sum N at the edges' actions (0 elsewhere)
+// and the index of the played edge -- tau = 1 (made < temp_moves): sampled ~ N with the counter RNG (seed, game id, moves
+// made), else the first maximum of N
 template <class G>
-__global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.g_state[g] != 0) return;
-    Node root = E.nodes[(size_t)g * E.ncap];
-    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
-    int n = (int)(root.info & 0xFFu);
-    u32 sumN = 0;
-    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
-    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
-    if (nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
-    size_t row = rowbase + nex;
-    float* pi = E.ex_pi + row * G::NA;
+__device__ __forceinline__ int dev_puct_choice(const EngineDev& E, int g, const Edge* ed, int n, u32 sumN, int made, int round,
+                                               float* pi) {
     for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
     int pick = 0;
     if (made < E.temp_moves) {  // tau = 1: sample ~ N with the counter RNG (seed, game id, moves made)
@@ -1431,6 +1527,49 @@ __global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) {
             if (N > bn) { bn = N; pick = i; }
         }
     }
+    return pick;
+}
+
+// The Gumbel move choice, shared by k_gumbel_play and k_root_policy: pi = softmax(logf(P~) + sigma) at the
+// edges' actions (0 elsewhere; the softmax sequence of DESIGN.md 3.5) and the index of the played edge, the first maximum of
+// base + sigma among the edges with N = max N
+template <class G>
+__device__ __forceinline__ int dev_gumbel_choice(const GumbelDev& Gm, int g, const Edge* ed, int n, float* pi) {
+    for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
+    const GumbelStats st = gumbel_stats(Gm, ed, n, Gm.vroot[g]);
+    const float* base = Gm.base + (size_t)g * G::MAXCH;
+    int pick = -1;
+    float bests = 0.0f, m = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const Edge e = ed[i];
+        const float sg = gumbel_sigma(st, gumbel_cq(e, st.vmix));
+        const float x = logf_spec(gumbel_pfloor(e.P)) + sg;
+        m = (i == 0 || x > m) ? x : m;
+        if (e_N(e.w0) == st.nmax) {
+            const float sc = base[i] + sg;
+            if (pick < 0 || sc > bests) { pick = i; bests = sc; }
+        }
+        pi[e_action(e.w0)] = x;  // (the logit for now: exponentiated below)
+    }
+    float s = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        float* p = pi + e_action(ed[i].w0);
+        const float ex = expf_spec(*p - m);
+        *p = ex;
+        s = s + ex;
+    }
+    for (int i = 0; i < n; ++i) {
+        float* p = pi + e_action(ed[i].w0);
+        *p = fdiv(*p, s);
+    }
+    return pick < 0 ? 0 : pick;
+}
+
+// M5's rest after the choice of root edge `pick`: example row, env step, pass rule (reversi_terminal.py:31-35), terminal
+// handling, z back-fill (k_play and k_gumbel_play)
+template <class G>
+__device__ __forceinline__ void dev_play_tail(const EngineDev& E, int g, const Node& root, const Edge* ed, int pick, int round,
+                                              int nex, int made, int tm, size_t rowbase, size_t row, int restart) {
     const Edge pk = ed[pick];
     int a = e_action(pk.w0);
     u32 keep_node = e_child(pk.w3), keep_N = e_N(pk.w0);  // subtree reuse: the chosen child and its visits
@@ -1464,6 +1603,92 @@ __global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) {
         E.hot[g].root_base = ok ? keep_N - 1u : 0u;
     }
     E.g_own[g] = own; E.g_opp[g] = opp; E.g_to_move[g] = (int8_t)tm; E.g_moves[g] = made; E.g_nex[g] = nex;
+}
+
+// M5 + the reference's turn loop: pi, move choice, example row, env step,
+// pass rule (reversi_terminal.py:31-35), terminal handling, z back-fill.
+template <class G>
+__global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    int n = (int)(root.info & 0xFFu);
+    u32 sumN = 0;
+    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
+    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
+    if (nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
+    size_t row = rowbase + nex;
+    const int pick = dev_puct_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA);
+    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart);
+}
+
+// M5 of a Gumbel search: the improved policy as pi, the Gumbel move, then k_play's tail
+template <class G>
+__global__ void __launch_bounds__(256) k_gumbel_play(EngineDev E, GumbelDev Gm, int restart) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    int n = (int)(root.info & 0xFFu);
+    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
+    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
+    if (nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
+    size_t row = rowbase + nex;
+    const int pick = dev_gumbel_choice<G>(Gm, g, ed, n, E.ex_pi + row * G::NA);
+    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart);
+}
+
+// the pi and the action bz_engine_play would write and play, into pi [B][NA] / action [B] (idle or finished slots: zeros, -1)
+template <class G>
+__global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, float* pi_out, int32_t* act_out) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    float* pi = pi_out + (size_t)g * G::NA;
+    const Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    const int n = (int)(root.info & 0xFFu);
+    if (E.g_state[g] != 0 || n == 0) {  // (n == 0: no search has expanded this slot's root)
+        for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
+        act_out[g] = -1;
+        return;
+    }
+    int pick;
+    if (Gm.m > 0) {
+        pick = dev_gumbel_choice<G>(Gm, g, ed, n, pi);
+    } else {
+        u32 sumN = 0;
+        for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+        pick = dev_puct_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+    }
+    act_out[g] = e_action(ed[pick].w0);
+}
+
+// Gumbel preparation of every active game's freshly expanded root, in the style of k_root_noise:
+// base_i = g_i + logf(P~_i), g_i = scale * -log(-log u) while moves made < temp_moves (and scale > 0), else 0
+template <class G>
+__global__ void __launch_bounds__(256) k_gumbel_root(EngineDev E, GumbelDev Gm) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    const int n = (int)(r.info & 0xFFu);
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    float* base = Gm.base + (size_t)g * G::MAXCH;
+    const bool noise = E.g_moves[g] < E.temp_moves && Gm.scale > 0.0f;
+    const u64 gid = E.id_base + (u64)E.g_round[g] * E.id_stride + (u64)g, ply = (u64)E.g_moves[g];
+    for (int i = 0; i < n && i < G::MAXCH; ++i) {
+        const float lp = logf_spec(gumbel_pfloor(ed[i].P));
+        float gn = 0.0f;
+        if (noise) {
+            const float u = u01_spec(rng_noise(E.seed ^ 0x6A09E667F3BCC908ULL, gid, ply, (u64)i));
+            float y = logf_spec(u);
+            y = -y;
+            y = logf_spec(y);
+            gn = Gm.scale * (-y);
+        }
+        base[i] = gn + lp;
+    }
 }
 
 __global__ void __launch_bounds__(256) k_count_active(EngineDev E) {
@@ -1571,6 +1796,7 @@ struct bz_engine {
     // stream (created on first use)
     hipEvent_t ahead[4];
     int n_ahead;
+    GumbelDev gumbel;  // Gumbel root search (bz_engine_set_gumbel); gumbel.m = 0: off
 };
 
 namespace {
@@ -1704,6 +1930,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     bz_engine* e = new (std::nothrow) bz_engine();
     if (!e) { set_error("out of host memory"); return BZ_ENOMEM; }
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
+    e->gumbel = GumbelDev{};  // off
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -1852,7 +2079,8 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
         if (do_select) e->pack_parity = (int)((sim_idx / (uint32_t)e->dev.K) & 1u);
         return BZ_OK;
     }
-    BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
+    if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
+    else BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
     if (do_select) e->pack_parity = (int)(sim_idx & 1u);
     return BZ_OK;
 }
@@ -1893,10 +2121,12 @@ BZ_EXPORT int32_t bz_engine_expand_backup(bz_engine* e, void* stream) {
     return tree_step(e, 1, 0, 0, stream);
 }
 
-/* Dirichlet noise on the priors of every active slot's (expanded) root; a no-op when cfg.dirichlet_eps == 0.
+/* Dirichlet noise on the priors of every active slot's (expanded) root -- a no-op when cfg.dirichlet_eps == 0 -- and, with
+ * Gumbel root search on (bz_engine_set_gumbel), the search's Gumbel preparation of the expanded roots (k_gumbel_root).
  * Step-API order: root_begin, evaluate, expand_backup, root_noise, then select(0) ... -- what bz_engine_search does. */
 BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_root, stream, e->dev, e->gumbel);
     if (!(e->dev.dir_eps > 0.0f)) return BZ_OK;
     hipLaunchKernelGGL(k_root_noise, dim3((e->dev.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->dev);
     BZ_LAUNCH_CHECK("k_root_noise");
@@ -1906,7 +2136,8 @@ BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
 BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     int ek = e->cfg.eval_kind;
-    const bool noise = e->dev.dir_eps > 0.0f;
+    // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
+    const bool noise = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
     if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
@@ -1951,11 +2182,109 @@ BZ_EXPORT int32_t bz_engine_root_stats(bz_engine* e, void* stream) {
     return BZ_OK;
 }
 
+/* ---- Gumbel root search */
+BZ_EXPORT int32_t bz_gumbel_considered_visits(int32_t n_considered, int32_t sims, uint16_t* out) {
+    BZ_REQUIRE(out, "bz_gumbel_considered_visits: null pointer");
+    BZ_REQUIRE(n_considered >= 1 && n_considered <= BZ_GUMBEL_MAX_CONSIDERED && sims >= 1 && sims <= BZ_ENGINE_MAX_SIMS,
+               "bz_gumbel_considered_visits: n_considered must be in 1..64 and sims in 1..8189");
+    if (n_considered <= 1) {
+        for (int k = 0; k < sims; ++k) out[k] = (uint16_t)k;
+        return BZ_OK;
+    }
+    // mctx's get_sequence_of_considered_visits: rounds of sequential halving, each giving every considered action
+    // max(1, sims / (log2max * considered)) more visits, the considered count halving down to 2
+    int log2max = 0;
+    while ((1 << log2max) < n_considered) ++log2max;  // ceil(log2(n_considered))
+    int visits[BZ_GUMBEL_MAX_CONSIDERED] = {0};
+    int len = 0, nc = n_considered;
+    while (len < sims) {
+        const int q = sims / (log2max * nc), extra = q > 1 ? q : 1;
+        for (int r = 0; r < extra; ++r) {
+            for (int i = 0; i < nc; ++i) {
+                if (len < sims) out[len] = (uint16_t)visits[i];
+                ++len;
+            }
+            for (int i = 0; i < nc; ++i) visits[i]++;
+        }
+        nc = nc / 2 > 2 ? nc / 2 : 2;
+    }
+    return BZ_OK;
+}
+
+namespace {
+struct GumbelOffsets { int64_t T, base, vroot, total; };
+GumbelOffsets gumbel_carve(const bz_engine_cfg& c, int m) {
+    GumbelOffsets o{};
+    Carver k;
+    const int64_t B = c.n_games, maxch = c.game == BZ_GAME_TTT ? TicTacToe::MAXCH : Reversi::MAXCH;
+    o.T = k.take((int64_t)m * c.sims * 2);
+    o.base = k.take(B * maxch * 4);
+    o.vroot = k.take(B * 4);
+    o.total = k.off;
+    return o;
+}
+// the combinations Gumbel root search refuses (nullptr: none)
+const char* gumbel_refusal(const bz_engine_cfg& c) {
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "Gumbel root search does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "Gumbel root search does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
+    if (c.dirichlet_eps > 0.0f) return "Gumbel root search does not combine with Dirichlet noise (dirichlet_eps > 0)";
+    return nullptr;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_gumbel_bytes(const bz_engine_cfg* cfg, int32_t max_considered) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_gumbel_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_gumbel_bytes: %s", kBadCfg); return -1; }
+    if (max_considered < 1 || max_considered > BZ_GUMBEL_MAX_CONSIDERED) {
+        set_error("bz_engine_gumbel_bytes: max_considered must be in 1..64 (got %d)", (int)max_considered);
+        return -1;
+    }
+    if (const char* why = gumbel_refusal(*cfg)) { set_error("bz_engine_gumbel_bytes: %s", why); return -1; }
+    return gumbel_carve(*cfg, max_considered).total;
+}
+
+BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, float gumbel_scale, float maxvisit_init,
+                                       float value_scale, void* buf, int64_t buf_bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_gumbel: null engine");
+    if (max_considered == 0) {  // off: the next search is a PUCT search again
+        e->gumbel.m = 0;
+        return BZ_OK;
+    }
+    BZ_REQUIRE(max_considered >= 1 && max_considered <= BZ_GUMBEL_MAX_CONSIDERED, "bz_engine_set_gumbel: max_considered must be in 0..64");
+    const bool finite = __builtin_isfinite(gumbel_scale) && __builtin_isfinite(maxvisit_init) && __builtin_isfinite(value_scale);
+    BZ_REQUIRE(finite && gumbel_scale >= 0.0f && maxvisit_init >= 0.0f && value_scale >= 0.0f,
+               "bz_engine_set_gumbel: gumbel_scale, maxvisit_init and value_scale must be finite and >= 0");
+    if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
+    const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
+    if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
+    // T [m][sims]: setup, not the hot path -- built on the host and uploaded once
+    const int sims = e->cfg.sims;
+    uint16_t* T = new (std::nothrow) uint16_t[(size_t)max_considered * sims];
+    if (!T) { set_error("out of host memory"); return BZ_ENOMEM; }
+    for (int nc = 1; nc <= max_considered; ++nc) (void)bz_gumbel_considered_visits(nc, sims, T + (size_t)(nc - 1) * sims);
+    hipError_t he = hipMemcpyAsync(at<char>(buf, o.T), T, (size_t)max_considered * sims * 2, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
+    delete[] T;
+    if (he != hipSuccess) return hip_fail(he, "bz_engine_set_gumbel: upload of the considered-visit table");
+    GumbelDev& gd = e->gumbel;
+    gd.m = max_considered; gd.scale = gumbel_scale; gd.mvi = maxvisit_init; gd.vs = value_scale;
+    gd.T = at<uint16_t>(buf, o.T); gd.base = at<float>(buf, o.base); gd.vroot = at<float>(buf, o.vroot);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
+    BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
+    BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, pi, action);
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     BZ_REQUIRE(e, "null engine");
     {
         ProfScope ps(BZ_PROF_PLAY, stream);
-        BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
+        if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
+        else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
     if (e->dev.reuse) {  // the tree just searched becomes the source of the next root_begin's subtree copy
         Node* tn = e->dev.nodes; e->dev.nodes = e->dev.nodes_alt; e->dev.nodes_alt = tn;
@@ -2061,10 +2390,12 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
         BZ_REQUIRE(engines[i], "bz_engines_step: null engine");
         BZ_REQUIRE(engines[i]->cfg.sims == engines[0]->cfg.sims, "bz_engines_step: the engines must search the same number of simulations");
         BZ_REQUIRE(engines[i]->dev.K == engines[0]->dev.K, "bz_engines_step: the engines must take the same leaves per step");
+        BZ_REQUIRE((engines[i]->gumbel.m > 0) == (engines[0]->gumbel.m > 0),
+                   "bz_engines_step: the engines must all search with Gumbel root search or all without");
         const int ek = engines[i]->cfg.eval_kind;
         BZ_REQUIRE(ek != BZ_EVAL_EXTERNAL, "bz_engines_step: BZ_EVAL_EXTERNAL callers drive the step API");
         if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !engines[i]->dev.reuse && !(engines[i]->dev.dir_eps > 0.0f) &&
-            engines[i]->dev.K == 1) stepwise = false;
+            engines[i]->dev.K == 1 && engines[i]->gumbel.m == 0) stepwise = false;
     }
     int32_t rc;
     if (!stepwise) {  // a fused search is one launch per engine: nothing to interleave
@@ -2076,7 +2407,7 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
         bz_engine* e = engines[i];
         if ((rc = bz_engine_root_begin(e, streams[i])) != BZ_OK) return rc;
         if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
-        if (e->dev.dir_eps > 0.0f) {
+        if (e->dev.dir_eps > 0.0f || e->gumbel.m > 0) {
             if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_root_noise(e, streams[i])) != BZ_OK) return rc;
         }
@@ -2088,7 +2419,8 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
     for (int s = 0, step = 0; s < sims; s += K, ++step) {
         for (int i = 0; i < n; ++i) {
             bz_engine* e = engines[i];
-            if ((rc = tree_step(e, (e->dev.dir_eps > 0.0f && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
+            const bool prep = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
+            if ((rc = tree_step(e, (prep && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
         }
         if (q && (step + 1) % q == 0)

@@ -124,11 +124,49 @@ def check_leaves_per_step(leaves_per_step):
     return int(k)
 
 
+MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
+
+
+@dataclass(frozen=True)
+class GumbelConfig:
+    """Gumbel root search (Danihelka et al., ICLR 2022).  The defaults are those of mctx's
+    gumbel_muzero_policy: max_considered root actions (1..64) for the sequential halving, the Gumbel noise scale (0: no
+    noise), and sigma's maxvisit_init / value_scale."""
+    max_considered: int = 16
+    scale: float = 1.0
+    maxvisit_init: float = 50.0
+    value_scale: float = 0.1
+
+
+def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0.0):
+    """None / False: off (None returned); True: GumbelConfig(); or a GumbelConfig -- validated, and refused with subtree
+    reuse, leaves_per_step > 1 and Dirichlet noise (ValueError, before any device is touched)"""
+    if gumbel is None or gumbel is False:
+        return None
+    cfg = GumbelConfig() if gumbel is True else gumbel
+    if not isinstance(cfg, GumbelConfig):
+        raise ValueError(f"gumbel must be None, False, True or a GumbelConfig (got {gumbel!r})")
+    m = cfg.max_considered
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= MAX_CONSIDERED:
+        raise ValueError(f"gumbel: max_considered must be an int in 1..{MAX_CONSIDERED} (got {m!r})")
+    for name in ("scale", "maxvisit_init", "value_scale"):
+        x = getattr(cfg, name)
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x < 0:
+            raise ValueError(f"gumbel: {name} must be a finite number >= 0 (got {x!r})")
+    if reuse_subtree:
+        raise ValueError("gumbel: Gumbel root search does not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("gumbel: Gumbel root search does not combine with leaves_per_step > 1")
+    if dirichlet_eps > 0:
+        raise ValueError("gumbel: Gumbel root search does not combine with Dirichlet noise (dirichlet_eps > 0)")
+    return GumbelConfig(int(m), float(cfg.scale), float(cfg.maxvisit_init), float(cfg.value_scale))
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1):
+                 leaves_per_step=1, gumbel=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -139,9 +177,15 @@ class SelfPlayEngine:
 
         leaves_per_step = K (BZ_ENGINE_LEAVES_*): every tree step runs K PUCT walks per game with virtual
         loss, and the evaluator takes up to K x n_games rows per launch; 1 (the default) is the one-walk engine, unchanged.
-        counters()["n_collisions"] (K > 1 only) counts the walks that stopped at a node another walk of the same step created."""
+        counters()["n_collisions"] (K > 1 only) counts the walks that stopped at a node another walk of the same step created.
+
+        gumbel: None / False = PUCT at every node (the default, unchanged); True or a GumbelConfig = Gumbel
+        root search: Gumbel-top-k plus sequential halving at the root (PUCT below it), the move is the halving's survivor and
+        the example rows' pi is the improved policy.  Gumbel noise is drawn while moves made < temp_moves (and scale > 0).
+        Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0."""
         check_sims(sims, reuse_subtree)
         self.K = check_leaves_per_step(leaves_per_step)
+        self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -178,6 +222,15 @@ class SelfPlayEngine:
                 _lib.check(L.bz_engine_set_mlp(self.h, net.h))
             else:
                 _lib.check(L.bz_engine_set_net(self.h, net.h))
+        if self.gumbel is not None:  # the engine's Gumbel buffer (caller-owned, like the workspace)
+            gc = self.gumbel
+            gbytes = L.bz_engine_gumbel_bytes(C.byref(self.cfg), gc.max_considered)
+            if gbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.gws = torch.zeros(gbytes + 256, dtype=torch.uint8, device=self.device)
+            gpad = (-self.gws.data_ptr()) & 255
+            self._call(L.bz_engine_set_gumbel, gc.max_considered, gc.scale, gc.maxvisit_init, gc.value_scale,
+                       self.gws.data_ptr() + gpad, gbytes)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -268,6 +321,20 @@ class SelfPlayEngine:
         W = self._view(self.lay.root_W, torch.float32, shp).cpu().numpy()
         P = self._view(self.lay.root_P, torch.float32, shp).cpu().numpy()
         return N, W, P
+
+    def root_policy_dev(self):
+        """root_policy() as CUDA tensors (pi float32 [B, NA], action int32 [B]) on the current stream, nothing copied"""
+        pi = torch.empty((self.B, self.na), dtype=torch.float32, device=self.device)
+        act = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        self._call(_lib.lib().bz_engine_root_policy, pi.data_ptr(), act.data_ptr())
+        return pi, act
+
+    def root_policy(self):
+        """after a search: the pi and the action play() would write and play, per slot (pi float32 [B, NA], action int32
+        [B]; idle or finished slots: zeros and -1).  PUCT: N / sum N and the visit-count move (tau = 1 sampling while moves
+        made < temp_moves); Gumbel: the improved policy and the Gumbel move"""
+        pi, act = self.root_policy_dev()
+        return pi.cpu().numpy(), act.cpu().numpy()
 
     def counters(self):
         """the work counters by name (_lib.COUNTER_NAMES); "n_collisions" only for leaves_per_step > 1"""
@@ -603,9 +670,10 @@ class PipelinedSelfPlay:
     host, and everything that hands data out (status, counters, pack_examples, examples ...) joins first."""
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
-                 game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, **engine_kwargs):
+                 game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_leaves_per_step(leaves_per_step)
+        check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
         self.run_ahead = run_ahead
@@ -615,7 +683,8 @@ class PipelinedSelfPlay:
         assert len(self.streams) == pipelines
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
-                                       game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, **engine_kwargs)
+                                       game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
+                                       **engine_kwargs)
                         for i in range(pipelines)]
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
@@ -728,13 +797,15 @@ class PipelinedSelfPlay:
 
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
-              reuse_subtree=False, pipelines=None, leaves_per_step=1):
+              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
     With a net evaluator the games run as two pipelines on two HIP streams (PipelinedSelfPlay: the shape bench.py
-    measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine."""
+    measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine (DESIGN.md 3.12);
+    gumbel: SelfPlayEngine -- pi is then the improved policy."""
     check_leaves_per_step(leaves_per_step)
+    check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -743,7 +814,8 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     sp = PipelinedSelfPlay(game, n_games, sims, evaluator, net, pipelines, game_id_base=game_id_base,
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
-                           dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step)
+                           dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
+                           gumbel=gumbel)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -147,12 +147,17 @@ class MCTSPlayer(Player):
     from `board` with `symbol` to move; plays argmax visit count (ties -> lowest
     action).  Works for TicTacToeBoard and 8x8 ReversiBoard; evaluator "net_bf16"
     / "net_f32" need a betazero_amd.net.DeviceNet (Reversi, any of the reference's board sizes); "mlp_f32" (the default
-    with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0)."""
+    with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0).
+    gumbel (True or an engine.GumbelConfig): Gumbel root search -- the move is the one the Gumbel search
+    plays (SelfPlayEngine.root_policy) and last_policy its improved policy; the player draws no Gumbel noise (temp_moves 0),
+    so it is deterministic."""
 
-    def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1):
-        from .engine import check_leaves_per_step, check_sims
+    def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1,
+                 gumbel=None):
+        from .engine import check_gumbel, check_leaves_per_step, check_sims
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
         self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step (DESIGN.md 3.12)
+        self.gumbel = check_gumbel(gumbel, leaves_per_step=self.leaves_per_step)
         self.symbol, self.sims, self.net, self.c_puct, self.device = symbol, sims, net, c_puct, device
         # evaluator: "uniform" | "hash" | "net_bf16" | "net_f32" | "net_fp8", or a callable (own, opp, kind) -> (logits, value)
         # on CUDA tensors (SelfPlayEngine.search_external): any torch module, e.g. an MLP for tic-tac-toe
@@ -164,12 +169,13 @@ class MCTSPlayer(Player):
         self.evaluator = evaluator or (("mlp_f32" if self._mlp else "net_bf16") if net is not None else "uniform")
         self._eng = {}
         self.last_visits = None
+        self.last_policy = None  # Gumbel mode: the improved policy of the last search, float32 [NA]
 
     def _engine(self, game):
         from .engine import SelfPlayEngine
         if game not in self._eng:
             self._eng[game] = SelfPlayEngine(game, 1, self.sims, self.evaluator, self.net, self.c_puct,
-                                             device=self.device, leaves_per_step=self.leaves_per_step)
+                                             device=self.device, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel)
         return self._eng[game]
 
     def get_move(self, board):
@@ -191,6 +197,14 @@ class MCTSPlayer(Player):
         N, _, _ = eng.root_stats()
         eng.status()  # raises on engine error flags (e.g. terminal root)
         self.last_visits = N[0]
+        if self.gumbel is not None:
+            pi, act = eng.root_policy()
+            self.last_policy = pi[0]
+            a = int(act[0])
+            if a < 0 or a == 64:
+                return (None, None)  # mover has no move (reversi_players.py:32)
+            n = 3 if game == "ttt" else 8
+            return a // n, a % n
         a = int(np.argmax(N[0]))  # first maximum = lowest action
         if N[0][a] == 0 or a == 64:
             return (None, None)  # mover has no move (reversi_players.py:32)

@@ -363,7 +363,8 @@ int32_t bz_engine_root_begin(bz_engine* e, void* stream);   /* roots -> leaf buf
 int32_t bz_engine_select(bz_engine* e, uint32_t sim_index, void* stream); /* M2: PUCT walk + env step */
 int32_t bz_engine_evaluate(bz_engine* e, void* stream);     /* run cfg.eval_kind on leaves */
 int32_t bz_engine_expand_backup(bz_engine* e, void* stream);/* M3 + M4                     */
-/* Dirichlet root noise (cfg.dirichlet_eps > 0; a no-op otherwise) on the priors of the expanded roots.  Step-API
+/* Dirichlet root noise (cfg.dirichlet_eps > 0; a no-op otherwise) on the priors of the expanded roots, and with Gumbel root
+ * search on (bz_engine_set_gumbel) the per-search Gumbel preparation of the expanded roots.  Step-API
  * callers run it once per search, after the expand_backup that follows root_begin and before select(0) -- the order
  * bz_engine_search uses. */
 int32_t bz_engine_root_noise(bz_engine* e, void* stream);
@@ -372,6 +373,30 @@ int32_t bz_engine_root_stats(bz_engine* e, void* stream);
 /* M5: pi, move choice, example row, env step, pass rule, terminal handling.
  * restart != 0: a finished slot starts its next game (next round) at once. */
 int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream);
+/* Gumbel root search (Danihelka et al., ICLR 2022), opt-in per engine.  The root's edge of every walk is
+ * chosen by Gumbel-top-k sampling plus sequential halving over the max_considered best root actions; every deeper level of
+ * the walk stays PUCT.  The move is the considered action that survives the halving, and the example row's pi is the improved
+ * policy softmax(log P + sigma(completed Q)).  Gumbel noise is drawn while moves made < cfg.temp_moves and gumbel_scale > 0
+ * (tau = 1 visit sampling is not used in this mode).  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one
+ * leaf per step, Dirichlet noise.  The evaluation cache works unchanged.  Searches go through the step kernels. */
+#define BZ_GUMBEL_MAX_CONSIDERED 64
+/* bytes of the caller-owned Gumbel buffer for cfg and max_considered (1..64): the considered-visit table u16
+ * [max_considered][sims], every root edge's base value f32 [n_games][MAXCH] and the root's value f32 [n_games], each array
+ * 256-byte aligned.  Needs no GPU; -1 (bz_last_error says why) for bad arguments or a refused combination. */
+int64_t bz_engine_gumbel_bytes(const bz_engine_cfg* cfg, int32_t max_considered);
+/* switch Gumbel root search on (max_considered 1..64; defaults of mctx's gumbel_muzero_policy: 16, gumbel_scale 1.0,
+ * maxvisit_init 50.0, value_scale 0.1) or off (max_considered 0), between searches.  buf: device memory of
+ * >= bz_engine_gumbel_bytes bytes, 256-byte aligned, owned by the caller and kept alive while the mode is on.  The
+ * considered-visit table is filled at once (the call synchronises `stream`). */
+int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, float gumbel_scale, float maxvisit_init,
+                             float value_scale, void* buf, int64_t buf_bytes, void* stream);
+/* the considered-visit sequence T[n_considered][k], k = 0 .. sims - 1, of mctx's get_sequence_of_considered_visits (the table
+ * bz_engine_set_gumbel uploads; n_considered 1..64, sims 1..BZ_ENGINE_MAX_SIMS).  Host only. */
+int32_t bz_gumbel_considered_visits(int32_t n_considered, int32_t sims, uint16_t* out);
+/* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
+ * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
+ * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
+int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream);
 /* synchronises the stream; number of active slots / finished games so far.  error_flags (sticky until the next
  * reset_games / set_roots): 1 = a game's edge arena overflowed, 2 = a root position was already terminal, 4 = more example
  * rows than t_max, 8 = a walk deeper than the path buffer, 16 = the evaluator returned a non-finite logit or value (the
