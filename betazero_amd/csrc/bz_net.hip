@@ -83,11 +83,12 @@ __global__ void k_stem(const u64* __restrict__ own, const u64* __restrict__ opp,
             int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
             if (yy < 0 || yy > 7 || xx < 0 || xx > 7) continue;
             int c2 = yy * 8 + xx;
-            if ((me >> c2) & 1ULL) acc = acc + wr[2 * t];
-            if ((you >> c2) & 1ULL) acc = acc + wr[2 * t + 1];
+            // the oracle's fmaf(plane, w, acc) with the plane in {0, 1}: a stone adds w, an empty cell adds 0 * w (NaN for
+            // an infinite w, as torch's convolution gives)
+            acc = __builtin_fmaf((float)((me >> c2) & 1ULL), wr[2 * t], acc);
+            acc = __builtin_fmaf((float)((you >> c2) & 1ULL), wr[2 * t + 1], acc);
         }
-        acc = acc > 0.0f ? acc : 0.0f;
-        out[((size_t)pos * 64 + cell) * C + co] = (OutT)acc;
+        out[((size_t)pos * 64 + cell) * C + co] = (OutT)relu_f32(acc);
     }
 }
 
@@ -131,7 +132,7 @@ __global__ void __launch_bounds__(256) k_conv_f32(const float* __restrict__ in, 
             size_t o = ((size_t)pos * 64 + c0 + j) * C + co;
             float v = acc[j];
             if (skip) v = v + skip[o];
-            out[o] = v > 0.0f ? v : 0.0f;
+            out[o] = relu_f32(v);
         }
     }
 }
@@ -164,7 +165,7 @@ __global__ void __launch_bounds__(192) k_heads(const InT* __restrict__ act, int 
         float acc = j < 2 ? pol_b[j] : val_b[0];
         const float* xi = xs + cell * (C + 1);
         for (int c = 0; c < C; ++c) acc = __builtin_fmaf(xi[c], wj[c], acc);
-        acc = acc > 0.0f ? acc : 0.0f;
+        acc = relu_f32(acc);
         if (j < 2) pf[j * 64 + cell] = acc; else vf[cell] = acc;
     }
     __syncthreads();
@@ -176,7 +177,7 @@ __global__ void __launch_bounds__(192) k_heads(const InT* __restrict__ act, int 
         int h = tid - 128;
         float acc = v1_b[h];
         for (int i = 0; i < 64; ++i) acc = __builtin_fmaf(vf[i], v1_wT[i * VH + h], acc);
-        vh[h] = acc > 0.0f ? acc : 0.0f;
+        vh[h] = relu_f32(acc);
     }
     __syncthreads();
     if (tid == 0) {
@@ -401,9 +402,9 @@ k_tower_bf16(TowerArgs T) {
             }
             if (h == 0) {  // rows 0..2 of D live in registers 0..2 of lanes 0..31
                 float a0 = acc[0] + pb0, a1 = acc[1] + pb1, a2 = acc[2] + vb;
-                S[cell] = a0 > 0.0f ? a0 : 0.0f;
-                S[64 + cell] = a1 > 0.0f ? a1 : 0.0f;
-                S[128 + cell] = a2 > 0.0f ? a2 : 0.0f;
+                S[cell] = relu_f32(a0);
+                S[64 + cell] = relu_f32(a1);
+                S[128 + cell] = relu_f32(a2);
             }
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS writes have landed
@@ -426,7 +427,7 @@ k_tower_bf16(TowerArgs T) {
             float a = T.v1_b[lane];
 #pragma unroll 32
             for (int i = 0; i < 64; ++i) a = __builtin_fmaf(S[128 + i], T.v1_wT[i * T.VH + lane], a);
-            vh = (a > 0.0f ? a : 0.0f) * T.v2_w[lane];
+            vh = relu_f32(a) * T.v2_w[lane];
         }
         vh = wave_sum(vh);
         if (lane == 0) T.value[pos] = tanhf_spec(vh + T.v2_b[0]);
@@ -556,7 +557,13 @@ __device__ __forceinline__ void run_taps(f32x16 (&acc)[8], v8i (&A0)[2], v8i (&A
 }
 
 // e4m3(16 * relu(acc * dq + bias (+ skip))) -> LDS, computed in the x16 domain: fma(acc, 16 dq, 16 bias)
-// (+ the stored skip code, which already is 16 x), one v_med3 for ReLU + saturation, cvt_pk.
+// (+ the stored skip code, which already is 16 x), ReLU + saturation, cvt_pk.
+// ReLU and saturation: IEEE maximum(v, +0), then minimum(., 448) -- both propagate a NaN, which v_cvt_pk_fp8_f32 stores as
+// the e4m3fn NaN code, so a NaN carries into the next layer (a v_med3_f32 clamp need not); +inf saturates to 448 as any
+// value above it does, -0 and negatives become +0
+__device__ __forceinline__ float relu_sat(float v) {
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, 0.0f), 448.0f);
+}
 // lane (r, h) register 4q+i of unit u = channel 32w + 8q + 4h + i of board cell (row u, column r & 7) of position r >> 3
 struct Scale { f32x4 dq[4], b[4]; };  // 16 x dequant factor and 16 x bias of the lane's channels
 __device__ __forceinline__ void load_scale(Scale& sc, const float* __restrict__ dq, const float* __restrict__ bl, int w, int h) {
@@ -596,7 +603,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[8], char* out, bool secon
                 }
                 float v[4] = {lo[0], lo[1], hi[0], hi[1]};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], 0.0f, 448.0f);
+                for (int i = 0; i < 4; ++i) v[i] = relu_sat(v[i]);
                 int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
                 pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
                 *reinterpret_cast<int*>(out + off) = pk;
@@ -714,9 +721,9 @@ __global__ void __launch_bounds__(256, 2) k_tower_fp8(TowerArgs T) {
             }
             if (h == 0) {
                 float a0 = acc[0] * d0 + pb0, a1 = acc[1] * d1 + pb1, a2 = acc[2] * d2 + vb;
-                S[cell] = a0 > 0.0f ? a0 : 0.0f;
-                S[64 + cell] = a1 > 0.0f ? a1 : 0.0f;
-                S[128 + cell] = a2 > 0.0f ? a2 : 0.0f;
+                S[cell] = relu_f32(a0);
+                S[64 + cell] = relu_f32(a1);
+                S[128 + cell] = relu_f32(a2);
             }
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -737,7 +744,7 @@ __global__ void __launch_bounds__(256, 2) k_tower_fp8(TowerArgs T) {
             float a = T.v1_b[lane];
 #pragma unroll 32
             for (int i = 0; i < 64; ++i) a = __builtin_fmaf(S[128 + i], T.v1_wT[i * T.VH + lane], a);
-            vh = (a > 0.0f ? a : 0.0f) * T.v2_w[lane];
+            vh = relu_f32(a) * T.v2_w[lane];
         }
         vh = wave_sum(vh);
         if (lane == 0) T.value[pos] = tanhf_spec(vh + T.v2_b[0]);
@@ -789,8 +796,10 @@ bool shape_ok(int C, int NB, int VH, int mb) {
 uint16_t f2bf(float f) {
     u32 u;
     __builtin_memcpy(&u, &f, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u) return (uint16_t)(u >> 16);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    // infinities keep their bits; a NaN stays a NaN (quiet bit set: the top 7 mantissa bits alone may be zero, and the
+    // rounding below would carry a NaN into an infinity or a zero)
+    if ((u & 0x7F800000u) == 0x7F800000u) return (uint16_t)((u >> 16) | ((u & 0x7FFFFFu) ? 0x40u : 0u));
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // round to nearest even
 }
 // OCP e4m3fn encode (RNE, saturating at 448)
 uint8_t f2e4m3(float f) {

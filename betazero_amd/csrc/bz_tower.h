@@ -302,6 +302,12 @@ __device__ __forceinline__ void run_chunks(f32x16 (&acc)[G::MW][G::NU], WSets<G>
 // the layer's biases for the lane's channels.  Fetched BEFORE the K-loop: issued at the head of the epilogue they cost
 // it a full L2 round trip with nothing to overlap (the per-tap scheduling regions keep the compiler from hoisting them)
 template <class G> struct Bias { f32x4 q[G::MW][4]; };
+// The inference ReLU is torch's: IEEE maximum(v, +0) on the fp32 value before the bf16 conversion -- a NaN of either sign
+// passes (v_cvt_pk_bf16_f32 keeps it a NaN), -0 and negatives become +0, and finite values get the bits that a max on the
+// rounded bf16 bits gave (rounding keeps the sign).  That int16 max turned a NaN with its sign bit set into +0, so a
+// diverged net gave finite logits.  One v_maximum3_f32 per value, as the training epilogue.
+__device__ __forceinline__ f32x4 relu_f32x4(f32x4 v) { return __builtin_elementwise_maximum(v, (f32x4)(0.0f)); }
+__device__ __forceinline__ float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
 template <class G>
 __device__ __forceinline__ void load_bias(Bias<G>& b, const float* __restrict__ bl, int wt0, int h) {
 #pragma unroll
@@ -334,15 +340,12 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[G::MW][G::NU], char* out,
                         bf16x4 sk = *reinterpret_cast<const bf16x4*>(out + off);
                         v = v + __builtin_convertvector(sk, f32x4);
                     }
-                    // ReLU on the bf16 bit patterns: rounding keeps the sign, so max(int16 bits, 0) of the rounded value
-                    // = the rounded max(v, 0) bit for bit (-0 -> +0 included), at two packed ops per four channels
-                    // (two 2-element conversions: one v_cvt_pk_bf16_f32 each; the 4-element form converts every
-                    // value on its own and packs with v_perm)
+                    // torch's ReLU on the fp32 value, then RNE to bf16 (relu_f32x4 above); two 2-element conversions: one
+                    // v_cvt_pk_bf16_f32 each (the 4-element form converts every value on its own and packs with v_perm)
+                    v = relu_f32x4(v);
                     f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
                     s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
                     s16x2 hi = __builtin_bit_cast(s16x2, __builtin_convertvector(vhi, bf16x2));
-                    lo = __builtin_elementwise_max(lo, (s16x2)(0));
-                    hi = __builtin_elementwise_max(hi, (s16x2)(0));
                     *reinterpret_cast<uint2*>(out + off) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
                 }
     }
@@ -481,11 +484,10 @@ __device__ __forceinline__ void epilogue16(f32x16 (&acc)[G::MW][G::NU], char* ou
                         bf16x4 sk = *reinterpret_cast<const bf16x4*>(out + off);
                         v = v + __builtin_convertvector(sk, f32x4);
                     }
+                    v = relu_f32x4(v);
                     f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
                     s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
                     s16x2 hi = __builtin_bit_cast(s16x2, __builtin_convertvector(vhi, bf16x2));
-                    lo = __builtin_elementwise_max(lo, (s16x2)(0));
-                    hi = __builtin_elementwise_max(hi, (s16x2)(0));
                     *reinterpret_cast<uint2*>(out + off) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
                 }
     }

@@ -3,7 +3,9 @@
   * tower conv weights and the two head conv1x1 weights: per OUTPUT CHANNEL power-of-two scale
     s = 2^floor(log2(448 / max|w|)), w_q = e4m3(w * s) (RNE, saturating), effective weight w_q / s;
   * tower activations are stored as e4m3(x * 16) (fixed activation scale 2^4, saturating at 448);
-  * stem weights, biases and the FC layers stay as in the bf16 net.
+  * stem weights, biases and the FC layers stay as in the bf16 net;
+  * ReLU is torch's, IEEE maximum(x, +0): a NaN (weight or activation) passes and is stored as the e4m3fn NaN code, +inf
+    saturates to 448 like any value above it, -0 becomes +0.
 The engine derives the same scales from the effective weights, so passing the fake-quantised
 parameter vector to bz_net_create is all that is needed."""
 import numpy as np

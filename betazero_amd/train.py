@@ -247,8 +247,9 @@ class GraphedTrainStep:
 def refresh_device_net(device_net, module):
     """push the trained weights into the HIP engine's net (bf16-rounded copy for the MFMA path).  Raises
     FloatingPointError when a parameter is not finite (one isfinite reduction per refresh): the losses of a step are
-    computed BEFORE its optimiser update, so a last step that overflows is invisible in them, and a net with such
-    weights makes every search return garbage (the engine then raises ERR_EVAL_NONFINITE far from the cause)."""
+    computed BEFORE its optimiser update, so a last step that overflows is invisible in them.  A net with such weights
+    gives non-finite logits or values (the inference ReLUs pass a NaN), and the engine would then raise
+    ERR_EVAL_NONFINITE in the next search, far from the cause."""
     import copy
     bad = [n for n, p in module.named_parameters() if not bool(torch.isfinite(p.detach()).all())]
     if bad:

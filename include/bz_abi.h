@@ -180,14 +180,20 @@ int32_t bz_net_update(bz_net* net, const float* params_host, void* stream);
 /* own/opp: device u64[n]; logits: device f32[n][65]; value: device f32[n].
  * _f32: exact parity mode (k-ordered fmaf chains == oracle bit for bit).
  * _bf16: MFMA path (bf16 activations/weights, fp32 accumulate); C = 64, 128 or 256
- *        (C = 32 nets run on the _f32 path only). */
+ *        (C = 32 nets run on the _f32 path only).
+ * Every ReLU of all three paths is torch's, IEEE maximum(y, +0): a NaN of either sign passes (a NaN
+ * weight stays a NaN through the bf16 / e4m3 packing), -0 becomes +0.  A net with a NaN or infinite
+ * parameter thus gives a non-finite logit or value wherever torch's fp32 PolicyValueNet does (except
+ * through the products with the board's zero padding, which the kernels skip), and the engine's
+ * ERR_EVAL_NONFINITE guard fires on it. */
 int32_t bz_net_forward_f32(bz_net* net, const uint64_t* own, const uint64_t* opp, int32_t n,
                            float* logits, float* value, void* stream);
 int32_t bz_net_forward_bf16(bz_net* net, const uint64_t* own, const uint64_t* opp, int32_t n,
                             float* logits, float* value, void* stream);
 /* _fp8: e4m3 weights (per-output-channel power-of-two scale) and activations (x16) on the
  * MX-scaled 32x32x64 MFMA (BASELINE config 5); pass parameters fake-quantised by
- * betazero_amd/quant.py.  Needs C == 128. */
+ * betazero_amd/quant.py.  Needs C == 128.  The activation store saturates at 448 (+inf included);
+ * a NaN is stored as the e4m3fn NaN code and carries into the next layer. */
 int32_t bz_net_forward_fp8(bz_net* net, const uint64_t* own, const uint64_t* opp, int32_t n,
                            float* logits, float* value, void* stream);
 

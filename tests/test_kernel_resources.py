@@ -53,7 +53,7 @@ def test_tree_kernels_stay_within_their_register_budget(tmp_path):
 def test_net_kernels_do_not_spill(tmp_path):
     res = _resources("bz_net.hip", tmp_path)
     for parts in (("k_tower_bf16", "Li128ELi4ELb1E"), ("k_tower_bf16", "Li64ELi8E"), ("k_tower_bf16", "Li256ELi2E"),
-                  ("k_tower_bf16", "Li128ELi1E"), ("k_tower_fp8",)):
+                  ("k_tower_bf16", "Li128ELi1E"), ("k_tower_bf16", "Li64ELi2E"), ("k_tower_bf16", "Li256ELi1E"), ("k_tower_fp8",)):
         k = _find(res, *parts)
         assert k["vspill"] == 0 and k["scratch"] == 0 and k["vgpr"] <= 512, (parts, k)
     assert _find(res, "k_tower_fp8")["vgpr"] <= 256  # two workgroups per CU
