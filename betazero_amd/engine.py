@@ -124,6 +124,18 @@ def check_leaves_per_step(leaves_per_step):
     return int(k)
 
 
+EVAL_CACHE_MODES = (True, "carry", "search", False, None)
+
+
+def check_eval_cache(eval_cache):
+    """True / "carry": the evaluation cache with carry-over; "search": within a search only; False / None: off.  Anything
+    else (a misspelt mode such as "off" is truthy) is refused with ValueError, before any device is touched."""
+    if not any(eval_cache is m or (isinstance(m, str) and isinstance(eval_cache, str) and eval_cache == m)
+               for m in EVAL_CACHE_MODES):
+        raise ValueError(f"eval_cache must be one of True, 'carry', 'search', False, None (got {eval_cache!r})")
+    return eval_cache
+
+
 MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
 
 
@@ -170,7 +182,8 @@ class SelfPlayEngine:
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
-        is re-created node for node by the new search), "search" only from the same search, False none.  Every result is bit
+        is re-created node for node by the new search), "search" only from the same search, False / None none; any other
+        value is refused (ValueError, before any device is touched).  Every result is bit
         for bit what it is without the cache (the net is a function of the position); counters()["n_cache_hits"] (of which
         "n_cache_hits_prev" from the previous search) says how often it fired.  Ignored for the synthetic / external
         evaluators, with reuse_subtree and with leaves_per_step > 1.
@@ -184,6 +197,7 @@ class SelfPlayEngine:
         the example rows' pi is the improved policy.  Gumbel noise is drawn while moves made < temp_moves (and scale > 0).
         Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0."""
         check_sims(sims, reuse_subtree)
+        check_eval_cache(eval_cache)
         self.K = check_leaves_per_step(leaves_per_step)
         self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
@@ -674,6 +688,7 @@ class PipelinedSelfPlay:
         assert 1 <= pipelines <= n_games
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
+        check_eval_cache(engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
         self.run_ahead = run_ahead

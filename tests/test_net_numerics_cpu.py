@@ -128,9 +128,11 @@ def mode_params(P, mode):
 
 
 # ---------------------------------------------------------------- the reference
-def net_forward_ref(own, opp, P, mode, stats=None):
+def net_forward_ref(own, opp, P, mode, stats=None, feats=None):
     """(logits [n, 65], value [n]) as float64 tensors holding the kernels' fp32 results (P: float64 tensors, KEYS; on the
-    device the tower runs on).  stats: a dict that receives per-layer counts of what the stores met."""
+    device the tower runs on).  stats: a dict that receives per-layer counts of what the stores met; feats: a dict that
+    receives the tower's output ("x" [n, 64, C]) and the inputs of the policy FC ("hf" [n, 128]) and of the second value FC
+    ("v1h" [n, VH])."""
     assert mode in MODES
     Q = mode_params(P, mode)
     dev = Q["tw"].device
@@ -199,6 +201,8 @@ def net_forward_ref(own, opp, P, mode, stats=None):
     v2w = Q["v2_w"].reshape(-1)
     vpre = v1h @ v2w + Q["v2_b"]
     _exact(v1h.abs() @ v2w.abs() + Q["v2_b"].abs(), min(lsb64(v1h) * lsb64(v2w), lsb64(Q["v2_b"])), "value FC 2")
+    if feats is not None:
+        feats.update(x=x, hf=hf, v1h=v1h)
     _is_f32(logits, "logits")
     _is_f32(vpre, "value pre-activation")
     import oracle.oracle as orc
