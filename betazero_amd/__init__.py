@@ -12,11 +12,15 @@ from .players import (Player, ReversiPlayer, RandomPlayer, ReversiRandomPlayer, 
 __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadless", "process_game_positions",
            "Player", "ReversiPlayer", "RandomPlayer", "ReversiRandomPlayer", "MCTSPlayer",
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
-           "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model"]
+           "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
+           "MatchPlayer", "MatchResult", "play_match"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
     if name in ("TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model"):
         from . import mlp
         return getattr(mlp, name)
+    if name in ("MatchPlayer", "MatchResult", "play_match"):  # head-to-head matches
+        from . import match
+        return getattr(match, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

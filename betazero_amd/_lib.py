@@ -40,6 +40,19 @@ class EngineLayout(C.Structure):
                [("na", i32), ("t_max", i32)] + [(n, i64) for n in ("ex_begin", "ex_bytes", "ex_meta")]
 
 
+class MatchLayout(C.Structure):      # bz_match_layout
+    _fields_ = [(n, i64) for n in ("own", "opp", "to_move", "active", "winner", "plies", "a_colour", "to_move_a", "to_move_b",
+                                   "log_action", "log_mover")] + [("n_games", i32), ("max_plies", i32)]
+
+
+class MatchHdr(C.Structure):         # bz_match_hdr: the one host read of a match ply
+    _fields_ = [("ply", i32), ("n_active", i32), ("n_to_move_a", i32), ("n_to_move_b", i32), ("error", u32),
+                ("engine_err_a", u32), ("engine_err_b", u32), ("reserved", u32)]
+
+
+MATCH_ERR_ILLEGAL, MATCH_ERR_NO_ACTION, MATCH_ERR_SLOT_MASK = 0xC0000000, 0xA0000000, 0x00FFFFFF
+
+
 class TrainHeadParams(C.Structure):   # bz_train_head_params: one fp32 device pointer per head parameter tensor
     _fields_ = [(n, vp) for n in ("pol_w", "pol_b", "polfc_w", "polfc_b", "val_w", "val_b", "v1_w", "v1_b", "v2_w", "v2_b")]
 
@@ -133,6 +146,15 @@ _SIGS = {
     "bz_mcts_expand_backup": (i32, [vp, vp]),
     "bz_selfplay_run": (i32, [vp, i32, vp]),
     "bz_engines_step": (i32, [C.POINTER(vp), C.POINTER(vp), i32, i32, i32]),
+    "bz_engines_search": (i32, [C.POINTER(vp), C.POINTER(vp), i32, i32]),
+    "bz_match_workspace_bytes": (i64, [i32, i32, i32]),
+    "bz_match_create": (i32, [i32, i32, i32, vp, i64, C.POINTER(vp)]),
+    "bz_match_destroy": (i32, [vp]),
+    "bz_match_get_layout": (i32, [vp, C.POINTER(MatchLayout)]),
+    "bz_match_begin": (i32, [vp, u64, i32, vp]),
+    "bz_match_ply": (i32, [vp, vp, vp, vp, vp, vp]),
+    "bz_match_header": (i32, [vp, vp, C.POINTER(MatchHdr)]),
+    "bz_match_opening_index": (i32, [u64, u64, i32, i32, C.POINTER(i32)]),
     "bz_engine_reset_counters": (i32, [vp, vp]),
     "bz_engine_sum_counters": (i32, [vp, vp]),
     "bz_examples_packed_bytes": (i64, [i32, i64]),

@@ -2382,6 +2382,64 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
     return BZ_OK;
 }
 
+// an engine whose whole search is one launch (k_search_fused / k_search_fused_ttt): nothing to interleave
+static bool search_is_fused(const bz_engine* e) {
+    const int ek = e->cfg.eval_kind;
+    return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !(e->dev.dir_eps > 0.0f) && e->dev.K == 1 &&
+           e->gumbel.m == 0;
+}
+
+// the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree
+// step by tree step -- each with its own sims, K and mode -- and, with `play`, the move behind each
+static int32_t engines_run(bz_engine* const* engines, void* const* streams, int n, int run_ahead_sims, bool play, int restart) {
+    int32_t rc;
+    int steps = 0, Kmax = 1;
+    for (int i = 0; i < n; ++i) {
+        bz_engine* e = engines[i];
+        if (!e || search_is_fused(e)) continue;
+        const int ns = (e->cfg.sims + e->dev.K - 1) / e->dev.K;
+        steps = ns > steps ? ns : steps;
+        Kmax = e->dev.K > Kmax ? e->dev.K : Kmax;
+        if ((rc = bz_engine_root_begin(e, streams[i])) != BZ_OK) return rc;
+        if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
+        if (e->dev.dir_eps > 0.0f || e->gumbel.m > 0) {
+            if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
+            if ((rc = bz_engine_root_noise(e, streams[i])) != BZ_OK) return rc;
+        }
+    }
+    for (int i = 0; i < n; ++i) {  // (behind the stepwise engines' root launches, so that those streams have work first)
+        bz_engine* e = engines[i];
+        if (!e || !search_is_fused(e)) continue;
+        if ((rc = bz_engine_search(e, streams[i])) != BZ_OK) return rc;
+        if (play && (rc = bz_engine_play(e, restart, streams[i])) != BZ_OK) return rc;
+    }
+    // (K > 1: one step = K simulations; the run-ahead bound counts steps of q / K, at least one)
+    const int q0 = run_ahead_sims > 0 ? (run_ahead_sims >= 2 ? run_ahead_sims / 2 : 1) : 0;
+    const int q = q0 ? (q0 / Kmax > 0 ? q0 / Kmax : 1) : 0;
+    for (int step = 0; step < steps; ++step) {
+        for (int i = 0; i < n; ++i) {
+            bz_engine* e = engines[i];
+            if (!e || search_is_fused(e)) continue;
+            const int s = step * e->dev.K;
+            if (s >= e->cfg.sims) continue;
+            const bool prep = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
+            if ((rc = tree_step(e, (prep && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
+            if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
+        }
+        if (q && (step + 1) % q == 0)
+            for (int i = 0; i < n; ++i)
+                if (engines[i] && !search_is_fused(engines[i]) &&
+                    (rc = ahead_mark(engines[i], (step + 1) / q - 1, (hipStream_t)streams[i])) != BZ_OK) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        bz_engine* e = engines[i];
+        if (!e || search_is_fused(e)) continue;
+        if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
+        if (play && (rc = bz_engine_play(e, restart, streams[i])) != BZ_OK) return rc;
+    }
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* streams, int32_t n, int32_t restart,
                                   int32_t run_ahead_sims) {
     BZ_REQUIRE(engines && streams && n >= 1 && n <= 16 && run_ahead_sims >= 0, "bz_engines_step: bad arguments");
@@ -2392,44 +2450,26 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
         BZ_REQUIRE(engines[i]->dev.K == engines[0]->dev.K, "bz_engines_step: the engines must take the same leaves per step");
         BZ_REQUIRE((engines[i]->gumbel.m > 0) == (engines[0]->gumbel.m > 0),
                    "bz_engines_step: the engines must all search with Gumbel root search or all without");
-        const int ek = engines[i]->cfg.eval_kind;
-        BZ_REQUIRE(ek != BZ_EVAL_EXTERNAL, "bz_engines_step: BZ_EVAL_EXTERNAL callers drive the step API");
-        if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !engines[i]->dev.reuse && !(engines[i]->dev.dir_eps > 0.0f) &&
-            engines[i]->dev.K == 1 && engines[i]->gumbel.m == 0) stepwise = false;
+        BZ_REQUIRE(engines[i]->cfg.eval_kind != BZ_EVAL_EXTERNAL, "bz_engines_step: BZ_EVAL_EXTERNAL callers drive the step API");
+        if (search_is_fused(engines[i])) stepwise = false;
     }
-    int32_t rc;
     if (!stepwise) {  // a fused search is one launch per engine: nothing to interleave
+        int32_t rc;
         for (int i = 0; i < n; ++i)
             if ((rc = bz_selfplay_run(engines[i], restart, streams[i])) != BZ_OK) return rc;
         return BZ_OK;
     }
-    for (int i = 0; i < n; ++i) {
-        bz_engine* e = engines[i];
-        if ((rc = bz_engine_root_begin(e, streams[i])) != BZ_OK) return rc;
-        if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
-        if (e->dev.dir_eps > 0.0f || e->gumbel.m > 0) {
-            if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
-            if ((rc = bz_engine_root_noise(e, streams[i])) != BZ_OK) return rc;
-        }
-    }
-    // (K > 1: one step = K simulations; the run-ahead bound counts steps of q / K, at least one)
-    const int sims = engines[0]->cfg.sims, K = engines[0]->dev.K;
-    const int q0 = run_ahead_sims > 0 ? (run_ahead_sims >= 2 ? run_ahead_sims / 2 : 1) : 0;
-    const int q = q0 ? (q0 / K > 0 ? q0 / K : 1) : 0;
-    for (int s = 0, step = 0; s < sims; s += K, ++step) {
-        for (int i = 0; i < n; ++i) {
-            bz_engine* e = engines[i];
-            const bool prep = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
-            if ((rc = tree_step(e, (prep && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
-            if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
-        }
-        if (q && (step + 1) % q == 0)
-            for (int i = 0; i < n; ++i)
-                if ((rc = ahead_mark(engines[i], (step + 1) / q - 1, (hipStream_t)streams[i])) != BZ_OK) return rc;
-    }
-    for (int i = 0; i < n; ++i) {
-        if ((rc = tree_step(engines[i], 1, 0, 0, streams[i])) != BZ_OK) return rc;
-        if ((rc = bz_engine_play(engines[i], restart, streams[i])) != BZ_OK) return rc;
-    }
-    return BZ_OK;
+    return engines_run(engines, streams, n, run_ahead_sims, true, restart);
 }
+
+BZ_EXPORT int32_t bz_engines_search(bz_engine* const* engines, void* const* streams, int32_t n, int32_t run_ahead_sims) {
+    BZ_REQUIRE(engines && streams && n >= 1 && n <= 16 && run_ahead_sims >= 0, "bz_engines_search: bad arguments");
+    for (int i = 0; i < n; ++i)
+        BZ_REQUIRE(!engines[i] || engines[i]->cfg.eval_kind != BZ_EVAL_EXTERNAL,
+                   "bz_engines_search: BZ_EVAL_EXTERNAL callers drive the step API");
+    return engines_run(engines, streams, n, run_ahead_sims, false, 0);
+}
+
+// the engine's sticky error word (FLAG_ERR: BZ_ENGINE_ERR_* bits) in device memory -- bz_match.hip's ply kernel folds it
+// into the match header, so that a match needs no bz_engine_status round trip per ply
+const uint32_t* bz_engine_error_word_dev(const bz_engine* e) { return e->dev.flags + FLAG_ERR; }

@@ -457,6 +457,84 @@ int32_t bz_engine_reset_counters(bz_engine* e, void* stream);
 int32_t bz_engine_sum_counters(bz_engine* e, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Head-to-head match between two search players: B games   */
+/* over the same B slots of TWO engines, one per side (A and B), colours     */
+/* swapped inside every pair of games.  The turn loop is the one of          */
+/*   ReversiTerminal.play  reversi_terminal.py:16-38 (pass rule :31-35)      */
+/*   TicTacToeHeadless.play  src/tic_tac_toe/tic_tac_toe.py:13-34            */
+/* with a search player on both sides.  Everything between two searches is   */
+/* ONE kernel per ply (csrc/bz_match.hip) and the host reads 32 bytes.       */
+/*                                                                           */
+/* Per ply the caller runs                                                   */
+/*   bz_engine_set_roots(A, ws + own, ws + opp, ws + to_move_a)   (B alike)  */
+/*   a search of every engine whose side has a slot to move                  */
+/*   bz_engine_root_policy(A, ., act_a)                           (B alike)  */
+/*   bz_match_ply(m, act_a, act_b, A, B)      bz_match_header(m, ., &h)      */
+/* until h.n_active == 0 (or h.error != 0).                                  */
+/* Games 2k and 2k+1 are a pair: the same opening, A plays +1 (X, moves      */
+/* first) in game 2k and -1 in game 2k+1.  While a slot has made fewer than  */
+/* opening_plies moves its move is the r-th legal move in ascending action   */
+/* order, r = bz_match_opening_index(seed, k, moves made, n_legal); neither  */
+/* engine searches the slot then.  A side without a move in an unfinished    */
+/* game is passed over (the other side moves again; a pass is no ply), so    */
+/* every active slot makes exactly one move per ply.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct bz_match bz_match;
+#define BZ_MATCH_MAX_GAMES (1 << 24)
+/* error word: 0, or the kind and the slot of the FIRST refused move (sticky; the slot is frozen as it stood, every
+ * other game goes on): the side to move handed in an action that is not a legal move / no action at all (-1) */
+#define BZ_MATCH_ERR_ILLEGAL 0xC0000000u
+#define BZ_MATCH_ERR_NO_ACTION 0xA0000000u
+#define BZ_MATCH_ERR_SLOT_MASK 0x00FFFFFFu
+/* offsets (bytes, from the workspace base) of the caller-visible arrays */
+typedef struct bz_match_layout {
+    int64_t own, opp;               /* u64 [B] position seen by the side to move = the roots of both engines */
+    int64_t to_move;                /* i8 [B] absolute colour of the side to move */
+    int64_t active;                 /* u8 [B] 1 = running, 0 = finished, 2 = frozen by a refused move */
+    int64_t winner;                 /* i8 [B] absolute colour +1 / -1 / 0, valid once the slot has finished */
+    int64_t plies;                  /* i32 [B] moves made */
+    int64_t a_colour;               /* i8 [B] the colour side A plays */
+    int64_t to_move_a, to_move_b;   /* i8 [B] to_move of the next search's roots per engine: the colour where that side is
+                                     * to move in a running slot past its opening, else 0 (slot idle in that engine) */
+    int64_t log_action, log_mover;  /* u8 / i8 [max_plies][B]: 255 / 0 = no move by this slot at this ply */
+    int32_t n_games, max_plies;
+} bz_match_layout;
+/* what the host reads once per ply: the state BEFORE ply `ply` (the next one to be played) */
+typedef struct bz_match_hdr {
+    int32_t ply;                    /* plies played so far */
+    int32_t n_active;               /* running slots */
+    int32_t n_to_move_a, n_to_move_b; /* slots the next search of engine A / B serves (0: that engine need not search) */
+    uint32_t error;                 /* BZ_MATCH_ERR_* | slot, or 0 */
+    uint32_t engine_err_a, engine_err_b; /* the BZ_ENGINE_ERR_* bits the engines raised in any search so far */
+    uint32_t reserved;
+} bz_match_hdr;
+/* game: BZ_GAME_*; n_games even, 2 .. BZ_MATCH_MAX_GAMES; max_plies 1..64 rows of the move log, 0 = the game's longest
+ * game (9 / 60 / 32 / 12).  Needs no GPU; -1 (bz_last_error says why) for bad arguments. */
+int64_t bz_match_workspace_bytes(int32_t game, int32_t n_games, int32_t max_plies);
+/* workspace: device memory of >= bz_match_workspace_bytes bytes, 256-byte aligned, owned by the caller */
+int32_t bz_match_create(int32_t game, int32_t n_games, int32_t max_plies, void* workspace, int64_t workspace_bytes,
+                        bz_match** out);
+int32_t bz_match_destroy(bz_match* m);
+int32_t bz_match_get_layout(const bz_match* m, bz_match_layout* out);
+/* every slot at the game's start position (any board size), colours, an empty log, the roots of ply 0 */
+int32_t bz_match_begin(bz_match* m, uint64_t seed, int32_t opening_plies, void* stream);
+/* one ply of every running slot.  action_a / action_b: device i32 [B] as bz_engine_root_policy writes them (-1 = idle);
+ * the action of the side to move is played (the opening move during a slot's opening).  engine_a / engine_b (optional,
+ * may be null): the engines, whose error words the kernel folds into the header.  A refused move is reported through
+ * the header's error word, never through a fault.  BZ_ESTATE after max_plies plies. */
+int32_t bz_match_ply(bz_match* m, const int32_t* action_a, const int32_t* action_b, const bz_engine* engine_a,
+                     const bz_engine* engine_b, void* stream);
+/* synchronises the stream: the ONE host read of a ply */
+int32_t bz_match_header(bz_match* m, void* stream, bz_match_hdr* out);
+/* the opening draw, host side: *index = rng_draw(seed ^ C_MATCH, pair, ply) mod n_legal (1 <= n_legal <= 64) */
+int32_t bz_match_opening_index(uint64_t seed, uint64_t pair, int32_t ply, int32_t n_legal, int32_t* index);
+/* one search for n engines (n <= 16), engine i on streams[i], issued by ONE host thread and interleaved tree step by
+ * tree step like bz_engines_step, without the play: each engine with its own simulations, leaves per step and mode
+ * (an engine whose search is one fused launch is simply launched).  engines[i] may be null (skipped).  Results are
+ * those of bz_engine_search on every engine.  run_ahead_sims as in bz_engines_step. */
+int32_t bz_engines_search(bz_engine* const* engines, void* const* streams, int32_t n, int32_t run_ahead_sims);
+
+/* ------------------------------------------------------------------------ */
 /* Training step of the residual tower: hand-written  */
 /* bf16 MFMA kernels for forward-with-saved-activations, backward-data and   */
 /* backward-weights of its n_layers = 2 NB conv3x3 layers.  The loop they    */

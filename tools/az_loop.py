@@ -12,6 +12,9 @@
          agreement -- the reference's per-epoch validation line, SL/train.py:121-146)
       -> weights pushed back into the engine's net (refresh_device_net)
       -> batched arena against the reference's depth-limited minimax player (play_arena)
+      -> with --gate-games N: a head-to-head match (play_match) of the freshly trained net against the net
+         self-play currently uses; the candidate is promoted to self-play only at score >= --gate-score (AlphaGo Zero's
+         0.55), otherwise self-play keeps the old weights while training continues from the new ones
 
 It prints one JSON line per iteration and a final summary; `--out` keeps them.  The yard-stick is the reference's
 OptimalPlayer (src/reversi/players/reversi_players.py:35-77, stone-difference minimax) at `--depth`; the same arena
@@ -32,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
 from betazero_amd.engine import PipelinedSelfPlay, concat_device_examples  # noqa: E402
+from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
                                 train_step, validate)
@@ -59,6 +63,12 @@ def main():
     ap.add_argument("--depth", type=int, default=3, help="search depth of the minimax opponent")
     ap.add_argument("--final-depths", default="1,3,5", help="minimax depths the final net is also played against")
     ap.add_argument("--opening-plies", type=int, default=4, help="random legal moves before the arena players take over")
+    ap.add_argument("--gumbel", action="store_true", help="self-play with Gumbel root search (DESIGN.md 3.13): the example rows' pi is the "
+                    "improved policy, Gumbel noise on the first --temp-moves moves, no Dirichlet noise; the gate's and the arena's players "
+                    "then play the Gumbel move too")
+    ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
+                    "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
+    ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -72,8 +82,11 @@ def main():
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup)
-    bmax = max(args.games, args.arena_games)
+    bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
+    # with the gate on, the freshly trained weights live in a net of their own until they have won their match
+    cand = DeviceNet.from_module(module, bmax) if args.gate_games else dnet
+    gumbel = True if args.gumbel else None
     lines = []
 
     def emit(d):
@@ -84,7 +97,7 @@ def main():
         t0 = time.time()
         try:
             res = play_arena("reversi", args.arena_games, args.arena_sims, opponent_depth=depth or args.depth, evaluator=evaluator,
-                             net=net, seed=args.seed, opening_plies=args.opening_plies)
+                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel)
         except RuntimeError:  # keep the weights that were in play for a post-mortem
             if args.out:
                 np.save(args.out + ".failed_params.npy", module.flat_params())
@@ -102,7 +115,8 @@ def main():
     for it in range(1, args.iters + 1):
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
-                               openings=1, seed=args.seed * 1000 + it, dirichlet_alpha=0.3, dirichlet_eps=0.25)
+                               openings=1, seed=args.seed * 1000 + it, gumbel=gumbel,
+                               **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
         winners, _ = sp.winners()
@@ -132,9 +146,20 @@ def main():
         if not np.isfinite(losses).all():
             raise RuntimeError(f"training diverged in iteration {it}: first non-finite loss at step "
                                f"{int(np.argmax(~np.isfinite(losses).all(1)))} of {steps}")
-        refresh_device_net(dnet, module)
+        refresh_device_net(cand, module)
         t_train = time.time() - t1
-        val_after = validate(dnet, val)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
+        val_after = validate(cand, val)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
+        gate = {}
+        if args.gate_games:  # the candidate (A) against the net self-play uses (B)
+            t2 = time.time()
+            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel),
+                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel), opening_plies=args.opening_plies,
+                             seed=args.seed * 1000 + it)
+            g = res.summary()
+            g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
+            if g["promoted"]:
+                refresh_device_net(dnet, module)
+            gate = {"gate": g}
         head, tail = np.mean(losses[: max(1, steps // 10)], axis=0), np.mean(losses[-max(1, steps // 10):], axis=0)
         emit({"what": "iteration", "iter": it, "games": args.games, "plies": plies, "examples": int(len(ex)),
               "augmented_rows": int(len(aug)), "train_rows": int(len(data)), "steps": steps,
@@ -146,7 +171,7 @@ def main():
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1), "train_s": round(t_train, 1),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
-              "arena": arena("net_bf16", dnet)})
+              "arena": arena("net_bf16", cand), **gate})
     for d in (int(x) for x in args.final_depths.split(",") if x):
         emit({"what": "final arena", "opponent_depth": d, "sims": args.arena_sims, "trained": arena("net_bf16", dnet, d),
               "uniform_evaluator": arena("uniform", None, d)})
