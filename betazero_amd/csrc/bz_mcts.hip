@@ -133,6 +133,19 @@ struct GumbelDev {
     const uint16_t* T; float *base, *vroot;
 };
 
+// Playout cap randomisation (fast = 0: off), set by bz_engine_set_playout_cap: every slot's simulation budget
+// for the current search, b_g [B] in the caller's buffer (k_cap_budget writes it behind k_root_begin; 0 = the slot sits the
+// search out).  Like GumbelDev a kernel argument of the cap kernels only.
+struct CapDev {
+    int fast; u32 full_q;
+    u32* budget;
+};
+constexpr u64 kCapKey = 0x706C61796F757443ULL;
+// the budget draw: all-integer, so the host (bz_playout_cap_budget), the kernel and the twin agree on every bit
+__host__ __device__ __forceinline__ u32 cap_budget(u64 seed, u64 gid, u64 made, int sims, int fast, u32 full_q) {
+    return (u32)(rng_draw(seed ^ kCapKey, gid, made) & 0xFFFFULL) < full_q ? (u32)sims : (u32)fast;
+}
+
 struct Cnt { u32 v[CNT_N]; };
 
 // Diagnostic build only (betazero_amd.build.build_variant("treestamps", ["-DBZ_EXP_TREE_STAMPS"]), tools/exp_tree_stamps.py):
@@ -905,9 +918,13 @@ __global__ void __launch_bounds__(256) k_root_begin(EngineDev E, u32 tt_gen, int
 // kernels (inlined into the expansion it took k_tree_step from 78 to 129 VGPRs and the cfg-2 kernel from 93 to 219):
 // P' = (1 - eps) P + eps g / sum(g) over the root's edges in ascending action order, for every active game whose
 // root is expanded -- freshly (by the expand-only tree step before this launch) or kept from the previous move.
-__global__ void __launch_bounds__(64) k_root_noise(EngineDev E) {
+// kCap: the masked form (playout cap randomisation) -- noise on the roots of the FULL searches only, same key,
+// same bits; with kCap = false it is k_root_noise's code exactly.
+template <bool kCap>
+__device__ __forceinline__ void root_noise_body(const EngineDev& E, const u32* budget) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.B || E.g_state[g] != 0) return;
+    if (kCap && budget[g] < (u32)E.sims) return;
     const Node r = E.nodes[(size_t)g * E.ncap];
     const int n = (int)(r.info & 0xFFu);
     if (n == 0 || r.legal == 0) return;  // not expanded / a forced-pass root (P = 1 stays)
@@ -922,6 +939,21 @@ __global__ void __launch_bounds__(64) k_root_noise(EngineDev E) {
         float t2 = E.dir_eps * fdiv(gamma_spec(E.dir_alpha, E.seed, gid, ply, i), gs);
         ed[i].P = t1 + t2;
     }
+}
+__global__ void __launch_bounds__(64) k_root_noise(EngineDev E) { root_noise_body<false>(E, nullptr); }
+__global__ void __launch_bounds__(64) k_cap_noise(EngineDev E, CapDev Cp) { root_noise_body<true>(E, Cp.budget); }
+
+// every slot's budget for the search k_root_begin has just set up: sims with probability full_q / 65536, else
+// fast, drawn from (seed ^ kCapKey, game id, moves made) -- the key of the Dirichlet noise; 0 for a slot that is not in a game
+__global__ void __launch_bounds__(256) k_cap_budget(EngineDev E, CapDev Cp) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    u32 b = 0;
+    if (E.g_state[g] == 0) {
+        const u64 gid = E.id_base + (u64)E.g_round[g] * E.id_stride + (u64)g;
+        b = cap_budget(E.seed, gid, (u64)E.g_moves[g], E.sims, Cp.fast, Cp.full_q);
+    }
+    Cp.budget[g] = b;
 }
 
 // synthetic evaluators as a separate step (used by the step-by-step API)
@@ -949,8 +981,11 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 
 // The body of k_tree_step and of k_gumbel_step (kGumbel: the Gumbel root rule at depth 0 of the walk and v_root stored
 // with the root's expansion); with kGumbel = false it is k_tree_step's code exactly.
-template <class G, bool kGumbel>
-__device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx) {
+// kCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget; both flags off, the code is
+// k_tree_step's / k_gumbel_step's as before.
+template <class G, bool kGumbel, bool kCap = false>
+__device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
+                                               const u32* budget = nullptr) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -972,6 +1007,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
         u64 nlegal = hot.leaf_legal, rown = E.g_own[g], ropp = E.g_opp[g];
         u32 root_base = E.reuse ? hot.root_base : 0u;
         PathEnt pe0 = path[sub];  // (maxd >= kGW for every game)
+        u32 bud = 0;
+        if (kCap) { bud = budget[g]; pin(bud); }
         // the walk's first load too: root edges 0..kGW-1 (the root's edges start at index 0; whatever this step's
         // backup / expansion changes in them is patched in registers below) -- their latency hides behind the
         // evaluator row's round trip and the softmax instead of heading the walk
@@ -982,6 +1019,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
         pin(kind); pin(state); pin(leaf); pin(ninfo); pin(ne); pin(nn); pin(row); pin(depth0); pin(root_n); pin(rtm);
         pin(nlegal); pin(rown); pin(ropp); pin(root_base); pin(pe0.eidx); pin(pe0.w0); pin(pe0.W);
         const bool active = state == 0 && kind != LEAF_NONE;
+        // a slot at its budget expands and backs up its last leaf below, selects nothing and is left LEAF_NONE: idle from then on
+        const bool walk = kCap ? (active && sim_idx < bud) : active;
         st.mark(0);
         if (do_expand && (kind == LEAF_EVAL || kind == LEAF_TERMINAL || kind == LEAF_COPY)) {
             float v;
@@ -1027,7 +1066,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
         st.mark(2);
         if (do_select) {
             uint8_t kind8 = LEAF_NONE;
-            if (active) {
+            if (walk) {
                 group_fence();  // edges written above are read below
                 u32 leaf2; int k2, depth; float tv;
                 LeafPos lpos; lpos.own = 0; lpos.opp = 0; lpos.legal = 0; lpos.info = 0; lpos.src = 0; lpos.src_e0 = 0;
@@ -1082,6 +1121,13 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
 template <class G>
 __global__ void __launch_bounds__(256) k_gumbel_step(EngineDev E, GumbelDev Gm, int do_expand, int do_select, u32 sim_idx) {
     tree_step_body<G, true>(E, Gm, do_expand, do_select, sim_idx);
+}
+
+// The tree step under playout cap randomisation: k_tree_step, every slot walking for its own budget.
+template <class G>
+__global__ void __launch_bounds__(256) k_cap_step(EngineDev E, CapDev Cp, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -1504,10 +1550,11 @@ __global__ void __launch_bounds__(256) k_root_stats(EngineDev E) {
 // M5's move choice, shared by k_play and k_root_policy: pi = N / sum N at the edges' actions (0 elsewhere)
 // and the index of the played edge -- tau = 1 (made < temp_moves): sampled ~ N with the counter RNG (seed, game id, moves
 // made), else the first maximum of N
-template <class G>
+// (kPi = false: the choice alone, pi is not touched -- a fast search under playout cap randomisation)
+template <class G, bool kPi = true>
 __device__ __forceinline__ int dev_puct_choice(const EngineDev& E, int g, const Edge* ed, int n, u32 sumN, int made, int round,
                                                float* pi) {
-    for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
+    if (kPi) for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
     int pick = 0;
     if (made < E.temp_moves) {  // tau = 1: sample ~ N with the counter RNG (seed, game id, moves made)
         u64 gid = E.id_base + (u64)round * E.id_stride + (u64)g;
@@ -1515,7 +1562,7 @@ __device__ __forceinline__ int dev_puct_choice(const EngineDev& E, int g, const 
         bool found = false;
         for (int i = 0; i < n; ++i) {
             const u32 w0 = ed[i].w0, N = e_N(w0);
-            pi[e_action(w0)] = fdiv((float)N, (float)sumN);
+            if (kPi) pi[e_action(w0)] = fdiv((float)N, (float)sumN);
             cum += N;
             if (!found && cum > rr) { pick = i; found = true; }
         }
@@ -1523,7 +1570,7 @@ __device__ __forceinline__ int dev_puct_choice(const EngineDev& E, int g, const 
         u32 bn = 0;
         for (int i = 0; i < n; ++i) {
             const u32 w0 = ed[i].w0, N = e_N(w0);
-            pi[e_action(w0)] = fdiv((float)N, (float)sumN);
+            if (kPi) pi[e_action(w0)] = fdiv((float)N, (float)sumN);
             if (N > bn) { bn = N; pick = i; }
         }
     }
@@ -1566,15 +1613,18 @@ __device__ __forceinline__ int dev_gumbel_choice(const GumbelDev& Gm, int g, con
 }
 
 // M5's rest after the choice of root edge `pick`: example row, env step, pass rule (reversi_terminal.py:31-35), terminal
-// handling, z back-fill (k_play and k_gumbel_play)
+// handling, z back-fill (k_play, k_gumbel_play and k_cap_play).  record = false: the move is played but no row is written and
+// nex does not advance (a fast search); a game may then finish with ex_len = 0
 template <class G>
 __device__ __forceinline__ void dev_play_tail(const EngineDev& E, int g, const Node& root, const Edge* ed, int pick, int round,
-                                              int nex, int made, int tm, size_t rowbase, size_t row, int restart) {
+                                              int nex, int made, int tm, size_t rowbase, size_t row, int restart, bool record = true) {
     const Edge pk = ed[pick];
     int a = e_action(pk.w0);
     u32 keep_node = e_child(pk.w3), keep_N = e_N(pk.w0);  // subtree reuse: the chosen child and its visits
-    E.ex_own[row] = root.own; E.ex_opp[row] = root.opp; E.ex_mover[row] = (int8_t)tm; E.ex_act[row] = (uint8_t)a;
-    nex++;
+    if (record) {
+        E.ex_own[row] = root.own; E.ex_opp[row] = root.opp; E.ex_mover[row] = (int8_t)tm; E.ex_act[row] = (uint8_t)a;
+        nex++;
+    }
     u64 own, opp;
     G::apply(root.own, root.opp, a, &own, &opp);
     tm = -tm; made++;
@@ -1638,6 +1688,27 @@ __global__ void __launch_bounds__(256) k_gumbel_play(EngineDev E, GumbelDev Gm, 
     size_t row = rowbase + nex;
     const int pick = dev_gumbel_choice<G>(Gm, g, ed, n, E.ex_pi + row * G::NA);
     dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart);
+}
+
+// M5 under playout cap randomisation: k_play, but only a full search (budget = sims) records its row; a fast
+// one plays its move by the same rule (tau = 1 sampling over its own visit sum included) and writes nothing
+template <class G>
+__global__ void __launch_bounds__(256) k_cap_play(EngineDev E, CapDev Cp, int restart) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    int n = (int)(root.info & 0xFFu);
+    u32 sumN = 0;
+    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
+    const bool full = Cp.budget[g] >= (u32)E.sims;
+    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
+    if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
+    size_t row = rowbase + nex;
+    const int pick = full ? dev_puct_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
+                          : dev_puct_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
+    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
 }
 
 // the pi and the action bz_engine_play would write and play, into pi [B][NA] / action [B] (idle or finished slots: zeros, -1)
@@ -1797,6 +1868,7 @@ struct bz_engine {
     hipEvent_t ahead[4];
     int n_ahead;
     GumbelDev gumbel;  // Gumbel root search (bz_engine_set_gumbel); gumbel.m = 0: off
+    CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
 };
 
 namespace {
@@ -1931,6 +2003,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     if (!e) { set_error("out of host memory"); return BZ_ENOMEM; }
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
     e->gumbel = GumbelDev{};  // off
+    e->cap = CapDev{};
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2068,6 +2141,10 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     const int carry_ok = epoch == e->eval_epoch;
     e->eval_epoch = epoch;
     BZ_DISPATCH(e, k_root_begin, stream, e->dev, e->search_seq, carry_ok);
+    if (e->cap.fast > 0) {  // this search's budgets
+        hipLaunchKernelGGL(k_cap_budget, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->cap);
+        BZ_LAUNCH_CHECK("k_cap_budget");
+    }
     e->pack_parity = 1;
     return BZ_OK;
 }
@@ -2080,6 +2157,7 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
         return BZ_OK;
     }
     if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
+    else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_cap_step, stream, e->dev, e->cap, do_expand, do_select, sim_idx);  // 
     else BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
     if (do_select) e->pack_parity = (int)(sim_idx & 1u);
     return BZ_OK;
@@ -2128,6 +2206,11 @@ BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_root, stream, e->dev, e->gumbel);
     if (!(e->dev.dir_eps > 0.0f)) return BZ_OK;
+    if (e->cap.fast > 0) {  // playout cap randomisation: the full searches only
+        hipLaunchKernelGGL(k_cap_noise, dim3((e->dev.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->dev, e->cap);
+        BZ_LAUNCH_CHECK("k_cap_noise");
+        return BZ_OK;
+    }
     hipLaunchKernelGGL(k_root_noise, dim3((e->dev.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->dev);
     BZ_LAUNCH_CHECK("k_root_noise");
     return BZ_OK;
@@ -2138,7 +2221,8 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     int ek = e->cfg.eval_kind;
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
     const bool noise = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
-    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1) {
+    // (playout cap randomisation: per-slot budgets live in the step kernels only)
+    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -2255,6 +2339,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     BZ_REQUIRE(finite && gumbel_scale >= 0.0f && maxvisit_init >= 0.0f && value_scale >= 0.0f,
                "bz_engine_set_gumbel: gumbel_scale, maxvisit_init and value_scale must be finite and >= 0");
     if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
     const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
     if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -2273,6 +2358,50 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     return BZ_OK;
 }
 
+/* ---- playout cap randomisation */
+namespace {
+// the combinations playout cap randomisation refuses (nullptr: none)
+const char* cap_refusal(const bz_engine_cfg& c) {
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "playout cap randomisation does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "playout cap randomisation does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
+    return nullptr;
+}
+inline int64_t cap_bytes(const bz_engine_cfg& c) { Carver k; k.take((int64_t)c.n_games * 4); return k.off; }
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_playout_cap_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_playout_cap_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_playout_cap_bytes: %s", kBadCfg); return -1; }
+    if (const char* why = cap_refusal(*cfg)) { set_error("bz_engine_playout_cap_bytes: %s", why); return -1; }
+    return cap_bytes(*cfg);
+}
+
+BZ_EXPORT int32_t bz_engine_set_playout_cap(bz_engine* e, int32_t fast_sims, uint32_t full_q, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_playout_cap: null engine");
+    if (fast_sims == 0) {  // off: every search has cfg.sims simulations and records its row again
+        e->cap = CapDev{};
+        return BZ_OK;
+    }
+    BZ_REQUIRE(fast_sims >= 1 && fast_sims < e->cfg.sims, "bz_engine_set_playout_cap: fast_sims must be 0 (off) or in 1 .. sims - 1");
+    BZ_REQUIRE(full_q <= 65536u, "bz_engine_set_playout_cap: full_q must be in 0 .. 65536 (the probability of a full search in units of 2^-16)");
+    if (const char* why = cap_refusal(e->cfg)) { set_error("bz_engine_set_playout_cap: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_playout_cap: playout cap randomisation does not combine with Gumbel root search (bz_engine_set_gumbel)");
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_playout_cap: the buffer must be non-null and 256-byte aligned");
+    const int64_t need = cap_bytes(e->cfg);
+    if (bytes < need) { set_error("bz_engine_set_playout_cap: buffer too small (%lld < %lld)", (long long)bytes, (long long)need); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)e->cfg.n_games * 4, (hipStream_t)stream));  // no search yet: no budgets
+    e->cap.fast = fast_sims; e->cap.full_q = full_q; e->cap.budget = static_cast<u32*>(buf);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t moves_made, int32_t sims, int32_t fast_sims, uint32_t full_q) {
+    if (!(sims >= 2 && sims <= BZ_ENGINE_MAX_SIMS && fast_sims >= 1 && fast_sims < sims && full_q <= 65536u)) {
+        set_error("bz_playout_cap_budget: need 1 <= fast_sims < sims <= %d and full_q in 0 .. 65536", (int)BZ_ENGINE_MAX_SIMS);
+        return -1;
+    }
+    return (int32_t)cap_budget(seed, gid, (u64)moves_made, sims, fast_sims, full_q);
+}
+
 BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
     BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
     BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, pi, action);
@@ -2284,6 +2413,7 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     {
         ProfScope ps(BZ_PROF_PLAY, stream);
         if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
+        else if (e->cap.fast > 0) BZ_DISPATCH(e, k_cap_play, stream, e->dev, e->cap, (int)restart);  // 
         else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
     if (e->dev.reuse) {  // the tree just searched becomes the source of the next root_begin's subtree copy
@@ -2386,7 +2516,7 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
 static bool search_is_fused(const bz_engine* e) {
     const int ek = e->cfg.eval_kind;
     return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !(e->dev.dir_eps > 0.0f) && e->dev.K == 1 &&
-           e->gumbel.m == 0;
+           e->gumbel.m == 0 && e->cap.fast == 0;
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree

@@ -174,11 +174,49 @@ def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0
     return GumbelConfig(int(m), float(cfg.scale), float(cfg.maxvisit_init), float(cfg.value_scale))
 
 
+@dataclass(frozen=True)
+class PlayoutCap:
+    """Playout cap randomisation (KataGo, Wu 2019, section 3.1): before every move a game draws a full
+    search (`sims` simulations, probability full_prob, records its example row) or a fast one (`fast_sims` simulations,
+    only plays its move).  1 <= fast_sims < sims; full_prob in [0, 1], applied in units of 2^-16."""
+    fast_sims: int
+    full_prob: float = 0.25
+
+    @property
+    def full_q(self):
+        """the probability of a full search in units of 2^-16 (what the engine compares 16 random bits with)"""
+        return int(round(float(self.full_prob) * 65536))
+
+
+def check_playout_cap(playout_cap, sims=None, reuse_subtree=False, leaves_per_step=1, gumbel=None):
+    """None / False: off (None returned); or a PlayoutCap -- validated, and refused with subtree reuse, leaves_per_step > 1
+    and Gumbel root search (ValueError, before any device is touched)"""
+    if playout_cap is None or playout_cap is False:
+        return None
+    cap = playout_cap
+    if not isinstance(cap, PlayoutCap):
+        raise ValueError(f"playout_cap must be None, False or a PlayoutCap (got {playout_cap!r})")
+    n = cap.fast_sims
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1 or (sims is not None and n >= int(sims)):
+        raise ValueError(f"playout_cap: fast_sims must be an int in 1..sims - 1 (got {n!r}" +
+                         (f", sims = {sims})" if sims is not None else ")"))
+    p = cap.full_prob
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= p <= 1.0:  # (NaN fails)
+        raise ValueError(f"playout_cap: full_prob must be a number in [0, 1] (got {p!r})")
+    if reuse_subtree:
+        raise ValueError("playout_cap: playout cap randomisation does not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("playout_cap: playout cap randomisation does not combine with leaves_per_step > 1")
+    if gumbel is not None and gumbel is not False:
+        raise ValueError("playout_cap: playout cap randomisation does not combine with Gumbel root search (gumbel)")
+    return PlayoutCap(int(n), float(p))
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1, gumbel=None):
+                 leaves_per_step=1, gumbel=None, playout_cap=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -195,11 +233,17 @@ class SelfPlayEngine:
         gumbel: None / False = PUCT at every node (the default, unchanged); True or a GumbelConfig = Gumbel
         root search: Gumbel-top-k plus sequential halving at the root (PUCT below it), the move is the halving's survivor and
         the example rows' pi is the improved policy.  Gumbel noise is drawn while moves made < temp_moves (and scale > 0).
-        Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0."""
+        Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0.
+
+        playout_cap: None / False = every search has `sims` simulations (the default, unchanged); a
+        PlayoutCap(fast_sims, full_prob) = every move draws a full search (sims, records its example row) or a fast one
+        (fast_sims, records nothing; Dirichlet noise is drawn on full searches only).  budgets() reads the last search's
+        draws.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel."""
         check_sims(sims, reuse_subtree)
         check_eval_cache(eval_cache)
         self.K = check_leaves_per_step(leaves_per_step)
         self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
+        self.playout_cap = check_playout_cap(playout_cap, sims, reuse_subtree, self.K, gumbel)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -245,6 +289,14 @@ class SelfPlayEngine:
             gpad = (-self.gws.data_ptr()) & 255
             self._call(L.bz_engine_set_gumbel, gc.max_considered, gc.scale, gc.maxvisit_init, gc.value_scale,
                        self.gws.data_ptr() + gpad, gbytes)
+        if self.playout_cap is not None:  # the engine's budget buffer (caller-owned, like the workspace)
+            pc = self.playout_cap
+            cbytes = L.bz_engine_playout_cap_bytes(C.byref(self.cfg))
+            if cbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.cws = torch.zeros(cbytes + 256, dtype=torch.uint8, device=self.device)
+            self._cpad = (-self.cws.data_ptr()) & 255
+            self._call(L.bz_engine_set_playout_cap, pc.fast_sims, pc.full_q, self.cws.data_ptr() + self._cpad, cbytes)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -349,6 +401,15 @@ class SelfPlayEngine:
         made < temp_moves); Gumbel: the improved policy and the Gumbel move"""
         pi, act = self.root_policy_dev()
         return pi.cpu().numpy(), act.cpu().numpy()
+
+    def budgets(self):
+        """playout cap randomisation: the simulation budget every slot drew for the last search, uint32 [B]
+        read from the device -- sims (full) or fast_sims; 0 for a slot that took no part (finished / idle, or no search yet)"""
+        if self.playout_cap is None:
+            raise RuntimeError("budgets(): the engine was built without playout_cap")
+        self.drain()
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.cws[self._cpad:self._cpad + 4 * self.B].view(torch.int32).cpu().numpy().view(np.uint32)
 
     def counters(self):
         """the work counters by name (_lib.COUNTER_NAMES); "n_collisions" only for leaves_per_step > 1"""
@@ -684,10 +745,12 @@ class PipelinedSelfPlay:
     host, and everything that hands data out (status, counters, pack_examples, examples ...) joins first."""
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
-                 game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, **engine_kwargs):
+                 game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
+                 **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
+        check_playout_cap(playout_cap, sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_eval_cache(engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
@@ -699,7 +762,7 @@ class PipelinedSelfPlay:
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                                       **engine_kwargs)
+                                       playout_cap=playout_cap, **engine_kwargs)
                         for i in range(pipelines)]
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
@@ -764,6 +827,11 @@ class PipelinedSelfPlay:
     def reset_counters(self):
         self._each(lambda e: e.reset_counters())
 
+    def budgets(self):
+        """the last search's budgets of all pipelines, in slot order (SelfPlayEngine.budgets)"""
+        self.sync()
+        return np.concatenate([e.budgets() for e in self.engines])
+
     def counters(self):
         tot = {}
         for c in self._each(lambda e: e.counters()):
@@ -812,15 +880,17 @@ class PipelinedSelfPlay:
 
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
-              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None):
+              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
     With a net evaluator the games run as two pipelines on two HIP streams (PipelinedSelfPlay: the shape bench.py
     measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine (DESIGN.md 3.12);
-    gumbel: SelfPlayEngine -- pi is then the improved policy."""
+    gumbel: SelfPlayEngine -- pi is then the improved policy.  playout_cap: SelfPlayEngine
+    -- only the moves searched with the full budget yield rows."""
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
+    check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -830,7 +900,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
-                           gumbel=gumbel)
+                           gumbel=gumbel, playout_cap=playout_cap)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -399,6 +399,27 @@ int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, float gumbel_
 /* the considered-visit sequence T[n_considered][k], k = 0 .. sims - 1, of mctx's get_sequence_of_considered_visits (the table
  * bz_engine_set_gumbel uploads; n_considered 1..64, sims 1..BZ_ENGINE_MAX_SIMS).  Host only. */
 int32_t bz_gumbel_considered_visits(int32_t n_considered, int32_t sims, uint16_t* out);
+/* Playout cap randomisation (KataGo, Wu 2019, section 3.1), opt-in per engine.  Before every search each
+ * slot draws its simulation budget: cfg.sims (a "full" search) when (rng_draw(seed ^ 0x706C61796F757443, game id, moves made)
+ * & 0xFFFF) < full_q, else fast_sims -- game id and moves made as the Dirichlet noise keys them.  The slot searches with that
+ * budget (its tree is bit for bit that of an engine with sims = budget) and then idles: it uses no evaluator row, while the
+ * caller still issues cfg.sims steps.  bz_engine_play records an example row for a full search only; a fast search plays its
+ * move by the same rule and writes nothing, so a finished game may have ex_len = 0 (unfinished stays -1) -- the packed block
+ * counts such a game in n_games.  Dirichlet noise is drawn on full searches only.  The budgets are drawn by
+ * bz_engine_root_begin, so step-API callers need no new call.  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more
+ * than one leaf per step, Gumbel root search.  Every evaluator and evaluation-cache mode works unchanged.  Searches go through
+ * the step kernels. */
+/* bytes of the caller-owned buffer: the budgets u32 [n_games] of the current search (0 = the slot took no part), rounded up
+ * to 256 bytes.  Needs no GPU; -1 (bz_last_error says why) for a bad config or a refused combination. */
+int64_t bz_engine_playout_cap_bytes(const bz_engine_cfg* cfg);
+/* switch the cap on (1 <= fast_sims < cfg.sims; full_q in 0 .. 65536 = the probability of a full search in units of 2^-16:
+ * 65536 = every search full, 0 = every search fast) or off (fast_sims 0), between searches.  buf: device memory of >=
+ * bz_engine_playout_cap_bytes bytes, 256-byte aligned, owned by the caller and kept alive while the mode is on; it is zeroed
+ * on `stream`. */
+int32_t bz_engine_set_playout_cap(bz_engine* e, int32_t fast_sims, uint32_t full_q, void* buf, int64_t bytes, void* stream);
+/* the budget the engine draws for game `gid` at `moves_made` (sims or fast_sims; -1 for bad arguments).  Host only: for tests
+ * and for callers who want to predict a game's budgets. */
+int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t moves_made, int32_t sims, int32_t fast_sims, uint32_t full_q);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
