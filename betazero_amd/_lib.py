@@ -143,6 +143,9 @@ _SIGS = {
     "bz_engine_playout_cap_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_set_playout_cap": (i32, [vp, i32, u32, vp, i64, vp]),
     "bz_playout_cap_budget": (i32, [u64, u64, u32, i32, i32, u32]),
+    "bz_engine_set_forced_playouts": (i32, [vp, C.c_float, i32, vp]),
+    "bz_engine_forced_playouts_check": (i32, [C.POINTER(EngineCfg), C.c_float]),
+    "bz_forced_prune": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),

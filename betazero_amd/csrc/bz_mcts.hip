@@ -146,6 +146,60 @@ __host__ __device__ __forceinline__ u32 cap_budget(u64 seed, u64 gid, u64 made, 
     return (u32)(rng_draw(seed ^ kCapKey, gid, made) & 0xFFFFULL) < full_q ? (u32)sims : (u32)fast;
 }
 
+// Forced playouts and policy target pruning (k = 0: off), set by bz_engine_set_forced_playouts.  Like CapDev a
+// kernel argument of the forced kernels only.
+struct ForcedDev { float k; int prune; };
+// n_forced of a root edge with prior P at the root's child visit sum sumN
+__host__ __device__ __forceinline__ float forced_nf(float k, float P, u32 sumN) {
+    float t = k * P;
+    t = t * (float)sumN;
+    return fsqrt(t);
+}
+// the DESIGN.md 3.3 score of an edge with mean value q and prior P at Nf visits
+__host__ __device__ __forceinline__ float puct_score(float q, float c_puct, float P, float sq, float Nf) {
+    float u = c_puct * P;
+    u = u * sq;
+    u = fdiv(u, 1.0f + Nf);
+    return q + u;
+}
+// Policy target pruning over the root's n edges: sink(i, edge, N') for every edge in ascending order, the sum
+// of the N' returned.  The kernels (sink: the pi row) and bz_forced_prune (sink: N_out) run this one function.
+template <class Sink>
+__host__ __device__ __forceinline__ u32 forced_prune(const Edge* ed, int n, float c_puct, float k, Sink&& sink) {
+    u32 sumN = 0, bn = 0;
+    int cs = 0;
+    for (int i = 0; i < n; ++i) {
+        const u32 N = e_N(ed[i].w0);
+        sumN += N;
+        if (N > bn) { bn = N; cs = i; }
+    }
+    const float sq = fsqrt((float)(sumN > 1u ? sumN : 1u));
+    float ss = 0.0f;
+    if (n > 0) {
+        const Edge b = ed[cs];
+        ss = puct_score(bn > 0 ? fdiv(b.W, (float)bn) : 0.0f, c_puct, b.P, sq, (float)bn);
+    }
+    u32 sum2 = 0;
+    for (int i = 0; i < n; ++i) {
+        const Edge e = ed[i];
+        const u32 N = e_N(e.w0);
+        u32 Np = N;
+        if (i != cs && N > 0) {
+            const float nf = forced_nf(k, e.P, sumN);
+            const u32 lim = !(nf < (float)N) ? N : (u32)__builtin_ceilf(nf);  // min(m, N), m the smallest integer >= nf
+            const float q = fdiv(e.W, (float)N);
+            for (u32 t = 1; t <= lim; ++t) {
+                if (!(puct_score(q, c_puct, e.P, sq, (float)(N - t)) < ss)) break;
+                Np = N - t;
+            }
+            if (Np < N && Np <= 1u) Np = 0;
+        }
+        sink(i, e, Np);
+        sum2 += Np;
+    }
+    return sum2;
+}
+
 struct Cnt { u32 v[CNT_N]; };
 
 // Diagnostic build only (betazero_amd.build.build_variant("treestamps", ["-DBZ_EXP_TREE_STAMPS"]), tools/exp_tree_stamps.py):
@@ -507,10 +561,12 @@ __device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const Gumbel
 // M2: PUCT walk from the root; creates the child node behind the chosen unexpanded edge (env step:
 // apply + legal + terminal).  All lanes of the group return the same values.
 // kGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead; every deeper level is PUCT.
-template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false>
+// kForced (k_forced_step / k_forced_cap_step): at the root an edge with 0 < N < fsqrt(fk P sumN) scores +inf
+// (fk = 0: this slot does not force); every deeper level is PUCT.
+template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
-                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr) {
+                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f) {
     constexpr int kGW = G::GW;
     Node* nodes = E.nodes + (size_t)g * E.ncap;
     Edge* edges = E.edges + (size_t)g * E.ecap;
@@ -540,6 +596,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
                 u = u * sq;
                 u = fdiv(u, 1.0f + (float)N);
                 cd.sc = q + u; cd.w0 = e.w0; cd.w3 = e.w3; cd.W = e.W;
+                if (kForced && depth == 0 && fk > 0.0f && N > 0 && (float)N < forced_nf(fk, e.P, sumN)) cd.sc = __builtin_inff();
             }
             group_argmax<kGW>(cd);
             if (cd.sc > bests) { bests = cd.sc; best = cd.i; bestw0 = cd.w0; bestw3 = cd.w3; bestW = cd.W; }
@@ -983,9 +1040,10 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 // with the root's expansion); with kGumbel = false it is k_tree_step's code exactly.
 // kCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget; both flags off, the code is
 // k_tree_step's / k_gumbel_step's as before.
-template <class G, bool kGumbel, bool kCap = false>
+// kForced: forced playouts with parameter fk at the root -- under kCap in the full searches only.
+template <class G, bool kGumbel, bool kCap = false, bool kForced = false>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
-                                               const u32* budget = nullptr) {
+                                               const u32* budget = nullptr, float fk = 0.0f) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1073,7 +1131,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 RootRef root; root.own = rown; root.opp = ropp; root.tm = rtm; root.n = root_n;
                 root.sumN = sim_idx + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
                 PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
-                dev_select<G, PathHbm<kGW>, false, kGumbel>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm);  // ---- one round trip per level
+                const float fslot = (kForced && (!kCap || bud >= (u32)E.sims)) ? fk : 0.0f;
+                dev_select<G, PathHbm<kGW>, false, kGumbel, kForced>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
                 sink.flush(sub, depth);
                 if (sub == 0) {
                     E.hot[g].n_nodes = nn; E.hot[g].leaf_node = leaf2; E.hot[g].depth = (u32)depth;
@@ -1128,6 +1187,19 @@ template <class G>
 __global__ void __launch_bounds__(256) k_cap_step(EngineDev E, CapDev Cp, int do_expand, int do_select, u32 sim_idx) {
     const GumbelDev none{};
     tree_step_body<G, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget);
+}
+
+// The tree step with forced playouts at the root: k_tree_step / k_cap_step with the forced rule in the root's
+// scores.  F.k travels as a kernel argument.
+template <class G>
+__global__ void __launch_bounds__(256) k_forced_step(EngineDev E, ForcedDev F, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, F.k);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_forced_cap_step(EngineDev E, CapDev Cp, ForcedDev F, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -1711,6 +1783,77 @@ __global__ void __launch_bounds__(256) k_cap_play(EngineDev E, CapDev Cp, int re
     dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
 }
 
+// The move and the pi of a search with forced playouts: the DESIGN.md 3.7 choice over the raw N; pi from the
+// pruned N' (F.prune) or the raw N.  pi = nullptr: the choice alone.
+template <class G>
+__device__ __forceinline__ int dev_forced_choice(const EngineDev& E, const ForcedDev& F, int g, const Edge* ed, int n, u32 sumN,
+                                                 int made, int round, float* pi) {
+    const int pick = dev_puct_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
+    if (pi) {
+        for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
+        const auto sink = [pi](int, const Edge& e, u32 Np) { pi[e_action(e.w0)] = (float)Np; };  // (the count for now: divided below)
+        u32 S = sumN;
+        if (F.prune) S = forced_prune(ed, n, E.c_puct, F.k, sink);
+        else for (int i = 0; i < n; ++i) sink(i, ed[i], e_N(ed[i].w0));
+        for (int i = 0; i < n; ++i) {
+            float* p = pi + e_action(ed[i].w0);
+            *p = fdiv(*p, (float)S);
+        }
+    }
+    return pick;
+}
+
+// M5 with forced playouts: k_play / k_cap_play with the pruned pi in the recorded row; the move is theirs.
+// Under the cap (kCap) a fast search was not forced and records nothing.
+template <class G, bool kCap>
+__device__ __forceinline__ void forced_play_body(const EngineDev& E, const u32* budget, const ForcedDev& F, int restart) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    int n = (int)(root.info & 0xFFu);
+    u32 sumN = 0;
+    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
+    const bool full = kCap ? budget[g] >= (u32)E.sims : true;
+    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
+    if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
+    size_t row = rowbase + nex;
+    const int pick = dev_forced_choice<G>(E, F, g, ed, n, sumN, made, round, full ? E.ex_pi + row * G::NA : nullptr);
+    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_forced_play(EngineDev E, ForcedDev F, int restart) {
+    forced_play_body<G, false>(E, nullptr, F, restart);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_forced_cap_play(EngineDev E, CapDev Cp, ForcedDev F, int restart) {
+    forced_play_body<G, true>(E, Cp.budget, F, restart);
+}
+
+// k_root_policy with forced playouts: the pruned pi and the unchanged action; under the cap (Cp.fast > 0) a
+// fast search was not forced and reports its raw pi
+template <class G>
+__global__ void __launch_bounds__(256) k_forced_root_policy(EngineDev E, CapDev Cp, ForcedDev F, float* pi_out, int32_t* act_out) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    float* pi = pi_out + (size_t)g * G::NA;
+    const Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    const int n = (int)(root.info & 0xFFu);
+    if (E.g_state[g] != 0 || n == 0) {  // (n == 0: no search has expanded this slot's root)
+        for (int a = 0; a < G::NA; ++a) pi[a] = 0.0f;
+        act_out[g] = -1;
+        return;
+    }
+    u32 sumN = 0;
+    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    ForcedDev Fg = F;
+    if (Cp.fast > 0 && Cp.budget[g] < (u32)E.sims) Fg.prune = 0;
+    const int pick = dev_forced_choice<G>(E, Fg, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+    act_out[g] = e_action(ed[pick].w0);
+}
+
 // the pi and the action bz_engine_play would write and play, into pi [B][NA] / action [B] (idle or finished slots: zeros, -1)
 template <class G>
 __global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, float* pi_out, int32_t* act_out) {
@@ -1869,6 +2012,7 @@ struct bz_engine {
     int n_ahead;
     GumbelDev gumbel;  // Gumbel root search (bz_engine_set_gumbel); gumbel.m = 0: off
     CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
+    ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
 };
 
 namespace {
@@ -2004,6 +2148,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
     e->gumbel = GumbelDev{};  // off
     e->cap = CapDev{};
+    e->forced = ForcedDev{};
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2157,6 +2302,8 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
         return BZ_OK;
     }
     if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
+    else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH_G(e, k_forced_cap_step, stream, e->dev, e->cap, e->forced, do_expand, do_select, sim_idx);
+    else if (e->forced.k > 0.0f) BZ_DISPATCH_G(e, k_forced_step, stream, e->dev, e->forced, do_expand, do_select, sim_idx);  // 
     else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_cap_step, stream, e->dev, e->cap, do_expand, do_select, sim_idx);  // 
     else BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
     if (do_select) e->pack_parity = (int)(sim_idx & 1u);
@@ -2221,8 +2368,8 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     int ek = e->cfg.eval_kind;
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
     const bool noise = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
-    // (playout cap randomisation: per-slot budgets live in the step kernels only)
-    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0) {
+    // (playout cap randomisation: per-slot budgets live in the step kernels only; forced playouts: the forced root rule too)
+    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f)) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -2340,6 +2487,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
                "bz_engine_set_gumbel: gumbel_scale, maxvisit_init and value_scale must be finite and >= 0");
     if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
     BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
+    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_gumbel: Gumbel root search does not combine with forced playouts (bz_engine_set_forced_playouts)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
     const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
     if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -2402,8 +2550,55 @@ BZ_EXPORT int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t mo
     return (int32_t)cap_budget(seed, gid, (u64)moves_made, sims, fast_sims, full_q);
 }
 
+/* ---- forced playouts and policy target pruning */
+namespace {
+// what forced playouts refuse (nullptr: nothing)
+const char* forced_refusal(const bz_engine_cfg& c, float k) {
+    if (!(k >= 0.0f && k <= 3.0e38f)) return "forced playouts: k must be finite and >= 0 (0 = off)";
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "forced playouts do not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "forced playouts do not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
+    return nullptr;
+}
+}  // namespace
+
+BZ_EXPORT int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_forced_playouts_check: %s", kBadFlags); return BZ_EINVAL; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_forced_playouts_check: %s", kBadCfg); return BZ_EINVAL; }
+    if (const char* why = forced_refusal(*cfg, k)) { set_error("bz_engine_forced_playouts_check: %s", why); return BZ_EINVAL; }
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t prune, void* stream) {
+    (void)stream;  // (nothing is uploaded: k and the prune flag travel as kernel arguments)
+    BZ_REQUIRE(e, "bz_engine_set_forced_playouts: null engine");
+    if (k == 0.0f) {  // off: the plain (or the cap's) kernels again
+        e->forced = ForcedDev{};
+        return BZ_OK;
+    }
+    if (const char* why = forced_refusal(e->cfg, k)) { set_error("bz_engine_set_forced_playouts: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_forced_playouts: forced playouts do not combine with Gumbel root search (bz_engine_set_gumbel)");
+    e->forced.k = k; e->forced.prune = prune ? 1 : 0;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_forced_prune(const uint32_t* N, const float* W, const float* P, int32_t n, float c_puct, float k, uint32_t* N_out) {
+    BZ_REQUIRE(N && W && P && N_out && n >= 1 && n <= 255, "bz_forced_prune: null pointer or n outside 1 .. 255");
+    BZ_REQUIRE(k > 0.0f && k <= 3.0e38f, "bz_forced_prune: k must be finite and > 0");
+    Edge ed[255];
+    for (int i = 0; i < n; ++i) {
+        if (N[i] > kNMask) { set_error("bz_forced_prune: N[%d] = %u exceeds %u", i, N[i], kNMask); return BZ_EINVAL; }
+        ed[i].w0 = N[i]; ed[i].W = W[i]; ed[i].P = P[i]; ed[i].w3 = 0;
+    }
+    forced_prune(ed, n, c_puct, k, [N_out](int i, const Edge&, u32 Np) { N_out[i] = Np; });
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
     BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
+    if (e->forced.k > 0.0f) {  // 
+        BZ_DISPATCH(e, k_forced_root_policy, stream, e->dev, e->cap, e->forced, pi, action);
+        return BZ_OK;
+    }
     BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, pi, action);
     return BZ_OK;
 }
@@ -2413,6 +2608,8 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     {
         ProfScope ps(BZ_PROF_PLAY, stream);
         if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
+        else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH(e, k_forced_cap_play, stream, e->dev, e->cap, e->forced, (int)restart);
+        else if (e->forced.k > 0.0f) BZ_DISPATCH(e, k_forced_play, stream, e->dev, e->forced, (int)restart);  // 
         else if (e->cap.fast > 0) BZ_DISPATCH(e, k_cap_play, stream, e->dev, e->cap, (int)restart);  // 
         else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
@@ -2516,7 +2713,7 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
 static bool search_is_fused(const bz_engine* e) {
     const int ek = e->cfg.eval_kind;
     return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !(e->dev.dir_eps > 0.0f) && e->dev.K == 1 &&
-           e->gumbel.m == 0 && e->cap.fast == 0;
+           e->gumbel.m == 0 && e->cap.fast == 0 && !(e->forced.k > 0.0f);
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree

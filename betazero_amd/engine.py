@@ -212,11 +212,44 @@ def check_playout_cap(playout_cap, sims=None, reuse_subtree=False, leaves_per_st
     return PlayoutCap(int(n), float(p))
 
 
+@dataclass(frozen=True)
+class ForcedPlayouts:
+    """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2): every visited root child
+    is searched until it has sqrt(k P sum N) visits (P the prior after the Dirichlet noise); the recorded pi then drops
+    the visits PUCT would not have made on its own (prune=True) or stays N / sum N (prune=False).  k > 0, finite."""
+    k: float = 2.0
+    prune: bool = True
+
+
+def check_forced_playouts(forced_playouts, reuse_subtree=False, leaves_per_step=1, gumbel=None):
+    """None / False: off (None returned); True: ForcedPlayouts(); or a ForcedPlayouts -- validated, and refused with subtree
+    reuse, leaves_per_step > 1 and Gumbel root search (ValueError, before any device is touched)"""
+    if forced_playouts is None or forced_playouts is False:
+        return None
+    fp = ForcedPlayouts() if forced_playouts is True else forced_playouts
+    if not isinstance(fp, ForcedPlayouts):
+        raise ValueError(f"forced_playouts must be None, False, True or a ForcedPlayouts (got {forced_playouts!r})")
+    k = fp.k
+    with np.errstate(over="ignore", under="ignore"):
+        k32 = float(np.float32(k)) if not isinstance(k, bool) and isinstance(k, (int, float, np.integer, np.floating)) else 0.0
+    if not 0.0 < k32 < np.inf:
+        raise ValueError(f"forced_playouts: k must be a finite number > 0 in float32 (got {k!r})")  # (NaN fails)
+    if not isinstance(fp.prune, (bool, np.bool_)):
+        raise ValueError(f"forced_playouts: prune must be a bool (got {fp.prune!r})")
+    if reuse_subtree:
+        raise ValueError("forced_playouts: forced playouts do not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("forced_playouts: forced playouts do not combine with leaves_per_step > 1")
+    if gumbel is not None and gumbel is not False:
+        raise ValueError("forced_playouts: forced playouts do not combine with Gumbel root search (gumbel)")
+    return ForcedPlayouts(float(k), bool(fp.prune))
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1, gumbel=None, playout_cap=None):
+                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -238,12 +271,18 @@ class SelfPlayEngine:
         playout_cap: None / False = every search has `sims` simulations (the default, unchanged); a
         PlayoutCap(fast_sims, full_prob) = every move draws a full search (sims, records its example row) or a fast one
         (fast_sims, records nothing; Dirichlet noise is drawn on full searches only).  budgets() reads the last search's
-        draws.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel."""
+        draws.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel.
+
+        forced_playouts: None / False = off (the default, unchanged); True or a ForcedPlayouts(k, prune) =
+        forced playouts at the root and, with prune, the pruned policy target in the example rows and in root_policy().  The
+        move choice and root_stats() keep the raw visits.  Under playout_cap only the full searches force.  Refused with
+        reuse_subtree, leaves_per_step > 1 and gumbel."""
         check_sims(sims, reuse_subtree)
         check_eval_cache(eval_cache)
         self.K = check_leaves_per_step(leaves_per_step)
         self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
         self.playout_cap = check_playout_cap(playout_cap, sims, reuse_subtree, self.K, gumbel)
+        self.forced_playouts = check_forced_playouts(forced_playouts, reuse_subtree, self.K, gumbel)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -297,6 +336,8 @@ class SelfPlayEngine:
             self.cws = torch.zeros(cbytes + 256, dtype=torch.uint8, device=self.device)
             self._cpad = (-self.cws.data_ptr()) & 255
             self._call(L.bz_engine_set_playout_cap, pc.fast_sims, pc.full_q, self.cws.data_ptr() + self._cpad, cbytes)
+        if self.forced_playouts is not None:
+            self._call(L.bz_engine_set_forced_playouts, self.forced_playouts.k, int(self.forced_playouts.prune))
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -746,11 +787,12 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 **engine_kwargs):
+                 forced_playouts=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
         check_playout_cap(playout_cap, sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
+        check_forced_playouts(forced_playouts, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_eval_cache(engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
@@ -762,7 +804,7 @@ class PipelinedSelfPlay:
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                                       playout_cap=playout_cap, **engine_kwargs)
+                                       playout_cap=playout_cap, forced_playouts=forced_playouts, **engine_kwargs)
                         for i in range(pipelines)]
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
@@ -880,17 +922,19 @@ class PipelinedSelfPlay:
 
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
-              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None):
+              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
     With a net evaluator the games run as two pipelines on two HIP streams (PipelinedSelfPlay: the shape bench.py
     measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine (DESIGN.md 3.12);
     gumbel: SelfPlayEngine -- pi is then the improved policy.  playout_cap: SelfPlayEngine
-    -- only the moves searched with the full budget yield rows."""
+    -- only the moves searched with the full budget yield rows.  forced_playouts: SelfPlayEngine -- pi is
+    then the pruned policy target."""
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
     check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
+    check_forced_playouts(forced_playouts, reuse_subtree, leaves_per_step, gumbel)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -900,7 +944,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
-                           gumbel=gumbel, playout_cap=playout_cap)
+                           gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

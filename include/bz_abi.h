@@ -420,6 +420,28 @@ int32_t bz_engine_set_playout_cap(bz_engine* e, int32_t fast_sims, uint32_t full
 /* the budget the engine draws for game `gid` at `moves_made` (sims or fast_sims; -1 for bad arguments).  Host only: for tests
  * and for callers who want to predict a game's budgets. */
 int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t moves_made, int32_t sims, int32_t fast_sims, uint32_t full_q);
+/* Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2), opt-in per engine, for self-play.
+ * Forced playouts: at the root (depth 0 of a walk) an edge with N > 0 and float(N) < fsqrt((k * P) * float(sum N)) -- P the prior
+ * after the Dirichlet noise, sum N the root's child visit sum so far -- scores +inf; the walk takes the first maximum, so the
+ * lowest forced action.  Policy target pruning (prune != 0): the pi of the example row and of bz_engine_root_policy is N' / sum N'
+ * with the N' of bz_forced_prune below; the move is chosen from the raw N as before, and bz_engine_root_stats
+ * reports the raw N.  prune == 0: forcing alone, pi = N / sum N.  Under playout cap randomisation only the full searches force
+ * (and only they record).  Refused (BZ_EINVAL with a message): subtree reuse, more than one leaf per step, Gumbel root search,
+ * a negative or non-finite k.  Dirichlet noise, the playout cap, every evaluator and every evaluation-cache mode work
+ * unchanged.  Searches go through the step kernels. */
+/* switch forced playouts on (k > 0; KataGo's default is 2.0) or off (k == 0), between searches.  Nothing is uploaded: `stream`
+ * is accepted for symmetry with the other setters. */
+int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t prune, void* stream);
+/* BZ_OK when an engine of this config accepts bz_engine_set_forced_playouts(e, k, ...), else BZ_EINVAL (bz_last_error says
+ * why: a bad config, a refused combination, a bad k).  Needs no GPU.  (Gumbel root search is not part of the config: the two
+ * setters refuse each other.) */
+int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k);
+/* Policy target pruning of one root, the function the kernels run.  N, W, P [n]: the root edges' visits, value sums and priors
+ * in edge order (ascending action), n in 1 .. 255, N[i] <= 16383, k finite and > 0.  N_out [n]: with c* the first maximum of N
+ * and s* its DESIGN.md 3.3 score, every other visited edge loses visits one at a time, up to min(ceil(fsqrt((k * P) *
+ * float(sum N))), N), while its score with the reduced N in the u term stays below s*; an edge that lost a visit and is left
+ * with <= 1 gets 0; c* and unvisited edges keep theirs.  Host only. */
+int32_t bz_forced_prune(const uint32_t* N, const float* W, const float* P, int32_t n, float c_puct, float k, uint32_t* N_out);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */

@@ -34,7 +34,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
-from betazero_amd.engine import PipelinedSelfPlay, PlayoutCap, check_playout_cap, concat_device_examples  # noqa: E402
+from betazero_amd.engine import (ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_playout_cap,  # noqa: E402
+                                 concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
@@ -70,6 +71,11 @@ def main():
                     "is searched with --sims simulations with probability --full-prob (and recorded) or with this many (and not "
                     "recorded); 0 = off.  Not with --gumbel")
     ap.add_argument("--full-prob", type=float, default=0.25, help="probability of a full search under --fast-sims")
+    ap.add_argument("--forced-k", type=float, default=0.0, help="self-play with forced playouts and policy target pruning (DESIGN.md "
+                    "3.16; KataGo uses 2): every visited root child is searched up to sqrt(k P sum N) visits and the recorded pi drops "
+                    "the visits PUCT would not have made; 0 = off.  Composes with --fast-sims (full searches only) and the Dirichlet "
+                    "noise; not with --gumbel")
+    ap.add_argument("--no-prune", action="store_true", help="under --forced-k: record the raw N / sum N (ablation)")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -92,6 +98,7 @@ def main():
     cand = DeviceNet.from_module(module, bmax) if args.gate_games else dnet
     gumbel = True if args.gumbel else None
     cap = check_playout_cap(PlayoutCap(args.fast_sims, args.full_prob) if args.fast_sims else None, args.sims, gumbel=gumbel)
+    forced = check_forced_playouts(ForcedPlayouts(args.forced_k, not args.no_prune) if args.forced_k else None, gumbel=gumbel)
     lines = []
 
     def emit(d):
@@ -120,7 +127,7 @@ def main():
     for it in range(1, args.iters + 1):
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
-                               openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap,
+                               openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
                                **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
@@ -175,6 +182,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
               "arena": arena("net_bf16", cand), **gate})
