@@ -146,6 +146,13 @@ _SIGS = {
     "bz_engine_set_forced_playouts": (i32, [vp, C.c_float, i32, vp]),
     "bz_engine_forced_playouts_check": (i32, [C.POINTER(EngineCfg), C.c_float]),
     "bz_forced_prune": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
+    "bz_engine_surprise_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_surprise": (i32, [vp, vp, i64, vp]),
+    "bz_engine_pack_surprise": (i32, [vp, vp, i64, i32, vp]),
+    "bz_surprise_kl": (i32, [vp, vp, i32, vp]),
+    "bz_surprise_resample_workspace_bytes": (i64, [i64]),
+    "bz_surprise_resample": (i32, [vp, vp, vp, vp, vp, i64, C.c_float, u64, vp, i64, vp, vp, i64, vp, vp]),
+    "bz_surprise_count": (i32, [C.c_float, C.c_float, C.c_float, u64, i64, i32, u64, u64, C.POINTER(i32)]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),

@@ -36,6 +36,7 @@
 #include "bz_common.h"
 #include "bz_math.h"
 #include "bz_rules.h"
+#include "bz_surprise.h"
 
 using namespace bz;
 
@@ -199,6 +200,12 @@ __host__ __device__ __forceinline__ u32 forced_prune(const Edge* ed, int n, floa
     }
     return sum2;
 }
+
+// Policy surprise weighting (prior = nullptr: off), set by bz_engine_set_surprise in the caller's buffer: every
+// root's raw prior [B][MAXCH] in edge order as the expansion stored it (k_surp_save, before any noise), the row the play
+// kernel is about to write per slot (row + 1; 0 = none) and the rows' kl [rounds][B][t_max].  A kernel argument of the
+// surprise kernels only: the feature observes, no other kernel's code changes.
+struct SurpDev { float* prior; u64* pend; float* ex_kl; };
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -1992,6 +1999,59 @@ __global__ void __launch_bounds__(256) k_pack_rows(EngineDev E, char* blk, Packe
     for (int k = lane; k < len * E.na; k += 64) pi[k] = sp[k];
 }
 
+// ---- policy surprise weighting: one-lane-per-game kernels around the search and the play kernels
+// the raw priors of every active game's expanded root -- fresh or kept from the previous move -- before k_root_noise /
+// k_cap_noise rewrite them (bz_engine_root_noise); without noise nothing rewrites them and bz_engine_play launches this
+template <class G>
+__global__ void __launch_bounds__(256) k_surp_save(EngineDev E, SurpDev S) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    const int n = (int)(r.info & 0xFFu);
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    float* pr = S.prior + (size_t)g * G::MAXCH;
+    for (int i = 0; i < n && i < G::MAXCH; ++i) pr[i] = ed[i].P;
+}
+// in front of the play kernel: the row it is about to write, by its own rule (budget: the playout cap's, or null -- a fast
+// search records nothing)
+__global__ void __launch_bounds__(256) k_surp_note(EngineDev E, SurpDev S, const u32* budget) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    u64 p = 0;
+    const int nex = E.g_state[g] == 0 ? E.g_nex[g] : E.t_max;
+    if (nex < E.t_max && !(budget && budget[g] < (u32)E.sims))
+        p = ((u64)E.g_round[g] * (u64)E.B + (u64)g) * (u64)E.t_max + (u64)nex + 1ULL;
+    S.pend[g] = p;
+}
+// behind it: the noted row's kl from the pi the play kernel recorded and the saved priors (the searched tree is still in
+// place: the root's edges give the actions)
+template <class G>
+__global__ void __launch_bounds__(256) k_surp_kl(EngineDev E, SurpDev S) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    const u64 p = S.pend[g];
+    if (p == 0) return;
+    S.pend[g] = 0;
+    const size_t row = (size_t)(p - 1ULL);
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    int n = (int)(r.info & 0xFFu);
+    n = n < G::MAXCH ? n : G::MAXCH;
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    const float* pi = E.ex_pi + row * G::NA;
+    const float* pr = S.prior + (size_t)g * G::MAXCH;
+    S.ex_kl[row] = surprise_kl(n, [pi, ed](int i) { return pi[e_action(ed[i].w0)]; }, [pr](int i) { return pr[i]; });
+}
+// ex_kl in the packed block's row order: the pack_off k_pack_scan left (it counts the rows earlier engines appended)
+__global__ void __launch_bounds__(256) k_pack_kl(EngineDev E, SurpDev S, float* out, int64_t cap) {
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= E.rounds * E.B) return;
+    const int off = E.pack_off[i];
+    if (off < 0) return;
+    const int len = E.ex_len[i];
+    const size_t src = (size_t)i * E.t_max;
+    for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = S.ex_kl[src + t];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2013,6 +2073,7 @@ struct bz_engine {
     GumbelDev gumbel;  // Gumbel root search (bz_engine_set_gumbel); gumbel.m = 0: off
     CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
     ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
+    SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
 };
 
 namespace {
@@ -2149,6 +2210,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->gumbel = GumbelDev{};  // off
     e->cap = CapDev{};
     e->forced = ForcedDev{};
+    e->surp = SurpDev{};
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2351,6 +2413,8 @@ BZ_EXPORT int32_t bz_engine_expand_backup(bz_engine* e, void* stream) {
  * Step-API order: root_begin, evaluate, expand_backup, root_noise, then select(0) ... -- what bz_engine_search does. */
 BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    //  the raw priors, before the noise rewrites them; without noise nothing ever does and bz_engine_play saves them
+    if (e->surp.prior && e->dev.dir_eps > 0.0f) BZ_DISPATCH(e, k_surp_save, stream, e->dev, e->surp);
     if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_root, stream, e->dev, e->gumbel);
     if (!(e->dev.dir_eps > 0.0f)) return BZ_OK;
     if (e->cap.fast > 0) {  // playout cap randomisation: the full searches only
@@ -2363,11 +2427,14 @@ BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
     return BZ_OK;
 }
 
+// the roots are expanded on their own and bz_engine_root_noise runs before the first walk: Dirichlet noise, Gumbel root search
+static bool root_prep(const bz_engine* e) { return e->dev.dir_eps > 0.0f || e->gumbel.m > 0; }
+
 BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     int ek = e->cfg.eval_kind;
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
-    const bool noise = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
+    const bool noise = root_prep(e);
     // (playout cap randomisation: per-slot budgets live in the step kernels only; forced playouts: the forced root rule too)
     if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f)) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
@@ -2593,6 +2660,52 @@ BZ_EXPORT int32_t bz_forced_prune(const uint32_t* N, const float* W, const float
     return BZ_OK;
 }
 
+/* ---- policy surprise weighting */
+namespace {
+struct SurpOffsets { int64_t prior, pend, ex_kl, total; };
+SurpOffsets surp_carve(const bz_engine_cfg& c) {
+    SurpOffsets o{};
+    Carver k;
+    const int64_t B = c.n_games, maxch = c.game == BZ_GAME_TTT ? TicTacToe::MAXCH : Reversi::MAXCH;
+    o.prior = k.take(B * maxch * 4);
+    o.pend = k.take(B * 8);
+    o.ex_kl = k.take((int64_t)c.rounds * B * c.t_max * 4);
+    o.total = k.off;
+    return o;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_surprise_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_surprise_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_surprise_bytes: %s", kBadCfg); return -1; }
+    return surp_carve(*cfg).total;
+}
+
+BZ_EXPORT int32_t bz_engine_set_surprise(bz_engine* e, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_surprise: null engine");
+    if (!buf) {  // off: no extra launch
+        e->surp = SurpDev{};
+        return BZ_OK;
+    }
+    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_surprise: the buffer must be 256-byte aligned");
+    const SurpOffsets o = surp_carve(e->cfg);
+    if (bytes < o.total) { set_error("bz_engine_set_surprise: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no prior saved, no row pending, every kl 0
+    e->surp.prior = at<float>(buf, o.prior); e->surp.pend = at<u64>(buf, o.pend); e->surp.ex_kl = at<float>(buf, o.ex_kl);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_pack_surprise(bz_engine* e, float* out, int64_t cap_rows, int32_t append_rows, void* stream) {
+    BZ_REQUIRE(e && out, "bz_engine_pack_surprise: null pointer");
+    BZ_REQUIRE(e->surp.prior, "bz_engine_pack_surprise: policy surprise weighting is off (bz_engine_set_surprise)");
+    BZ_REQUIRE(cap_rows >= 1 && cap_rows <= (int64_t(1) << 31) - 1 && append_rows >= 0 && append_rows <= cap_rows,
+               "bz_engine_pack_surprise: bad capacity or append_rows");
+    const int n = e->dev.rounds * e->dev.B;
+    hipLaunchKernelGGL(k_pack_kl, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp, out, cap_rows);
+    BZ_LAUNCH_CHECK("k_pack_kl");
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
     BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
     if (e->forced.k > 0.0f) {  // 
@@ -2605,6 +2718,14 @@ BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action
 
 BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    if (e->surp.prior) {  //  the row this play is about to write
+        // without Dirichlet noise the searched root still holds its raw priors (only the noise ever rewrites a prior): saved here,
+        // whichever way the search ran -- fused, step kernels, the step API
+        if (!(e->dev.dir_eps > 0.0f)) BZ_DISPATCH(e, k_surp_save, stream, e->dev, e->surp);
+        hipLaunchKernelGGL(k_surp_note, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp,
+                           e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+        BZ_LAUNCH_CHECK("k_surp_note");
+    }
     {
         ProfScope ps(BZ_PROF_PLAY, stream);
         if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
@@ -2613,6 +2734,7 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         else if (e->cap.fast > 0) BZ_DISPATCH(e, k_cap_play, stream, e->dev, e->cap, (int)restart);  // 
         else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
+    if (e->surp.prior) BZ_DISPATCH(e, k_surp_kl, stream, e->dev, e->surp);  // ... and its kl (before the arenas swap below)
     if (e->dev.reuse) {  // the tree just searched becomes the source of the next root_begin's subtree copy
         Node* tn = e->dev.nodes; e->dev.nodes = e->dev.nodes_alt; e->dev.nodes_alt = tn;
         Edge* te = e->dev.edges; e->dev.edges = e->dev.edges_alt; e->dev.edges_alt = te;
@@ -2712,8 +2834,8 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
 // an engine whose whole search is one launch (k_search_fused / k_search_fused_ttt): nothing to interleave
 static bool search_is_fused(const bz_engine* e) {
     const int ek = e->cfg.eval_kind;
-    return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !(e->dev.dir_eps > 0.0f) && e->dev.K == 1 &&
-           e->gumbel.m == 0 && e->cap.fast == 0 && !(e->forced.k > 0.0f);
+    return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && e->dev.K == 1 &&
+           e->cap.fast == 0 && !(e->forced.k > 0.0f);
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree
@@ -2729,7 +2851,7 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
         Kmax = e->dev.K > Kmax ? e->dev.K : Kmax;
         if ((rc = bz_engine_root_begin(e, streams[i])) != BZ_OK) return rc;
         if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
-        if (e->dev.dir_eps > 0.0f || e->gumbel.m > 0) {
+        if (root_prep(e)) {
             if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_root_noise(e, streams[i])) != BZ_OK) return rc;
         }
@@ -2749,7 +2871,7 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
             if (!e || search_is_fused(e)) continue;
             const int s = step * e->dev.K;
             if (s >= e->cfg.sims) continue;
-            const bool prep = e->dev.dir_eps > 0.0f || e->gumbel.m > 0;
+            const bool prep = root_prep(e);
             if ((rc = tree_step(e, (prep && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
         }

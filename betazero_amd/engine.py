@@ -40,6 +40,7 @@ class Examples:
     game: np.ndarray
     ply: np.ndarray
     size: int
+    kl: np.ndarray = None  # policy surprise: KL(pi || raw prior) per row, f32 [n]; None = not recorded
 
     def __len__(self):
         return self.own.shape[0]
@@ -68,6 +69,7 @@ class DeviceExamples:
     game: torch.Tensor
     ply: torch.Tensor
     size: int
+    kl: torch.Tensor = None  # policy surprise: f32 [n], or None = not recorded
 
     def __len__(self):
         return int(self.own.shape[0])
@@ -76,14 +78,16 @@ class DeviceExamples:
         """-> Examples (numpy, host)"""
         n = lambda t: t.cpu().numpy()  # noqa: E731
         return Examples(own=n(self.own).view(np.uint64), opp=n(self.opp).view(np.uint64), pi=n(self.pi), z=n(self.z),
-                        mover=n(self.mover), act=n(self.act), game=n(self.game), ply=n(self.ply).astype(np.int32), size=self.size)
+                        mover=n(self.mover), act=n(self.act), game=n(self.game), ply=n(self.ply).astype(np.int32), size=self.size,
+                        kl=None if self.kl is None else n(self.kl))
 
     @staticmethod
     def from_host(ex, device="cuda:0"):
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(device)  # noqa: E731
         return DeviceExamples(own=t(ex.own.view(np.int64)), opp=t(ex.opp.view(np.int64)), pi=t(ex.pi.astype(np.float32)),
                               z=t(ex.z.astype(np.int8)), mover=t(ex.mover.astype(np.int8)), act=t(ex.act.astype(np.uint8)),
-                              game=t(np.asarray(ex.game, np.int64)), ply=t(np.asarray(ex.ply, np.int32)), size=ex.size)
+                              game=t(np.asarray(ex.game, np.int64)), ply=t(np.asarray(ex.ply, np.int32)), size=ex.size,
+                              kl=None if ex.kl is None else t(np.asarray(ex.kl, np.float32)))
 
     def states(self):
         """canonical boards [n, size, size] int8 on the device: +1 = side to move, -1 = opponent"""
@@ -95,10 +99,18 @@ class DeviceExamples:
         return a - b
 
 
+def _all_or_none_kl(parts):
+    """True when every part carries kl, False when none does; a mixture has no meaningful concatenation"""
+    have = [p.kl is not None for p in parts]
+    if any(have) and not all(have):
+        raise ValueError("concatenating examples: every part must carry kl (policy surprise), or none")
+    return all(have) and len(have) > 0
+
+
 def concat_device_examples(parts):
     cat = lambda f: torch.cat([getattr(p, f) for p in parts])  # noqa: E731
     return DeviceExamples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                          parts[0].size)
+                          parts[0].size, cat("kl") if _all_or_none_kl(parts) else None)
 
 
 MAX_SIMS, MAX_SIMS_REUSE = 8189, 2045  # BZ_ENGINE_MAX_SIMS / BZ_ENGINE_MAX_SIMS_REUSE (include/bz_abi.h)
@@ -249,7 +261,7 @@ class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None):
+                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -276,7 +288,15 @@ class SelfPlayEngine:
         forced_playouts: None / False = off (the default, unchanged); True or a ForcedPlayouts(k, prune) =
         forced playouts at the root and, with prune, the pruned policy target in the example rows and in root_policy().  The
         move choice and root_stats() keep the raw visits.  Under playout_cap only the full searches force.  Refused with
-        reuse_subtree, leaves_per_step > 1 and gumbel."""
+        reuse_subtree, leaves_per_step > 1 and gumbel.
+
+        surprise: False = off (the default, unchanged); True = policy surprise weighting: every recorded
+        row also gets kl = KL(pi || the root's raw prior), which examples() / device_examples() then carry as `kl` and
+        betazero_amd.surprise.surprise_resample turns into repeat counts.  Searches, moves and rows are what they are
+        without it; it combines with everything the engine accepts.  surprise_rows() is the unpacked per-row view."""
+        if not isinstance(surprise, (bool, np.bool_)):
+            raise ValueError(f"surprise must be a bool (got {surprise!r})")
+        self.surprise = bool(surprise)
         check_sims(sims, reuse_subtree)
         check_eval_cache(eval_cache)
         self.K = check_leaves_per_step(leaves_per_step)
@@ -338,6 +358,14 @@ class SelfPlayEngine:
             self._call(L.bz_engine_set_playout_cap, pc.fast_sims, pc.full_q, self.cws.data_ptr() + self._cpad, cbytes)
         if self.forced_playouts is not None:
             self._call(L.bz_engine_set_forced_playouts, self.forced_playouts.k, int(self.forced_playouts.prune))
+        if self.surprise:  # the engine's surprise buffer (caller-owned, like the workspace)
+            sbytes = L.bz_engine_surprise_bytes(C.byref(self.cfg))
+            if sbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.sws = torch.zeros(sbytes + 256, dtype=torch.uint8, device=self.device)
+            self._spad = (-self.sws.data_ptr()) & 255
+            self._sbytes = sbytes
+            self._call(L.bz_engine_set_surprise, self.sws.data_ptr() + self._spad, sbytes)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -495,9 +523,37 @@ class SelfPlayEngine:
         o = self._pad + self.lay.ex_begin
         return self.ws[o:o + self.lay.ex_bytes]
 
+    def surprise_rows(self):
+        """policy surprise weighting: the engine's ex_kl, a float32 [rounds, B, t_max] view of the surprise
+        buffer indexed like example_tensors()["pi"] (rows past a game's ex_len hold whatever an earlier game left)"""
+        if not self.surprise:
+            raise RuntimeError("surprise_rows(): the engine was built without surprise=True")
+        n = self.rounds * self.B * self.t_max * 4
+        o = self._spad + self._sbytes - ((n + 255) & ~255)  # ex_kl is the buffer's last array
+        return self.sws[o:o + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
+
+    def pack_surprise(self, out=None, cap_rows=None, append=False):
+        """the finished games' kl in the row order of the packed block the preceding pack_examples() (same cap_rows, same
+        stream) filled: float32 [cap_rows] on the device, rows [0, n_rows) valid"""
+        cap = int(cap_rows or self.rounds * self.B * self.t_max)
+        if out is None:
+            assert not append
+            out = torch.zeros(cap, dtype=torch.float32, device=self.device)
+        self._call(_lib.lib().bz_engine_pack_surprise, out.data_ptr(), cap, int(append))
+        return out
+
+    def _packed_kl(self, n_rows):
+        """kl of the finished games' rows in (round, slot, ply) order -- the order of examples() and device_examples()"""
+        cap = self.rounds * self.B * self.t_max
+        self.pack_examples(cap_rows=cap)
+        return self.pack_surprise(cap_rows=cap)[:n_rows]
+
     def examples(self):
         """finished games' rows, compacted on the device; only the valid rows cross PCIe"""
-        return unpack_example_block(self.example_block())
+        ex = unpack_example_block(self.example_block())
+        if self.surprise:
+            ex.kl = self._packed_kl(len(ex)).cpu().numpy()
+        return ex
 
     def block_geometry(self):
         """host-side description of this engine's example block (what its 256-byte header says), so that a block of the
@@ -510,7 +566,10 @@ class SelfPlayEngine:
 
     def device_examples(self):
         """finished games' rows as DeviceExamples: nothing leaves the GPU"""
-        return unpack_example_block_device(self.example_block(), self.block_geometry())
+        ex = unpack_example_block_device(self.example_block(), self.block_geometry())
+        if self.surprise:
+            ex.kl = self._packed_kl(len(ex))
+        return ex
 
     def winners(self):
         t = self.example_tensors()
@@ -642,7 +701,7 @@ def unpack_example_block_device(block, geom):
 def concat_examples(parts):
     cat = lambda f: np.concatenate([getattr(p, f) for p in parts])  # noqa: E731
     return Examples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                    parts[0].size)
+                    parts[0].size, cat("kl") if _all_or_none_kl(parts) else None)
 
 
 # ---------------------------------------------------------------- packed example blocks (include/bz_abi.h)
@@ -787,7 +846,7 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 forced_playouts=None, **engine_kwargs):
+                 forced_playouts=None, surprise=False, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
@@ -804,8 +863,9 @@ class PipelinedSelfPlay:
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                                       playout_cap=playout_cap, forced_playouts=forced_playouts, **engine_kwargs)
+                                       playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise, **engine_kwargs)
                         for i in range(pipelines)]
+        self.surprise = bool(surprise)
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
 
@@ -902,11 +962,36 @@ class PipelinedSelfPlay:
             e.pack_examples(out, cap, append=i > 0)
         return out
 
+    def pack_examples_with_surprise(self, out=None, cap_rows=None):
+        """pack_examples() plus the rows' kl (surprise=True): (block, float32 [cap_rows] device tensor in the block's row
+        order).  Each engine's kl is packed right behind its rows, while the row offsets its pack left are current."""
+        if not self.surprise:
+            raise RuntimeError("pack_examples_with_surprise(): built without surprise=True")
+        cap = int(cap_rows or self.packed_capacity())
+        if out is None:
+            out = alloc_packed_block(self.na, cap, self.device)
+        kl = torch.zeros(cap, dtype=torch.float32, device=self.device)
+        self.join()
+        for i, e in enumerate(self.engines):
+            e.pack_examples(out, cap, append=i > 0)
+            e.pack_surprise(kl, cap, append=i > 0)
+        return out, kl
+
     def device_examples(self):
-        return unpack_packed_block_device(self.pack_examples())
+        if not self.surprise:
+            return unpack_packed_block_device(self.pack_examples())
+        blk, kl = self.pack_examples_with_surprise()
+        ex = unpack_packed_block_device(blk)
+        ex.kl = kl[:len(ex)]
+        return ex
 
     def examples(self):
-        return unpack_packed_block(self.pack_examples())
+        if not self.surprise:
+            return unpack_packed_block(self.pack_examples())
+        blk, kl = self.pack_examples_with_surprise()
+        ex = unpack_packed_block(blk)
+        ex.kl = kl[:len(ex)].cpu().numpy()
+        return ex
 
     def winners(self):
         self.join()
@@ -922,7 +1007,8 @@ class PipelinedSelfPlay:
 
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
-              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None):
+              reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
+              surprise=False):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -930,7 +1016,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine (DESIGN.md 3.12);
     gumbel: SelfPlayEngine -- pi is then the improved policy.  playout_cap: SelfPlayEngine
     -- only the moves searched with the full budget yield rows.  forced_playouts: SelfPlayEngine -- pi is
-    then the pruned policy target."""
+    then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`."""
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
     check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
@@ -944,7 +1030,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
-                           gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts)
+                           gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -69,7 +69,7 @@ def holdout_split(n_rows, val_fraction=0.2, generator=None, device="cuda:0"):
 def select_rows(ex, idx):
     """DeviceExamples holding the rows `idx` (a device index tensor) of ex"""
     return DeviceExamples(own=ex.own[idx], opp=ex.opp[idx], pi=ex.pi[idx], z=ex.z[idx], mover=ex.mover[idx], act=ex.act[idx],
-                          game=ex.game[idx], ply=ex.ply[idx], size=ex.size)
+                          game=ex.game[idx], ply=ex.ply[idx], size=ex.size, kl=None if ex.kl is None else ex.kl[idx])
 
 
 @torch.no_grad()

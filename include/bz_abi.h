@@ -442,6 +442,52 @@ int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k);
  * float(sum N))), N), while its score with the reduced N in the u term stays below s*; an edge that lost a visit and is left
  * with <= 1 gets 0; c* and unvisited edges keep theirs.  Host only. */
 int32_t bz_forced_prune(const uint32_t* N, const float* W, const float* P, int32_t n, float c_puct, float k, uint32_t* N_out);
+/* Policy surprise weighting (KataGo, Wu 2019, section 3.3), opt-in per engine.  Every row bz_engine_play
+ * records gets kl = sum over the root's edges in ascending action order with pi_a > 0 of pi_a * (logf(pi_a) - logf(max(P_a,
+ * FLT_MIN))), every operation one binary32 operation, then kl > 0 ? kl : 0 (a rounding negative or a NaN: 0).
+ * pi = the row's recorded pi, whatever produced it (N / sum N, the pruned target of 3.16, Gumbel's improved policy); P = the
+ * root's raw prior as the expansion stored it, before the Dirichlet noise.  The feature observes: searches, moves, pi and the
+ * example arrays are what they are without it, and bz_engine_layout does not change.  With cfg.dirichlet_eps > 0
+ * bz_engine_root_noise saves the priors in front of the noise; without noise nothing ever rewrites a prior, and bz_engine_play
+ * saves them from the searched root -- so step-API callers need no new call, and every search runs the kernels it runs with the
+ * mode off (the fused single-launch searches included: the work counters stay the same too).  bz_engine_play notes the row in
+ * front of its play kernel and computes the kl behind it (a fast search under the playout cap records no row and no kl).
+ * Nothing the engine accepts is refused: PUCT, leaves_per_step > 1, subtree reuse, Gumbel, the cap, forced playouts, every
+ * evaluator and evaluation-cache mode. */
+/* bytes of the caller-owned buffer: the saved raw priors f32 [n_games][MAXCH] (34 Reversi, 9 tic-tac-toe; edge order), a
+ * pending-row word u64 [n_games] and ex_kl f32 [rounds][n_games][t_max] (the row index of ex_pi), each 256-byte aligned.
+ * Needs no GPU; -1 (bz_last_error says why) for a bad config. */
+int64_t bz_engine_surprise_bytes(const bz_engine_cfg* cfg);
+/* switch the mode on (buf: device memory of >= bz_engine_surprise_bytes bytes, 256-byte aligned, owned by the caller and kept
+ * alive while the mode is on; zeroed on `stream`) or off (buf == NULL), between searches. */
+int32_t bz_engine_set_surprise(bz_engine* e, void* buf, int64_t bytes, void* stream);
+/* ex_kl in the packed block's row order: out f32 [cap_rows], row r of the block bz_engine_pack_examples has just filled gets
+ * its kl.  Call it after that bz_engine_pack_examples, on the same stream, with the same cap_rows: it uses the per-game row
+ * offsets that call left, which already count the rows earlier engines appended -- so the second pipeline of a rank lands
+ * behind the first.  append_rows (>= 0): the rows already in `out`, 0 for the first engine; they are left alone.  Games that
+ * did not fit into the block stay out of `out` too. */
+int32_t bz_engine_pack_surprise(bz_engine* e, float* out, int64_t cap_rows, int32_t append_rows, void* stream);
+/* the kl of one row, the function the kernels run: pi, P [n] in edge order, n in 1 .. 255.  Host only. */
+int32_t bz_surprise_kl(const float* pi, const float* P, int32_t n, float* kl);
+/* From surprise to repeat counts: rows are repeated in the data, not reweighted in the loss.  Device only,
+ * asynchronous, nothing read back.  kl f32, game i64, ply i32, own / opp u64 [n]: the rows (n <= 2^26, else BZ_EINVAL).
+ *   mean = float(double(sum_i (u64)(kl_i * 2^30)) / (double(n) * 2^30)): an exact 64-bit integer sum, the same bits every run
+ *          (kl_i is first cleaned: negative or NaN -> 0, above 128 -> 128)
+ *   w_i = uniform_frac + (1 - uniform_frac) * (kl_i / mean), single binary32 operations, uniform_frac in [0, 1] (KataGo: 0.5);
+ *         mean == 0: w_i = 1; w_i is capped at 2^30
+ *   count_i = floor(w_i) + [draw_i < (u32)(frac(w_i) * 2^24)], draw_i = mix64(rng_draw(seed ^ 0x7375727072697365, game_i,
+ *         ply_i) ^ hash_pos(own_i, opp_i)) >> 40: keyed by the row's content, not by its index
+ * count i32 [n] gets the counts; idx_out i64 [idx_cap] row i repeated count_i times, ascending; *n_out (device i64) =
+ * min(sum count, idx_cap).  Entries beyond idx_cap are dropped and counted: the workspace starts with three u64 words -- the
+ * integer kl sum, sum count and the number of dropped entries -- that the caller may read once the stream has run.
+ * ws: bz_surprise_resample_workspace_bytes(n) bytes, 256-byte aligned. */
+int64_t bz_surprise_resample_workspace_bytes(int64_t n);
+int32_t bz_surprise_resample(const float* kl, const int64_t* game, const int32_t* ply, const uint64_t* own, const uint64_t* opp,
+                             int64_t n, float uniform_frac, uint64_t seed, void* ws, int64_t ws_bytes, int32_t* count,
+                             int64_t* idx_out, int64_t idx_cap, int64_t* n_out, void* stream);
+/* count_i of one row, the function the kernels run.  Host only. */
+int32_t bz_surprise_count(float kl, float mean, float uniform_frac, uint64_t seed, int64_t game, int32_t ply, uint64_t own,
+                          uint64_t opp, int32_t* count);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */

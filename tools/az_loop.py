@@ -38,6 +38,7 @@ from betazero_amd.engine import (ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, 
                                  concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
+from betazero_amd.surprise import surprise_resample  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
                                 train_step, validate)
 
@@ -76,6 +77,12 @@ def main():
                     "the visits PUCT would not have made; 0 = off.  Composes with --fast-sims (full searches only) and the Dirichlet "
                     "noise; not with --gumbel")
     ap.add_argument("--no-prune", action="store_true", help="under --forced-k: record the raw N / sum N (ablation)")
+    ap.add_argument("--surprise", action="store_true", help="policy surprise weighting (DESIGN.md 3.17; KataGo): self-play records every "
+                    "row's KL(pi || the net's raw prior) and the training batches draw row i in proportion to --surprise-uniform + "
+                    "(1 - --surprise-uniform) kl_i / mean kl (rows are repeated in the data, not reweighted in the loss); validation rows "
+                    "are not resampled")
+    ap.add_argument("--surprise-uniform", type=float, default=0.5, help="the share of the weight every row gets regardless of its "
+                    "surprise (KataGo's 0.5)")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -128,7 +135,7 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
+                               surprise=args.surprise, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
         winners, _ = sp.winners()
@@ -146,8 +153,17 @@ def main():
         val_before = validate(dnet, val)   # the net that just played, on rows it has not been trained on
         steps = max(1, int(args.epochs * len(data) / args.batch))
         losses = []
+        surprise = {}
+        res = None
+        if args.surprise:  # once per iteration, over the window: row i stands count_i times in res
+            res, counts = surprise_resample(data, args.surprise_uniform, seed=args.seed * 1000 + it, return_counts=True)
+            surprise = {"surprise": {"mean_kl": round(float(data.kl.mean()), 5), "resampled_over_rows": round(len(res) / len(data), 4),
+                                     "max_count": int(counts.max()), "share_count_0": round(float((counts == 0).float().mean()), 4),
+                                     "uniform": args.surprise_uniform}}
         for _ in range(steps):
-            idx = torch.randint(0, len(data), (args.batch,), device=data.own.device, generator=gen)
+            idx = torch.randint(0, len(data) if res is None else len(res), (args.batch,), device=data.own.device, generator=gen)
+            if res is not None:
+                idx = res[idx]
             if graphed is not None:
                 losses.append(graphed(data, idx))
             else:
@@ -182,7 +198,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
-              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}),
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise,
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
               "arena": arena("net_bf16", cand), **gate})
