@@ -19,6 +19,9 @@ ENGINE_EVAL_CACHE = 2   # BZ_ENGINE_EVAL_CACHE: a position met again inside one 
 ENGINE_EVAL_CACHE_CARRY = 4   # BZ_ENGINE_EVAL_CACHE_CARRY: ... and the previous search's evaluations serve the next search too
 ENGINE_LEAVES_SHIFT = 8   # BZ_ENGINE_LEAVES_SHIFT / _MASK: flag bits 8..12 hold leaves_per_step - 1
 ENGINE_LEAVES_MASK = 31 << ENGINE_LEAVES_SHIFT
+PROBE_OPS = ("expf_spec", "logf_spec", "tanhf_spec", "fsqrt", "fdiv", "u01_spec", "hash_logit", "hash_value", "gamma_spec")  # BZ_PROBE_*
+PROBE_HOST, PROBE_DEVICE = 0, 1
+PROBE_MAP, PROBE_SWEEP = 0, 1
 PROF_SLOTS = ("tower", "stem", "heads", "select", "expand_backup", "search_fused", "play", "env_step")
 COUNTER_NAMES = ("n_sims", "n_path_nodes", "n_child_scored", "n_edges_backed", "n_expanded",
                  "n_child_written", "n_env_steps", "n_net_leaves", "n_cache_hits", "n_cache_hits_prev", "n_collisions")
@@ -173,6 +176,7 @@ _SIGS = {
     "bz_examples_packed_bytes": (i64, [i32, i64]),
     "bz_engine_pack_examples": (i32, [vp, vp, i64, i64, i32, vp]),
     "bz_stream_overlap_probe": (i32, [vp, vp, i32, i32, C.POINTER(C.c_float)]),
+    "bz_spec_probe": (i32, [i32, i32, i32, vp, vp, i64, u64, u64, vp, vp]),
     "bz_train_wf_bytes": (i64, [i32, i32]),
     "bz_train_positions_per_workgroup": (i32, [i32]),
     "bz_train_mask_bytes": (i64, [i32, i32, i32]),

@@ -24,16 +24,14 @@ BZ_HD float fdiv(float a, float b) {
     return a / b;
 #endif
 }
-BZ_HD float fsqrt(float a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fsqrt_rn(a);
-#else
-    return __builtin_sqrtf(a);
-#endif
-}
+// Correctly rounded on both sides.  (Not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers make it the native
+// square root, a bare v_sqrt_f32 good to 1 ulp.  __builtin_sqrtf gets the corrected sequence on gfx950, which is the default of
+// -fhip-fp32-correctly-rounded-divide-sqrt; tests/test_gpu_spec_math.py pins device == host over all 2^32 inputs.)
+BZ_HD float fsqrt(float a) { return __builtin_sqrtf(a); }
 
-// exp(x), x <= 0.  mul and add are separate roundings.
+// exp(x), x <= 0.  mul and add are separate roundings.  NaN in, NaN out: ahead of (int)n, which is undefined for a NaN.
 BZ_HD float expf_spec(float x) {
+    if (x != x) return x;
     if (x < -87.0f) return 0.0f;
     float t = x * 1.44269504f;
     float n = __builtin_floorf(t + 0.5f);

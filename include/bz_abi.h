@@ -754,6 +754,31 @@ int32_t bz_profile_intervals(int32_t slot, double* starts_ms, double* ends_ms, i
  * (two engines on two streams) picks its stream pair with it.  Synchronises both streams. */
 int32_t bz_stream_overlap_probe(void* stream_a, void* stream_b, int32_t spin_us, int32_t reps, float* serial_ratio);
 
+/* ------------------------------------------------------------------------ */
+/* The float primitives of csrc/bz_math.h one at a time, as   */
+/* the host build or as the gfx950 build of one translation unit computes     */
+/* them: what the tests compare the two builds through.                       */
+/* ------------------------------------------------------------------------ */
+enum { BZ_PROBE_EXPF = 0, BZ_PROBE_LOGF = 1, BZ_PROBE_TANHF = 2, BZ_PROBE_FSQRT = 3, BZ_PROBE_FDIV = 4, BZ_PROBE_U01 = 5,
+       BZ_PROBE_HASH_LOGIT = 6, BZ_PROBE_HASH_VALUE = 7, BZ_PROBE_GAMMA = 8 };
+enum { BZ_PROBE_HOST = 0, BZ_PROBE_DEVICE = 1 };
+enum { BZ_PROBE_MAP = 0, BZ_PROBE_SWEEP = 1 };
+/* where = BZ_PROBE_HOST: a, b, out are host pointers, stream is ignored and HIP is never touched (runs without a GPU).
+ * where = BZ_PROBE_DEVICE: device pointers, the work is queued on `stream`.
+ * mode = BZ_PROBE_MAP: out[i] (float [n], the result's bits untouched) = op of element i.  Operands:
+ *   EXPF, LOGF, TANHF, FSQRT  a = float [n]
+ *   FDIV                      a / b, both float [n]
+ *   U01, HASH_VALUE           a = uint64 [n]
+ *   HASH_LOGIT                a = uint64 [n] (the position hash), b = uint64 [n] (the action)
+ *   GAMMA                     a = float [n] (alpha), b = uint64 [n][4] (seed, game, ply, edge)
+ * mode = BZ_PROBE_SWEEP (EXPF, LOGF, TANHF, FSQRT): the op at every 32-bit pattern p in [lo, hi), hi <= 2^32; a, b, n are
+ *   ignored.  out = uint64 [((hi - 1) >> 24) - (lo >> 24) + 1], one checksum per chunk of 2^24 patterns:
+ *   out[(p >> 24) - (lo >> 24)] = sum over the chunk's p of mix64(p << 32 | canon(bits of op(p))) mod 2^64, where canon
+ *   turns every NaN into 0x7FC00000.  The sum does not depend on the order: host and device give the same number exactly
+ *   when they agree on every pattern of the chunk (up to a 2^-64 coincidence). */
+int32_t bz_spec_probe(int32_t op, int32_t where, int32_t mode, const void* a, const void* b, int64_t n, uint64_t lo, uint64_t hi,
+                      void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,9 @@ Fixtures:
                                 under fixed `random` seeds: ReversiTerminal transcripts (4/6/8), TTT
                                 OptimalPlayer games, a Reversi OptimalPlayer-vs-RandomPlayer opening,
                                 the states / actions of its collect_game_data loop
+  F14 spec_math.npz             the float primitives of csrc/bz_math.h as the HOST build of libbz_hip.so computes them
+                                (bz_spec_probe): a checksum per 2^24-pattern chunk of every sweep domain, and the
+                                exhaustive maxima of the error against float64 (no reference code involved)
 
 Run:  python oracle/gen_golden.py
 """
@@ -668,6 +671,31 @@ def gen_f13():
     print("F13", {k: len(v) for k, v in out.items()})
 
 
+# ---------------------------------------------------------------- F14: the float primitives, from the host build
+def gen_f14():
+    """tests/golden/spec_math.npz (tests/test_spec_math_cpu.py, tests/test_gpu_spec_math.py; oracle/spec_math.py has the
+    domains).  Per sweep op: <op>_lo / _hi / _sum = the pattern range and the checksum of every chunk, in the order of
+    spec_math.chunks(SWEEPS[op]).  Per function with an accuracy bound: <op>_max_err / _max_at = the largest error over the
+    WHOLE accuracy domain and the first pattern it is at.  Needs a built libbz_hip.so; a full sweep takes some tens of seconds
+    per op, spread over 8 threads (ctypes releases the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from oracle import spec_math as sm
+    out = {}
+    with ThreadPoolExecutor(8) as ex:
+        for op, ranges in sm.SWEEPS.items():
+            ch = sm.chunks(ranges)
+            out[op + "_lo"] = np.array([c[0] for c in ch], np.uint64)
+            out[op + "_hi"] = np.array([c[1] for c in ch], np.uint64)
+            out[op + "_sum"] = np.array(list(ex.map(lambda c: int(sm.host_sweep(op, *c)[0]), ch)), np.uint64)
+            print("F14", op, len(ch), "chunks")
+        for op, ranges in sm.ACCURACY.items():
+            err, at = max(ex.map(lambda c: sm.chunk_max_error(op, *c), sm.chunks(ranges)), key=lambda r: (r[0], -r[1]))
+            out[op + "_max_err"], out[op + "_max_at"] = np.float64(err), np.uint32(at)
+            print("F14 %s max error %.4e at 0x%08X (x = %.9g)" % (op, err, at, np.array([at], np.uint32).view(np.float32)[0]))
+    np.savez_compressed(os.path.join(OUT, "spec_math.npz"), **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f7", "f8", "f9", "f10", "f11", "f12", "f13"]
     if "f1" in which: gen_f1()
@@ -682,3 +710,4 @@ if __name__ == "__main__":
     if "f11" in which: gen_f11()
     if "f12" in which: gen_f12()
     if "f13" in which: gen_f13()
+    if "f14" in which: gen_f14()   # (not in the default list: it needs the built library, not the reference)

@@ -64,6 +64,8 @@ def rng_draw(seed, gid, ply):
 def expf_spec(x):
     """exp for x <= 0, single float32 roundings, no fma."""
     x = f32(x)
+    if x != x:
+        return x
     if x < f32(-87.0):
         return f32(0.0)
     t = x * f32(1.44269504)

@@ -10,12 +10,15 @@ import pytest
 from test_kernel_resources import HIPCC, _find, _resources
 
 GAMES = ("ReversiTILi8", "ReversiTILi6", "ReversiTILi4", "TicTacToe")
-# VGPRs of the kernels the feature is launched next to, at the commit before it (Reversi 8 / 6 / 4, tic-tac-toe)
+# VGPRs of the kernels the feature is launched next to, at the commit before it (Reversi 8 / 6 / 4, tic-tac-toe).
+# (Since fsqrt became the correctly rounded __builtin_sqrtf, DESIGN.md 3.4, the corrected sequence's residual takes one more
+# register where a square root sits at the kernel's peak: k_tree_step of tic-tac-toe 104 -> 105, 4 waves per SIMD as before;
+# k_forced_play 96 -> 97, 4 waves instead of 5 for a kernel that runs once per move.  The surprise kernels change neither.)
 BEFORE = {
-    "k_tree_step": (96, 96, 96, 104),
+    "k_tree_step": (96, 96, 96, 105),
     "k_playI": (64, 64, 55, 52),
     "k_cap_play": (63, 63, 55, 52),
-    "k_forced_playI": (96, 96, 96, 96),
+    "k_forced_playI": (97, 97, 97, 97),
     "k_gumbel_play": (65, 65, 61, 61),
 }
 
