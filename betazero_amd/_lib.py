@@ -156,6 +156,12 @@ _SIGS = {
     "bz_surprise_resample_workspace_bytes": (i64, [i64]),
     "bz_surprise_resample": (i32, [vp, vp, vp, vp, vp, i64, C.c_float, u64, vp, i64, vp, vp, i64, vp, vp]),
     "bz_surprise_count": (i32, [C.c_float, C.c_float, C.c_float, u64, i64, i32, u64, u64, C.POINTER(i32)]),
+    "bz_engine_search_value_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_search_value": (i32, [vp, vp, i64, vp]),
+    "bz_engine_pack_search_value": (i32, [vp, vp, i64, i32, vp]),
+    "bz_root_value": (i32, [vp, vp, i32, vp]),
+    "bz_value_targets": (i32, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp]),
+    "bz_value_targets_segment": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),
@@ -190,6 +196,7 @@ _SIGS = {
     "bz_train_stem_fwd": (i32, [vp, i32, vp, vp, i32, vp, vp]),
     "bz_train_stem_wgrad": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "bz_train_heads": (i32, [vp, vp, i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
+    "bz_train_heads_vt": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
     "bz_train_heads_wgrad": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "bz_train_finish": (i32, [C.POINTER(TrainPartials), C.POINTER(TrainTensors), i32, i32, i32, i32, vp, C.POINTER(TrainAdam), vp]),
     "bz_profile_enable": (i32, [i32]),

@@ -41,7 +41,7 @@ def _first_occurrences(key8, own8, opp8, pi8):
 def augment_examples(ex, dedupe=True, device="cuda:0"):
     """Examples / DeviceExamples (n rows) -> the same type (<= 8n rows, row 8*i+t = transform t of row i before dedupe).
     z, mover and game carry over; `act` is permuted with the board; `ply` is kept; `kl` (policy surprise, when present) is the
-    source row's: the eight copies share it, and the dedupe keeps the first occurrence's."""
+    source row's: the eight copies share it, and the dedupe keeps the first occurrence's; `q` and `vt` likewise."""
     _lib.require_gpu()
     host_in = isinstance(ex, Examples)
     if host_in:
@@ -70,5 +70,6 @@ def augment_examples(ex, dedupe=True, device="cuda:0"):
     src = keep // 8
     out = DeviceExamples(own=own8[keep], opp=opp8[keep], pi=pi8[keep], z=ex.z[src], mover=ex.mover[src],
                          act=act8[keep].argmax(1).to(torch.uint8), game=ex.game[src], ply=ex.ply[src], size=size,
-                         kl=None if ex.kl is None else ex.kl[src])
+                         kl=None if ex.kl is None else ex.kl[src], q=None if ex.q is None else ex.q[src],
+                         vt=None if ex.vt is None else ex.vt[src])
     return out.cpu() if host_in else out

@@ -37,6 +37,7 @@
 #include "bz_math.h"
 #include "bz_rules.h"
 #include "bz_surprise.h"
+#include "bz_value.h"
 
 using namespace bz;
 
@@ -206,6 +207,9 @@ __host__ __device__ __forceinline__ u32 forced_prune(const Edge* ed, int n, floa
 // kernel is about to write per slot (row + 1; 0 = none) and the rows' kl [rounds][B][t_max].  A kernel argument of the
 // surprise kernels only: the feature observes, no other kernel's code changes.
 struct SurpDev { float* prior; u64* pend; float* ex_kl; };
+// Search-value targets (ex_q = nullptr: off), set by bz_engine_set_search_value in the caller's buffer: the root's
+// search value of every recorded row, f32 [rounds][B][t_max] indexed like ex_pi.  Read and written by the two value kernels only.
+struct ValueDev { float* ex_q; };
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -2014,14 +2018,18 @@ __global__ void __launch_bounds__(256) k_surp_save(EngineDev E, SurpDev S) {
 }
 // in front of the play kernel: the row it is about to write, by its own rule (budget: the playout cap's, or null -- a fast
 // search records nothing)
+// (the row rule, shared with k_root_q, DESIGN.md 3.18: an active slot with room for a row whose search had the full budget;
+// 1 + the row's index into the [rounds][B][t_max] example arrays, 0: this play records nothing)
+__device__ __forceinline__ u64 dev_pending_row(const EngineDev& E, int g, const u32* budget) {
+    const int nex = E.g_state[g] == 0 ? E.g_nex[g] : E.t_max;
+    if (nex < E.t_max && !(budget && budget[g] < (u32)E.sims))
+        return ((u64)E.g_round[g] * (u64)E.B + (u64)g) * (u64)E.t_max + (u64)nex + 1ULL;
+    return 0;
+}
 __global__ void __launch_bounds__(256) k_surp_note(EngineDev E, SurpDev S, const u32* budget) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.B) return;
-    u64 p = 0;
-    const int nex = E.g_state[g] == 0 ? E.g_nex[g] : E.t_max;
-    if (nex < E.t_max && !(budget && budget[g] < (u32)E.sims))
-        p = ((u64)E.g_round[g] * (u64)E.B + (u64)g) * (u64)E.t_max + (u64)nex + 1ULL;
-    S.pend[g] = p;
+    S.pend[g] = dev_pending_row(E, g, budget);
 }
 // behind it: the noted row's kl from the pi the play kernel recorded and the saved priors (the searched tree is still in
 // place: the root's edges give the actions)
@@ -2052,6 +2060,29 @@ __global__ void __launch_bounds__(256) k_pack_kl(EngineDev E, SurpDev S, float* 
     for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = S.ex_kl[src + t];
 }
 
+// ---- search-value targets: in front of the play kernel, while the searched tree is in place -- the row the
+// play is about to write gets the root's search value from the raw visit statistics (whatever the play kernel records as pi:
+// Gumbel's improved policy, the pruned visits of forced playouts), one lane per game
+__global__ void __launch_bounds__(256) k_root_q(EngineDev E, ValueDev V, const u32* budget) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    const u64 p = dev_pending_row(E, g, budget);
+    if (p == 0) return;
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    V.ex_q[(size_t)(p - 1ULL)] = root_value((int)(r.info & 0xFFu), [ed](int i) { return e_N(ed[i].w0); }, [ed](int i) { return ed[i].W; });
+}
+// ex_q in the packed block's row order (k_pack_kl's walk over the pack_off k_pack_scan left)
+__global__ void __launch_bounds__(256) k_pack_q(EngineDev E, ValueDev V, float* out, int64_t cap) {
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= E.rounds * E.B) return;
+    const int off = E.pack_off[i];
+    if (off < 0) return;
+    const int len = E.ex_len[i];
+    const size_t src = (size_t)i * E.t_max;
+    for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = V.ex_q[src + t];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2074,6 +2105,7 @@ struct bz_engine {
     CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
     ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
     SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
+    ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
 };
 
 namespace {
@@ -2211,6 +2243,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->cap = CapDev{};
     e->forced = ForcedDev{};
     e->surp = SurpDev{};
+    e->value = ValueDev{};
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2706,6 +2739,52 @@ BZ_EXPORT int32_t bz_engine_pack_surprise(bz_engine* e, float* out, int64_t cap_
     return BZ_OK;
 }
 
+/* ---- search-value targets */
+namespace {
+int64_t value_bytes(const bz_engine_cfg& c) {
+    Carver k;
+    k.take((int64_t)c.rounds * c.n_games * c.t_max * 4);
+    return k.off;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_search_value_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_search_value_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_search_value_bytes: %s", kBadCfg); return -1; }
+    return value_bytes(*cfg);
+}
+
+BZ_EXPORT int32_t bz_engine_set_search_value(bz_engine* e, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_search_value: null engine");
+    if (!buf) {  // off: no extra launch
+        e->value = ValueDev{};
+        return BZ_OK;
+    }
+    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_search_value: the buffer must be 256-byte aligned");
+    const int64_t total = value_bytes(e->cfg);
+    if (bytes < total) { set_error("bz_engine_set_search_value: buffer too small (%lld < %lld)", (long long)bytes, (long long)total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)total, (hipStream_t)stream));  // every q 0
+    e->value.ex_q = static_cast<float*>(buf);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_pack_search_value(bz_engine* e, float* out, int64_t cap_rows, int32_t append_rows, void* stream) {
+    BZ_REQUIRE(e && out, "bz_engine_pack_search_value: null pointer");
+    BZ_REQUIRE(e->value.ex_q, "bz_engine_pack_search_value: the search value is not recorded (bz_engine_set_search_value)");
+    BZ_REQUIRE(cap_rows >= 1 && cap_rows <= (int64_t(1) << 31) - 1 && append_rows >= 0 && append_rows <= cap_rows,
+               "bz_engine_pack_search_value: bad capacity or append_rows");
+    const int n = e->dev.rounds * e->dev.B;
+    hipLaunchKernelGGL(k_pack_q, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->value, out, cap_rows);
+    BZ_LAUNCH_CHECK("k_pack_q");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_root_value(const uint32_t* N, const float* W, int32_t n, float* q) {
+    BZ_REQUIRE(N && W && q && n >= 1 && n <= 255, "bz_root_value: null pointer or n outside 1 .. 255");
+    *q = root_value(n, [N](int i) { return N[i]; }, [W](int i) { return W[i]; });
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
     BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
     if (e->forced.k > 0.0f) {  // 
@@ -2725,6 +2804,11 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         hipLaunchKernelGGL(k_surp_note, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp,
                            e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
         BZ_LAUNCH_CHECK("k_surp_note");
+    }
+    if (e->value.ex_q) {  //  the root's search value of the row this play is about to write
+        hipLaunchKernelGGL(k_root_q, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->value,
+                           e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+        BZ_LAUNCH_CHECK("k_root_q");
     }
     {
         ProfScope ps(BZ_PROF_PLAY, stream);

@@ -225,8 +225,10 @@ template <int C> struct Hd {
                          NP = O_LOSS + 4;
 };
 
-template <int C>
-__global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
+// (kVT: the value target of a position is vt[row], an fp32 array whose address is read from the device word *vt_slot at launch
+// time -- bz_train_heads_vt, DESIGN.md 3.18 -- instead of (float)z[row]; nothing else differs between the two kernels)
+template <int C, bool kVT>
+__device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A, const float* const* vt_slot) {
     typedef Hd<C> H;
     constexpr int ZC = C / 8, CPL = C / 64;
     extern __shared__ float lds[];
@@ -270,6 +272,7 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
     }
     for (int i = tid; i < 3 * C; i += 256) hwS[i] = i < 2 * C ? A.pol_w[i] : A.val_w[i - 2 * C];
     const bz_train_batch B = *A.batch;
+    const float* vt = kVT ? *vt_slot : nullptr;
     const float hb[3] = {A.pol_b[0], A.pol_b[1], A.val_b[0]};
     const float pfb = A.polfc_b[lane], pfb64 = A.polfc_b[64], v2b = A.v2_b[0];
     const float v1b = lane < A.VH ? A.v1_b[lane] : 0.0f, v2w = lane < A.VH ? A.v2_w[lane] : 0.0f;
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
         const long long row = batch_row(B, pos);
         acc_bad += batch_row_bad(B, pos) ? 1.0f : 0.0f;
         // (the targets are needed in steps B and C: asked for now, they arrive under step A)
-        const float pa = B.pi[(size_t)row * 65 + lane], p64 = B.pi[(size_t)row * 65 + 64], zf = (float)B.z[row];
+        const float pa = B.pi[(size_t)row * 65 + lane], p64 = B.pi[(size_t)row * 65 + 64], zf = kVT ? vt[row] : (float)B.z[row];
         __syncthreads();   // the previous pass's copy-out has read xs; (first pass: the weight tables are in place)
 #pragma unroll
         for (int k = 0; k < ZC; ++k) { const int i = lane + 64 * k; *reinterpret_cast<u32x4*>(xs + (i / ZC) * H::XS + (i % ZC) * 8) = xr[k]; }
@@ -418,6 +421,11 @@ __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) {
     for (int o = tid; o < H::NP; o += 256)
         A.partial[(size_t)blockIdx.x * H::NP + o] = (lds[o] + lds[H::NP + o]) + (lds[2 * H::NP + o] + lds[3 * H::NP + o]);
 }
+
+template <int C>
+__global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) { train_heads_body<C, false>(A, nullptr); }
+template <int C>
+__global__ __launch_bounds__(256) void k_train_heads_vt(HeadArgs A, const float* const* vt_slot) { train_heads_body<C, true>(A, vt_slot); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the FC weight gradients that reduce over the batch:  d polfc.weight[a][i] = sum_pos dl[pos][a] h[pos][i]  (65 x 128),
@@ -611,13 +619,20 @@ BZ_EXPORT int32_t bz_train_stem_wgrad(const bz_train_batch* batch_dev, const voi
     return BZ_OK;
 }
 
-BZ_EXPORT int32_t bz_train_heads(const void* act_top, const bz_train_batch* batch_dev, int32_t n, int32_t C, int32_t VH,
-                                 const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1, float* partial, void* stream) {
-    BZ_REQUIRE(act_top && batch_dev && P && g_top && hv && dl && dv1 && partial && ends_shape_ok(C, n) && VH >= 1 && VH <= 64,
-               "bz_train_heads: bad arguments (C = 64 or 128, n a multiple of 4, value_hidden <= 64)");
-    BZ_REQUIRE(P->pol_w && P->pol_b && P->polfc_w && P->polfc_b && P->val_w && P->val_b && P->v1_w && P->v1_b && P->v2_w && P->v2_b,
-               "bz_train_heads: a head parameter pointer is null");
-    if (bz_device_count() <= 0) { set_error("bz_train_heads: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+namespace {
+// bz_train_heads (vt_slot == nullptr, `who` names the entry point in messages) and bz_train_heads_vt
+int32_t launch_heads(const char* who, const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot, bool with_vt,
+                     int32_t n, int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
+                     float* partial, void* stream) {
+    if (!(act_top && batch_dev && (vt_slot || !with_vt) && P && g_top && hv && dl && dv1 && partial && ends_shape_ok(C, n) && VH >= 1 && VH <= 64)) {
+        set_error("%s: bad arguments (C = 64 or 128, n a multiple of 4, value_hidden <= 64)", who);
+        return BZ_EINVAL;
+    }
+    if (!(P->pol_w && P->pol_b && P->polfc_w && P->polfc_b && P->val_w && P->val_b && P->v1_w && P->v1_b && P->v2_w && P->v2_b)) {
+        set_error("%s: a head parameter pointer is null", who);
+        return BZ_EINVAL;
+    }
+    if (bz_device_count() <= 0) { set_error("%s: no HIP device (the training kernels have no CPU path)", who); return BZ_ENOGPU; }
     HeadArgs A;
     A.x = static_cast<const __bf16*>(act_top); A.batch = batch_dev; A.n = n; A.VH = VH; A.inv_n = 1.0f / (float)n;
     A.pol_w = P->pol_w; A.pol_b = P->pol_b; A.polfc_w = P->polfc_w; A.polfc_b = P->polfc_b; A.val_w = P->val_w; A.val_b = P->val_b;
@@ -625,17 +640,37 @@ BZ_EXPORT int32_t bz_train_heads(const void* act_top, const bz_train_batch* batc
     A.g_top = static_cast<__bf16*>(g_top); A.hv = hv; A.dl = dl; A.dv1 = dv1; A.partial = partial;
     const dim3 grid(heads_blocks(n));
     hipStream_t s = (hipStream_t)stream;
-    if (C == 64) {
+    if (!with_vt && C == 64) {
         static unsigned done = 0;
         if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads<64>), Hd<64>::LDS, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads)");
         hipLaunchKernelGGL(k_train_heads<64>, grid, dim3(256), Hd<64>::LDS, s, A);
-    } else {
+    } else if (!with_vt) {
         static unsigned done = 0;
         if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads<128>), Hd<128>::LDS, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads)");
         hipLaunchKernelGGL(k_train_heads<128>, grid, dim3(256), Hd<128>::LDS, s, A);
+    } else if (C == 64) {
+        static unsigned done = 0;
+        if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_vt<64>), Hd<64>::LDS, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_vt)");
+        hipLaunchKernelGGL(k_train_heads_vt<64>, grid, dim3(256), Hd<64>::LDS, s, A, vt_slot);
+    } else {
+        static unsigned done = 0;
+        if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_vt<128>), Hd<128>::LDS, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_vt)");
+        hipLaunchKernelGGL(k_train_heads_vt<128>, grid, dim3(256), Hd<128>::LDS, s, A, vt_slot);
     }
-    BZ_LAUNCH_CHECK("k_train_heads");
+    BZ_LAUNCH_CHECK(with_vt ? "k_train_heads_vt" : "k_train_heads");
     return BZ_OK;
+}
+}  // namespace
+
+BZ_EXPORT int32_t bz_train_heads(const void* act_top, const bz_train_batch* batch_dev, int32_t n, int32_t C, int32_t VH,
+                                 const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1, float* partial, void* stream) {
+    return launch_heads("bz_train_heads", act_top, batch_dev, nullptr, false, n, C, VH, P, g_top, hv, dl, dv1, partial, stream);
+}
+
+BZ_EXPORT int32_t bz_train_heads_vt(const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot_dev, int32_t n,
+                                    int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
+                                    float* partial, void* stream) {
+    return launch_heads("bz_train_heads_vt", act_top, batch_dev, vt_slot_dev, true, n, C, VH, P, g_top, hv, dl, dv1, partial, stream);
 }
 
 BZ_EXPORT int32_t bz_train_heads_wgrad(const float* hv, const float* dl, const float* dv1, int32_t n, int32_t VH, float* partial, void* stream) {

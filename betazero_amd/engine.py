@@ -41,6 +41,8 @@ class Examples:
     ply: np.ndarray
     size: int
     kl: np.ndarray = None  # policy surprise: KL(pi || raw prior) per row, f32 [n]; None = not recorded
+    q: np.ndarray = None   # search value: the root's sum W / sum N for the mover, f32 [n]; None = not recorded
+    vt: np.ndarray = None  # value target (betazero_amd.value_targets), f32 [n]; None = train on z
 
     def __len__(self):
         return self.own.shape[0]
@@ -70,6 +72,8 @@ class DeviceExamples:
     ply: torch.Tensor
     size: int
     kl: torch.Tensor = None  # policy surprise: f32 [n], or None = not recorded
+    q: torch.Tensor = None   # search value: f32 [n], or None = not recorded
+    vt: torch.Tensor = None  # value target: f32 [n], or None = train on z
 
     def __len__(self):
         return int(self.own.shape[0])
@@ -79,7 +83,8 @@ class DeviceExamples:
         n = lambda t: t.cpu().numpy()  # noqa: E731
         return Examples(own=n(self.own).view(np.uint64), opp=n(self.opp).view(np.uint64), pi=n(self.pi), z=n(self.z),
                         mover=n(self.mover), act=n(self.act), game=n(self.game), ply=n(self.ply).astype(np.int32), size=self.size,
-                        kl=None if self.kl is None else n(self.kl))
+                        kl=None if self.kl is None else n(self.kl), q=None if self.q is None else n(self.q),
+                        vt=None if self.vt is None else n(self.vt))
 
     @staticmethod
     def from_host(ex, device="cuda:0"):
@@ -87,7 +92,9 @@ class DeviceExamples:
         return DeviceExamples(own=t(ex.own.view(np.int64)), opp=t(ex.opp.view(np.int64)), pi=t(ex.pi.astype(np.float32)),
                               z=t(ex.z.astype(np.int8)), mover=t(ex.mover.astype(np.int8)), act=t(ex.act.astype(np.uint8)),
                               game=t(np.asarray(ex.game, np.int64)), ply=t(np.asarray(ex.ply, np.int32)), size=ex.size,
-                              kl=None if ex.kl is None else t(np.asarray(ex.kl, np.float32)))
+                              kl=None if ex.kl is None else t(np.asarray(ex.kl, np.float32)),
+                              q=None if ex.q is None else t(np.asarray(ex.q, np.float32)),
+                              vt=None if ex.vt is None else t(np.asarray(ex.vt, np.float32)))
 
     def states(self):
         """canonical boards [n, size, size] int8 on the device: +1 = side to move, -1 = opponent"""
@@ -99,18 +106,21 @@ class DeviceExamples:
         return a - b
 
 
-def _all_or_none_kl(parts):
-    """True when every part carries kl, False when none does; a mixture has no meaningful concatenation"""
-    have = [p.kl is not None for p in parts]
+_OPTIONAL_FIELDS = (("kl", "policy surprise"), ("q", "search value"), ("vt", "value target"))
+
+
+def _all_or_none(parts, field, what):
+    """True when every part carries `field`, False when none does; a mixture has no meaningful concatenation"""
+    have = [getattr(p, field) is not None for p in parts]
     if any(have) and not all(have):
-        raise ValueError("concatenating examples: every part must carry kl (policy surprise), or none")
+        raise ValueError(f"concatenating examples: every part must carry {field} ({what}), or none")
     return all(have) and len(have) > 0
 
 
 def concat_device_examples(parts):
     cat = lambda f: torch.cat([getattr(p, f) for p in parts])  # noqa: E731
     return DeviceExamples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                          parts[0].size, cat("kl") if _all_or_none_kl(parts) else None)
+                          parts[0].size, *(cat(f) if _all_or_none(parts, f, what) else None for f, what in _OPTIONAL_FIELDS))
 
 
 MAX_SIMS, MAX_SIMS_REUSE = 8189, 2045  # BZ_ENGINE_MAX_SIMS / BZ_ENGINE_MAX_SIMS_REUSE (include/bz_abi.h)
@@ -257,11 +267,18 @@ def check_forced_playouts(forced_playouts, reuse_subtree=False, leaves_per_step=
     return ForcedPlayouts(float(k), bool(fp.prune))
 
 
+def check_search_value(search_value):
+    """search-value targets: a bool, anything else is refused (ValueError, before any device is touched)"""
+    if not isinstance(search_value, (bool, np.bool_)):
+        raise ValueError(f"search_value must be a bool (got {search_value!r})")
+    return bool(search_value)
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False):
+                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -293,10 +310,17 @@ class SelfPlayEngine:
         surprise: False = off (the default, unchanged); True = policy surprise weighting: every recorded
         row also gets kl = KL(pi || the root's raw prior), which examples() / device_examples() then carry as `kl` and
         betazero_amd.surprise.surprise_resample turns into repeat counts.  Searches, moves and rows are what they are
-        without it; it combines with everything the engine accepts.  surprise_rows() is the unpacked per-row view."""
+        without it; it combines with everything the engine accepts.  surprise_rows() is the unpacked per-row view.
+
+        search_value: False = off (the default, unchanged); True = every recorded row also gets q = the root's
+        sum W / sum N of its search (the mover's expected outcome, from the raw visit statistics), which examples() /
+        device_examples() then carry as `q` and betazero_amd.value_targets.value_targets turns into value targets.  Searches,
+        moves and rows are what they are without it; it combines with everything the engine accepts.  search_value_rows() is
+        the unpacked per-row view."""
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
         self.surprise = bool(surprise)
+        self.search_value = check_search_value(search_value)
         check_sims(sims, reuse_subtree)
         check_eval_cache(eval_cache)
         self.K = check_leaves_per_step(leaves_per_step)
@@ -366,6 +390,13 @@ class SelfPlayEngine:
             self._spad = (-self.sws.data_ptr()) & 255
             self._sbytes = sbytes
             self._call(L.bz_engine_set_surprise, self.sws.data_ptr() + self._spad, sbytes)
+        if self.search_value:  # the engine's ex_q buffer (caller-owned, like the workspace)
+            vbytes = L.bz_engine_search_value_bytes(C.byref(self.cfg))
+            if vbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.vws = torch.zeros(vbytes + 256, dtype=torch.uint8, device=self.device)
+            self._vpad = (-self.vws.data_ptr()) & 255
+            self._call(L.bz_engine_set_search_value, self.vws.data_ptr() + self._vpad, vbytes)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -548,11 +579,37 @@ class SelfPlayEngine:
         self.pack_examples(cap_rows=cap)
         return self.pack_surprise(cap_rows=cap)[:n_rows]
 
+    def search_value_rows(self):
+        """search-value targets: the engine's ex_q, a float32 [rounds, B, t_max] view of the search-value
+        buffer indexed like example_tensors()["pi"] (rows past a game's ex_len hold whatever an earlier game left)"""
+        if not self.search_value:
+            raise RuntimeError("search_value_rows(): the engine was built without search_value=True")
+        n = self.rounds * self.B * self.t_max * 4
+        return self.vws[self._vpad:self._vpad + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
+
+    def pack_search_value(self, out=None, cap_rows=None, append=False):
+        """the finished games' q in the row order of the packed block the preceding pack_examples() (same cap_rows, same
+        stream) filled: float32 [cap_rows] on the device, rows [0, n_rows) valid"""
+        cap = int(cap_rows or self.rounds * self.B * self.t_max)
+        if out is None:
+            assert not append
+            out = torch.zeros(cap, dtype=torch.float32, device=self.device)
+        self._call(_lib.lib().bz_engine_pack_search_value, out.data_ptr(), cap, int(append))
+        return out
+
+    def _packed_q(self, n_rows):
+        """q of the finished games' rows in (round, slot, ply) order -- the order of examples() and device_examples()"""
+        cap = self.rounds * self.B * self.t_max
+        self.pack_examples(cap_rows=cap)
+        return self.pack_search_value(cap_rows=cap)[:n_rows]
+
     def examples(self):
         """finished games' rows, compacted on the device; only the valid rows cross PCIe"""
         ex = unpack_example_block(self.example_block())
         if self.surprise:
             ex.kl = self._packed_kl(len(ex)).cpu().numpy()
+        if self.search_value:
+            ex.q = self._packed_q(len(ex)).cpu().numpy()
         return ex
 
     def block_geometry(self):
@@ -569,6 +626,8 @@ class SelfPlayEngine:
         ex = unpack_example_block_device(self.example_block(), self.block_geometry())
         if self.surprise:
             ex.kl = self._packed_kl(len(ex))
+        if self.search_value:
+            ex.q = self._packed_q(len(ex))
         return ex
 
     def winners(self):
@@ -701,7 +760,7 @@ def unpack_example_block_device(block, geom):
 def concat_examples(parts):
     cat = lambda f: np.concatenate([getattr(p, f) for p in parts])  # noqa: E731
     return Examples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                    parts[0].size, cat("kl") if _all_or_none_kl(parts) else None)
+                    parts[0].size, *(cat(f) if _all_or_none(parts, f, what) else None for f, what in _OPTIONAL_FIELDS))
 
 
 # ---------------------------------------------------------------- packed example blocks (include/bz_abi.h)
@@ -846,8 +905,9 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 forced_playouts=None, surprise=False, **engine_kwargs):
+                 forced_playouts=None, surprise=False, search_value=False, **engine_kwargs):
         assert 1 <= pipelines <= n_games
+        check_search_value(search_value)
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
         check_playout_cap(playout_cap, sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
@@ -863,9 +923,10 @@ class PipelinedSelfPlay:
         stride = n_games if game_id_stride is None else game_id_stride
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                                       playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise, **engine_kwargs)
+                                       playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
+                                       search_value=search_value, **engine_kwargs)
                         for i in range(pipelines)]
-        self.surprise = bool(surprise)
+        self.surprise, self.search_value = bool(surprise), bool(search_value)
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
 
@@ -962,35 +1023,51 @@ class PipelinedSelfPlay:
             e.pack_examples(out, cap, append=i > 0)
         return out
 
-    def pack_examples_with_surprise(self, out=None, cap_rows=None):
-        """pack_examples() plus the rows' kl (surprise=True): (block, float32 [cap_rows] device tensor in the block's row
-        order).  Each engine's kl is packed right behind its rows, while the row offsets its pack left are current."""
-        if not self.surprise:
-            raise RuntimeError("pack_examples_with_surprise(): built without surprise=True")
+    def _pack_with_extras(self, out=None, cap_rows=None):
+        """pack_examples() plus the per-row arrays the engines record next to the block: (block, kl or None, q or None), each
+        array a float32 [cap_rows] device tensor in the block's row order.  Each engine's arrays are packed right behind its
+        rows, while the row offsets its pack left are current."""
         cap = int(cap_rows or self.packed_capacity())
         if out is None:
             out = alloc_packed_block(self.na, cap, self.device)
-        kl = torch.zeros(cap, dtype=torch.float32, device=self.device)
+        kl = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.surprise else None
+        q = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.search_value else None
         self.join()
         for i, e in enumerate(self.engines):
             e.pack_examples(out, cap, append=i > 0)
-            e.pack_surprise(kl, cap, append=i > 0)
-        return out, kl
+            if kl is not None:
+                e.pack_surprise(kl, cap, append=i > 0)
+            if q is not None:
+                e.pack_search_value(q, cap, append=i > 0)
+        return out, kl, q
+
+    def pack_examples_with_surprise(self, out=None, cap_rows=None):
+        """pack_examples() plus the rows' kl (surprise=True): (block, float32 [cap_rows] device tensor in the block's row
+        order)"""
+        if not self.surprise:
+            raise RuntimeError("pack_examples_with_surprise(): built without surprise=True")
+        return self._pack_with_extras(out, cap_rows)[:2]
+
+    def pack_examples_with_search_value(self, out=None, cap_rows=None):
+        """pack_examples() plus the rows' q (search_value=True): (block, float32 [cap_rows] device tensor in the block's row
+        order)"""
+        if not self.search_value:
+            raise RuntimeError("pack_examples_with_search_value(): built without search_value=True")
+        blk, _, q = self._pack_with_extras(out, cap_rows)
+        return blk, q
 
     def device_examples(self):
-        if not self.surprise:
-            return unpack_packed_block_device(self.pack_examples())
-        blk, kl = self.pack_examples_with_surprise()
+        blk, kl, q = self._pack_with_extras()
         ex = unpack_packed_block_device(blk)
-        ex.kl = kl[:len(ex)]
+        ex.kl = None if kl is None else kl[:len(ex)]
+        ex.q = None if q is None else q[:len(ex)]
         return ex
 
     def examples(self):
-        if not self.surprise:
-            return unpack_packed_block(self.pack_examples())
-        blk, kl = self.pack_examples_with_surprise()
+        blk, kl, q = self._pack_with_extras()
         ex = unpack_packed_block(blk)
-        ex.kl = kl[:len(ex)].cpu().numpy()
+        ex.kl = None if kl is None else kl[:len(ex)].cpu().numpy()
+        ex.q = None if q is None else q[:len(ex)].cpu().numpy()
         return ex
 
     def winners(self):
@@ -1008,7 +1085,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False):
+              surprise=False, search_value=False):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1016,7 +1093,9 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     measures); `pipelines` overrides.  The rows do not depend on it.  leaves_per_step: SelfPlayEngine (DESIGN.md 3.12);
     gumbel: SelfPlayEngine -- pi is then the improved policy.  playout_cap: SelfPlayEngine
     -- only the moves searched with the full budget yield rows.  forced_playouts: SelfPlayEngine -- pi is
-    then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`."""
+    then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`.
+    search_value: SelfPlayEngine -- the Examples then carry `q`."""
+    check_search_value(search_value)
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
     check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
@@ -1030,7 +1109,8 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            game_id_stride=game_id_stride, device=device, c_puct=c_puct, temp_moves=temp_moves,
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
-                           gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise)
+                           gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
+                           search_value=search_value)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -30,21 +30,23 @@ def make_optimizer(module, lr=1e-4):
     return torch.optim.Adam(module.parameters(), lr=lr)  # train.py:87,192
 
 
-def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True):
+def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False):
     """one Adam step on the rows `idx` of ex (Reversi 8x8 net).  ex: DeviceExamples (stays on the GPU; idx a device
     index tensor or None = all rows) or host Examples (uploaded first).  Returns (loss, policy CE, value MSE) as
-    detached device scalars."""
+    detached device scalars.  value_targets: the value MSE is against ex.vt (fp32) instead of z."""
     if isinstance(ex, Examples):
         ex = DeviceExamples.from_host(ex, device)
+    if value_targets and ex.vt is None:
+        raise ValueError("train_step: value_targets=True needs examples with vt (betazero_amd.value_targets.value_targets)")
     dev = ex.own.device
     if next(module.parameters()).device != dev:
         module.to(dev)
     module.train()
     if idx is None:
-        own, opp, pi, z = ex.own, ex.opp, ex.pi, ex.z
+        own, opp, pi, z = ex.own, ex.opp, ex.pi, ex.vt if value_targets else ex.z
     else:
         idx = torch.as_tensor(idx, device=dev)
-        own, opp, pi, z = ex.own[idx], ex.opp[idx], ex.pi[idx], ex.z[idx]
+        own, opp, pi, z = ex.own[idx], ex.opp[idx], ex.pi[idx], (ex.vt if value_targets else ex.z)[idx]
     x = planes_from_bits(own, opp)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
         logits, v = module(x)
@@ -69,7 +71,8 @@ def holdout_split(n_rows, val_fraction=0.2, generator=None, device="cuda:0"):
 def select_rows(ex, idx):
     """DeviceExamples holding the rows `idx` (a device index tensor) of ex"""
     return DeviceExamples(own=ex.own[idx], opp=ex.opp[idx], pi=ex.pi[idx], z=ex.z[idx], mover=ex.mover[idx], act=ex.act[idx],
-                          game=ex.game[idx], ply=ex.ply[idx], size=ex.size, kl=None if ex.kl is None else ex.kl[idx])
+                          game=ex.game[idx], ply=ex.ply[idx], size=ex.size, kl=None if ex.kl is None else ex.kl[idx],
+                          q=None if ex.q is None else ex.q[idx], vt=None if ex.vt is None else ex.vt[idx])
 
 
 @torch.no_grad()
@@ -108,7 +111,10 @@ class GraphedTrainStep:
     The forms of the step that go through torch autograd run eagerly unless capture_autograd=True (see __init__)."""
 
     def __init__(self, module, lr=1e-4, batch=1024, na=65, device="cuda:0", autocast=True, tower_kernels=None, lr_warmup_steps=0,
-                 step_kernels=None, fused_adam=None, capture_autograd=False):
+                 step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False):
+        # value_targets (DESIGN.md 3.18): the value loss is against the examples' fp32 `vt` instead of z -- on the all-kernel
+        # step through k_train_heads_vt (the graph is captured once with that kernel), on the autograd forms as the MSE target
+        self.value_targets = bool(value_targets)
         # (NCHW on purpose: channels-last convolutions measured ~20 % faster per step in tools/bench_train.py, but the
         # closed loop then failed to learn the value head in one run and produced non-finite weights in two others --
         # profiles/r03_az_loop_channels_last_failure.txt -- so that layout is not offered)
@@ -128,7 +134,7 @@ class GraphedTrainStep:
             if not getattr(module, "fused_tower", False):
                 raise ValueError("tower_kernels / step_kernels need PolicyValueNet(..., fused_tower=True)")
             if step_kernels:
-                self.step_plan = self.plan = StepPlan(self.module, batch, device)
+                self.step_plan = self.plan = StepPlan(self.module, batch, device, value_targets=self.value_targets)
                 self.idx = torch.zeros(batch, dtype=torch.int64, device=self.dev)   # the batch's rows: the kernels gather them themselves
             else:
                 self.plan = TowerPlan(module.C, 2 * module.NB, batch, device)
@@ -162,7 +168,7 @@ class GraphedTrainStep:
         self.own = torch.zeros(batch, dtype=torch.int64, device=self.dev)
         self.opp = torch.zeros(batch, dtype=torch.int64, device=self.dev)
         self.pi = torch.full((batch, na), 1.0 / na, dtype=torch.float32, device=self.dev)
-        self.z = torch.zeros(batch, dtype=torch.int8, device=self.dev)
+        self.z = torch.zeros(batch, dtype=torch.float32 if self.value_targets else torch.int8, device=self.dev)
         self.graph, self.out = None, None
 
     def _lr_at(self, k):
@@ -214,14 +220,16 @@ class GraphedTrainStep:
 
     def __call__(self, ex, idx):
         assert idx.numel() == self.batch, "GraphedTrainStep replays a fixed batch size"
+        if self.value_targets and ex.vt is None:
+            raise ValueError("GraphedTrainStep(value_targets=True) needs examples with vt (betazero_amd.value_targets.value_targets)")
         if self.step_plan is not None:   # the kernels read rows idx of the data set themselves: one 8-byte-per-row copy, no gathers
             self.idx.copy_(idx)
-            self.step_plan.set_batch(ex.own, ex.opp, ex.pi, ex.z, self.idx)
+            self.step_plan.set_batch(ex.own, ex.opp, ex.pi, ex.z, self.idx, vt=ex.vt if self.value_targets else None)
         else:
             torch.index_select(ex.own, 0, idx, out=self.own)
             torch.index_select(ex.opp, 0, idx, out=self.opp)
             torch.index_select(ex.pi, 0, idx, out=self.pi)
-            torch.index_select(ex.z, 0, idx, out=self.z)
+            torch.index_select(ex.vt if self.value_targets else ex.z, 0, idx, out=self.z)
         if not self.capture:   # an autograd form of the step: eager (see capture_autograd in __init__)
             self.module.train()
             self.lr_t.fill_(self._lr_at(self.steps_done))

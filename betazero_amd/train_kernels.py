@@ -145,7 +145,9 @@ class StepPlan(TowerPlan):
 
     NAMES = ("stem_w", "stem_b", "tower_w", "tower_b", "pol_w", "pol_b", "polfc_w", "polfc_b", "val_w", "val_b", "v1_w", "v1_b", "v2_w", "v2_b")
 
-    def __init__(self, module, batch, device="cuda:0"):
+    def __init__(self, module, batch, device="cuda:0", value_targets=False):
+        """value_targets: the head kernel reads a float value target per row (set_batch(..., vt=...)) in place
+        of z, through k_train_heads_vt; everything else of the step is the same"""
         if not getattr(module, "fused_tower", False):
             raise ValueError("StepPlan needs PolicyValueNet(..., fused_tower=True)")
         if module.VH > 64:
@@ -174,12 +176,17 @@ class StepPlan(TowerPlan):
                                             heads=self.heads_partial.data_ptr(), heads_w=self.heads_w_partial.data_ptr(), splits=self.splits)
         self.batch_desc = torch.zeros(ct.sizeof(_lib.TrainBatch), dtype=torch.uint8, device=dev)
         self._batch_refs = None
+        # the address of the data set's fp32 value targets: one device word, rewritten by set_batch like the descriptor
+        self.value_targets = bool(value_targets)
+        self.vt_slot = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._vt_ref = None
         self._adam, self.adam_m, self.adam_v, self.hyper = None, None, None, None
 
     # ---- the batch
-    def set_batch(self, own, opp, pi, z, idx=None):
+    def set_batch(self, own, opp, pi, z, idx=None, vt=None):
         """point the step at rows `idx` (int64 [batch], on the device; None: rows 0..batch-1) of the data set (own, opp, pi,
-        z).  Asynchronous on the current stream; the tensors are kept alive until the next call."""
+        z).  Asynchronous on the current stream; the tensors are kept alive until the next call.  vt: the data set's value
+        targets, fp32 [rows] (a plan built with value_targets=True needs them; they are gathered by the same idx)."""
         n, dev = self.n, self.device
         rows = int(own.shape[0])
         if rows < 1:
@@ -189,6 +196,11 @@ class StepPlan(TowerPlan):
               all(t.is_contiguous() and t.device == dev for t in (own, opp, pi, z)))
         if not ok:
             raise ValueError("set_batch: own / opp int64 [rows], pi fp32 [rows, 65], z int8 [rows], contiguous, on the plan's device")
+        if self.value_targets:
+            if vt is None or not (vt.dtype == torch.float32 and vt.shape == (rows,) and vt.is_contiguous() and vt.device == dev):
+                raise ValueError("set_batch: a plan with value_targets=True needs vt fp32 [rows], contiguous, on the plan's device")
+        elif vt is not None:
+            raise ValueError("set_batch: vt given, but the plan was built without value_targets=True")
         if idx is None:
             if rows < n:
                 raise ValueError(f"set_batch: the data set has {rows} rows, the batch needs {n}")
@@ -201,6 +213,11 @@ class StepPlan(TowerPlan):
             with torch.cuda.device(dev):
                 self.batch_desc.copy_(torch.frombuffer(bytearray(key), dtype=torch.uint8))
         self._batch_refs = (key, own, opp, pi, z, idx)
+        if self.value_targets:
+            if self._vt_ref is None or self._vt_ref.data_ptr() != vt.data_ptr():
+                with torch.cuda.device(dev):
+                    self.vt_slot.copy_(torch.tensor([vt.data_ptr()], dtype=torch.int64))
+            self._vt_ref = vt
 
     # ---- the optimiser as the step's tenth launch
     def enable_adam(self, lr, betas=(0.9, 0.999), eps=1e-8, warmup_steps=0):
@@ -258,8 +275,15 @@ class StepPlan(TowerPlan):
             chk(L.bz_train_pack_weights(p["tower_w"].data_ptr(), Cc, Ly, self.wf_fwd.data_ptr(), self.wf_bwd.data_ptr(), st))
             chk(L.bz_train_tower_fwd(self.acts[0].data_ptr(), self.wf_fwd.data_ptr(), p["tower_b"].data_ptr(), Cc, Ly, n, self.acts[1].data_ptr(),
                                      self.masks.data_ptr(), st))
-            chk(L.bz_train_heads(self.acts[Ly].data_ptr(), bd, n, Cc, self.VH, ct.byref(self._head), self.gs[Ly].data_ptr(),
-                                 self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(), self.heads_partial.data_ptr(), st))
+            if self.value_targets:
+                if self._vt_ref is None:
+                    raise RuntimeError("StepPlan: set_batch(..., vt=...) first")
+                chk(L.bz_train_heads_vt(self.acts[Ly].data_ptr(), bd, self.vt_slot.data_ptr(), n, Cc, self.VH, ct.byref(self._head),
+                                        self.gs[Ly].data_ptr(), self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(),
+                                        self.heads_partial.data_ptr(), st))
+            else:
+                chk(L.bz_train_heads(self.acts[Ly].data_ptr(), bd, n, Cc, self.VH, ct.byref(self._head), self.gs[Ly].data_ptr(),
+                                     self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(), self.heads_partial.data_ptr(), st))
             chk(L.bz_train_tower_bwd(self.gs[Ly].data_ptr(), self.wf_bwd.data_ptr(), self.zeros_c.data_ptr(), self.masks.data_ptr(), Cc, Ly, n,
                                      self.gs[0].data_ptr(), st))
             chk(L.bz_train_wgrad(self.acts[0].data_ptr(), self.gs[1].data_ptr(), Cc, Ly, n, self.splits, self.partial.data_ptr(),
@@ -287,11 +311,11 @@ class StepPlan(TowerPlan):
             raise IndexError(f"StepPlan: {n} batch position(s) had a row index outside the data set since the last check; "
                              "the kernels clamp instead of faulting, so those steps trained on the wrong rows")
 
-    def grads(self, own=None, opp=None, pi=None, z=None, idx=None):
+    def grads(self, own=None, opp=None, pi=None, z=None, idx=None, vt=None):
         """forward, losses, backward: every parameter's .grad is set; returns the static [loss, CE, MSE, error word] tensor.
-        (own, opp, pi, z[, idx]) given: set_batch() first."""
+        (own, opp, pi, z[, idx][, vt]) given: set_batch() first."""
         if own is not None:
-            self.set_batch(own, opp, pi, z, idx)
+            self.set_batch(own, opp, pi, z, idx, vt=vt)
         return self.launch(adam=False)
 
     def step(self):

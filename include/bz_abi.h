@@ -488,6 +488,40 @@ int32_t bz_surprise_resample(const float* kl, const int64_t* game, const int32_t
 /* count_i of one row, the function the kernels run.  Host only. */
 int32_t bz_surprise_count(float kl, float mean, float uniform_frac, uint64_t seed, int64_t game, int32_t ply, uint64_t own,
                           uint64_t opp, int32_t* count);
+/* Search-value targets, opt-in per engine.  Every row bz_engine_play records also gets the root's search
+ * value q: over the root's edges in edge order (ascending action) sW = 0.0f, sW = sW + W_i (one binary32 add each), sN = sum
+ * N_i (integer), q = sN > 0 ? fdiv(sW, (float)sN) : 0.0f.  W is stored for the mover at the root: q is the
+ * mover's expected outcome.  Always the RAW visit statistics: under Gumbel, under forced playouts (not the pruned visits), with
+ * subtree reuse (carried visits included) and with leaves_per_step > 1 (no virtual loss is left after a search).  The feature
+ * observes: bz_engine_play launches one one-lane-per-game kernel in front of its play kernel, while the searched tree is in
+ * place -- so it does not depend on how the search ran (fused, step kernels, the step API), and searches, rows, counters and
+ * bz_engine_layout are what they are without it.  A fast search under the playout cap records no row and no q. */
+/* bytes of the caller-owned buffer: ex_q f32 [rounds][n_games][t_max] (the row index of ex_pi), 256-byte aligned.  Needs no
+ * GPU; -1 (bz_last_error says why) for a bad config. */
+int64_t bz_engine_search_value_bytes(const bz_engine_cfg* cfg);
+/* switch the mode on (buf: device memory of >= bz_engine_search_value_bytes bytes, 256-byte aligned, owned by the caller and
+ * kept alive while the mode is on; zeroed on `stream`) or off (buf == NULL), between searches. */
+int32_t bz_engine_set_search_value(bz_engine* e, void* buf, int64_t bytes, void* stream);
+/* ex_q in the packed block's row order: bz_engine_pack_surprise's contract (after bz_engine_pack_examples, same stream, same
+ * cap_rows; append_rows: the rows already in `out`). */
+int32_t bz_engine_pack_search_value(bz_engine* e, float* out, int64_t cap_rows, int32_t append_rows, void* stream);
+/* q of one root, the function the kernel runs: N, W [n] in edge order, n in 1 .. 255.  Host only. */
+int32_t bz_root_value(const uint32_t* N, const float* W, int32_t n, float* q);
+/* Value targets from (q, z) (TD(lambda): Sutton 1988).  Device only, asynchronous, nothing read back.  q f32, z
+ * i8, mover i8 (+-1), game i64, ply i32 [n]: the rows, n <= 2^26; lam, q_mix in [0, 1] (anything else, NaN included: BZ_EINVAL
+ * before a launch).  Row i starts a segment iff i == 0, game[i] != game[i-1] or ply[i] <= ply[i-1]: a segment is one game's
+ * recorded rows in ply order (what the packed block delivers).  Per segment of T rows, every line one binary32 operation:
+ *   c_t = q_t != q_t ? 0 : clamp(q_t, -1, 1);  A_t = mover_t == 1 ? c_t : -c_t;  Z = (float)(mover_{T-1} * z_{T-1})
+ *   G_{T-1} = Z;  for t = T-2 .. 0:  a = 1 - lam; a = a * A_{t+1}; b = lam * G_{t+1}; G_t = a + b
+ *   c = 1 - q_mix; c = c * G_t; d = q_mix * A_t; T_t = clamp(c + d, -1, 1);  vt_t = mover_t == 1 ? T_t : -T_t
+ * lam = 1, q_mix = 0: vt == (float)z by value; lam = 0, q_mix = 1: vt == the cleaned q.  One lane per segment walks it
+ * backward, at most 1024 rows (the engine's segments have at most 256): a longer segment gets vt = (float)z on all its rows
+ * and adds 1 to *status_dev, a u64 word in device memory that the call zeroes first and the caller may read once the stream
+ * has run.  vt f32 [n]. */
+int32_t bz_value_targets(const float* q, const int8_t* z, const int8_t* mover, const int64_t* game, const int32_t* ply, int64_t n,
+                         float lam, float q_mix, float* vt, uint64_t* status_dev, void* stream);
+/* one segment, the function the kernel runs: q, z, mover, vt [T], T in 1 .. 1024.  Host only. */
+int32_t bz_value_targets_segment(const float* q, const int8_t* z, const int8_t* mover, int32_t T, float lam, float q_mix, float* vt);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
@@ -720,6 +754,14 @@ int32_t bz_train_stem_wgrad(const bz_train_batch* batch_dev, const void* act0, c
  * weight gradients (hv fp32 [n][192], dl [n][65], dv1 [n][64]) and partial [sizes[2]][sizes[3]]. */
 int32_t bz_train_heads(const void* act_top, const bz_train_batch* batch_dev, int32_t n, int32_t C, int32_t VH,
                        const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1, float* partial, void* stream);
+/* The same with a float value target: loss = mean CE + mean (v - vt)^2.  vt_slot_dev is ONE pointer-sized word
+ * in DEVICE memory holding the address of an fp32 [n_rows] array, gathered by the batch's idx with the same clamping and
+ * error word as z -- a device word for the reason bz_train_batch lives in device memory: a captured step keeps working when
+ * the data set (and its targets) is replaced.  Everything else is bz_train_heads: with vt == (float)z every output is the
+ * same bits. */
+int32_t bz_train_heads_vt(const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot_dev, int32_t n,
+                          int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
+                          float* partial, void* stream);
 /* partial [sizes[4]][sizes[5]] */
 int32_t bz_train_heads_wgrad(const float* hv, const float* dl, const float* dv1, int32_t n, int32_t VH, float* partial, void* stream);
 /* every partial sum -> the gradient tensors G (torch layouts); losses[4] = loss, policy CE, value MSE of the batch, and the

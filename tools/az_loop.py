@@ -39,6 +39,7 @@ from betazero_amd.engine import (ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, 
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
+from betazero_amd.value_targets import value_targets  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
                                 train_step, validate)
 
@@ -83,6 +84,11 @@ def main():
                     "are not resampled")
     ap.add_argument("--surprise-uniform", type=float, default=0.5, help="the share of the weight every row gets regardless of its "
                     "surprise (KataGo's 0.5)")
+    ap.add_argument("--value-lambda", type=float, default=None, help="search-value targets (DESIGN.md 3.18): the value head trains on the "
+                    "TD(lambda) return bootstrapped from the later roots' search values instead of the game's outcome; 1 = the outcome, "
+                    "0 = the next recorded root's value.  Switches the recording of the root value on")
+    ap.add_argument("--value-q-mix", type=float, default=None, help="search-value targets: the weight of the row's own root value in the "
+                    "target, (1 - M) * return + M * q; 0.5 at --value-lambda 1 averages z and q.  Switches the recording on")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -95,10 +101,13 @@ def main():
 
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
+    use_vt = args.value_lambda is not None or args.value_q_mix is not None
+    v_lam, v_mix = 1.0 if args.value_lambda is None else args.value_lambda, 0.0 if args.value_q_mix is None else args.value_q_mix
     kernels = not (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256)
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
-    graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup)
+    graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
+                                                                  value_targets=use_vt)
     bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
@@ -135,9 +144,14 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
+                               surprise=args.surprise, search_value=use_vt, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
+        vt_info = {}
+        if use_vt:  # while every game's rows stand together in ply order: before the split and the augmentation
+            ex = value_targets(ex, v_lam, v_mix)
+            vt_info = {"value_targets": {"lambda": v_lam, "q_mix": v_mix,
+                                         "mean_abs_vt_minus_z": round(float((ex.vt - ex.z.to(torch.float32)).abs().mean()), 5)}}
         winners, _ = sp.winners()
         cnt = sp.counters()
         torch.cuda.synchronize()
@@ -167,7 +181,7 @@ def main():
             if graphed is not None:
                 losses.append(graphed(data, idx))
             else:
-                losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train)))
+                losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train, value_targets=use_vt)))
         losses = torch.stack(losses).cpu().numpy()  # one transfer per iteration, after the last step
         if graphed is not None:
             graphed.check()                         # an out-of-range row index in any step of the iteration raises here
@@ -198,7 +212,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
-              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise,
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
               "arena": arena("net_bf16", cand), **gate})
