@@ -112,6 +112,11 @@ _SIGS = {
     "bz_net_forward_f32": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "bz_net_forward_bf16": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "bz_net_forward_fp8": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "bz_sym_index": (u32, [u64, u64, u64]),
+    "bz_sym_board": (i32, [u64, i32, i32, C.POINTER(u64)]),
+    "bz_sym_action_map": (i32, [i32, i32, vp]),
+    "bz_net_sym_scratch_bytes": (i64, [i64]),
+    "bz_net_forward_sym": (i32, [vp, i32, vp, vp, i32, i32, i32, u64, vp, i64, vp, vp, vp]),
     "bz_mlp_param_count": (i64, [i32]),
     "bz_mlp_workspace_bytes": (i64, [i32, i32]),
     "bz_mlp_create": (i32, [i32, i32, vp, vp, i64, vp, C.POINTER(vp)]),
@@ -130,6 +135,7 @@ _SIGS = {
     "bz_engine_set_net": (i32, [vp, vp]),
     "bz_engine_set_mlp": (i32, [vp, vp]),
     "bz_engine_debug_set_search_seq": (i32, [vp, C.c_uint32]),
+    "bz_engine_set_eval_symmetry": (i32, [vp, i32, u64]),
     "bz_engine_reset_games": (i32, [vp, vp]),
     "bz_engine_set_roots": (i32, [vp, vp, vp, vp, vp]),
     "bz_engine_search": (i32, [vp, vp]),

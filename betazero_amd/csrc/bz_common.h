@@ -49,6 +49,10 @@ int32_t bz_mlp_max_batch(const bz_mlp* mlp);
 // bz_net.hip: forward over the first *n_dev (device counter, <= max_n) positions; n_dev may be null
 int32_t bz_net_forward_dev(bz_net* net, int bf16, const uint64_t* own, const uint64_t* opp, int32_t max_n,
                            const uint32_t* n_dev, float* logits, float* value, void* stream);
+// bz_net.hip: the same under a board symmetry (bz_abi.h: bz_net_forward_sym; MEAN takes no device-side count)
+int32_t bz_net_forward_sym_dev(bz_net* net, int kind, const uint64_t* own, const uint64_t* opp, int32_t max_n, const uint32_t* n_dev,
+                               int32_t size, int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits,
+                               float* value, void* stream);
 // bz_mlp.hip: MLP forward over the first *n_dev (<= max_n) rows of own/opp (or of x when it is not null); value
 // (optional) gets 0 per row -- the MLP has no value head
 int32_t bz_mlp_forward_dev(bz_mlp* mlp, int bf16, const uint64_t* own, const uint64_t* opp, const float* x, int32_t max_n,

@@ -2106,6 +2106,10 @@ struct bz_engine {
     ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
     SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
+    // hashed evaluation symmetry (bz_engine_set_eval_symmetry); on the engine, not on the net: two pipelines
+    // and two match players share one bz_net
+    int sym_on;
+    uint64_t sym_seed;
 };
 
 namespace {
@@ -2239,6 +2243,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     bz_engine* e = new (std::nothrow) bz_engine();
     if (!e) { set_error("out of host memory"); return BZ_ENOMEM; }
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
+    e->sym_on = 0; e->sym_seed = 0;
     e->gumbel = GumbelDev{};  // off
     e->cap = CapDev{};
     e->forced = ForcedDev{};
@@ -2325,6 +2330,20 @@ BZ_EXPORT int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp) {
     BZ_REQUIRE(e->dev.K == 1 || !mlp || (int64_t)bz_mlp_max_batch(mlp) >= (int64_t)e->dev.K * e->dev.B,
                "bz_engine_set_mlp: the MLP's max_batch is below leaves_per_step x n_games (the evaluator rows of one step)");
     e->mlp = mlp;
+    return BZ_OK;
+}
+
+/* Hashed evaluation symmetry: on != 0 -> bz_engine_evaluate runs the net's HASHED forward with `seed`; the
+ * evaluator stays a function of the position, so the cache, the carry-over and every search option keep their guarantees.
+ * A change of the setting or of the seed is a change of evaluator: like a change of weights, nothing is carried over it. */
+BZ_EXPORT int32_t bz_engine_set_eval_symmetry(bz_engine* e, int32_t on, uint64_t seed) {
+    BZ_REQUIRE(e, "bz_engine_set_eval_symmetry: null engine");
+    on = on != 0;
+    if (!on) seed = 0;
+    BZ_REQUIRE(!on || (net_eval(e->cfg.eval_kind) && e->cfg.game != BZ_GAME_TTT),
+               "bz_engine_set_eval_symmetry: the evaluation symmetry serves the net_f32 / net_bf16 / net_fp8 evaluators on the Reversi boards");
+    if (on != e->sym_on || seed != e->sym_seed) e->eval_epoch = 0;  // no net has epoch 0
+    e->sym_on = on; e->sym_seed = seed;
     return BZ_OK;
 }
 
@@ -2432,6 +2451,11 @@ BZ_EXPORT int32_t bz_engine_evaluate(bz_engine* e, void* stream) {
     // every size), cells outside are never stones and never legal, so the same net serves them
     BZ_REQUIRE(e->cfg.game != BZ_GAME_TTT, "bz_engine_evaluate: the conv net serves the Reversi boards, not tic-tac-toe");
     // leaves were packed by select: evaluate only the first flags[NEVAL] slots (device-side count)
+    const int kind = ek == BZ_EVAL_NET_BF16 ? 1 : (ek == BZ_EVAL_NET_FP8 ? 2 : 0);
+    if (e->sym_on)  // every leaf under the symmetry its position and the seed hash to
+        return bz_net_forward_sym_dev(e->net, kind, e->dev.c_own, e->dev.c_opp, e->dev.B * e->dev.K, e->dev.flags + FLAG_NEVAL + e->pack_parity,
+                                      e->cfg.game == BZ_GAME_REVERSI6 ? 6 : (e->cfg.game == BZ_GAME_REVERSI4 ? 4 : 8), BZ_SYM_HASHED,
+                                      e->sym_seed, nullptr, 0, e->dev.logits, e->dev.value, stream);
     return bz_net_forward_dev(e->net, ek == BZ_EVAL_NET_BF16 ? 1 : (ek == BZ_EVAL_NET_FP8 ? 2 : 0), e->dev.c_own, e->dev.c_opp, e->dev.B * e->dev.K,
                               e->dev.flags + FLAG_NEVAL + e->pack_parity, e->dev.logits, e->dev.value, stream);
 }

@@ -30,6 +30,7 @@
 
 #include "bz_common.h"
 #include "bz_math.h"
+#include "bz_sym.h"
 #include "bz_tower.h"
 
 using namespace bz;
@@ -62,35 +63,14 @@ struct bz_net {
 
 namespace {
 
-// ------------------------------------------------------------------ stem
-// thread = output channel, block = position.  x in {0,1}: fmaf(1,w,acc) == acc + w.
-template <class OutT>
-__global__ void k_stem(const u64* __restrict__ own, const u64* __restrict__ opp, int n, const u32* n_dev, int C,
-                       const float* __restrict__ w, const float* __restrict__ b, OutT* __restrict__ out) {
-    int pos = blockIdx.x, co = threadIdx.x;
-    if (n_dev) n = (int)*n_dev;
-    if (pos >= n || co >= C) return;
-    u64 me = own[pos], you = opp[pos];
-    float wr[18];
-#pragma unroll
-    for (int i = 0; i < 18; ++i) wr[i] = w[i * C + co];
-    float bias = b[co];
-    for (int cell = 0; cell < 64; ++cell) {
-        int y = cell >> 3, x = cell & 7;
-        float acc = bias;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-            if (yy < 0 || yy > 7 || xx < 0 || xx > 7) continue;
-            int c2 = yy * 8 + xx;
-            // the oracle's fmaf(plane, w, acc) with the plane in {0, 1}: a stone adds w, an empty cell adds 0 * w (NaN for
-            // an infinite w, as torch's convolution gives)
-            acc = __builtin_fmaf((float)((me >> c2) & 1ULL), wr[2 * t], acc);
-            acc = __builtin_fmaf((float)((you >> c2) & 1ULL), wr[2 * t + 1], acc);
-        }
-        out[((size_t)pos * 64 + cell) * C + co] = (OutT)relu_f32(acc);
-    }
-}
+// ------------------------------------------------------------------ stem and heads (f32 parity path)
+// k_stem, k_heads and, under a board symmetry, k_sym_stem, k_sym_heads: one text compiled twice
+#define BZ_NET_SYM 0
+#include "bz_net_ends_body.h"
+#undef BZ_NET_SYM
+#define BZ_NET_SYM 1
+#include "bz_net_ends_body.h"
+#undef BZ_NET_SYM
 
 // ------------------------------------------------------------------ f32 conv (parity path)
 // block = position, 256 threads; thread = (co, cell group); 8 cells per pass.
@@ -134,56 +114,6 @@ __global__ void __launch_bounds__(256) k_conv_f32(const float* __restrict__ in, 
             if (skip) v = v + skip[o];
             out[o] = relu_f32(v);
         }
-    }
-}
-
-// ------------------------------------------------------------------ heads (both paths)
-// block = position, 192 threads.  Every dot product is a sequential fmaf chain in
-// the oracle's order, so with f32 activations the result is bit-identical.
-template <class InT>
-__global__ void __launch_bounds__(192) k_heads(const InT* __restrict__ act, int n, const u32* n_dev, int C, int VH,
-                                               const float* __restrict__ pol_w, const float* __restrict__ pol_b,
-                                               const float* __restrict__ polfc_wT, const float* __restrict__ polfc_b,
-                                               const float* __restrict__ val_w, const float* __restrict__ val_b,
-                                               const float* __restrict__ v1_wT, const float* __restrict__ v1_b,
-                                               const float* __restrict__ v2_w, const float* __restrict__ v2_b,
-                                               float* __restrict__ logits, float* __restrict__ value) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* xs = reinterpret_cast<float*>(smem_raw);  // [64][C+1]
-    float* pf = xs + 64 * (C + 1);                   // [128]
-    float* vf = pf + 128;                            // [64]
-    float* vh = vf + 64;                             // [VH]
-    int pos = blockIdx.x, tid = threadIdx.x;
-    if (n_dev) n = (int)*n_dev;
-    if (pos >= n) return;
-    const InT* x = act + (size_t)pos * 64 * C;
-    for (int i = tid; i < 64 * C; i += 192) xs[(i / C) * (C + 1) + (i % C)] = (float)x[i];
-    __syncthreads();
-    {   // conv1x1: threads 0..127 -> policy (j, cell); 128..191 -> value (cell)
-        int cell = tid & 63, j = tid >> 6;
-        const float* wj = j < 2 ? pol_w + (size_t)j * C : val_w;
-        float acc = j < 2 ? pol_b[j] : val_b[0];
-        const float* xi = xs + cell * (C + 1);
-        for (int c = 0; c < C; ++c) acc = __builtin_fmaf(xi[c], wj[c], acc);
-        acc = relu_f32(acc);
-        if (j < 2) pf[j * 64 + cell] = acc; else vf[cell] = acc;
-    }
-    __syncthreads();
-    if (tid < 65) {
-        float acc = polfc_b[tid];
-        for (int i = 0; i < 128; ++i) acc = __builtin_fmaf(pf[i], polfc_wT[i * 65 + tid], acc);
-        logits[(size_t)pos * 65 + tid] = acc;
-    } else if (tid >= 128 && tid - 128 < VH) {
-        int h = tid - 128;
-        float acc = v1_b[h];
-        for (int i = 0; i < 64; ++i) acc = __builtin_fmaf(vf[i], v1_wT[i * VH + h], acc);
-        vh[h] = relu_f32(acc);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float acc = v2_b[0];
-        for (int h = 0; h < VH; ++h) acc = __builtin_fmaf(vh[h], v2_w[h], acc);
-        value[pos] = tanhf_spec(acc);
     }
 }
 
@@ -260,189 +190,13 @@ __device__ __forceinline__ float wave_sum(float x) {
     return x;
 }
 
-// The whole net forward for P positions per workgroup: stem (MFMA, K = 18 padded to 32, fed from
-// the bitboards) -> residual tower (activations resident in LDS) -> heads (conv1x1 by MFMA, the
-// small FCs by one wave per position).  HBM traffic per position: 16 B in, 264 B out.
-template <class G>
-__global__ void __launch_bounds__(256, 1)
-k_tower_bf16(TowerArgs T) {
-    constexpr int C = G::C, P = G::P, PW = G::PW, MW = G::MW;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pos0 = blockIdx.x * P;
-    if (T.n_dev) T.n = (int)*T.n_dev;
-    if (pos0 >= T.n) return;  // block-uniform, before any barrier
-    [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0}, tk0 = 0, tk1 = 0, tr0 = 0, tr1 = 0;
-    BZ_STAMP(tk0);
-#ifdef BZ_EXP_STAMPS
-    tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    char* bufX = smem;
-    char* bufM = smem + G::BUF;
-    const int r = lane & 31, h = lane >> 5;
-
-    // ---- zero cells (conv halo: cell indices 0, 9, .., 72 of every position) of both buffers
-    constexpr int ZC = G::CELL / 16;  // 16-byte chunks per cell
-    for (int i = tid; i < 2 * P * 9 * ZC; i += 256) {
-        int k = i % ZC, j = (i / ZC) % 9, pb = i / (9 * ZC);  // pb = buffer * P + position: BUF = P * TILE
-        *reinterpret_cast<uint4*>(smem + pb * G::TILE + j * G::ROWC * G::CELL + k * 16) = make_uint4(0, 0, 0, 0);
-    }
-    // weight-fragment stream of this wave: k-step ks, M-tile mt -> wf[(ks * MT + mt) * 64 + lane], linear over layers
-    const int wt0 = G::wt0(w), wp0 = G::pos0(w);
-    // wave-uniform base (scalar registers) + lane: the loads take the SGPR-base addressing mode, so advancing the stream
-    // costs scalar adds instead of 64-bit vector adds between the MFMAs
-    const uint4* ap = G::M16 ? T.wf16 + (size_t)wt0 * 2 * 64 : T.wf + (size_t)wt0 * 64;
-    typename WSetsOf<G>::type WS;
-    if constexpr (G::M16) {  // tap 0 of the first layer: KQ steps x 2 channel halves
-#pragma unroll
-        for (int kq = 0; kq < G::KQ; ++kq)
-#pragma unroll
-            for (int a = 0; a < 2; ++a) WS.s[0][kq][a] = __builtin_bit_cast(bf16x8, ap[(kq * G::MT * 2 + a) * 64 + (unsigned)lane]);
-        ap += G::KQ * G::MT * 2 * 64;
-    } else {
-#pragma unroll
-        for (int d = 0; d + 1 < G::DEPTH; ++d) {  // chunks 0 .. DEPTH - 2 of the first layer
-#pragma unroll
-            for (int kc = 0; kc < G::KS; ++kc)
-#pragma unroll
-                for (int mt = 0; mt < MW; ++mt) WS.s[d][kc][mt] = __builtin_bit_cast(bf16x8, ap[(kc * G::MT + mt) * 64 + (unsigned)lane]);
-            ap += G::KS * G::MT * 64;
-        }
-    }
-
-    // ---- stem: conv3x3 2 -> C as a [C x 32] x [32 x 64] GEMM per position
-    if constexpr (G::M16) {  // K = 32 is ONE 16x16x32 MFMA per quarter: lane (c, g) feeds cell c of half b with k = 8g ..
-        f32x16 acc[MW][G::NU];
-        Bias<G> bias;
-        const int c = lane & 15, g = lane >> 4;
-        load_bias16<G>(bias, T.stem_b, wt0, g);
-        bf16x8 sa[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) sa[a] = __builtin_bit_cast(bf16x8, T.stem_wf16[(wt0 * 2 + a) * 64 + lane]);
-        u64 own[2], opp[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            int pos = pos0 + wp0 + 2 * b + (c >> 3);
-            pos = pos < T.n ? pos : T.n - 1;
-            own[b] = T.own[pos]; opp[b] = T.opp[pos];
-        }
-#pragma unroll
-        for (int u = 0; u < G::NU; ++u) {
-            acc[0][u] = (f32x16)(0.0f);
-            const int cell = 8 * u + (c & 7);
-            const bf16x8 f0 = stem_frag16(nbhd(own[0], cell), nbhd(opp[0], cell), g);
-            const bf16x8 f1 = stem_frag16(nbhd(own[1], cell), nbhd(opp[1], cell), g);
-            mfma16_quarter<0>(acc[0][u], sa[0], f0);
-            mfma16_quarter<1>(acc[0][u], sa[0], f1);
-            mfma16_quarter<2>(acc[0][u], sa[1], f0);
-            mfma16_quarter<3>(acc[0][u], sa[1], f1);
-        }
-        epilogue16<G>(acc, bufX + wp0 * G::TILE, false, bias, wt0, lane);
-    } else {
-        f32x16 acc[MW][G::NU];
-        Bias<G> bias;
-        load_bias<G>(bias, T.stem_b, wt0, h);
-        bf16x8 sa[2][MW];
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc)
-#pragma unroll
-            for (int mt = 0; mt < MW; ++mt) sa[kc][mt] = __builtin_bit_cast(bf16x8, T.stem_wf[(kc * G::MT + wt0 + mt) * 64 + lane]);
-        constexpr int NB = G::ROWT ? 1 : PW;  // row-tile units: every lane feeds ONE position (r >> 3) in all units
-        u64 own[NB], opp[NB];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            int pos = pos0 + wp0 + (G::ROWT ? r >> 3 : i);
-            pos = pos < T.n ? pos : T.n - 1;
-            own[i] = T.own[pos]; opp[i] = T.opp[pos];
-        }
-#pragma unroll
-        for (int u = 0; u < G::NU; ++u) {
-            const int i = G::ROWT ? 0 : u >> 1;
-            const int cell = G::unit_cell(u, r);
-            const unsigned n_own = nbhd(own[i], cell), n_opp = nbhd(opp[i], cell);
-            bf16x8 sf[2] = {stem_frag<0>(n_own, n_opp, h), stem_frag<1>(n_own, n_opp, h)};
-#pragma unroll
-            for (int mt = 0; mt < MW; ++mt) {
-                acc[mt][u] = (f32x16)(0.0f);
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc)
-                    acc[mt][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[kc][mt], sf[kc], acc[mt][u], 0, 0, 0);
-            }
-        }
-        epilogue<G>(acc, bufX + wp0 * G::TILE, false, bias, wt0, r, h);
-    }
-    __syncthreads();
-
-    // ---- tower: a residual block = conv1 (X -> M) + conv2 (M -> X in place, + skip X)
-#pragma unroll 1
-    for (int blk = 0; blk < T.n_layers / 2; ++blk) {
-        conv_layer<0, G>(bufX, bufM, false, T.bias + (size_t)(2 * blk) * C, WS, ap, w, r, h, tacc);
-        conv_layer<G::NCH % G::DEPTH, G>(bufM, bufX, true, T.bias + (size_t)(2 * blk + 1) * C, WS, ap, w, r, h, tacc);
-    }
-    BZ_STAMP(tk1);
-
-    // ---- heads: wave w serves positions w, w + 4, ...  conv1x1 (policy 2 ch + value 1 ch) by MFMA against
-    // the resident tile, then the FCs in fp32 with the position's 192 features staged in LDS (M is dead now).
-    float* S = reinterpret_cast<float*>(bufM + w * 1024);  // [pf 128 | vf 64], one scratch per wave
-    const float pb0 = T.pol_b[0], pb1 = T.pol_b[1], vb = T.val_b[0];
-    bf16x8 hw[G::KC];  // all head-conv fragments in flight at once (one L2 round trip, not one per MFMA)
-#pragma unroll
-    for (int kc = 0; kc < G::KC; ++kc) hw[kc] = __builtin_bit_cast(bf16x8, T.head_wf[kc * 64 + lane]);
-    for (int p = w; p < P && pos0 + p < T.n; p += 4) {
-        const int pos = pos0 + p;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            f32x16 acc = (f32x16)(0.0f);
-            const int cell = 32 * nt + r;
-#pragma unroll
-            for (int kc = 0; kc < G::KC; ++kc) {
-                bf16x8 b = *reinterpret_cast<const bf16x8*>(bufX + p * G::TILE + G::cell_off(p, cell, 2 * kc + h));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hw[kc], b, acc, 0, 0, 0);
-            }
-            if (h == 0) {  // rows 0..2 of D live in registers 0..2 of lanes 0..31
-                float a0 = acc[0] + pb0, a1 = acc[1] + pb1, a2 = acc[2] + vb;
-                S[cell] = relu_f32(a0);
-                S[64 + cell] = relu_f32(a1);
-                S[128 + cell] = relu_f32(a2);
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS writes have landed
-        // policy FC 128 -> 65: lane a owns logit a; logit 64 (pass) is a wave reduction
-        // (the fma chains below keep their order; the unroll factors only decide how many weight loads are in flight)
-        float acc = T.polfc_b[lane], part = 0.0f;
-#pragma unroll 8
-        for (int i = 0; i < 128; i += 4) {
-            f32x4 s4 = *reinterpret_cast<const f32x4*>(S + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_fmaf(s4[j], T.polfc_wT[(i + j) * 65 + lane], acc);
-        }
-        part = S[lane] * T.polfc_wT[lane * 65 + 64] + S[lane + 64] * T.polfc_wT[(lane + 64) * 65 + 64];
-        part = wave_sum(part);
-        T.logits[(size_t)pos * 65 + lane] = acc;
-        if (lane == 0) T.logits[(size_t)pos * 65 + 64] = part + T.polfc_b[64];
-        // value FC 64 -> VH -> 1, tanh
-        float vh = 0.0f;
-        if (lane < T.VH) {
-            float a = T.v1_b[lane];
-#pragma unroll 32
-            for (int i = 0; i < 64; ++i) a = __builtin_fmaf(S[128 + i], T.v1_wT[i * T.VH + lane], a);
-            vh = relu_f32(a) * T.v2_w[lane];
-        }
-        vh = wave_sum(vh);
-        if (lane == 0) T.value[pos] = tanhf_spec(vh + T.v2_b[0]);
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // the scratch is reused for the wave's next position
-    }
-#ifdef BZ_EXP_STAMPS
-    unsigned long long tk2; BZ_STAMP(tk2);
-    tr1 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0 && blockIdx.x < 4096) {
-        unsigned long long* d = g_dbg + blockIdx.x * 8;
-        d[0] = tacc[0]; d[1] = tacc[1]; d[2] = tacc[2]; d[3] = tk1 - tk0; d[4] = tk2 - tk0; d[5] = tr1 - tr0; d[6] = tk0; d[7] = tr0;
-    }
-#endif
-}
-
+// The whole net forward for P positions per workgroup, k_tower_bf16<G>, and the same under a board symmetry, k_sym_bf16<G>
+#define BZ_NET_SYM 0
+#include "bz_net_tower_bf16_body.h"
+#undef BZ_NET_SYM
+#define BZ_NET_SYM 1
+#include "bz_net_tower_bf16_body.h"
+#undef BZ_NET_SYM
 
 // ====================================================================================
 // fp8 variant (BASELINE config 5): same decomposition, tower on
@@ -636,129 +390,31 @@ __device__ __forceinline__ void conv_layer(const char* in, char* out, bool secon
     tacc[0] += t1 - t0; tacc[1] += t2 - t1; tacc[2] += t3 - t2;
 }
 
-// 74.8 KB of LDS per workgroup: two workgroups per CU hide each other's epilogues (launch bound 2 waves per SIMD)
-__global__ void __launch_bounds__(256, 2) k_tower_fp8(TowerArgs T) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pos0 = blockIdx.x * 4;
-    if (T.n_dev) T.n = (int)*T.n_dev;
-    if (pos0 >= T.n) return;
-    [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0}, tk0 = 0, tk1 = 0, tr0 = 0, tr1 = 0;
-    BZ_STAMP(tk0);
-#ifdef BZ_EXP_STAMPS
-    tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    char* bufX = smem;
-    char* bufM = smem + kBuf;
-    const int r = lane & 31, h = lane >> 5;
-
-    for (int i = tid; i < 2 * 4 * 9 * 8; i += 256) {  // zero cells 0, 9, .., 72 of 2 buffers x 4 positions (8 x 16 B each)
-        int k = i & 7, j = (i >> 3) % 9, pb = i / 72;
-        *reinterpret_cast<uint4*>(smem + pb * kTile + j * kRowC * kCell + k * 16) = make_uint4(0, 0, 0, 0);
-    }
-    // weight stream: tap t, k-step ks, co-tile w, 16-byte halves: wf8[(((t*2 + ks)*4 + w)*2 + half)*64 + lane]
-    const uint4* ap = T.wf8 + (size_t)(w * 2) * 64;  // wave-uniform base + lane (SGPR-base addressing)
-    v8i A0[2], A1[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        uint4 lo = ap[((ks * 4) * 2 + 0) * 64 + (unsigned)lane], hi = ap[((ks * 4) * 2 + 1) * 64 + (unsigned)lane];
-        v8i v = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-        A0[ks] = v;
-    }
-    ap += 2 * 4 * 2 * 64;
-
-    // ---- stem (bf16 MFMA, exact 0/1 inputs) -> e4m3 activations
-    {
-        f32x16 acc[8];
-        Scale sc;
-        load_scale(sc, T.ones, T.stem_b, w, h);
-        bf16x8 sa[2];
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) sa[kc] = __builtin_bit_cast(bf16x8, T.stem_wf[(kc * 4 + w) * 64 + lane]);
-        int pos = pos0 + (r >> 3) < T.n ? pos0 + (r >> 3) : T.n - 1;  // every lane feeds ONE position in all units
-        u64 own = T.own[pos], opp = T.opp[pos];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const unsigned n_own = nbhd(own, 8 * u + (r & 7)), n_opp = nbhd(opp, 8 * u + (r & 7));
-            acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0], stem_frag<0>(n_own, n_opp, h), (f32x16)(0.0f), 0, 0, 0);
-            acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[1], stem_frag<1>(n_own, n_opp, h), acc[u], 0, 0, 0);
-        }
-        epilogue(acc, bufX, false, sc, w, r, h);
-    }
-    __syncthreads();
-
-#pragma unroll 1
-    for (int blk = 0; blk < T.n_layers / 2; ++blk) {
-        conv_layer<0>(bufX, bufM, false, T.dq8 + (size_t)(2 * blk) * kTC, T.bias + (size_t)(2 * blk) * kTC, A0, A1, ap, w, r, h, tacc);
-        conv_layer<1>(bufM, bufX, true, T.dq8 + (size_t)(2 * blk + 1) * kTC, T.bias + (size_t)(2 * blk + 1) * kTC, A0, A1, ap, w,
-                      r, h, tacc);
-    }
-
-    BZ_STAMP(tk1);
-    // ---- heads: wave p serves position p (conv1x1 in fp8, FCs in fp32)
-    if (pos0 + w < T.n) {
-        const int p = w, pos = pos0 + w;
-        float* S = reinterpret_cast<float*>(bufM + p * 1024);
-        const float pb0 = T.pol_b[0], pb1 = T.pol_b[1], vb = T.val_b[0];
-        const float d0 = T.head_dq8[0], d1 = T.head_dq8[1], d2 = T.head_dq8[2];
-        v8i hw[2];  // both head-conv fragments in flight before the first MFMA
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 lo = T.head_wf8[(ks * 2 + 0) * 64 + lane], hi = T.head_wf8[(ks * 2 + 1) * 64 + lane];
-            v8i a = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-            hw[ks] = a;
-        }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            f32x16 acc = (f32x16)(0.0f);
-            const int cell = 32 * nt + r;
-            const int cb = cell_at(cell >> 3, cell & 7) + (((2 * h) ^ sw3(p, cell & 7)) << 4);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                v8i b = ld32(bufX + p * kTile, cb ^ (ks << 6), 0);
-                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hw[ks], b, acc, 0, 0, 0, kUnit, 0, kUnit);
-            }
-            if (h == 0) {
-                float a0 = acc[0] * d0 + pb0, a1 = acc[1] * d1 + pb1, a2 = acc[2] * d2 + vb;
-                S[cell] = relu_f32(a0);
-                S[64 + cell] = relu_f32(a1);
-                S[128 + cell] = relu_f32(a2);
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        // (the fma chains below keep their order; the unroll factors only decide how many weight loads are in flight)
-        float acc = T.polfc_b[lane], part = 0.0f;
-#pragma unroll 8
-        for (int i = 0; i < 128; i += 4) {
-            f32x4 s4 = *reinterpret_cast<const f32x4*>(S + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_fmaf(s4[j], T.polfc_wT[(i + j) * 65 + lane], acc);
-        }
-        part = S[lane] * T.polfc_wT[lane * 65 + 64] + S[lane + 64] * T.polfc_wT[(lane + 64) * 65 + 64];
-        part = wave_sum(part);
-        T.logits[(size_t)pos * 65 + lane] = acc;
-        if (lane == 0) T.logits[(size_t)pos * 65 + 64] = part + T.polfc_b[64];
-        float vh = 0.0f;
-        if (lane < T.VH) {
-            float a = T.v1_b[lane];
-#pragma unroll 32
-            for (int i = 0; i < 64; ++i) a = __builtin_fmaf(S[128 + i], T.v1_wT[i * T.VH + lane], a);
-            vh = relu_f32(a) * T.v2_w[lane];
-        }
-        vh = wave_sum(vh);
-        if (lane == 0) T.value[pos] = tanhf_spec(vh + T.v2_b[0]);
-    }
-#ifdef BZ_EXP_STAMPS
-    unsigned long long tk2; BZ_STAMP(tk2);
-    tr1 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0 && blockIdx.x < 4096) {
-        unsigned long long* d = g_dbg + blockIdx.x * 8;
-        d[0] = tacc[0]; d[1] = tacc[1]; d[2] = tacc[2]; d[3] = tk1 - tk0; d[4] = tk2 - tk0; d[5] = tr1 - tr0; d[6] = tk0; d[7] = tr0;
-    }
-#endif
-}
+// k_tower_fp8 and k_sym_fp8
+#define BZ_NET_SYM 0
+#include "bz_net_tower_fp8_body.h"
+#undef BZ_NET_SYM
+#define BZ_NET_SYM 1
+#include "bz_net_tower_fp8_body.h"
+#undef BZ_NET_SYM
 }  // namespace f8
+
+// MEAN: the eight FIXED forwards sit in `part` as [8][n][65] logits followed by [8][n] values; every
+// output is ((..(x_0 + x_1) + ..) + x_7) * 0.125f in fp32, in this order
+__global__ void __launch_bounds__(256) k_sym_mean(const float* __restrict__ part, int n, float* __restrict__ logits,
+                                                  float* __restrict__ value) {
+    const int64_t nl = (int64_t)n * 65, total = nl + n;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const bool isv = i >= nl;
+        const float* src = isv ? part + 8 * nl + (i - nl) : part + i;
+        const int64_t stride = isv ? n : nl;
+        float acc = src[0] + src[stride];
+#pragma unroll
+        for (int s = 2; s < 8; ++s) acc = acc + src[s * stride];
+        acc = acc * 0.125f;
+        if (isv) value[i - nl] = acc; else logits[i] = acc;
+    }
+}
 
 // ------------------------------------------------------------------ host helpers
 struct Carver {
@@ -1021,10 +677,19 @@ BZ_EXPORT int32_t bz_net_create(int32_t C, int32_t NB, int32_t VH, int32_t max_b
         if (C == 256) { e3 = BZ_TOWER_LDS(Tw<256>); if (e3 == hipSuccess) e3 = BZ_TOWER_LDS(TwS256); }  // TwS256: 73 KB
 #undef BZ_TOWER_LDS
         if (e3 != hipSuccess) { delete n; return hip_fail(e3, "hipFuncSetAttribute(k_tower_bf16)"); }
+#define BZ_TOWER_LDS(GEOM) hipFuncSetAttribute(reinterpret_cast<const void*>(k_sym_bf16<GEOM>), hipFuncAttributeMaxDynamicSharedMemorySize, GEOM::LDS)
+        if (C == 64) { e3 = BZ_TOWER_LDS(Tw<64>); if (e3 == hipSuccess) e3 = BZ_TOWER_LDS(TwS64); }
+        if (C == 128) { e3 = BZ_TOWER_LDS(TwM16); if (e3 == hipSuccess) e3 = BZ_TOWER_LDS(TwS128); }
+        if (C == 256) { e3 = BZ_TOWER_LDS(Tw<256>); if (e3 == hipSuccess) e3 = BZ_TOWER_LDS(TwS256); }
+#undef BZ_TOWER_LDS
+        if (e3 != hipSuccess) { delete n; return hip_fail(e3, "hipFuncSetAttribute(k_sym_bf16)"); }
         // the f32 parity kernels stage a whole position in LDS: above 64 KB at C = 256
         if (C == 256) {
             e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_heads<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)((64 * (C + 1) + 128 + 64 + 64) * sizeof(float)));
+            if (e3 == hipSuccess)
+                e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sym_heads<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)((64 * (C + 1) + 128 + 64 + 64) * sizeof(float)));
             if (e3 == hipSuccess)
                 e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_f32), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)(64 * C * sizeof(float)));
@@ -1034,6 +699,8 @@ BZ_EXPORT int32_t bz_net_create(int32_t C, int32_t NB, int32_t VH, int32_t max_b
     if (C == kTC) {
         hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(f8::k_tower_fp8), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  f8::kLds);
+        if (e3 == hipSuccess)
+            e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(f8::k_sym_fp8), hipFuncAttributeMaxDynamicSharedMemorySize, f8::kLds);
         if (e3 != hipSuccess) { delete n; return hip_fail(e3, "hipFuncSetAttribute(k_tower_fp8)"); }
     }
     *out = n;
@@ -1061,12 +728,14 @@ BZ_EXPORT int32_t bz_debug_read(void* dst, int64_t bytes) {
 }
 #endif
 
+// Y (here and in forward_bf16): null = the plain kernels; otherwise the symmetric ones
 static int32_t forward_f32(bz_net* n, const uint64_t* own, const uint64_t* opp, int32_t cnt, const u32* n_dev,
-                           float* logits, float* value, void* stream) {
+                           float* logits, float* value, void* stream, const bz_sym::Args* Y = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     int C = n->C;
     if (n->f32_used) BZ_HIP(hipStreamWaitEvent(s, n->f32_done, 0));
-    hipLaunchKernelGGL(k_stem<float>, dim3(cnt), dim3(C), 0, s, own, opp, cnt, n_dev, C, n->stem_w, n->stem_b, n->act_a);
+    if (Y) hipLaunchKernelGGL(k_sym_stem<float>, dim3(cnt), dim3(C), 0, s, own, opp, cnt, n_dev, C, n->stem_w, n->stem_b, n->act_a, *Y);
+    else hipLaunchKernelGGL(k_stem<float>, dim3(cnt), dim3(C), 0, s, own, opp, cnt, n_dev, C, n->stem_w, n->stem_b, n->act_a);
     BZ_LAUNCH_CHECK("k_stem<float>");
     size_t lds = (size_t)64 * C * sizeof(float);
     for (int blk = 0; blk < n->NB; ++blk) {
@@ -1080,6 +749,10 @@ static int32_t forward_f32(bz_net* n, const uint64_t* own, const uint64_t* opp, 
         BZ_LAUNCH_CHECK("k_conv_f32");
     }
     size_t hl = (64 * (n->C + 1) + 128 + 64 + 64) * sizeof(float);
+    if (Y)
+        hipLaunchKernelGGL(k_sym_heads<float>, dim3(cnt), dim3(192), hl, s, n->act_a, cnt, n_dev, n->C, n->VH, n->pol_w, n->pol_b,
+                           n->polfc_wT, n->polfc_b, n->val_w, n->val_b, n->v1_wT, n->v1_b, n->v2_w, n->v2_b, logits, value, own, opp, *Y);
+    else
     hipLaunchKernelGGL(k_heads<float>, dim3(cnt), dim3(192), hl, s, n->act_a, cnt, n_dev, n->C, n->VH, n->pol_w, n->pol_b,
                        n->polfc_wT, n->polfc_b, n->val_w, n->val_b, n->v1_wT, n->v1_b, n->v2_w, n->v2_b, logits, value);
     BZ_LAUNCH_CHECK("k_heads<float>");
@@ -1089,7 +762,7 @@ static int32_t forward_f32(bz_net* n, const uint64_t* own, const uint64_t* opp, 
 }
 
 static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp, int32_t cnt, const u32* n_dev,
-                            float* logits, float* value, void* stream, bool fp8) {
+                            float* logits, float* value, void* stream, bool fp8, const bz_sym::Args* Y = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     TowerArgs T;
     T.own = own; T.opp = opp; T.n_dev = n_dev; T.n = cnt; T.n_layers = 2 * n->NB; T.VH = n->VH;
@@ -1103,16 +776,21 @@ static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp,
     T.v2_b = n->v2_b; T.logits = logits; T.value = value;
     {
         ProfScope ps(BZ_PROF_TOWER, stream);
-        if (fp8) hipLaunchKernelGGL(f8::k_tower_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T);
-        else {
-            // up to kSmallBatch positions: one (two at C = 64) per workgroup, i.e. per CU -- the latency shape
-            const bool small = cnt <= kSmallBatch;
-#define BZ_TOWER_LAUNCH(GEOM) hipLaunchKernelGGL(k_tower_bf16<GEOM>, dim3((cnt + GEOM::P - 1) / GEOM::P), dim3(256), GEOM::LDS, s, T)
-            if (n->C == 64) { if (small) BZ_TOWER_LAUNCH(TwS64); else BZ_TOWER_LAUNCH(Tw<64>); }
-            else if (n->C == 256) { if (small) BZ_TOWER_LAUNCH(TwS256); else BZ_TOWER_LAUNCH(Tw<256>); }
-            else { if (small) BZ_TOWER_LAUNCH(TwS128); else BZ_TOWER_LAUNCH(TwM16); }
+        // up to kSmallBatch positions: one (two at C = 64) per workgroup, i.e. per CU -- the latency shape
+        const bool small = cnt <= kSmallBatch;
+        // KERNEL = k_tower_bf16, or k_sym_bf16 with the symmetry as its second argument: the same geometries and launch shapes
+#define BZ_TOWER_LAUNCH(KERNEL, GEOM, ...) hipLaunchKernelGGL(KERNEL<GEOM>, dim3((cnt + GEOM::P - 1) / GEOM::P), dim3(256), GEOM::LDS, s, __VA_ARGS__)
+#define BZ_TOWER_PICK(KERNEL, ...) do {                                                                               \
+            if (n->C == 64) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS64, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<64>, __VA_ARGS__); }        \
+            else if (n->C == 256) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS256, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<256>, __VA_ARGS__); } \
+            else { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS128, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, TwM16, __VA_ARGS__); }                    \
+        } while (0)
+        if (fp8 && Y) hipLaunchKernelGGL(f8::k_sym_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T, *Y);
+        else if (fp8) hipLaunchKernelGGL(f8::k_tower_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T);
+        else if (Y) BZ_TOWER_PICK(k_sym_bf16, T, *Y);
+        else BZ_TOWER_PICK(k_tower_bf16, T);
+#undef BZ_TOWER_PICK
 #undef BZ_TOWER_LAUNCH
-        }
     }
     BZ_LAUNCH_CHECK("k_tower_bf16");
     return BZ_OK;
@@ -1144,4 +822,61 @@ BZ_EXPORT int32_t bz_net_forward_bf16(bz_net* n, const uint64_t* own, const uint
 BZ_EXPORT int32_t bz_net_forward_fp8(bz_net* n, const uint64_t* own, const uint64_t* opp, int32_t cnt, float* logits,
                                      float* value, void* stream) {
     return bz_net_forward_dev(n, 2, own, opp, cnt, nullptr, logits, value, stream);
+}
+
+// ------------------------------------------------------------------ the forward under a board symmetry
+static int64_t sym_scratch_bytes(int64_t n) { return ((8 * n * 66 * 4) + 255) & ~int64_t(255); }
+
+int32_t bz_net_forward_sym_dev(bz_net* n, int kind, const uint64_t* own, const uint64_t* opp, int32_t max_n, const uint32_t* n_dev,
+                               int32_t size, int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits,
+                               float* value, void* stream) {
+    BZ_REQUIRE(n && own && opp && logits && value, "bz_net_forward_sym: null pointer");
+    BZ_REQUIRE(kind >= 0 && kind <= 2, "bz_net_forward_sym: kind must be 0 (f32), 1 (bf16) or 2 (fp8)");
+    BZ_REQUIRE(kind != 1 || n->C == 64 || n->C == 128 || n->C == 256,
+               "bz_net_forward_sym: the MFMA tower is built for 64, 128 or 256 channels");
+    BZ_REQUIRE(kind != 2 || n->C == kTC, "bz_net_forward_sym: the fp8 tower is built for C == 128");
+    BZ_REQUIRE(max_n >= 0 && max_n <= n->max_batch, "bz_net_forward_sym: batch exceeds max_batch");
+    BZ_REQUIRE(size == 8 || size == 6 || size == 4, "bz_net_forward_sym: size must be 8, 6 or 4");
+    BZ_REQUIRE(mode == BZ_SYM_FIXED || mode == BZ_SYM_HASHED || mode == BZ_SYM_MEAN, "bz_net_forward_sym: unknown mode");
+    BZ_REQUIRE(mode != BZ_SYM_FIXED || arg < 8, "bz_net_forward_sym: FIXED takes a symmetry index 0..7");
+    if (max_n == 0) return BZ_OK;
+    auto run = [&](const bz_sym::Args& Y, float* lg, float* vl) {
+        return kind ? forward_bf16(n, own, opp, max_n, n_dev, lg, vl, stream, kind == 2, &Y)
+                    : forward_f32(n, own, opp, max_n, n_dev, lg, vl, stream, &Y);
+    };
+    if (mode != BZ_SYM_MEAN) return run(bz_sym::Args{arg, mode == BZ_SYM_HASHED, size}, logits, value);
+    BZ_REQUIRE(!n_dev, "bz_net_forward_sym: MEAN takes a host-side count");
+    BZ_REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "bz_net_forward_sym: MEAN needs a 256-byte aligned scratch");
+    if (scratch_bytes < sym_scratch_bytes(max_n)) { set_error("bz_net_forward_sym: scratch too small (bz_net_sym_scratch_bytes)"); return BZ_ENOMEM; }
+    float* part = static_cast<float*>(scratch);
+    for (int s = 0; s < 8; ++s) {
+        int32_t rc = run(bz_sym::Args{(uint64_t)s, 0, size}, part + (size_t)s * max_n * 65, part + (size_t)8 * max_n * 65 + (size_t)s * max_n);
+        if (rc != BZ_OK) return rc;
+    }
+    const int64_t total = (int64_t)max_n * 66;
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_sym_mean, dim3(blocks), dim3(256), 0, (hipStream_t)stream, part, max_n, logits, value);
+    BZ_LAUNCH_CHECK("k_sym_mean");
+    return BZ_OK;
+}
+
+BZ_EXPORT int64_t bz_net_sym_scratch_bytes(int64_t n) {
+    if (n < 0 || n > (int64_t)1 << 24) { set_error("bz_net_sym_scratch_bytes: n out of range"); return -1; }
+    return sym_scratch_bytes(n);
+}
+BZ_EXPORT int32_t bz_net_forward_sym(bz_net* n, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t cnt, int32_t size,
+                                     int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits, float* value,
+                                     void* stream) {
+    return bz_net_forward_sym_dev(n, kind, own, opp, cnt, nullptr, size, mode, arg, scratch, scratch_bytes, logits, value, stream);
+}
+BZ_EXPORT uint32_t bz_sym_index(uint64_t seed, uint64_t own, uint64_t opp) { return bz_sym::index(seed, own, opp); }
+BZ_EXPORT int32_t bz_sym_board(uint64_t b, int32_t size, int32_t s, uint64_t* out) {
+    BZ_REQUIRE(out && size >= 1 && size <= 8 && s >= 0 && s < 8, "bz_sym_board: size must be 1..8, s 0..7, out non-null");
+    *out = bz_sym::board(b, size, (u32)s);
+    return BZ_OK;
+}
+BZ_EXPORT int32_t bz_sym_action_map(int32_t size, int32_t s, uint8_t* map) {
+    BZ_REQUIRE(map && size >= 1 && size <= 8 && s >= 0 && s < 8, "bz_sym_action_map: size must be 1..8, s 0..7, map non-null");
+    for (int j = 0; j < 65; ++j) map[j] = (uint8_t)bz_sym::tau(size, (u32)s, j);
+    return BZ_OK;
 }

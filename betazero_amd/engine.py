@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .symmetry import EvalSymmetry, check_eval_symmetry  # noqa: F401  (EvalSymmetry: re-exported next to the other options)
 from ._lib import (EVAL_EXTERNAL, EVAL_HASH, EVAL_NET_BF16, EVAL_NET_F32, EVAL_NET_FP8, EVAL_UNIFORM, GAME_REVERSI,
                    GAME_REVERSI4, GAME_REVERSI6, GAME_TTT, EngineCfg, EngineLayout)
 
@@ -19,6 +20,9 @@ _EVALS = {"uniform": EVAL_UNIFORM, "hash": EVAL_HASH, "net_f32": EVAL_NET_F32, "
           "external": EVAL_EXTERNAL, "net_fp8": EVAL_NET_FP8,
           # the reference's tic-tac-toe MLP (betazero_amd.mlp.DeviceMLP as `net`): policy logits, value 0
           "mlp_f32": _lib.EVAL_MLP_F32, "mlp_bf16": _lib.EVAL_MLP_BF16}
+
+
+_EVAL_NAMES = {v: k for k, v in _EVALS.items()}
 
 
 def _u64(t):
@@ -278,7 +282,8 @@ class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
-                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False):
+                 leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
+                 eval_symmetry=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -316,7 +321,15 @@ class SelfPlayEngine:
         sum W / sum N of its search (the mover's expected outcome, from the raw visit statistics), which examples() /
         device_examples() then carry as `q` and betazero_amd.value_targets.value_targets turns into value targets.  Searches,
         moves and rows are what they are without it; it combines with everything the engine accepts.  search_value_rows() is
-        the unpacked per-row view."""
+        the unpacked per-row view.
+
+        eval_symmetry: None / False = off (the default, unchanged); True or an EvalSymmetry(seed) = every
+        leaf is evaluated under a board symmetry chosen by a hash of (its position, the seed) -- True takes the engine's
+        `seed` -- inside the fused net kernels; priors and values come back in the position's own orientation.  The
+        evaluator stays a function of the position, so it combines with everything the engine accepts and the cache stays
+        exact; set_eval_symmetry() changes it between searches.  Refused on tic-tac-toe and with the synthetic, external
+        and MLP evaluators."""
+        self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
         self.surprise = bool(surprise)
@@ -390,6 +403,8 @@ class SelfPlayEngine:
             self._spad = (-self.sws.data_ptr()) & 255
             self._sbytes = sbytes
             self._call(L.bz_engine_set_surprise, self.sws.data_ptr() + self._spad, sbytes)
+        if self.eval_symmetry is not None:
+            _lib.check(L.bz_engine_set_eval_symmetry(self.h, 1, self.eval_symmetry.seed))
         if self.search_value:  # the engine's ex_q buffer (caller-owned, like the workspace)
             vbytes = L.bz_engine_search_value_bytes(C.byref(self.cfg))
             if vbytes < 0:
@@ -424,6 +439,15 @@ class SelfPlayEngine:
         assert own.numel() == self.B
         self._call(_lib.lib().bz_engine_set_roots, own.data_ptr(), opp.data_ptr(), tm.data_ptr())
         torch.cuda.current_stream(self.device).synchronize()  # keep own/opp/tm alive until consumed
+
+    def set_eval_symmetry(self, eval_symmetry):
+        """switch the hashed evaluation symmetry on, off or to another seed, between searches: None /
+        False, True (the engine's seed) or an EvalSymmetry.  Like a change of weights it is a change of evaluator: the
+        evaluation cache carries nothing over it."""
+        es = check_eval_symmetry(eval_symmetry, int(self.cfg.seed), self.game, _EVAL_NAMES[self.cfg.eval_kind])
+        self.drain()
+        _lib.check(_lib.lib().bz_engine_set_eval_symmetry(self.h, int(es is not None), es.seed if es is not None else 0))
+        self.eval_symmetry = es
 
     def search(self):
         self._call(_lib.lib().bz_engine_search)
@@ -905,8 +929,10 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 forced_playouts=None, surprise=False, search_value=False, **engine_kwargs):
+                 forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
+        # every pipeline gets the same seed, so the same position has the same orientation in all of them
+        eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
         check_search_value(search_value)
         check_leaves_per_step(leaves_per_step)
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
@@ -924,7 +950,7 @@ class PipelinedSelfPlay:
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
                                        playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                                       search_value=search_value, **engine_kwargs)
+                                       search_value=search_value, eval_symmetry=eval_symmetry, **engine_kwargs)
                         for i in range(pipelines)]
         self.surprise, self.search_value = bool(surprise), bool(search_value)
         e0 = self.engines[0]
@@ -1085,7 +1111,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False, search_value=False):
+              surprise=False, search_value=False, eval_symmetry=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1094,7 +1120,8 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     gumbel: SelfPlayEngine -- pi is then the improved policy.  playout_cap: SelfPlayEngine
     -- only the moves searched with the full budget yield rows.  forced_playouts: SelfPlayEngine -- pi is
     then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`.
-    search_value: SelfPlayEngine -- the Examples then carry `q`."""
+    search_value: SelfPlayEngine -- the Examples then carry `q`.  eval_symmetry: SelfPlayEngine (DESIGN.md
+    3.19) -- every leaf is evaluated under a hashed board symmetry (True: seeded by `seed`)."""
     check_search_value(search_value)
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
@@ -1103,6 +1130,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
+    eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
     if pipelines is None:
         pipelines = 2 if (evaluator.startswith(("net_", "mlp_")) and n_games >= 2) else 1
     sp = PipelinedSelfPlay(game, n_games, sims, evaluator, net, pipelines, game_id_base=game_id_base,
@@ -1110,7 +1138,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
                            gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                           search_value=search_value)
+                           search_value=search_value, eval_symmetry=eval_symmetry)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

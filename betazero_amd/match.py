@@ -22,7 +22,9 @@ class MatchPlayer:
     """One side of a match; the fields are MCTSPlayer's.  evaluator: "uniform" | "hash" | "net_f32" | "net_bf16" | "net_fp8"
     (a betazero_amd.net.DeviceNet as `net`, Reversi) | "mlp_f32" | "mlp_bf16" (a betazero_amd.mlp.DeviceMLP, tic-tac-toe);
     default: "net_bf16" / "mlp_f32" with a net, else "uniform".  leaves_per_step: DESIGN.md 3.12; gumbel (True or an
-    engine.GumbelConfig): DESIGN.md 3.13, the side plays the Gumbel move without Gumbel noise; eval_cache: SelfPlayEngine's."""
+    engine.GumbelConfig): DESIGN.md 3.13, the side plays the Gumbel move without Gumbel noise; eval_cache: SelfPlayEngine's;
+    eval_symmetry (True or a symmetry.EvalSymmetry): DESIGN.md 3.19, the side evaluates every leaf under a hashed board
+    symmetry (True: seed 0) -- a match stays a pure function of its arguments."""
     sims: int = 800
     net: object = None
     evaluator: str = None
@@ -30,6 +32,7 @@ class MatchPlayer:
     leaves_per_step: int = 1
     gumbel: object = None
     eval_cache: object = True
+    eval_symmetry: object = None
 
     def checked(self, game, n_games, side):
         """-> (evaluator name, GumbelConfig or None); ValueError for anything a match cannot play, before any device is touched"""
@@ -52,6 +55,8 @@ class MatchPlayer:
             if self.net.max_batch < k * n_games:
                 raise ValueError(f"play_match: player {side}: the net's max_batch {self.net.max_batch} < n_games {n_games}" +
                                  (f" x leaves_per_step {k}" if k > 1 else "") + " (both engines hold all the match's slots)")
+        from .symmetry import check_eval_symmetry
+        check_eval_symmetry(self.eval_symmetry, 0, game, ev)
         return ev, gumbel
 
 
@@ -217,7 +222,7 @@ def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cud
     dev = torch.device(device)
     B = int(n_games)
     engs = [SelfPlayEngine(ename, B, p.sims, ev, p.net, p.c_puct, device=device, eval_cache=p.eval_cache,
-                           leaves_per_step=p.leaves_per_step, gumbel=gum)
+                           leaves_per_step=p.leaves_per_step, gumbel=gum, eval_symmetry=p.eval_symmetry)
             for p, ev, gum in ((a, ev_a, gum_a), (b, ev_b, gum_b))]
     m = Match(ename, B, device)
     streams = pipeline_streams(dev, 2)

@@ -144,15 +144,36 @@ class DeviceNet:
     def from_module(cls, module, max_batch, device="cuda:0"):
         return cls(module.C, module.NB, module.VH, module.flat_params(), max_batch, device)
 
-    def forward(self, own, opp, bf16=True, fp8=False):
-        """own/opp: uint64-as-int64 CUDA tensors [n] -> (logits [n,65] f32, value [n] f32)"""
+    def forward(self, own, opp, bf16=True, fp8=False, symmetry=None, size=8, seed=0):
+        """own/opp: uint64-as-int64 CUDA tensors [n] -> (logits [n,65] f32, value [n] f32).
+        symmetry: None = the plain forward (the default, unchanged); an int 0..7 = every row under that
+        board symmetry; "hash" = row i under bz_sym_index(seed, own_i, opp_i) -- what an engine with eval_symmetry runs;
+        "mean" = the fp32 mean over the eight symmetries (validation and analysis: eight forwards).  Outputs are in the
+        caller's orientation.  size: the board size (8, 6 or 4) the symmetries act on."""
+        from .symmetry import SYM_MEAN, check_forward_symmetry
+        sym = check_forward_symmetry(symmetry, size, seed)
         n = own.numel()
         logits = torch.empty((n, 65), dtype=torch.float32, device=self.device)
         value = torch.empty((n,), dtype=torch.float32, device=self.device)
-        fn = _lib.lib().bz_net_forward_fp8 if fp8 else (_lib.lib().bz_net_forward_bf16 if bf16 else _lib.lib().bz_net_forward_f32)
+        L = _lib.lib()
         with torch.cuda.device(self.device):
-            _lib.check(fn(self.h, own.data_ptr(), opp.data_ptr(), n, logits.data_ptr(), value.data_ptr(),
-                          torch.cuda.current_stream().cuda_stream))
+            st = torch.cuda.current_stream().cuda_stream
+            if sym is None:
+                fn = L.bz_net_forward_fp8 if fp8 else (L.bz_net_forward_bf16 if bf16 else L.bz_net_forward_f32)
+                _lib.check(fn(self.h, own.data_ptr(), opp.data_ptr(), n, logits.data_ptr(), value.data_ptr(), st))
+            else:
+                mode, arg = sym
+                scratch, sbytes, sptr = None, 0, 0
+                if mode == SYM_MEAN:
+                    sbytes = L.bz_net_sym_scratch_bytes(n)
+                    if sbytes < 0:
+                        raise RuntimeError(_lib.last_error())
+                    scratch = torch.empty(sbytes + 256, dtype=torch.uint8, device=self.device)
+                    sptr = (scratch.data_ptr() + 255) & ~255
+                _lib.check(L.bz_net_forward_sym(self.h, 2 if fp8 else (1 if bf16 else 0), own.data_ptr(), opp.data_ptr(), n, size,
+                                                mode, arg, sptr, sbytes, logits.data_ptr(), value.data_ptr(), st))
+                if scratch is not None:
+                    scratch.record_stream(torch.cuda.current_stream())
         return logits, value
 
     def update(self, params):

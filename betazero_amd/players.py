@@ -150,10 +150,11 @@ class MCTSPlayer(Player):
     with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0).
     gumbel (True or an engine.GumbelConfig): Gumbel root search -- the move is the one the Gumbel search
     plays (SelfPlayEngine.root_policy) and last_policy its improved policy; the player draws no Gumbel noise (temp_moves 0),
-    so it is deterministic."""
+    so it is deterministic.  eval_symmetry (True or a symmetry.EvalSymmetry): every leaf is evaluated under a hashed board
+    symmetry (True: seed 0); net evaluators on Reversi only."""
 
     def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1,
-                 gumbel=None):
+                 gumbel=None, eval_symmetry=None):
         from .engine import check_gumbel, check_leaves_per_step, check_sims
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
         self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step (DESIGN.md 3.12)
@@ -167,6 +168,8 @@ class MCTSPlayer(Player):
         from .mlp import DeviceMLP
         self._mlp = isinstance(net, DeviceMLP)
         self.evaluator = evaluator or (("mlp_f32" if self._mlp else "net_bf16") if net is not None else "uniform")
+        from .symmetry import check_eval_symmetry
+        self.eval_symmetry = check_eval_symmetry(eval_symmetry, 0, None, self.evaluator)
         self._eng = {}
         self.last_visits = None
         self.last_policy = None  # Gumbel mode: the improved policy of the last search, float32 [NA]
@@ -175,7 +178,8 @@ class MCTSPlayer(Player):
         from .engine import SelfPlayEngine
         if game not in self._eng:
             self._eng[game] = SelfPlayEngine(game, 1, self.sims, self.evaluator, self.net, self.c_puct,
-                                             device=self.device, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel)
+                                             device=self.device, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel,
+                                             eval_symmetry=self.eval_symmetry)
         return self._eng[game]
 
     def get_move(self, board):

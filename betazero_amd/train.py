@@ -76,12 +76,14 @@ def select_rows(ex, idx):
 
 
 @torch.no_grad()
-def validate(device_net, ex, idx=None):
+def validate(device_net, ex, idx=None, symmetry=None):
     """The validation line of the reference's training loop (SL/train.py:121-146: loss and accuracy on the held-out rows
     after every epoch) for (s, pi, z) examples, on the net the SEARCH uses -- the engine's bf16 MFMA forward
     (DeviceNet.forward), i.e. on the weights as they will play: mean policy cross-entropy against pi, value MSE against z,
     and top-1 agreement (argmax of the logits == argmax of pi; the reference's accuracy is `predicted == actions.argmax`,
-    :139-142).  Everything stays on the GPU; returns a dict of Python floats (one synchronisation)."""
+    :139-142).  Everything stays on the GPU; returns a dict of Python floats (one synchronisation).
+    symmetry: passed to DeviceNet.forward with the examples' board size -- e.g. "mean" validates the
+    symmetrised net; None (the default) is the plain forward."""
     own, opp, pi, z = (ex.own, ex.opp, ex.pi, ex.z) if idx is None else (ex.own[idx], ex.opp[idx], ex.pi[idx], ex.z[idx])
     n = int(own.shape[0])
     if n == 0:
@@ -90,7 +92,10 @@ def validate(device_net, ex, idx=None):
     se, hit = torch.zeros_like(ce), torch.zeros_like(ce)
     for a in range(0, n, device_net.max_batch):
         b = min(n, a + device_net.max_batch)
-        logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous())
+        if symmetry is None:
+            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous())
+        else:
+            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous(), symmetry=symmetry, size=ex.size)
         ce += -(pi[a:b] * F.log_softmax(logits, dim=1)).sum()
         se += ((v - z[a:b].to(torch.float32)) ** 2).sum()
         hit += (logits.argmax(1) == pi[a:b].argmax(1)).sum()

@@ -197,6 +197,33 @@ int32_t bz_net_forward_bf16(bz_net* net, const uint64_t* own, const uint64_t* op
 int32_t bz_net_forward_fp8(bz_net* net, const uint64_t* own, const uint64_t* opp, int32_t n,
                            float* logits, float* value, void* stream);
 
+/* ---- the forward under a board symmetry ----
+ * Eight elements s = 0..7 on the size x size corner of the 8x8 planes: 0..6 are bz_augment_d4_batch's transforms 0..6
+ * (id, flip rows, flip columns, rot90 x1, x2, x3, transpose), 7 is the anti-transpose out[r][c] = x[n-1-c][n-1-r] (which
+ * the reference's augmentation list lacks: its entry 7 repeats entry 5).  T_s moves a stone on cell j to tau_s(j); cells
+ * outside the corner and the pass action stay, so tau_s permutes 0..63 and fixes 64.
+ * bz_sym_index: the symmetry a position is evaluated under for a seed -- a hash of (seed, own, opp), so the evaluator stays
+ *   a function of the position alone (evaluation cache, carry-over and bit-for-bit replays keep their guarantees):
+ *     h = seed ^ (own * 0x9E3779B97F4A7C15); h = (h ^ (h >> 29)) * 0xBF58476D1CE4E5B9; h ^= opp * 0xC2B2AE3D27D4EB4F;
+ *     h = (h ^ (h >> 32)) * 0x94D049BB133111EB; s = (h ^ (h >> 31)) >> 61            (64-bit wrapping arithmetic)
+ * bz_sym_board: *out = T_s(b), size 1..8.  bz_sym_action_map: map[j] = tau_s(j), j = 0..64.  Host only, per item. */
+uint32_t bz_sym_index(uint64_t seed, uint64_t own, uint64_t opp);
+int32_t bz_sym_board(uint64_t b, int32_t size, int32_t s, uint64_t* out);
+int32_t bz_sym_action_map(int32_t size, int32_t s, uint8_t* map /* [65] */);
+enum { BZ_SYM_FIXED = 0, BZ_SYM_HASHED = 1, BZ_SYM_MEAN = 2 };
+/* kind: 0 = f32, 1 = bf16, 2 = fp8 (the shapes of the plain forwards); size 8, 6 or 4.  Per row, with L', v' what the plain
+ * forward gives on (T_s own, T_s opp): logits[j] = L'[tau_s(j)] (j < 64), logits[64] = L'[64], value = v'.  The transform
+ * and the permuted store are fused into the net kernels (separate instantiations: the plain forwards are untouched).
+ *   BZ_SYM_FIXED  (arg = s): every row under T_s.
+ *   BZ_SYM_HASHED (arg = seed): row i under s_i = bz_sym_index(seed, own_i, opp_i), computed in the kernel.
+ *   BZ_SYM_MEAN: the eight FIXED forwards into `scratch` (device memory, 256-byte aligned, bz_net_sym_scratch_bytes(n)
+ *     bytes), then ((..(x_0 + x_1) + ..) + x_7) * 0.125f in fp32 per logit and per value.  arg is ignored.
+ * scratch may be null for FIXED and HASHED. */
+int64_t bz_net_sym_scratch_bytes(int64_t n);
+int32_t bz_net_forward_sym(bz_net* net, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t n, int32_t size,
+                           int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits, float* value,
+                           void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* The reference's tic-tac-toe policy MLP, TicTacToeNet                       */
 /*   src/tic_tac_toe/SL/neural_networks.py: Linear(9,H)-ReLU-Linear(H,H)-     */
@@ -354,6 +381,16 @@ int32_t bz_engine_set_mlp(bz_engine* e, bz_mlp* mlp);
 /* test hook: set the count of searches begun so far (0 .. 2^19 - 3) -- the evaluation cache stamps its entries with it, cycling
  * through 1 .. 2^19 - 2; a test starts just below the wrap with this.  Nothing is carried over the jump. */
 int32_t bz_engine_debug_set_search_seq(bz_engine* e, uint32_t seq);
+/* Hashed evaluation symmetry, opt-in per engine, between searches.  on != 0: bz_engine_evaluate evaluates
+ * every packed leaf (the device-side count path included) by bz_net_forward_sym(.., BZ_SYM_HASHED, seed, ..) with the game's
+ * board size, i.e. under the symmetry bz_sym_index(seed, own, opp) of its own position.  The evaluator stays a function of
+ * the position alone, so the evaluation cache, its carry-over, subtree reuse, leaves_per_step, Gumbel, the playout cap, forced
+ * playouts, surprise, the search value and matches keep every guarantee they give without it.  The setting lives on the
+ * engine, not on the bz_net (two pipelines, or the two players of a match, share one net).  on == 0 (the default): the plain
+ * forward, the kernels and the bits of an engine that never heard of it.  BZ_EINVAL for on != 0 on tic-tac-toe and on the
+ * uniform / hash / external / MLP evaluators.  The cache's rule "nothing is carried over a change of weights" extends to a
+ * change of the setting or of the seed. */
+int32_t bz_engine_set_eval_symmetry(bz_engine* e, int32_t on, uint64_t seed);
 /* start every slot at the game's start position (round 0) */
 int32_t bz_engine_reset_games(bz_engine* e, void* stream);
 /* load arbitrary root positions (MCTSPlayer.get_move, the arena, tests): device arrays [B];

@@ -34,7 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
-from betazero_amd.engine import (ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_playout_cap,  # noqa: E402
+from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_playout_cap,  # noqa: E402
                                  concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
@@ -89,6 +89,9 @@ def main():
                     "0 = the next recorded root's value.  Switches the recording of the root value on")
     ap.add_argument("--value-q-mix", type=float, default=None, help="search-value targets: the weight of the row's own root value in the "
                     "target, (1 - M) * return + M * q; 0.5 at --value-lambda 1 averages z and q.  Switches the recording on")
+    ap.add_argument("--eval-symmetry", action="store_true", help="self-play evaluates every leaf under a hashed board symmetry (DESIGN.md "
+                    "3.19; AlphaGo Zero, KataGo), seeded with --seed + the iteration, so a position's orientation changes from net to net; "
+                    "the arena and gate players run plain, and the validation line also reports the symmetrised (mean over the eight) net")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -144,7 +147,8 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, search_value=use_vt, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
+                               surprise=args.surprise, search_value=use_vt,
+                               eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
         vt_info = {}
@@ -191,6 +195,8 @@ def main():
         refresh_device_net(cand, module)
         t_train = time.time() - t1
         val_after = validate(cand, val)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
+        val_mean = {"after_mean_of_8": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in validate(cand, val, symmetry="mean").items()
+                                        if k != "rows"}} if args.eval_symmetry else {}
         gate = {}
         if args.gate_games:  # the candidate (A) against the net self-play uses (B)
             t2 = time.time()
@@ -208,11 +214,13 @@ def main():
               "loss_first_tenth": [round(float(x), 4) for x in head], "loss_last_tenth": [round(float(x), 4) for x in tail],
               "validation": {"rows": val_after["rows"], "split": args.val_split,
                              "before": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in val_before.items() if k != "rows"},
-                             "after": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in val_after.items() if k != "rows"}},
+                             "after": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in val_after.items() if k != "rows"},
+                             **val_mean},
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
+              **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
               "arena": arena("net_bf16", cand), **gate})
