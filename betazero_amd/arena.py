@@ -37,7 +37,7 @@ class ArenaResult:
 
 def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=None, c_puct=1.5, seed=0, size=8,
                device="cuda:0", max_plies=200, opening_plies=0, leaves_per_step=1, gumbel=None,
-               eval_symmetry=None):
+               eval_symmetry=None, fpu=None):
     """MCTS (`sims` simulations, `evaluator`) vs minimax for n_games concurrent games; the MCTS side plays X
     (moves first) in the even-numbered games and O in the odd ones.  game: "ttt" | "reversi" (size 8, 6 or 4).
     Both players are deterministic, so without help there are only two distinct games (one per colour):
@@ -45,10 +45,12 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     makes the B games B different tests.  leaves_per_step: K walks per tree step of the MCTS side.
     gumbel (True or an engine.GumbelConfig): the MCTS side searches with Gumbel root search and plays its move
     (SelfPlayEngine.root_policy; no Gumbel noise), DESIGN.md 3.13.  eval_symmetry (True or a symmetry.EvalSymmetry): the
-    MCTS side evaluates every leaf under a hashed board symmetry (True: seed 0), DESIGN.md 3.19."""
-    from .engine import check_gumbel, check_leaves_per_step
+    MCTS side evaluates every leaf under a hashed board symmetry (True: seed 0), DESIGN.md 3.19.  fpu (True or an engine.Fpu):
+    the MCTS side searches with first-play urgency reduction, DESIGN.md 3.20."""
+    from .engine import check_fpu, check_gumbel, check_leaves_per_step
     from .symmetry import check_eval_symmetry
     check_leaves_per_step(leaves_per_step)
+    fpu = check_fpu(fpu, False, leaves_per_step, gumbel)
     gumbel = check_gumbel(gumbel, leaves_per_step=leaves_per_step)
     eval_symmetry = check_eval_symmetry(eval_symmetry, 0, "ttt" if game == "ttt" else "reversi", evaluator)
     if game != "ttt" and not 0 <= int(opponent_depth) <= 8:
@@ -61,7 +63,7 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     B = n_games
     ename = "ttt" if ttt else {8: "reversi", 6: "reversi6", 4: "reversi4"}[size]
     eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                         eval_symmetry=eval_symmetry)
+                         eval_symmetry=eval_symmetry, fpu=fpu)
     rng = np.random.default_rng(seed)
     st = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
     if ttt:

@@ -20,6 +20,7 @@
 // sims <= 120: root edges in registers, child header packed into the edge word, path in LDS).  Opt-in: Dirichlet root
 // noise (k_root_noise) and subtree reuse (two arenas, dev_reroot) -- DESIGN.md 3.9, 3.10; leaf-parallel search with virtual
 // loss (K walks per game per step, k_leaf_step) -- DESIGN.md 3.12.
+// First-play urgency reduction in the select rule (k_fpu_step and its cap / forced variants, csrc/bz_fpu.h) -- DESIGN.md 3.20.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -36,6 +37,7 @@
 #include "bz_common.h"
 #include "bz_math.h"
 #include "bz_rules.h"
+#include "bz_fpu.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
 
@@ -210,6 +212,11 @@ struct SurpDev { float* prior; u64* pend; float* ex_kl; };
 // Search-value targets (ex_q = nullptr: off), set by bz_engine_set_search_value in the caller's buffer: the root's
 // search value of every recorded row, f32 [rounds][B][t_max] indexed like ex_pi.  Read and written by the two value kernels only.
 struct ValueDev { float* ex_q; };
+// First-play urgency reduction (root_w = nullptr: off), set by bz_engine_set_fpu: the two reductions and every
+// root's running value sum Wr f32 [B] in the caller's buffer.  A kernel argument of the FPU kernels only.
+struct FpuDev { float reduction, root_reduction; float* root_w; };
+// what the FPU walk takes along: the reductions and the root's Wr as of this walk
+struct FpuSel { float r, r_root, Wr; };
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -277,6 +284,15 @@ __device__ __forceinline__ float group_max(float m) {
     if (kGW > 4) { float m2 = xchg<4>(m); m = m2 > m ? m2 : m; }
     if (kGW > 8) { float m2 = xchg<8>(m); m = m2 > m ? m2 : m; }
     return m;
+}
+// integer sum over the kGW lanes of a group (first-play urgency): whatever the order, the same bits
+template <int kGW>
+__device__ __forceinline__ u32 group_sum_u32(u32 x) {
+    if (kGW > 1) x += xchg<1>(x);
+    if (kGW > 2) x += xchg<2>(x);
+    if (kGW > 4) x += xchg<4>(x);
+    if (kGW > 8) x += xchg<8>(x);
+    return x;
 }
 
 // counters are accumulated by the lead lane of every lane group and flushed per wave into that wave's own slot
@@ -574,11 +590,20 @@ __device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const Gumbel
 // kGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead; every deeper level is PUCT.
 // kForced (k_forced_step / k_forced_cap_step): at the root an edge with 0 < N < fsqrt(fk P sumN) scores +inf
 // (fk = 0: this slot does not force); every deeper level is PUCT.
-template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false>
+// kFpu (k_fpu_*_step): at every level an edge with N == 0 takes q = the node's own value minus a reduction that
+// grows with the prior mass of the node's visited edges, instead of 0.  The mass needs all of the node's edges before any is
+// scored: its <= kCH chunks are loaded together into registers (still ONE dependent load per level), summed as integers across
+// the group, then scored from the registers.
+template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
-                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f) {
+                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f,
+                                           const FpuSel* fp = nullptr) {
     constexpr int kGW = G::GW;
+    constexpr int kCH = (G::MAXCH + kGW - 1) / kGW;
+    // kFpu: the value of the node whose edges are being scored -- the root's Wr / simulations so far, 0 before the first
+    float qx = 0.0f;
+    if (kFpu) qx = root.sumN > 0u ? fdiv(fp->Wr, (float)root.sumN) : 0.0f;
     Node* nodes = E.nodes + (size_t)g * E.ncap;
     Edge* edges = E.edges + (size_t)g * E.ecap;
     // sum of the root's child visits == simulations done so far (+ the visits a kept subtree came with)
@@ -595,6 +620,39 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             best = gumbel_root_pick<G>(E, *gm, g, ed, n, sumN);
             const Edge e = ed[best];
             bestw0 = e.w0; bestw3 = e.w3; bestW = e.W;
+        } else if (kFpu) {
+            Edge ev[kCH];
+            u32 S = 0;
+#pragma unroll
+            for (int k = 0; k < kCH; ++k) {
+                const int i = k * kGW + sub;
+                ev[k].w0 = 0; ev[k].W = 0.0f; ev[k].P = 0.0f; ev[k].w3 = 0;
+                if (i < n) {
+                    Edge e = root.pre;
+                    if (!(root.has_pre && depth == 0 && k == 0)) e = ed[i];
+                    ev[k] = e;
+                    if (e_N(e.w0) > 0u) S += fpu_pq(e.P);
+                }
+            }
+            S = group_sum_u32<kGW>(S);
+            const float f = fpu_value(S, qx, depth == 0 ? fp->r_root : fp->r);
+            // every lane's own first maximum over its <= kCH edges (ascending index, strict >), then ONE reduction over the group:
+            // the first maximum over all edges, the lowest index on ties
+            Cand cd; cd.i = sub; cd.sc = -__builtin_inff(); cd.W = 0.0f; cd.w0 = 0; cd.w3 = 0;
+#pragma unroll
+            for (int k = 0; k < kCH; ++k) {
+                const int i = k * kGW + sub;
+                if (i < n) {
+                    const Edge e = ev[k];
+                    const u32 N = e_N(e.w0);
+                    const float q = N > 0 ? fdiv(e.W, (float)N) : f;
+                    float sc = puct_score(q, E.c_puct, e.P, sq, (float)N);
+                    if (kForced && depth == 0 && fk > 0.0f && N > 0 && (float)N < forced_nf(fk, e.P, sumN)) sc = __builtin_inff();
+                    if (sc > cd.sc) { cd.sc = sc; cd.i = i; cd.w0 = e.w0; cd.w3 = e.w3; cd.W = e.W; }
+                }
+            }
+            group_argmax<kGW>(cd);
+            if (cd.sc > bests) { bests = cd.sc; best = cd.i; bestw0 = cd.w0; bestw3 = cd.w3; bestW = cd.W; }
         } else
         for (int base = 0; base < n; base += kGW) {
             Cand cd; cd.i = base + sub; cd.sc = -__builtin_inff(); cd.W = 0.0f; cd.w0 = 0; cd.w3 = 0;
@@ -625,6 +683,10 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             if (kLeafPar && e_nch(bestw0) == 0) { kind = LEAF_COLLIDE; leaf = child; tval = 0.0f; break; }
             // children's visits of X == visits of the edge into X minus the creating one
             e0 = e_edge0(bestw3); n = e_nch(bestw0); sumN = e_N(bestw0) - 1u;
+            if (kFpu) {  // X's value for its mover, from the edge the walk came in by (W is stored for the parent's mover; N >= 1)
+                qx = fdiv(bestW, (float)e_N(bestw0));
+                qx = -qx;
+            }
             // X's position is needed only if the walk ends by extending X: the load goes out beside X's edge load
             const Node* xn = nodes + child;
             pown = xn->own; popp = xn->opp;
@@ -1052,9 +1114,13 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 // kCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget; both flags off, the code is
 // k_tree_step's / k_gumbel_step's as before.
 // kForced: forced playouts with parameter fk at the root -- under kCap in the full searches only.
-template <class G, bool kGumbel, bool kCap = false, bool kForced = false>
+// kFpu: first-play urgency reduction at every level of the walk, and the root's running value sum Wr: loaded with
+// the per-game words, advanced by what this step's backup adds to the path's root edge and stored beside it.  sim_idx is the
+// number of simulations backed up once this step's backup is done (an expand-only step gets it from the host too): the backup of
+// simulation 0 starts Wr from 0, so no search needs a reset.
+template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
-                                               const u32* budget = nullptr, float fk = 0.0f) {
+                                               const u32* budget = nullptr, float fk = 0.0f, const FpuDev* fd = nullptr) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1078,6 +1144,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
         PathEnt pe0 = path[sub];  // (maxd >= kGW for every game)
         u32 bud = 0;
         if (kCap) { bud = budget[g]; pin(bud); }
+        [[maybe_unused]] float rw;
+        if constexpr (kFpu) { rw = fd->root_w[g]; pin(rw); }
         // the walk's first load too: root edges 0..kGW-1 (the root's edges start at index 0; whatever this step's
         // backup / expansion changes in them is patched in registers below) -- their latency hides behind the
         // evaluator row's round trip and the softmax instead of heading the walk
@@ -1124,6 +1192,10 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
             for (int d = sub + kGW; d < dmax; d += kGW)
                 backup_edge(edges, path[d], ((dmax - 1 - d) & 1) ? v : -v, d == depth0 - 1, leaf, e0, n);
             if (sub == 0) c.v[CNT_EDGES_BACKED] += (u32)dmax;
+            if constexpr (kFpu) if (dmax >= 1) {  // Wr = Wr + what path entry 0 just added to its edge's W, one addition per simulation
+                rw = (sim_idx == 1u ? 0.0f : rw) + (((dmax - 1) & 1) ? v : -v);
+                if (sub == 0) fd->root_w[g] = rw;
+            }
             if (dmax >= 1) {  // the path's root edge (lane 0 wrote it): the same words into the lane that holds it in re0
                 const u32 pe_e = (u32)__shfl((int)pe0.eidx, 0, kGW), w0n = (u32)__shfl((int)wr.x, 0, kGW), Wn = (u32)__shfl((int)wr.y, 0, kGW);
                 if ((u32)sub == pe_e) {
@@ -1143,6 +1215,10 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 root.sumN = sim_idx + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
                 PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
                 const float fslot = (kForced && (!kCap || bud >= (u32)E.sims)) ? fk : 0.0f;
+                if constexpr (kFpu) {
+                    FpuSel fs; fs.r = fd->reduction; fs.r_root = fd->root_reduction; fs.Wr = rw;
+                    dev_select<G, PathHbm<kGW>, false, false, kForced, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, nullptr, fslot, &fs);
+                } else
                 dev_select<G, PathHbm<kGW>, false, kGumbel, kForced>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
                 sink.flush(sub, depth);
                 if (sub == 0) {
@@ -1211,6 +1287,30 @@ template <class G>
 __global__ void __launch_bounds__(256) k_forced_cap_step(EngineDev E, CapDev Cp, ForcedDev F, int do_expand, int do_select, u32 sim_idx) {
     const GumbelDev none{};
     tree_step_body<G, false, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k);
+}
+
+// The tree steps with first-play urgency reduction: k_tree_step / k_cap_step / k_forced_step / k_forced_cap_step
+// with the FPU rule at every level of the walk.  Fp travels as a kernel argument.
+template <class G>
+__global__ void __launch_bounds__(256) k_fpu_step(EngineDev E, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, 0.0f, &Fp);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_fpu_cap_step(EngineDev E, CapDev Cp, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, true, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, 0.0f, &Fp);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_fpu_forced_step(EngineDev E, ForcedDev F, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, false, true, true>(E, none, do_expand, do_select, sim_idx, nullptr, F.k, &Fp);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_fpu_forced_cap_step(EngineDev E, CapDev Cp, ForcedDev F, FpuDev Fp, int do_expand, int do_select,
+                                                             u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, true, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k, &Fp);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -2105,6 +2205,8 @@ struct bz_engine {
     CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
     ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
     SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
+    FpuDev fpu;        // first-play urgency reduction (bz_engine_set_fpu); fpu.root_w = nullptr: off
+    int fpu_done;      // ... simulations selected so far in the current search: what an expand-only step has backed up when it is done
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
     // hashed evaluation symmetry (bz_engine_set_eval_symmetry); on the engine, not on the net: two pipelines
     // and two match players share one bz_net
@@ -2249,6 +2351,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->forced = ForcedDev{};
     e->surp = SurpDev{};
     e->value = ValueDev{};
+    e->fpu = FpuDev{}; e->fpu_done = 0;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2405,6 +2508,7 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
         BZ_LAUNCH_CHECK("k_cap_budget");
     }
     e->pack_parity = 1;
+    e->fpu_done = 0;
     return BZ_OK;
 }
 
@@ -2413,6 +2517,15 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
     if (e->dev.K > 1) {  // leaf-parallel: sim_idx is a multiple of K, the packed-leaf buffers alternate per step
         BZ_DISPATCH_G(e, k_leaf_step, stream, e->dev, do_expand, do_select, sim_idx);
         if (do_select) e->pack_parity = (int)((sim_idx / (uint32_t)e->dev.K) & 1u);
+        return BZ_OK;
+    }
+    if (e->fpu.root_w) {  //  the step kernels with the FPU rule; sim_idx = simulations backed up after this step
+        if (!do_select) sim_idx = (uint32_t)e->fpu_done;
+        if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH_G(e, k_fpu_forced_cap_step, stream, e->dev, e->cap, e->forced, e->fpu, do_expand, do_select, sim_idx);
+        else if (e->forced.k > 0.0f) BZ_DISPATCH_G(e, k_fpu_forced_step, stream, e->dev, e->forced, e->fpu, do_expand, do_select, sim_idx);
+        else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_fpu_cap_step, stream, e->dev, e->cap, e->fpu, do_expand, do_select, sim_idx);
+        else BZ_DISPATCH_G(e, k_fpu_step, stream, e->dev, e->fpu, do_expand, do_select, sim_idx);
+        if (do_select) { e->pack_parity = (int)(sim_idx & 1u); e->fpu_done = (int)sim_idx + 1; }
         return BZ_OK;
     }
     if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
@@ -2493,7 +2606,9 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
     const bool noise = root_prep(e);
     // (playout cap randomisation: per-slot budgets live in the step kernels only; forced playouts: the forced root rule too)
-    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f)) {
+    // (first-play urgency reduction: the rule lives in the step kernels only)
+    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f) &&
+        !e->fpu.root_w) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -2612,6 +2727,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
     BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
     BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_gumbel: Gumbel root search does not combine with forced playouts (bz_engine_set_forced_playouts)");
+    BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_gumbel: Gumbel root search does not combine with first-play urgency reduction (bz_engine_set_fpu)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
     const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
     if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -2715,6 +2831,65 @@ BZ_EXPORT int32_t bz_forced_prune(const uint32_t* N, const float* W, const float
     }
     forced_prune(ed, n, c_puct, k, [N_out](int i, const Edge&, u32 Np) { N_out[i] = Np; });
     return BZ_OK;
+}
+
+/* ---- first-play urgency reduction */
+namespace {
+inline bool fpu_red_ok(float r) { return r >= 0.0f && r <= 3.0e38f; }  // (a NaN fails)
+// what first-play urgency reduction refuses (nullptr: nothing)
+const char* fpu_refusal(const bz_engine_cfg& c) {
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "first-play urgency reduction does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "first-play urgency reduction does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
+    return nullptr;
+}
+inline int64_t fpu_bytes(const bz_engine_cfg& c) { Carver k; k.take((int64_t)c.n_games * 4); return k.off; }
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_fpu_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_fpu_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_fpu_bytes: %s", kBadCfg); return -1; }
+    if (const char* why = fpu_refusal(*cfg)) { set_error("bz_engine_fpu_bytes: %s", why); return -1; }
+    return fpu_bytes(*cfg);
+}
+
+BZ_EXPORT int32_t bz_engine_fpu_check(const bz_engine_cfg* cfg, float reduction, float root_reduction) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_fpu_check: %s", kBadFlags); return BZ_EINVAL; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_fpu_check: %s", kBadCfg); return BZ_EINVAL; }
+    if (const char* why = fpu_refusal(*cfg)) { set_error("bz_engine_fpu_check: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(fpu_red_ok(reduction) && fpu_red_ok(root_reduction),
+               "bz_engine_fpu_check: first-play urgency reduction: reduction and root_reduction must be finite and >= 0");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_set_fpu(bz_engine* e, int32_t on, float reduction, float root_reduction, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_fpu: null engine");
+    if (!on) {  // off: the plain (the cap's, the forced) kernels again
+        e->fpu = FpuDev{};
+        return BZ_OK;
+    }
+    if (const char* why = fpu_refusal(e->cfg)) { set_error("bz_engine_set_fpu: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(fpu_red_ok(reduction) && fpu_red_ok(root_reduction),
+               "bz_engine_set_fpu: first-play urgency reduction: reduction and root_reduction must be finite and >= 0");
+    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_fpu: first-play urgency reduction does not combine with Gumbel root search (bz_engine_set_gumbel)");
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_fpu: the buffer must be non-null and 256-byte aligned");
+    const int64_t need = fpu_bytes(e->cfg);
+    if (bytes < need) { set_error("bz_engine_set_fpu: buffer too small (%lld < %lld)", (long long)bytes, (long long)need); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)e->cfg.n_games * 4, (hipStream_t)stream));
+    e->fpu.reduction = reduction; e->fpu.root_reduction = root_reduction; e->fpu.root_w = static_cast<float*>(buf);
+    return BZ_OK;
+}
+
+BZ_EXPORT uint32_t bz_fpu_mass(const uint32_t* N, const float* P, int32_t n) {
+    if (!(N && P && n >= 1 && n <= 255)) { set_error("bz_fpu_mass: null pointer or n outside 1 .. 255"); return 0xFFFFFFFFu; }
+    for (int i = 0; i < n; ++i)  // (a prior is at most 1; 255 of them stay far below 2^32)
+        if (P[i] > 2.0f) { set_error("bz_fpu_mass: P[%d] = %g is no prior (> 2)", i, (double)P[i]); return 0xFFFFFFFFu; }
+    return fpu_mass(n, [N](int i) { return N[i]; }, [P](int i) { return P[i]; });
+}
+
+BZ_EXPORT float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float q_node, float reduction) {
+    const uint32_t S = bz_fpu_mass(N, P, n);
+    if (S == 0xFFFFFFFFu) return __builtin_nanf("");
+    return fpu_value(S, q_node, reduction);
 }
 
 /* ---- policy surprise weighting */
@@ -2943,7 +3118,7 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
 static bool search_is_fused(const bz_engine* e) {
     const int ek = e->cfg.eval_kind;
     return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && e->dev.K == 1 &&
-           e->cap.fast == 0 && !(e->forced.k > 0.0f);
+           e->cap.fast == 0 && !(e->forced.k > 0.0f) && !e->fpu.root_w;
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree

@@ -271,6 +271,41 @@ def check_forced_playouts(forced_playouts, reuse_subtree=False, leaves_per_step=
     return ForcedPlayouts(float(k), bool(fp.prune))
 
 
+@dataclass(frozen=True)
+class Fpu:
+    """First-play urgency reduction (Leela Zero, LC0, KataGo): the select rule scores a child that was never
+    visited with its parent's value minus reduction * sqrt(prior mass of the visited children) instead of with 0;
+    root_reduction is the reduction at the root.  Both finite and >= 0 (KataGo's fpuReductionMax / rootFpuReductionMax)."""
+    reduction: float = 0.2
+    root_reduction: float = 0.1
+
+
+def check_fpu(fpu, reuse_subtree=False, leaves_per_step=1, gumbel=None):
+    """None / False: off (None returned); True: Fpu(); or an Fpu -- validated, and refused with subtree reuse,
+    leaves_per_step > 1 and Gumbel root search (ValueError, before any device is touched)"""
+    if fpu is None or fpu is False:
+        return None
+    cfg = Fpu() if fpu is True else fpu
+    if not isinstance(cfg, Fpu):
+        raise ValueError(f"fpu must be None, False, True or an Fpu (got {fpu!r})")
+    out = []
+    for name in ("reduction", "root_reduction"):
+        x = getattr(cfg, name)
+        with np.errstate(over="ignore", under="ignore"):
+            ok = not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
+            x32 = float(np.float32(x)) if ok else -1.0
+        if not 0.0 <= x32 < np.inf:  # (NaN fails)
+            raise ValueError(f"fpu: {name} must be a finite number >= 0 in float32 (got {x!r})")
+        out.append(x32)
+    if reuse_subtree:
+        raise ValueError("fpu: first-play urgency reduction does not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("fpu: first-play urgency reduction does not combine with leaves_per_step > 1")
+    if gumbel is not None and gumbel is not False:
+        raise ValueError("fpu: first-play urgency reduction does not combine with Gumbel root search (gumbel)")
+    return Fpu(*out)
+
+
 def check_search_value(search_value):
     """search-value targets: a bool, anything else is refused (ValueError, before any device is touched)"""
     if not isinstance(search_value, (bool, np.bool_)):
@@ -283,7 +318,7 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None):
+                 eval_symmetry=None, fpu=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -328,7 +363,13 @@ class SelfPlayEngine:
         `seed` -- inside the fused net kernels; priors and values come back in the position's own orientation.  The
         evaluator stays a function of the position, so it combines with everything the engine accepts and the cache stays
         exact; set_eval_symmetry() changes it between searches.  Refused on tic-tac-toe and with the synthetic, external
-        and MLP evaluators."""
+        and MLP evaluators.
+
+        fpu: None / False = an unvisited child is scored with q = 0 (the default, unchanged); True or an
+        Fpu(reduction, root_reduction) = first-play urgency reduction at every level of every walk.  root_stats(), pi, the
+        move choice and the rows follow the usual rules on the tree this search builds.  Combines with Dirichlet noise,
+        playout_cap, forced_playouts, surprise, search_value, eval_symmetry, every evaluator and eval_cache mode; set_fpu()
+        changes it between searches.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel."""
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
@@ -340,6 +381,8 @@ class SelfPlayEngine:
         self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
         self.playout_cap = check_playout_cap(playout_cap, sims, reuse_subtree, self.K, gumbel)
         self.forced_playouts = check_forced_playouts(forced_playouts, reuse_subtree, self.K, gumbel)
+        self.fpu = check_fpu(fpu, reuse_subtree, self.K, gumbel)
+        self._reuse = bool(reuse_subtree)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -395,6 +438,8 @@ class SelfPlayEngine:
             self._call(L.bz_engine_set_playout_cap, pc.fast_sims, pc.full_q, self.cws.data_ptr() + self._cpad, cbytes)
         if self.forced_playouts is not None:
             self._call(L.bz_engine_set_forced_playouts, self.forced_playouts.k, int(self.forced_playouts.prune))
+        if self.fpu is not None:
+            self._set_fpu(self.fpu)
         if self.surprise:  # the engine's surprise buffer (caller-owned, like the workspace)
             sbytes = L.bz_engine_surprise_bytes(C.byref(self.cfg))
             if sbytes < 0:
@@ -448,6 +493,27 @@ class SelfPlayEngine:
         self.drain()
         _lib.check(_lib.lib().bz_engine_set_eval_symmetry(self.h, int(es is not None), es.seed if es is not None else 0))
         self.eval_symmetry = es
+
+    def _set_fpu(self, fp):
+        L = _lib.lib()
+        if fp is None:
+            self._call(L.bz_engine_set_fpu, 0, 0.0, 0.0, None, 0)
+            return
+        if getattr(self, "fws", None) is None:  # the engine's Wr buffer (caller-owned, like the workspace)
+            fbytes = L.bz_engine_fpu_bytes(C.byref(self.cfg))
+            if fbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.fws = torch.zeros(fbytes + 256, dtype=torch.uint8, device=self.device)
+            self._fpad, self._fbytes = (-self.fws.data_ptr()) & 255, fbytes
+        self._call(L.bz_engine_set_fpu, 1, fp.reduction, fp.root_reduction, self.fws.data_ptr() + self._fpad, self._fbytes)
+
+    def set_fpu(self, fpu):
+        """switch first-play urgency reduction on, off or to other reductions, between searches: None /
+        False, True (the defaults) or an Fpu"""
+        fp = check_fpu(fpu, self._reuse, self.K, self.gumbel)
+        self.drain()
+        self._set_fpu(fp)
+        self.fpu = fp
 
     def search(self):
         self._call(_lib.lib().bz_engine_search)
@@ -929,7 +995,7 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, **engine_kwargs):
+                 forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         # every pipeline gets the same seed, so the same position has the same orientation in all of them
         eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
@@ -938,6 +1004,7 @@ class PipelinedSelfPlay:
         check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
         check_playout_cap(playout_cap, sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_forced_playouts(forced_playouts, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
+        check_fpu(fpu, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_eval_cache(engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
@@ -950,7 +1017,7 @@ class PipelinedSelfPlay:
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
                                        playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                                       search_value=search_value, eval_symmetry=eval_symmetry, **engine_kwargs)
+                                       search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, **engine_kwargs)
                         for i in range(pipelines)]
         self.surprise, self.search_value = bool(surprise), bool(search_value)
         e0 = self.engines[0]
@@ -1111,7 +1178,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False, search_value=False, eval_symmetry=None):
+              surprise=False, search_value=False, eval_symmetry=None, fpu=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1121,12 +1188,14 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     -- only the moves searched with the full budget yield rows.  forced_playouts: SelfPlayEngine -- pi is
     then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`.
     search_value: SelfPlayEngine -- the Examples then carry `q`.  eval_symmetry: SelfPlayEngine (DESIGN.md
-    3.19) -- every leaf is evaluated under a hashed board symmetry (True: seeded by `seed`)."""
+    3.19) -- every leaf is evaluated under a hashed board symmetry (True: seeded by `seed`).  fpu: SelfPlayEngine (DESIGN.md
+    3.20) -- first-play urgency reduction in the select rule."""
     check_search_value(search_value)
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
     check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
     check_forced_playouts(forced_playouts, reuse_subtree, leaves_per_step, gumbel)
+    check_fpu(fpu, reuse_subtree, leaves_per_step, gumbel)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -1138,7 +1207,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
                            gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                           search_value=search_value, eval_symmetry=eval_symmetry)
+                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -151,14 +151,16 @@ class MCTSPlayer(Player):
     gumbel (True or an engine.GumbelConfig): Gumbel root search -- the move is the one the Gumbel search
     plays (SelfPlayEngine.root_policy) and last_policy its improved policy; the player draws no Gumbel noise (temp_moves 0),
     so it is deterministic.  eval_symmetry (True or a symmetry.EvalSymmetry): every leaf is evaluated under a hashed board
-    symmetry (True: seed 0); net evaluators on Reversi only."""
+    symmetry (True: seed 0); net evaluators on Reversi only.  fpu (True or an engine.Fpu): first-play urgency
+    reduction in the select rule; not with gumbel or leaves_per_step > 1."""
 
     def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1,
-                 gumbel=None, eval_symmetry=None):
-        from .engine import check_gumbel, check_leaves_per_step, check_sims
+                 gumbel=None, eval_symmetry=None, fpu=None):
+        from .engine import check_fpu, check_gumbel, check_leaves_per_step, check_sims
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
         self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step (DESIGN.md 3.12)
         self.gumbel = check_gumbel(gumbel, leaves_per_step=self.leaves_per_step)
+        self.fpu = check_fpu(fpu, False, self.leaves_per_step, gumbel)
         self.symbol, self.sims, self.net, self.c_puct, self.device = symbol, sims, net, c_puct, device
         # evaluator: "uniform" | "hash" | "net_bf16" | "net_f32" | "net_fp8", or a callable (own, opp, kind) -> (logits, value)
         # on CUDA tensors (SelfPlayEngine.search_external): any torch module, e.g. an MLP for tic-tac-toe
@@ -179,7 +181,7 @@ class MCTSPlayer(Player):
         if game not in self._eng:
             self._eng[game] = SelfPlayEngine(game, 1, self.sims, self.evaluator, self.net, self.c_puct,
                                              device=self.device, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel,
-                                             eval_symmetry=self.eval_symmetry)
+                                             eval_symmetry=self.eval_symmetry, fpu=self.fpu)
         return self._eng[game]
 
     def get_move(self, board):

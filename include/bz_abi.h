@@ -479,6 +479,42 @@ int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k);
  * float(sum N))), N), while its score with the reduced N in the u term stays below s*; an edge that lost a visit and is left
  * with <= 1 gets 0; c* and unvisited edges keep theirs.  Host only. */
 int32_t bz_forced_prune(const uint32_t* N, const float* W, const float* P, int32_t n, float c_puct, float k, uint32_t* N_out);
+/* First-play urgency (FPU) reduction (Leela Zero, LC0, KataGo's fpuReductionMax / rootFpuReductionMax), opt-in per
+ * engine: the select rule of DESIGN.md 3.3 scores an edge that was never visited with the value of its parent minus a reduction
+ * that grows with the prior mass already explored, instead of with q = 0.  At every level of every walk, for the node X whose
+ * edges are scored, every expression one binary32 operation in the written order:
+ *   S  = sum over X's edges with N > 0 of (P > 0 ? (u32)(P * 16777216.0f) : 0) -- an exact scaling, a truncating conversion, a
+ *        u32 sum (no order, so nothing rounds differently however the lanes reduce it); m = (float)S; m = m * 2^-24; m = fsqrt(m)
+ *   qx = below the root: fdiv(W_in, (float)N_in), negated, from the statistics of the edge the walk came in by as the walk read
+ *        them (W is stored for the parent's mover; N_in >= 1); at the root: sumN > 0 ? fdiv(Wr, (float)sumN) : 0, sumN = the
+ *        simulations done so far in this search and Wr their running sum: 0 at the start of every search, Wr = Wr + x after each
+ *        simulation, x = what that simulation's backup added to its root edge's W (one addition per simulation, in simulation
+ *        order -- NOT the sum over the root's edges)
+ *   f  = qx - (depth == 0 ? root_reduction : reduction) * m;  an edge with N == 0 takes q = f, one with N > 0 keeps fdiv(W, N);
+ *        u, s = q + u, the ascending order and the strict first maximum are unchanged.  No clamp: f may be below -1.
+ * The Dirichlet noise is in the root's P when the mass is taken.  Both reductions may be 0 (an unvisited child is then worth
+ * exactly its parent), which is still not "off".  bz_engine_root_stats, pi = N / sum N, the move choice and the example rows are
+ * what they are without it.  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step (virtual losses
+ * sit in W_in), Gumbel root search (the two setters refuse each other), a negative or non-finite reduction.  Dirichlet noise,
+ * the playout cap (fast searches use the rule too), forced playouts (the +inf of a forced edge still wins), surprise, search
+ * value, evaluation symmetry, every evaluator (the external one through the step API included) and every evaluation-cache mode
+ * work unchanged.  Searches go through the step kernels. */
+/* bytes of the caller-owned buffer: Wr f32 [n_games], rounded up to 256 bytes.  Needs no GPU; -1 (bz_last_error says why) for a
+ * bad config or a refused combination. */
+int64_t bz_engine_fpu_bytes(const bz_engine_cfg* cfg);
+/* BZ_OK when an engine of this config accepts bz_engine_set_fpu(e, 1, reduction, root_reduction, ...), else BZ_EINVAL
+ * (bz_last_error says why).  Needs no GPU. */
+int32_t bz_engine_fpu_check(const bz_engine_cfg* cfg, float reduction, float root_reduction);
+/* switch the rule on (on != 0; reduction, root_reduction finite and >= 0 -- KataGo's defaults are 0.2 and 0.1) or off (on == 0:
+ * the plain kernels again), between searches.  buf: device memory of >= bz_engine_fpu_bytes bytes, 256-byte aligned, owned by
+ * the caller and kept alive while the mode is on; it is zeroed on `stream`. */
+int32_t bz_engine_set_fpu(bz_engine* e, int32_t on, float reduction, float root_reduction, void* buf, int64_t bytes, void* stream);
+/* S of one node, the function the kernels run: N, P [n] the edges' visits and priors, n in 1 .. 255, every P <= 2 (or NaN);
+ * 0xFFFFFFFF (bz_last_error says why) for bad arguments.  Host only. */
+uint32_t bz_fpu_mass(const uint32_t* N, const float* P, int32_t n);
+/* f of that node for a node value q_node and a reduction: fpu_value(S, q_node, reduction) as the kernels compute it; NaN for
+ * bad arguments.  Host only. */
+float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float q_node, float reduction);
 /* Policy surprise weighting (KataGo, Wu 2019, section 3.3), opt-in per engine.  Every row bz_engine_play
  * records gets kl = sum over the root's edges in ascending action order with pi_a > 0 of pi_a * (logf(pi_a) - logf(max(P_a,
  * FLT_MIN))), every operation one binary32 operation, then kl > 0 ? kl : 0 (a rounding negative or a NaN: 0).

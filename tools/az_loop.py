@@ -34,8 +34,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
-from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_playout_cap,  # noqa: E402
-                                 concat_device_examples)
+from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
+                                 check_playout_cap, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
@@ -92,6 +92,11 @@ def main():
     ap.add_argument("--eval-symmetry", action="store_true", help="self-play evaluates every leaf under a hashed board symmetry (DESIGN.md "
                     "3.19; AlphaGo Zero, KataGo), seeded with --seed + the iteration, so a position's orientation changes from net to net; "
                     "the arena and gate players run plain, and the validation line also reports the symmetrised (mean over the eight) net")
+    ap.add_argument("--fpu-reduction", type=float, default=None, help="first-play urgency reduction (DESIGN.md 3.20; KataGo uses 0.2): the "
+                    "select rule scores a child that was never visited with its parent's value minus R sqrt(visited prior mass) instead of "
+                    "with 0, in self-play, for both players of the gate and for the arena's search player; not given = off (0 is a "
+                    "reduction).  Not with --gumbel")
+    ap.add_argument("--fpu-root-reduction", type=float, default=0.1, help="the reduction at the root under --fpu-reduction (KataGo's 0.1)")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -118,6 +123,7 @@ def main():
     gumbel = True if args.gumbel else None
     cap = check_playout_cap(PlayoutCap(args.fast_sims, args.full_prob) if args.fast_sims else None, args.sims, gumbel=gumbel)
     forced = check_forced_playouts(ForcedPlayouts(args.forced_k, not args.no_prune) if args.forced_k else None, gumbel=gumbel)
+    fpu = check_fpu(Fpu(args.fpu_reduction, args.fpu_root_reduction) if args.fpu_reduction is not None else None, gumbel=gumbel)
     lines = []
 
     def emit(d):
@@ -128,7 +134,7 @@ def main():
         t0 = time.time()
         try:
             res = play_arena("reversi", args.arena_games, args.arena_sims, opponent_depth=depth or args.depth, evaluator=evaluator,
-                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel)
+                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel, fpu=fpu)
         except RuntimeError:  # keep the weights that were in play for a post-mortem
             if args.out:
                 np.save(args.out + ".failed_params.npy", module.flat_params())
@@ -147,7 +153,7 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, search_value=use_vt,
+                               surprise=args.surprise, search_value=use_vt, fpu=fpu,
                                eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
@@ -200,8 +206,8 @@ def main():
         gate = {}
         if args.gate_games:  # the candidate (A) against the net self-play uses (B)
             t2 = time.time()
-            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel),
-                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel), opening_plies=args.opening_plies,
+            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu),
+                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu), opening_plies=args.opening_plies,
                              seed=args.seed * 1000 + it)
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
@@ -220,6 +226,7 @@ def main():
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
+              **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}),
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
