@@ -155,6 +155,9 @@ _SIGS = {
     "bz_engine_set_forced_playouts": (i32, [vp, C.c_float, i32, vp]),
     "bz_engine_forced_playouts_check": (i32, [C.POINTER(EngineCfg), C.c_float]),
     "bz_forced_prune": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
+    "bz_engine_gumbel_interior_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_gumbel_interior": (i32, [vp, i32, vp, i64, vp]),
+    "bz_gumbel_interior_pick": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, vp, vp]),
     "bz_engine_fpu_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_fpu_check": (i32, [C.POINTER(EngineCfg), C.c_float, C.c_float]),
     "bz_engine_set_fpu": (i32, [vp, i32, C.c_float, C.c_float, vp, i64, vp]),

@@ -44,7 +44,8 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     `opening_plies` > 0 plays that many uniformly random legal moves (seeded) before the players take over, which
     makes the B games B different tests.  leaves_per_step: K walks per tree step of the MCTS side.
     gumbel (True or an engine.GumbelConfig): the MCTS side searches with Gumbel root search and plays its move
-    (SelfPlayEngine.root_policy; no Gumbel noise), DESIGN.md 3.13.  eval_symmetry (True or a symmetry.EvalSymmetry): the
+    (SelfPlayEngine.root_policy; no Gumbel noise), DESIGN.md 3.13 -- with GumbelConfig(interior="gumbel") by the Gumbel interior
+    rule below the root, DESIGN.md 3.21.  eval_symmetry (True or a symmetry.EvalSymmetry): the
     MCTS side evaluates every leaf under a hashed board symmetry (True: seed 0), DESIGN.md 3.19.  fpu (True or an engine.Fpu):
     the MCTS side searches with first-play urgency reduction, DESIGN.md 3.20."""
     from .engine import check_fpu, check_gumbel, check_leaves_per_step

@@ -21,6 +21,7 @@
 // noise (k_root_noise) and subtree reuse (two arenas, dev_reroot) -- DESIGN.md 3.9, 3.10; leaf-parallel search with virtual
 // loss (K walks per game per step, k_leaf_step) -- DESIGN.md 3.12.
 // First-play urgency reduction in the select rule (k_fpu_step and its cap / forced variants, csrc/bz_fpu.h) -- DESIGN.md 3.20.
+// The Gumbel interior rule below the root of a Gumbel search (k_gfull_step, csrc/bz_gumbel_interior.h) -- DESIGN.md 3.21.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -38,6 +39,7 @@
 #include "bz_math.h"
 #include "bz_rules.h"
 #include "bz_fpu.h"
+#include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
 
@@ -217,6 +219,10 @@ struct ValueDev { float* ex_q; };
 struct FpuDev { float reduction, root_reduction; float* root_w; };
 // what the FPU walk takes along: the reductions and the root's Wr as of this walk
 struct FpuSel { float r, r_root, Wr; };
+// Gumbel interior selection (node_v = nullptr: off), set by bz_engine_set_gumbel_interior in the caller's buffer:
+// the value every node of the current search was expanded with, f32 [B][ncap] indexed like the nodes.  A kernel argument of
+// k_gfull_step only.
+struct GumbelInDev { float* node_v; };
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -284,6 +290,39 @@ __device__ __forceinline__ float group_max(float m) {
     if (kGW > 4) { float m2 = xchg<4>(m); m = m2 > m ? m2 : m; }
     if (kGW > 8) { float m2 = xchg<8>(m); m = m2 > m ? m2 : m; }
     return m;
+}
+template <int kGW>
+__device__ __forceinline__ float group_min(float m) {
+    if (kGW > 1) { float m2 = xchg<1>(m); m = m2 < m ? m2 : m; }
+    if (kGW > 2) { float m2 = xchg<2>(m); m = m2 < m ? m2 : m; }
+    if (kGW > 4) { float m2 = xchg<4>(m); m = m2 < m ? m2 : m; }
+    if (kGW > 8) { float m2 = xchg<8>(m); m = m2 < m ? m2 : m; }
+    return m;
+}
+template <int kGW>
+__device__ __forceinline__ u32 group_max_u32(u32 m) {
+    if (kGW > 1) { u32 m2 = xchg<1>(m); m = m2 > m ? m2 : m; }
+    if (kGW > 2) { u32 m2 = xchg<2>(m); m = m2 > m ? m2 : m; }
+    if (kGW > 4) { u32 m2 = xchg<4>(m); m = m2 > m ? m2 : m; }
+    if (kGW > 8) { u32 m2 = xchg<8>(m); m = m2 > m ? m2 : m; }
+    return m;
+}
+// SEQUENTIAL float sum over the kGW lanes of a group in ascending lane order (Gumbel interior rule): returns
+// ((carry + x_0) + x_1) + ... + x_{kGW-1} in every lane, each addition one rounding, left to right -- the bits of the serial loop.
+// A systolic pass: in every step each lane adds its x to what the lane before it holds (lane 0: to the carry), so after step s
+// the lanes 0 .. s hold their final prefix and recompute the same value from then on; kGW steps of one DPP move and one add.
+// A lane without a term passes x = +0.0f: the running sum starts from +0.0f and is therefore never -0.0f, so the addition
+// changes no bit.  (The DPP shift crosses into the neighbouring group only in lane 0, whose input is replaced by the carry.)
+template <int kGW>
+__device__ __forceinline__ float group_seq_sum(float carry, float x, int sub) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int s = 0; s < kGW; ++s) {
+        float t = row_shr1(acc);
+        t = sub == 0 ? carry : t;
+        acc = t + x;
+    }
+    return __shfl(acc, kGW - 1, kGW);
 }
 // integer sum over the kGW lanes of a group (first-play urgency): whatever the order, the same bits
 template <int kGW>
@@ -594,13 +633,19 @@ __device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const Gumbel
 // grows with the prior mass of the node's visited edges, instead of 0.  The mass needs all of the node's edges before any is
 // scored: its <= kCH chunks are loaded together into registers (still ONE dependent load per level), summed as integers across
 // the group, then scored from the registers.
-template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false>
+// kGfull (k_gfull_step; with kGumbel): every level below the root takes the edge whose visit share lags the node's
+// improved policy softmax(logf(P~) + sigma(completed Q)) the most, in place of PUCT.  Like kFpu the node's <= kCH edge chunks are
+// loaded together into registers, and the node's own value v_X (gnv, this game's row of the interior buffer) is loaded beside
+// its position: still ONE dependent load per level.  Per-edge terms are computed one edge per lane; max / min are group
+// reductions; the three sums run in ascending edge order (group_seq_sum), so the bits are those of gi_pick_serial.
+template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false, bool kGfull = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
                                            Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f,
-                                           const FpuSel* fp = nullptr) {
+                                           const FpuSel* fp = nullptr, const float* gnv = nullptr) {
     constexpr int kGW = G::GW;
     constexpr int kCH = (G::MAXCH + kGW - 1) / kGW;
+    [[maybe_unused]] float vx = 0.0f;  // kGfull: v_X of the node whose edges are being scored (depth >= 1)
     // kFpu: the value of the node whose edges are being scored -- the root's Wr / simulations so far, 0 before the first
     float qx = 0.0f;
     if (kFpu) qx = root.sumN > 0u ? fdiv(fp->Wr, (float)root.sumN) : 0.0f;
@@ -620,6 +665,75 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             best = gumbel_root_pick<G>(E, *gm, g, ed, n, sumN);
             const Edge e = ed[best];
             bestw0 = e.w0; bestw3 = e.w3; bestW = e.W;
+        } else if (kGfull) {  // (depth >= 1: X is expanded and not terminal)
+            Edge ev[kCH];
+#pragma unroll
+            for (int k = 0; k < kCH; ++k) {
+                const int i = k * kGW + sub;
+                ev[k].w0 = 0; ev[k].W = 0.0f; ev[k].P = 0.0f; ev[k].w3 = 0;
+                if (i < n) ev[k] = ed[i];
+            }
+            if (n <= 1) {  // a forced pass: edge 0 (lane 0 holds it)
+                best = 0;
+                bestw0 = (u32)__shfl((int)ev[0].w0, 0, kGW); bestw3 = (u32)__shfl((int)ev[0].w3, 0, kGW);
+                bestW = __shfl(ev[0].W, 0, kGW);
+            } else {
+                // ---- statistics: q one edge per lane, sp / spq sequentially in edge order, nmax by a group reduction
+                float cq[kCH];
+                float sp = 0.0f, spq = 0.0f;
+                u32 nmax = 0;
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    const u32 N = e_N(ev[k].w0);  // (0 in a lane without an edge)
+                    const bool vis = N > 0u;
+                    const float q = vis ? fdiv(ev[k].W, (float)N) : 0.0f, pf = gi_pfloor(ev[k].P);
+                    const float t = pf * q;
+                    cq[k] = q;
+                    nmax = N > nmax ? N : nmax;
+                    if (k * kGW < n) {  // (the same for the whole group)
+                        sp = group_seq_sum<kGW>(sp, vis ? pf : 0.0f, sub);
+                        spq = group_seq_sum<kGW>(spq, vis ? t : 0.0f, sub);
+                    }
+                }
+                nmax = group_max_u32<kGW>(nmax);
+                const float vmix = gi_vmix(sumN, sp, spq, vx);
+                float lo = __builtin_inff(), hi = -__builtin_inff();
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    if (e_N(ev[k].w0) == 0u) cq[k] = vmix;
+                    if (k * kGW + sub < n) { lo = cq[k] < lo ? cq[k] : lo; hi = cq[k] > hi ? cq[k] : hi; }
+                }
+                lo = group_min<kGW>(lo); hi = group_max<kGW>(hi);
+                const GiScale gs = gi_scale(lo, hi, nmax, gm->mvi, gm->vs);
+                // ---- the improved policy: x one edge per lane, the max by a group reduction, the sum sequentially
+                float m = -__builtin_inff();
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    cq[k] = gi_x(gs, ev[k].P, cq[k]);
+                    if (k * kGW + sub < n) m = cq[k] > m ? cq[k] : m;
+                }
+                m = group_max<kGW>(m);
+                float s = 0.0f;
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    cq[k] = (k * kGW + sub < n) ? expf_spec(cq[k] - m) : 0.0f;
+                    if (k * kGW < n) s = group_seq_sum<kGW>(s, cq[k], sub);
+                }
+                // ---- score and the first maximum: every lane's own over its <= kCH edges (ascending, strict >), then ONE reduction
+                const float den = 1.0f + (float)sumN;
+                Cand cd; cd.i = sub; cd.sc = -__builtin_inff(); cd.W = 0.0f; cd.w0 = 0; cd.w3 = 0;
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    const int i = k * kGW + sub;
+                    if (i < n) {
+                        const Edge e = ev[k];
+                        const float sc = gi_score(fdiv(cq[k], s), e_N(e.w0), den);
+                        if (sc > cd.sc) { cd.sc = sc; cd.i = i; cd.w0 = e.w0; cd.w3 = e.w3; cd.W = e.W; }
+                    }
+                }
+                group_argmax<kGW>(cd);
+                best = cd.i; bestw0 = cd.w0; bestw3 = cd.w3; bestW = cd.W;
+            }
         } else if (kFpu) {
             Edge ev[kCH];
             u32 S = 0;
@@ -690,6 +804,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             // X's position is needed only if the walk ends by extending X: the load goes out beside X's edge load
             const Node* xn = nodes + child;
             pown = xn->own; popp = xn->opp;
+            if (kGfull) vx = gnv[child];  // (beside them: X's own value)
             continue;
         }
         st.mark(3);
@@ -1118,9 +1233,12 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 // the per-game words, advanced by what this step's backup adds to the path's root edge and stored beside it.  sim_idx is the
 // number of simulations backed up once this step's backup is done (an expand-only step gets it from the host too): the backup of
 // simulation 0 starts Wr from 0, so no search needs a reset.
-template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false>
+// kGfull (with kGumbel): the Gumbel interior rule at every level below the root, and every expanded node's value
+// stored in the interior buffer with its expansion, on the EVAL and on the COPY path.
+template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false, bool kGfull = false>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
-                                               const u32* budget = nullptr, float fk = 0.0f, const FpuDev* fd = nullptr) {
+                                               const u32* budget = nullptr, float fk = 0.0f, const FpuDev* fd = nullptr,
+                                               const GumbelInDev* gi = nullptr) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1171,6 +1289,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                     E.hot[g].n_edges = ne; c.v[CNT_NET_LEAVES]++; if (leaf == 0) E.hot[g].root_n = (u32)n;
                     if (E.ecache) E.node_v[(size_t)g * E.ncap + leaf] = v;  // what a later repeat of this position copies
                     if (kGumbel && leaf == 0) Gm.vroot[g] = v;
+                    if constexpr (kGfull) gi->node_v[(size_t)g * E.ncap + leaf] = v;
                 }
                 if (leaf == 0) { root_n = n; pre_ok = false; }  // the root's edges did not exist when re0 was fetched
             } else if (kind == LEAF_COPY) {  // ---- round trip 2: the first evaluation's edges and value (evaluation cache)
@@ -1180,6 +1299,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 if (sub == 0) {
                     E.hot[g].n_edges = ne; E.node_v[(size_t)g * E.ncap + leaf] = v;
                     if (kGumbel && leaf == 0) Gm.vroot[g] = v;
+                    if constexpr (kGfull) gi->node_v[(size_t)g * E.ncap + leaf] = v;
                 }
             } else {
                 v = (float)((int)((ninfo >> 9) & 3u) - 1);
@@ -1218,6 +1338,9 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 if constexpr (kFpu) {
                     FpuSel fs; fs.r = fd->reduction; fs.r_root = fd->root_reduction; fs.Wr = rw;
                     dev_select<G, PathHbm<kGW>, false, false, kForced, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, nullptr, fslot, &fs);
+                } else if constexpr (kGfull) {
+                    dev_select<G, PathHbm<kGW>, false, true, false, false, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, 0.0f, nullptr,
+                                                                                 gi->node_v + (size_t)g * E.ncap);
                 } else
                 dev_select<G, PathHbm<kGW>, false, kGumbel, kForced>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
                 sink.flush(sub, depth);
@@ -1267,6 +1390,13 @@ __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, i
 template <class G>
 __global__ void __launch_bounds__(256) k_gumbel_step(EngineDev E, GumbelDev Gm, int do_expand, int do_select, u32 sim_idx) {
     tree_step_body<G, true>(E, Gm, do_expand, do_select, sim_idx);
+}
+
+// The tree step of a Gumbel search with the Gumbel interior rule: k_gumbel_step with the interior rule at every
+// level below the root and v_X stored with every expansion.  Gi travels as a kernel argument.
+template <class G>
+__global__ void __launch_bounds__(256) k_gfull_step(EngineDev E, GumbelDev Gm, GumbelInDev Gi, int do_expand, int do_select, u32 sim_idx) {
+    tree_step_body<G, true, false, false, false, true>(E, Gm, do_expand, do_select, sim_idx, nullptr, 0.0f, nullptr, &Gi);
 }
 
 // The tree step under playout cap randomisation: k_tree_step, every slot walking for its own budget.
@@ -2202,6 +2332,7 @@ struct bz_engine {
     hipEvent_t ahead[4];
     int n_ahead;
     GumbelDev gumbel;  // Gumbel root search (bz_engine_set_gumbel); gumbel.m = 0: off
+    GumbelInDev gin;   // Gumbel interior selection (bz_engine_set_gumbel_interior); gin.node_v = nullptr: off
     CapDev cap;        // playout cap randomisation (bz_engine_set_playout_cap); cap.fast = 0: off
     ForcedDev forced;  // forced playouts (bz_engine_set_forced_playouts); forced.k = 0: off
     SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
@@ -2347,6 +2478,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
     e->sym_on = 0; e->sym_seed = 0;
     e->gumbel = GumbelDev{};  // off
+    e->gin = GumbelInDev{};
     e->cap = CapDev{};
     e->forced = ForcedDev{};
     e->surp = SurpDev{};
@@ -2528,7 +2660,8 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
         if (do_select) { e->pack_parity = (int)(sim_idx & 1u); e->fpu_done = (int)sim_idx + 1; }
         return BZ_OK;
     }
-    if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
+    if (e->gumbel.m > 0 && e->gin.node_v) BZ_DISPATCH_G(e, k_gfull_step, stream, e->dev, e->gumbel, e->gin, do_expand, do_select, sim_idx);  // 
+    else if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
     else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH_G(e, k_forced_cap_step, stream, e->dev, e->cap, e->forced, do_expand, do_select, sim_idx);
     else if (e->forced.k > 0.0f) BZ_DISPATCH_G(e, k_forced_step, stream, e->dev, e->forced, do_expand, do_select, sim_idx);  // 
     else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_cap_step, stream, e->dev, e->cap, do_expand, do_select, sim_idx);  // 
@@ -2716,8 +2849,9 @@ BZ_EXPORT int64_t bz_engine_gumbel_bytes(const bz_engine_cfg* cfg, int32_t max_c
 BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, float gumbel_scale, float maxvisit_init,
                                        float value_scale, void* buf, int64_t buf_bytes, void* stream) {
     BZ_REQUIRE(e, "bz_engine_set_gumbel: null engine");
-    if (max_considered == 0) {  // off: the next search is a PUCT search again
+    if (max_considered == 0) {  // off: the next search is a PUCT search again (and the interior rule goes with it)
         e->gumbel.m = 0;
+        e->gin = GumbelInDev{};
         return BZ_OK;
     }
     BZ_REQUIRE(max_considered >= 1 && max_considered <= BZ_GUMBEL_MAX_CONSIDERED, "bz_engine_set_gumbel: max_considered must be in 0..64");
@@ -2744,6 +2878,47 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     gd.m = max_considered; gd.scale = gumbel_scale; gd.mvi = maxvisit_init; gd.vs = value_scale;
     gd.T = at<uint16_t>(buf, o.T); gd.base = at<float>(buf, o.base); gd.vroot = at<float>(buf, o.vroot);
     return BZ_OK;
+}
+
+/* ---- Gumbel interior selection */
+namespace {
+inline int64_t gumbel_interior_bytes(const bz_engine_cfg& c) { Carver k; k.take((int64_t)c.n_games * nodes_per_game(c) * 4); return k.off; }
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_gumbel_interior_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_gumbel_interior_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_gumbel_interior_bytes: %s", kBadCfg); return -1; }
+    if (const char* why = gumbel_refusal(*cfg)) { set_error("bz_engine_gumbel_interior_bytes: %s", why); return -1; }
+    return gumbel_interior_bytes(*cfg);
+}
+
+BZ_EXPORT int32_t bz_engine_set_gumbel_interior(bz_engine* e, int32_t on, void* buf, int64_t buf_bytes, void* stream) {
+    (void)stream;  // (nothing is uploaded or cleared: every node's value is written with its expansion before it is read)
+    BZ_REQUIRE(e, "bz_engine_set_gumbel_interior: null engine");
+    if (!on) {  // off: k_gumbel_step (or the PUCT kernels) again
+        e->gin = GumbelInDev{};
+        return BZ_OK;
+    }
+    BZ_REQUIRE(e->gumbel.m > 0, "bz_engine_set_gumbel_interior: the Gumbel interior rule needs Gumbel root search (bz_engine_set_gumbel first)");
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel_interior: the buffer must be non-null and 256-byte aligned");
+    const int64_t need = gumbel_interior_bytes(e->cfg);
+    if (buf_bytes < need) {
+        set_error("bz_engine_set_gumbel_interior: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)need);
+        return BZ_EINVAL;
+    }
+    e->gin.node_v = static_cast<float*>(buf);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_gumbel_interior_pick(const uint32_t* N, const float* W, const float* P, int32_t n, float v_node, float maxvisit_init,
+                                          float value_scale, float* p_out, float* score_out) {
+    if (!(N && W && P && n >= 1 && n <= kGiMaxN)) { set_error("bz_gumbel_interior_pick: null pointer or n outside 1 .. 64"); return -1; }
+    if (n == 1) {  // a forced pass: the walk takes edge 0; the policy of one action
+        if (p_out) p_out[0] = 1.0f;
+        if (score_out) score_out[0] = gi_score(1.0f, N[0], 1.0f + (float)N[0]);
+        return 0;
+    }
+    return gi_pick_serial(N, W, P, n, v_node, maxvisit_init, value_scale, p_out, score_out);
 }
 
 /* ---- playout cap randomisation */
@@ -3182,6 +3357,8 @@ BZ_EXPORT int32_t bz_engines_step(bz_engine* const* engines, void* const* stream
         BZ_REQUIRE(engines[i]->dev.K == engines[0]->dev.K, "bz_engines_step: the engines must take the same leaves per step");
         BZ_REQUIRE((engines[i]->gumbel.m > 0) == (engines[0]->gumbel.m > 0),
                    "bz_engines_step: the engines must all search with Gumbel root search or all without");
+        BZ_REQUIRE((engines[i]->gin.node_v != nullptr) == (engines[0]->gin.node_v != nullptr),
+                   "bz_engines_step: the engines must all search with the Gumbel interior rule or all without");
         BZ_REQUIRE(engines[i]->cfg.eval_kind != BZ_EVAL_EXTERNAL, "bz_engines_step: BZ_EVAL_EXTERNAL callers drive the step API");
         if (search_is_fused(engines[i])) stepwise = false;
     }

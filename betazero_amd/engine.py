@@ -169,11 +169,17 @@ MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
 class GumbelConfig:
     """Gumbel root search (Danihelka et al., ICLR 2022).  The defaults are those of mctx's
     gumbel_muzero_policy: max_considered root actions (1..64) for the sequential halving, the Gumbel noise scale (0: no
-    noise), and sigma's maxvisit_init / value_scale."""
+    noise), and sigma's maxvisit_init / value_scale.  interior: the select rule below the root -- "puct" (the default: PUCT
+    with c_puct, an unvisited child worth 0) or "gumbel" (the paper's interior rule, the action whose visit
+    share lags the node's improved policy softmax(log P + sigma(completed Q)) the most; no c_puct, no noise)."""
     max_considered: int = 16
     scale: float = 1.0
     maxvisit_init: float = 50.0
     value_scale: float = 0.1
+    interior: str = "puct"
+
+
+GUMBEL_INTERIORS = ("puct", "gumbel")
 
 
 def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0.0):
@@ -191,13 +197,15 @@ def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0
         x = getattr(cfg, name)
         if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x < 0:
             raise ValueError(f"gumbel: {name} must be a finite number >= 0 (got {x!r})")
+    if not isinstance(cfg.interior, str) or cfg.interior not in GUMBEL_INTERIORS:
+        raise ValueError(f"gumbel: interior must be 'puct' or 'gumbel' (got {cfg.interior!r})")
     if reuse_subtree:
         raise ValueError("gumbel: Gumbel root search does not combine with reuse_subtree")
     if leaves_per_step != 1:
         raise ValueError("gumbel: Gumbel root search does not combine with leaves_per_step > 1")
     if dirichlet_eps > 0:
         raise ValueError("gumbel: Gumbel root search does not combine with Dirichlet noise (dirichlet_eps > 0)")
-    return GumbelConfig(int(m), float(cfg.scale), float(cfg.maxvisit_init), float(cfg.value_scale))
+    return GumbelConfig(int(m), float(cfg.scale), float(cfg.maxvisit_init), float(cfg.value_scale), str(cfg.interior))
 
 
 @dataclass(frozen=True)
@@ -335,6 +343,8 @@ class SelfPlayEngine:
         gumbel: None / False = PUCT at every node (the default, unchanged); True or a GumbelConfig = Gumbel
         root search: Gumbel-top-k plus sequential halving at the root (PUCT below it), the move is the halving's survivor and
         the example rows' pi is the improved policy.  Gumbel noise is drawn while moves made < temp_moves (and scale > 0).
+        GumbelConfig(interior="gumbel") replaces PUCT below the root by the paper's interior rule (DESIGN.md 3.21);
+        set_gumbel_interior() changes it between searches.
         Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0.
 
         playout_cap: None / False = every search has `sims` simulations (the default, unchanged); a
@@ -428,6 +438,8 @@ class SelfPlayEngine:
             gpad = (-self.gws.data_ptr()) & 255
             self._call(L.bz_engine_set_gumbel, gc.max_considered, gc.scale, gc.maxvisit_init, gc.value_scale,
                        self.gws.data_ptr() + gpad, gbytes)
+            if gc.interior == "gumbel":
+                self._set_gumbel_interior(True)
         if self.playout_cap is not None:  # the engine's budget buffer (caller-owned, like the workspace)
             pc = self.playout_cap
             cbytes = L.bz_engine_playout_cap_bytes(C.byref(self.cfg))
@@ -493,6 +505,30 @@ class SelfPlayEngine:
         self.drain()
         _lib.check(_lib.lib().bz_engine_set_eval_symmetry(self.h, int(es is not None), es.seed if es is not None else 0))
         self.eval_symmetry = es
+
+    def _set_gumbel_interior(self, on):
+        L = _lib.lib()
+        if not on:
+            self._call(L.bz_engine_set_gumbel_interior, 0, None, 0)
+            return
+        if getattr(self, "giws", None) is None:  # the engine's v_X buffer (caller-owned, next to the Gumbel one)
+            ibytes = L.bz_engine_gumbel_interior_bytes(C.byref(self.cfg))
+            if ibytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.giws = torch.zeros(ibytes + 256, dtype=torch.uint8, device=self.device)
+            self._gipad, self._gibytes = (-self.giws.data_ptr()) & 255, ibytes
+        self._call(L.bz_engine_set_gumbel_interior, 1, self.giws.data_ptr() + self._gipad, self._gibytes)
+
+    def set_gumbel_interior(self, interior):
+        """switch the select rule below the root of a Gumbel search between "puct" and "gumbel" (DESIGN.md 3.21), between
+        searches; ValueError without Gumbel root search"""
+        if self.gumbel is None:
+            raise ValueError("gumbel: the interior rule needs Gumbel root search (gumbel=)")
+        from dataclasses import replace
+        gc = check_gumbel(replace(self.gumbel, interior=interior))
+        self.drain()
+        self._set_gumbel_interior(gc.interior == "gumbel")
+        self.gumbel = gc
 
     def _set_fpu(self, fp):
         L = _lib.lib()

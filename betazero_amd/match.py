@@ -25,7 +25,8 @@ class MatchPlayer:
     engine.GumbelConfig): DESIGN.md 3.13, the side plays the Gumbel move without Gumbel noise; eval_cache: SelfPlayEngine's;
     eval_symmetry (True or a symmetry.EvalSymmetry): DESIGN.md 3.19, the side evaluates every leaf under a hashed board
     symmetry (True: seed 0) -- a match stays a pure function of its arguments.  fpu (True or an engine.Fpu): DESIGN.md 3.20,
-    the side searches with first-play urgency reduction (not with gumbel or leaves_per_step > 1)."""
+    the side searches with first-play urgency reduction (not with gumbel or leaves_per_step > 1).  Each side has its own
+    GumbelConfig.interior ("puct" or "gumbel")."""
     sims: int = 800
     net: object = None
     evaluator: str = None

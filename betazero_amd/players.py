@@ -152,7 +152,8 @@ class MCTSPlayer(Player):
     plays (SelfPlayEngine.root_policy) and last_policy its improved policy; the player draws no Gumbel noise (temp_moves 0),
     so it is deterministic.  eval_symmetry (True or a symmetry.EvalSymmetry): every leaf is evaluated under a hashed board
     symmetry (True: seed 0); net evaluators on Reversi only.  fpu (True or an engine.Fpu): first-play urgency
-    reduction in the select rule; not with gumbel or leaves_per_step > 1."""
+    reduction in the select rule; not with gumbel or leaves_per_step > 1.  GumbelConfig(interior="gumbel"):
+    the Gumbel interior rule below the root instead of PUCT."""
 
     def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1,
                  gumbel=None, eval_symmetry=None, fpu=None):

@@ -436,6 +436,27 @@ int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, float gumbel_
 /* the considered-visit sequence T[n_considered][k], k = 0 .. sims - 1, of mctx's get_sequence_of_considered_visits (the table
  * bz_engine_set_gumbel uploads; n_considered 1..64, sims 1..BZ_ENGINE_MAX_SIMS).  Host only. */
 int32_t bz_gumbel_considered_visits(int32_t n_considered, int32_t sims, uint16_t* out);
+/* Gumbel interior selection (the interior rule of Gumbel MuZero, mctx's gumbel_muzero_interior_action_selection),
+ * opt-in per engine on top of Gumbel root search: below the root a walk standing at an expanded node X with n > 1 edges takes the
+ * first maximum of sc_i = p_i - float(N_i) / (1.0f + float(S)), S = the visit sum of X's children, p = the improved policy of X:
+ * softmax(logf(P~_i) + sigma_i) by the sequence of DESIGN.md 3.5 (ascending strict max, expf_spec, sequential sum, division),
+ * sigma_i from the "completed Q, sigma" paragraph of DESIGN.md 3.13 on X's current N / W / P with v_root replaced by v_X, the
+ * value X was expanded with (the evaluator's, or the one the evaluation cache copied).  n == 1 (a forced pass): edge 0.  No
+ * c_puct, no noise below the root; the root rule, expansion, backup, the move, pi' and the rows are those of DESIGN.md 3.13.
+ * Combines with everything Gumbel root search combines with.  Searches go through k_gfull_step in place of k_gumbel_step. */
+/* bytes of the caller-owned buffer: v_X f32 [n_games][node capacity of a game's arena = sims + 2], rounded up to 256 bytes.
+ * Needs no GPU; -1 (bz_last_error says why) for a bad config or a combination Gumbel root search refuses. */
+int64_t bz_engine_gumbel_interior_bytes(const bz_engine_cfg* cfg);
+/* switch the interior rule on (on != 0) or off (on == 0: k_gumbel_step again), between searches.  BZ_EINVAL (bz_last_error says
+ * why) when Gumbel root search is not on, or when buf is null, not 256-byte aligned or smaller than
+ * bz_engine_gumbel_interior_bytes.  buf: device memory owned by the caller and kept alive while the rule is on; it needs no
+ * initialisation (a node's value is written with its expansion).  bz_engine_set_gumbel(e, 0, ...) switches this off too. */
+int32_t bz_engine_set_gumbel_interior(bz_engine* e, int32_t on, void* buf, int64_t buf_bytes, void* stream);
+/* the rule for one node on the host, from the functions the kernel runs: N, W, P [n] the edges' visits, value sums (for X's
+ * mover) and priors in edge order, n in 1 .. 64, v_node = v_X.  Fills p_out [n] and score_out [n] (either may be null) and
+ * returns the chosen edge; -1 (bz_last_error says why) for bad arguments.  Host only. */
+int32_t bz_gumbel_interior_pick(const uint32_t* N, const float* W, const float* P, int32_t n, float v_node, float maxvisit_init,
+                                float value_scale, float* p_out, float* score_out);
 /* Playout cap randomisation (KataGo, Wu 2019, section 3.1), opt-in per engine.  Before every search each
  * slot draws its simulation budget: cfg.sims (a "full" search) when (rng_draw(seed ^ 0x706C61796F757443, game id, moves made)
  * & 0xFFFF) < full_q, else fast_sims -- game id and moves made as the Dirichlet noise keys them.  The slot searches with that

@@ -34,7 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
-from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
+from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
                                  check_playout_cap, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--gumbel", action="store_true", help="self-play with Gumbel root search (DESIGN.md 3.13): the example rows' pi is the "
                     "improved policy, Gumbel noise on the first --temp-moves moves, no Dirichlet noise; the gate's and the arena's players "
                     "then play the Gumbel move too")
+    ap.add_argument("--gumbel-interior", action="store_true", help="under --gumbel: the Gumbel interior rule below the root (DESIGN.md "
+                    "3.21; the action whose visit share lags the node's improved policy the most) instead of PUCT, in self-play, for "
+                    "both players of the gate and for the arena's search player.  An argument error without --gumbel")
     ap.add_argument("--fast-sims", type=int, default=0, help="self-play with playout cap randomisation (DESIGN.md 3.15): every move "
                     "is searched with --sims simulations with probability --full-prob (and recorded) or with this many (and not "
                     "recorded); 0 = off.  Not with --gumbel")
@@ -106,6 +109,8 @@ def main():
     ap.add_argument("--miopen-train", action="store_true", help="train the tower through stock autograd (MIOpen) instead of the HIP training kernels (csrc/bz_train.hip)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.gumbel_interior and not args.gumbel:
+        ap.error("--gumbel-interior takes effect only with --gumbel")
 
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
@@ -120,7 +125,7 @@ def main():
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
     cand = DeviceNet.from_module(module, bmax) if args.gate_games else dnet
-    gumbel = True if args.gumbel else None
+    gumbel = GumbelConfig(interior="gumbel" if args.gumbel_interior else "puct") if args.gumbel else None
     cap = check_playout_cap(PlayoutCap(args.fast_sims, args.full_prob) if args.fast_sims else None, args.sims, gumbel=gumbel)
     forced = check_forced_playouts(ForcedPlayouts(args.forced_k, not args.no_prune) if args.forced_k else None, gumbel=gumbel)
     fpu = check_fpu(Fpu(args.fpu_reduction, args.fpu_root_reduction) if args.fpu_reduction is not None else None, gumbel=gumbel)
@@ -227,6 +232,7 @@ def main():
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
               **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}),
+              **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
