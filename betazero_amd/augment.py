@@ -12,18 +12,16 @@ from . import _lib
 from .engine import DeviceExamples, Examples
 
 
-def _first_occurrences(key8, own8, opp8, pi8):
-    """indices (ascending = insertion order) of the rows to keep: the first of every set of EXACTLY equal
-    (own, opp, pi) rows -- SL/train.py:45-50 keeps the first of every exactly-equal pair.  Rows are grouped by the
-    kernel's 64-bit content key (stable sort: insertion order inside a group) and every row is compared with the HEAD
-    of its group on the full content: the head is kept, rows equal to it are duplicates and dropped, rows that differ
-    (another content sharing the key) go into the next pass among themselves -- so the result is exact whatever the
-    keys do: a collision can neither drop a distinct row nor keep a duplicate.  With honest keys that is one pass plus
-    one emptiness check.  pi is compared by BIT PATTERN (a row holding a NaN equals itself -- with float comparison a
-    group head containing a NaN differed from itself and was handed to the next pass for ever), and a pass never hands
-    its own heads on, so every pass removes at least one row: the loop ends."""
+def _first_by_key(key8, own8, opp8, pi8):
+    """indices (ascending = insertion order) of the first of every set of exactly equal (own, opp, pi) rows AMONG THE
+    ROWS THAT SHARE A KEY.  Rows are grouped by key (stable sort: insertion order inside a group) and every row is
+    compared with the HEAD of its group on the full content: the head is kept, rows equal to it are duplicates and
+    dropped, rows that differ (another content sharing the key) go into the next pass among themselves -- a collision
+    can neither drop a distinct row nor keep a duplicate.  With honest keys that is one pass plus one emptiness check.
+    pi8 holds the BIT PATTERNS (int32: a row holding a NaN equals itself -- with float comparison a group head
+    containing a NaN differed from itself and was handed to the next pass for ever), and a pass never hands its own
+    heads on, so every pass removes at least one row: the loop ends."""
     kept = []
-    pi8 = pi8.view(torch.int32)
     cur = torch.arange(key8.numel(), device=key8.device)
     while cur.numel():
         sk, o = torch.sort(key8[cur], stable=True)
@@ -36,6 +34,21 @@ def _first_occurrences(key8, own8, opp8, pi8):
         kept.append(order[newrun])
         cur = torch.sort(order[~same & ~newrun]).values          # ascending again: the stable sort keeps insertion order
     return torch.sort(torch.cat(kept)).values if kept else cur
+
+
+def _first_occurrences(key8, own8, opp8, pi8):
+    """indices (ascending = insertion order) of the rows to keep: the first of every set of EXACTLY equal
+    (own, opp, pi) rows -- SL/train.py:45-50 keeps the first of every exactly-equal pair -- whatever the keys do.
+    _first_by_key under the kernel's 64-bit content key does the work; it is exact when equal rows carry equal keys
+    (the kernel's key is a function of the content).  Keys that are NOT a function of the content would leave a copy
+    standing in every key group it occurs in, so the survivors go through _first_by_key once more under a key computed
+    here from the content alone (boards and the sum of pi's bit patterns: weak, and exact all the same).  After honest
+    keys the second round finds nothing: one more sort over the kept rows."""
+    pi8 = pi8.view(torch.int32)
+    keep = _first_by_key(key8, own8, opp8, pi8)
+    own, opp, pi = own8[keep], opp8[keep], pi8[keep]
+    content = own * -0x61C8864680B583EB + opp * -0x3D4D51C2D82B14B1 + pi.sum(1, dtype=torch.int64)  # (int64 wraps)
+    return keep[_first_by_key(content, own, opp, pi)]
 
 
 def augment_examples(ex, dedupe=True, device="cuda:0"):

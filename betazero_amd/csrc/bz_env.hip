@@ -508,9 +508,10 @@ BZ_EXPORT int32_t bz_ttt_step_batch(const uint16_t* own, const uint16_t* opp, co
 BZ_EXPORT int32_t bz_augment_d4_batch(const uint64_t* own, const uint64_t* opp, const float* pi, int64_t n, int32_t size,
                                       int32_t na, uint64_t* own8, uint64_t* opp8, float* pi8, uint64_t* key8,
                                       void* stream) {
-    BZ_REQUIRE(n >= 0 && own && opp && pi && own8 && opp8 && pi8, "bz_augment_d4_batch: null pointer");
+    BZ_REQUIRE(n >= 0, "bz_augment_d4_batch: n must be >= 0");
     BZ_REQUIRE((size == 3 || size == 8) && na >= size * size, "bz_augment_d4_batch: size must be 3 or 8, na >= size*size");
-    if (n == 0) return BZ_OK;
+    if (n == 0) return BZ_OK;  // before the pointers: an empty torch tensor hands over a null data_ptr()
+    BZ_REQUIRE(own && opp && pi && own8 && opp8 && pi8, "bz_augment_d4_batch: null pointer");
     int64_t blocks = (n * 8 + 255) / 256;
     hipLaunchKernelGGL(k_augment_d4, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, own, opp, pi, n, (int)size,
                        (int)na, own8, opp8, pi8, key8);

@@ -129,7 +129,8 @@ int32_t bz_ttt_step_batch(const uint16_t* own, const uint16_t* opp, const uint8_
  * transpose; the last equals rot90 x3 under torch semantics, as in the reference).
  * Row 8*i+t of the outputs = transform t of input row i; pi is permuted with the board
  * (entries beyond size*size -- Reversi's pass -- stay).  key8 (optional, may be null) gets a
- * 64-bit content key of each output row for the dedupe of train.py:45-50. */
+ * 64-bit content key of each output row for the dedupe of train.py:45-50.  n == 0 is a no-op
+ * whatever the pointers are (an empty tensor has a null data pointer). */
 int32_t bz_augment_d4_batch(const uint64_t* own, const uint64_t* opp, const float* pi, int64_t n, int32_t size,
                             int32_t na, uint64_t* own8, uint64_t* opp8, float* pi8, uint64_t* key8, void* stream);
 

@@ -732,7 +732,8 @@ def test_arena_batched_reversi_mcts_vs_depth_limited_minimax():
     res = play_arena("reversi", B, 300, opponent_depth=2, evaluator="hash", seed=5)
     print("reversi arena (untrained evaluator):", res.summary())
     L = _lib.lib()
-    for g in range(0, B, 5):
+    n_checked = n_none = 0
+    for g in range(B):
         x, o, cur = 0x0000001008000000, 0x0000000810000000, 1  # reversi_board.py:9-11 (+1 on the main diagonal)
         for act, mover in res.moves:
             if mover[g] == 0:
@@ -744,7 +745,10 @@ def test_arena_batched_reversi_mcts_vs_depth_limited_minimax():
             if cur != res.mcts_colour[g]:  # the minimax side: same decision as the scalar entry point
                 mv, sc = C.c_int32(), C.c_int32()
                 _lib.check(L.bz_reversi_minimax(own, opp, 8, 2, C.byref(mv), C.byref(sc)))
-                assert mv.value == a or mv.value == -1
+                # (-1 = the reference's None: every root move scores -inf and get_move draws one with `random`)
+                assert mv.value == a or mv.value == -1 and sc.value == -1000, (g, hex(own), hex(opp), a, mv.value, sc.value)
+                n_checked += 1
+                n_none += mv.value == -1
             no, np_, _ = orc.reversi_apply(own, opp, 8, a >> 3, a & 7)
             x, o = (no, np_) if cur == 1 else (np_, no)
             if orc.reversi_game_over(x, o):
@@ -754,6 +758,8 @@ def test_arena_batched_reversi_mcts_vs_depth_limited_minimax():
             if orc.reversi_legal(own, opp) == 0:  # pass rule, reversi_terminal.py:31-35
                 cur = -cur
         assert orc.reversi_game_over(x, o) and orc.reversi_score(x, o)[0] == res.winner[g]
+    print("minimax moves held to the scalar entry point:", n_checked, "of them None:", n_none)
+    assert n_checked >= 10 * B  # (a game has up to 60 placements, about half of them the minimax side's)
 
 
 def test_net_fp8_mfma_vs_oracle_fp8_emulation():
