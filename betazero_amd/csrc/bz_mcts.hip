@@ -2175,8 +2175,9 @@ __global__ void __launch_bounds__(1024) k_pack_scan(EngineDev E, PackedHdr* hdr,
     u32 carry = 0, games0 = 0;
     u64 dropped0 = 0;
     if (append) {  // every thread reads the header before thread 0 rewrites it (barriers below)
+        // (~0 in dropped_rows is final for a block: the header a bad append rewrote would otherwise match the next call)
         bad = hdr->magic != kPackedMagic || hdr->cap_rows != cap || hdr->na != (u64)E.na || hdr->bytes != (u64)L.total ||
-              hdr->game != (u64)game;
+              hdr->game != (u64)game || hdr->dropped_rows == ~0ULL;
         carry = (u32)hdr->n_rows; games0 = (u32)hdr->n_games; dropped0 = hdr->dropped_rows;
     }
     if (threadIdx.x == 0) { s_games = 0; s_rows_end = carry; }
@@ -2207,7 +2208,7 @@ __global__ void __launch_bounds__(1024) k_pack_scan(EngineDev E, PackedHdr* hdr,
         hdr->magic = kPackedMagic; hdr->cap_rows = cap; hdr->na = (u64)E.na; hdr->bytes = (u64)L.total;
         hdr->game = (u64)game;
         for (int k = 0; k < 8; ++k) hdr->offs[k] = (u64)L.offs[k];
-        hdr->n_rows = s_rows_end; hdr->n_games = games0 + s_games;
+        if (!bad) { hdr->n_rows = s_rows_end; hdr->n_games = games0 + s_games; }  // a bad append keeps both words as they are
         hdr->dropped_rows = bad ? ~0ULL : dropped0 + (u64)(total_all - s_rows_end);
     }
 }
@@ -2423,6 +2424,8 @@ Offsets carve(const bz_engine_cfg& c) {
     o.n_cnt_slots = (int)((B * 16 + 63) / 64) + 4;  // one slot per wave of the widest (group) launch (<= 16 lanes per game)
     o.cnt_slots = k.take((int64_t)o.n_cnt_slots * CNT_N * 8);
     o.flags = k.take(FLAG_N * 4);
+    // (tests/test_gpu_pack.py finds pack_off as the LAST array of a workspace without the evaluation cache -- the arrays below
+    // are then empty -- and proves that before it writes there: an array carved behind it makes that probe fail, not scribble)
     o.pack_off = k.take(R * B * 4);
     // the table's buckets: a power of two, >= 2 slots per live node (with carry-over two searches' entries are live)
     o.tt_buckets = 16;

@@ -646,8 +646,11 @@ int32_t bz_engine_status(bz_engine* e, void* stream, int32_t* n_active, int64_t*
 /*   own u64, opp u64, pi f32[NA], game id i64, z i8, mover i8, act u8,      */
 /*   ply u8                                                                  */
 /* dropped_rows = rows of finished games that did not fit (0 in a healthy    */
-/* run; ~0 = an append met a block of another geometry); rows [0, n_rows)    */
-/* of every array are valid.                                                 */
+/* run; ~0 = an append met a block of another geometry -- it stays: that     */
+/* append and every later APPEND write no row and keep n_rows, n_games and   */
+/* the ~0, whatever geometry they bring; a pack with append == 0 starts the  */
+/* block afresh, which is how a caller recovers the buffer); rows            */
+/* [0, n_rows) of every array are valid.                                     */
 /* ------------------------------------------------------------------------ */
 #define BZ_PACKED_MAGIC 0x425A50414B000001ULL
 int64_t bz_examples_packed_bytes(int32_t na, int64_t cap_rows);
