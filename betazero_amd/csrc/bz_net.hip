@@ -22,6 +22,7 @@
 //    touch HBM between the stem and the heads; one barrier per layer.
 //  * f32 (parity): per-layer VALU kernels whose every accumulation is the
 //    k-ordered fmaf chain of oracle/bz_oracle.c -> bit-identical to the oracle.
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <new>
@@ -56,6 +57,8 @@ struct bz_net {
     // different streams are ordered through this event (the MFMA paths have no such scratch)
     hipEvent_t f32_done;
     bool f32_used;
+    int adaptive;                    // bz_net_set_adaptive_shape: 0 off, 1 on (default), 2 the latency shape always
+    uint32_t* tally;                 // [kShapes] device counters: device-count tower launches that ran, by shape
     // stamp of the parameter upload the weights came from, unique over all nets of the process: an engine's evaluation
     // cache carries nothing over from a search made with another stamp
     uint64_t epoch;
@@ -122,11 +125,20 @@ typedef Tw<128, 1> TwS128;
 typedef Tw<256, 1> TwS256;
 typedef Tw<128, 4, true> TwM16;  // the benchmark net's throughput shape on v_mfma_f32_16x16x32_bf16 (bz_tower.h)
 constexpr int kSmallBatch = 256;  // one workgroup per position and per CU up to here
+// Device-count launches (the engine: the host knows max_n only, the packed-leaf count sits on the device) pick the shape
+// per launch from that count ("head of a move"): up to kAdaptT1 rows the latency shape, above it the
+// throughput shape.  Both are launched, each with a [lo, hi] window on the count, and the one outside its window exits.
+// kAdaptT1 = the crossover of the two-stream curves in profiles/tower_shape_sweep.jsonl (tools/bench_tower_shapes.py),
+// rounded down to a multiple of the 256 rows the latency shape holds on 256 CUs.
+constexpr int kAdaptT1 = 256;
+enum { kShapeLatency = 0, kShapeMiddle = 1, kShapeThroughput = 2, kShapes = 4 };  // tally slots (Middle: no such tier is built)
 
 struct TowerArgs {
     const u64 *own, *opp;            // [n] bitboards, side-to-move canonical
     const u32* n_dev;                // optional device-side count (<= n): workgroups beyond it exit at once
     int n, n_layers, VH;
+    int lo, hi;                      // the launch runs only when lo <= count <= hi (adaptive shape; 0, INT_MAX otherwise)
+    u32* tally;                      // optional: +1 per launch that ran (one lane of workgroup 0)
     const uint4* wf;                 // tower weight fragments (see bz_net_create)
     const uint4 *wf16, *stem_wf16;   // the same for the 16x16x32 path: [l][t][kq][wt][a][lane], [wt][a][lane]
     const float* bias;               // [n_layers][128]
@@ -423,7 +435,7 @@ struct Carver {
 };
 struct NetOffsets {
     int64_t stem_w, stem_b, conv_w, conv_b, conv_wf, stem_wf, head_wf, conv_wf16, stem_wf16, conv_wf8, head_wf8, dq8, head_dq8, ones, pol_w, pol_b, polfc_wT, polfc_b, val_w, val_b, v1_wT, v1_b, v2_w,
-        v2_b, act_a, act_b, total;
+        v2_b, act_a, act_b, tally, total;
 };
 NetOffsets net_carve(int C, int NB, int VH, int mb) {
     NetOffsets o{};
@@ -443,6 +455,7 @@ NetOffsets net_carve(int C, int NB, int VH, int mb) {
     o.val_w = k.take(C * 4LL); o.val_b = k.take(4); o.v1_wT = k.take(64LL * VH * 4); o.v1_b = k.take(VH * 4LL);
     o.v2_w = k.take(VH * 4LL); o.v2_b = k.take(4);
     o.act_a = k.take(mbp * 64 * C * 4); o.act_b = k.take(mbp * 64 * C * 4);
+    o.tally = k.take(kShapes * 4);
     o.total = k.off;
     return o;
 }
@@ -661,13 +674,17 @@ BZ_EXPORT int32_t bz_net_create(int32_t C, int32_t NB, int32_t VH, int32_t max_b
     n->v1_wT = at<float>(ws, o.v1_wT); n->v1_b = at<float>(ws, o.v1_b);
     n->v2_w = at<float>(ws, o.v2_w); n->v2_b = at<float>(ws, o.v2_b);
     n->act_a = at<float>(ws, o.act_a); n->act_b = at<float>(ws, o.act_b);
+    n->tally = at<uint32_t>(ws, o.tally); n->adaptive = 1;
 
     n->ws_base = ws;
     n->f32_used = false;
     if (hipEventCreateWithFlags(&n->f32_done, hipEventDisableTiming) != hipSuccess) {
         delete n; set_error("bz_net_create: hipEventCreate failed"); return BZ_EHIP;
     }
-    int32_t urc = upload_params(n, p, (hipStream_t)stream);
+    if (hipMemsetAsync(n->tally, 0, kShapes * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
+        (void)hipEventDestroy(n->f32_done); delete n; set_error("bz_net_create: hipMemsetAsync failed"); return BZ_EHIP;
+    }
+    int32_t urc = upload_params(n, p, (hipStream_t)stream);  // (synchronises the stream: the counters are zero from here on)
     if (urc != BZ_OK) { delete n; return urc; }
     {
         hipError_t e3 = hipSuccess;
@@ -774,25 +791,49 @@ static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp,
     T.dq8 = n->dq8; T.head_dq8 = n->head_dq8; T.ones = n->ones;
     T.polfc_wT = n->polfc_wT; T.polfc_b = n->polfc_b; T.v1_wT = n->v1_wT; T.v1_b = n->v1_b; T.v2_w = n->v2_w;
     T.v2_b = n->v2_b; T.logits = logits; T.value = value;
+    T.lo = 0; T.hi = INT_MAX; T.tally = nullptr;
     {
         ProfScope ps(BZ_PROF_TOWER, stream);
         // up to kSmallBatch positions: one (two at C = 64) per workgroup, i.e. per CU -- the latency shape
         const bool small = cnt <= kSmallBatch;
-        // KERNEL = k_tower_bf16, or k_sym_bf16 with the symmetry as its second argument: the same geometries and launch shapes
-#define BZ_TOWER_LAUNCH(KERNEL, GEOM, ...) hipLaunchKernelGGL(KERNEL<GEOM>, dim3((cnt + GEOM::P - 1) / GEOM::P), dim3(256), GEOM::LDS, s, __VA_ARGS__)
+        // a device-side count over a throughput-sized buffer at C = 128: the shape follows the count (kAdaptT1)
+        const bool dev128 = n_dev && !small && n->C == 128 && !fp8;
+        const int mode = dev128 ? n->adaptive : 0;
+        TowerArgs TS = T;  // the latency shape's launch of an adaptive pair: grid and window end at kAdaptT1
+        if (dev128) T.tally = n->tally + kShapeThroughput;
+        if (mode == 1) { TS.n = kAdaptT1 < cnt ? kAdaptT1 : cnt; TS.hi = kAdaptT1; TS.tally = n->tally + kShapeLatency; T.lo = kAdaptT1 + 1; }
+        if (mode == 2) T.tally = n->tally + kShapeLatency;
+        // KERNEL = k_tower_bf16, or k_sym_bf16 with the symmetry after its arguments TA: the same geometries and launch shapes
+#define BZ_TOWER_LAUNCH(KERNEL, GEOM, TA, ...) hipLaunchKernelGGL(KERNEL<GEOM>, dim3((TA.n + GEOM::P - 1) / GEOM::P), dim3(256), GEOM::LDS, s, TA, ##__VA_ARGS__)
 #define BZ_TOWER_PICK(KERNEL, ...) do {                                                                               \
-            if (n->C == 64) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS64, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<64>, __VA_ARGS__); }        \
-            else if (n->C == 256) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS256, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<256>, __VA_ARGS__); } \
-            else { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS128, __VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, TwM16, __VA_ARGS__); }                    \
+            if (n->C == 64) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS64, T, ##__VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<64>, T, ##__VA_ARGS__); }        \
+            else if (n->C == 256) { if (small) BZ_TOWER_LAUNCH(KERNEL, TwS256, T, ##__VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, Tw<256>, T, ##__VA_ARGS__); } \
+            else if (mode == 1) { BZ_TOWER_LAUNCH(KERNEL, TwS128, TS, ##__VA_ARGS__); BZ_TOWER_LAUNCH(KERNEL, TwM16, T, ##__VA_ARGS__); }                    \
+            else { if (small || mode == 2) BZ_TOWER_LAUNCH(KERNEL, TwS128, T, ##__VA_ARGS__); else BZ_TOWER_LAUNCH(KERNEL, TwM16, T, ##__VA_ARGS__); }       \
         } while (0)
         if (fp8 && Y) hipLaunchKernelGGL(f8::k_sym_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T, *Y);
         else if (fp8) hipLaunchKernelGGL(f8::k_tower_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T);
-        else if (Y) BZ_TOWER_PICK(k_sym_bf16, T, *Y);
-        else BZ_TOWER_PICK(k_tower_bf16, T);
+        else if (Y) BZ_TOWER_PICK(k_sym_bf16, *Y);
+        else BZ_TOWER_PICK(k_tower_bf16);
 #undef BZ_TOWER_PICK
 #undef BZ_TOWER_LAUNCH
     }
     BZ_LAUNCH_CHECK("k_tower_bf16");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_net_set_adaptive_shape(bz_net* n, int32_t mode) {
+    BZ_REQUIRE(n && mode >= 0 && mode <= 2, "bz_net_set_adaptive_shape: null net, or mode not 0 (off), 1 (on) or 2 (latency shape always)");
+    n->adaptive = mode;
+    return BZ_OK;
+}
+BZ_EXPORT int32_t bz_net_shape_tally(bz_net* n, int64_t* counts, void* stream) {
+    BZ_REQUIRE(n && counts, "bz_net_shape_tally: null pointer");
+    uint32_t h[kShapes];
+    BZ_HIP(hipMemcpyAsync(h, n->tally, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    BZ_HIP(hipMemsetAsync(n->tally, 0, sizeof(h), (hipStream_t)stream));
+    BZ_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < 3; ++i) counts[i] = h[i];
     return BZ_OK;
 }
 
@@ -822,6 +863,11 @@ BZ_EXPORT int32_t bz_net_forward_bf16(bz_net* n, const uint64_t* own, const uint
 BZ_EXPORT int32_t bz_net_forward_fp8(bz_net* n, const uint64_t* own, const uint64_t* opp, int32_t cnt, float* logits,
                                      float* value, void* stream) {
     return bz_net_forward_dev(n, 2, own, opp, cnt, nullptr, logits, value, stream);
+}
+BZ_EXPORT int32_t bz_net_forward_counted(bz_net* n, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t max_n,
+                                         const uint32_t* n_dev, float* logits, float* value, void* stream) {
+    BZ_REQUIRE(kind >= 0 && kind <= 2 && n_dev, "bz_net_forward_counted: kind must be 0 (f32), 1 (bf16) or 2 (fp8), n_dev non-null");
+    return bz_net_forward_dev(n, kind, own, opp, max_n, n_dev, logits, value, stream);
 }
 
 // ------------------------------------------------------------------ the forward under a board symmetry
@@ -868,6 +914,12 @@ BZ_EXPORT int32_t bz_net_forward_sym(bz_net* n, int32_t kind, const uint64_t* ow
                                      int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits, float* value,
                                      void* stream) {
     return bz_net_forward_sym_dev(n, kind, own, opp, cnt, nullptr, size, mode, arg, scratch, scratch_bytes, logits, value, stream);
+}
+BZ_EXPORT int32_t bz_net_forward_sym_counted(bz_net* n, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t max_n,
+                                             const uint32_t* n_dev, int32_t size, int32_t mode, uint64_t arg, float* logits,
+                                             float* value, void* stream) {
+    BZ_REQUIRE(n_dev && mode != BZ_SYM_MEAN, "bz_net_forward_sym_counted: n_dev non-null, mode FIXED or HASHED");
+    return bz_net_forward_sym_dev(n, kind, own, opp, max_n, n_dev, size, mode, arg, nullptr, 0, logits, value, stream);
 }
 BZ_EXPORT uint32_t bz_sym_index(uint64_t seed, uint64_t own, uint64_t opp) { return bz_sym::index(seed, own, opp); }
 BZ_EXPORT int32_t bz_sym_board(uint64_t b, int32_t size, int32_t s, uint64_t* out) {

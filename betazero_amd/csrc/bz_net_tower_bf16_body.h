@@ -22,7 +22,8 @@ k_tower_bf16(TowerArgs T) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pos0 = blockIdx.x * P;
     if (T.n_dev) T.n = (int)*T.n_dev;
-    if (pos0 >= T.n) return;  // block-uniform, before any barrier
+    if (pos0 >= T.n || T.n < T.lo || T.n > T.hi) return;  // block-uniform, before any barrier
+    if (T.tally && blockIdx.x == 0 && tid == 0) atomicAdd(T.tally, 1u);
     [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0}, tk0 = 0, tk1 = 0, tr0 = 0, tr1 = 0;
     BZ_STAMP(tk0);
 #ifdef BZ_EXP_STAMPS

@@ -176,6 +176,43 @@ class DeviceNet:
                     scratch.record_stream(torch.cuda.current_stream())
         return logits, value
 
+    def forward_counted(self, own, opp, count, logits, value, bf16=True, fp8=False, symmetry=None, size=8, seed=0):
+        """The engine's call: the forward over the first count[0] rows (a uint32-as-int32 CUDA tensor, read on the device
+        when the kernel runs) of own / opp [max_n] into the caller's logits [max_n, 65] / value [max_n]; the rows from
+        count[0] on are not written.  symmetry: None, an int 0..7 or "hash", as in forward().  At 128 channels, bf16 and
+        max_n > 256 the tower's workgroup shape follows the count (set_adaptive_shape)."""
+        from .symmetry import SYM_MEAN, check_forward_symmetry
+        sym = check_forward_symmetry(symmetry, size, seed)
+        if sym is not None and sym[0] == SYM_MEAN:
+            raise ValueError("forward_counted: the mean over the symmetries takes a host-side count (forward)")
+        n, kind = own.numel(), 2 if fp8 else (1 if bf16 else 0)
+        assert opp.numel() == n and logits.shape == (n, 65) and value.shape == (n,) and count.numel() >= 1
+        assert logits.dtype == value.dtype == torch.float32 and logits.is_contiguous() and count.element_size() == 4
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            if sym is None:
+                _lib.check(L.bz_net_forward_counted(self.h, kind, own.data_ptr(), opp.data_ptr(), n, count.data_ptr(),
+                                                    logits.data_ptr(), value.data_ptr(), st))
+            else:
+                _lib.check(L.bz_net_forward_sym_counted(self.h, kind, own.data_ptr(), opp.data_ptr(), n, count.data_ptr(), size,
+                                                        sym[0], sym[1], logits.data_ptr(), value.data_ptr(), st))
+
+    SHAPE_NAMES = ("latency", "middle", "throughput")
+
+    def set_adaptive_shape(self, mode=True):
+        """device-count forwards (an engine's, forward_counted) pick the tower's workgroup shape from the count: True / 1 =
+        on (the default), False / 0 = the throughput shape always, 2 = the latency shape always (measurement).  Results
+        are bit for bit the same in every mode."""
+        _lib.check(_lib.lib().bz_net_set_adaptive_shape(self.h, int(mode)))
+
+    def shape_tally(self):
+        """{shape: device-count tower launches that did work since the last call}; waits for the current stream"""
+        c = (C.c_int64 * 3)()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bz_net_shape_tally(self.h, c, torch.cuda.current_stream().cuda_stream))
+        return dict(zip(self.SHAPE_NAMES, (int(v) for v in c)))
+
     def update(self, params):
         """replace the weights in place (same architecture), e.g. after a training step"""
         params = np.ascontiguousarray(params, dtype=np.float32)

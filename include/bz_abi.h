@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define BZ_ABI_VERSION 7
+#define BZ_ABI_VERSION 7  /* grown since by additions only: the symmetric forwards, the counted forwards + adaptive shape */
 
 enum { BZ_OK = 0, BZ_EINVAL = 1, BZ_EILLEGAL_MOVE = 2, BZ_EHIP = 3, BZ_ENOMEM = 4, BZ_ENOGPU = 5,
        BZ_ESTATE = 6 };
@@ -198,6 +198,23 @@ int32_t bz_net_forward_bf16(bz_net* net, const uint64_t* own, const uint64_t* op
 int32_t bz_net_forward_fp8(bz_net* net, const uint64_t* own, const uint64_t* opp, int32_t n,
                            float* logits, float* value, void* stream);
 
+/* ---- device-side row counts and the adaptive tower shape (an addition to ABI 7) ----
+ * _counted: the forward over the first *n_dev rows (device u32, <= max_n <= max_batch) of buffers of max_n rows -- the
+ * call the engine makes with its packed-leaf count.  Rows >= *n_dev are never written; a count of 0 touches no memory.
+ * At C == 128, bf16 and max_n > 256 the tower's workgroup shape follows the count: the latency shape (one position per
+ * workgroup) up to the threshold, the throughput shape above it; both are launched and the one the count rules out exits
+ * at once.  Every row is bit for bit what either shape gives (they agree by construction of the accumulation order).
+ * bz_net_set_adaptive_shape: 1 = on (the default), 0 = off (the throughput shape whatever the count: what every
+ *   device-count launch did before the shape adapted), 2 = the latency shape whatever the count (measurement: tools/bench_tower_shapes.py).  Takes effect
+ *   for the launches issued after it.  Host-count forwards never adapt.
+ * bz_net_shape_tally: counts[3] = such launches that did work since the last call, by shape {latency, middle (no such
+ *   tier is built: always 0), throughput}, counted on the device by the launch itself (a count of 0 runs no shape);
+ *   reads and clears behind the work queued on `stream` and synchronises it. */
+int32_t bz_net_forward_counted(bz_net* net, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t max_n,
+                               const uint32_t* n_dev, float* logits, float* value, void* stream);
+int32_t bz_net_set_adaptive_shape(bz_net* net, int32_t mode);
+int32_t bz_net_shape_tally(bz_net* net, int64_t* counts /* [3] */, void* stream);
+
 /* ---- the forward under a board symmetry ----
  * Eight elements s = 0..7 on the size x size corner of the 8x8 planes: 0..6 are bz_augment_d4_batch's transforms 0..6
  * (id, flip rows, flip columns, rot90 x1, x2, x3, transpose), 7 is the anti-transpose out[r][c] = x[n-1-c][n-1-r] (which
@@ -224,6 +241,10 @@ int64_t bz_net_sym_scratch_bytes(int64_t n);
 int32_t bz_net_forward_sym(bz_net* net, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t n, int32_t size,
                            int32_t mode, uint64_t arg, void* scratch, int64_t scratch_bytes, float* logits, float* value,
                            void* stream);
+/* the same over the first *n_dev rows (see bz_net_forward_counted); FIXED and HASHED only */
+int32_t bz_net_forward_sym_counted(bz_net* net, int32_t kind, const uint64_t* own, const uint64_t* opp, int32_t max_n,
+                                   const uint32_t* n_dev, int32_t size, int32_t mode, uint64_t arg, float* logits,
+                                   float* value, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* The reference's tic-tac-toe policy MLP, TicTacToeNet                       */
