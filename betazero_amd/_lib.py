@@ -74,6 +74,11 @@ class TrainAdam(C.Structure):         # bz_train_adam
                 ("p", TrainTensors), ("m", TrainTensors), ("v", TrainTensors)]
 
 
+class TrainOptim(C.Structure):        # bz_train_optim
+    _fields_ = [("hyper", vp), ("stats", vp), ("partials", vp), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("decay_biases", i32), ("p", TrainTensors), ("m", TrainTensors), ("v", TrainTensors), ("ema", C.POINTER(TrainTensors))]
+
+
 class MlpAdam(C.Structure):          # bz_mlp_adam (host)
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", i32)]
 
@@ -217,6 +222,9 @@ _SIGS = {
     "bz_train_heads_vt": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
     "bz_train_heads_wgrad": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "bz_train_finish": (i32, [C.POINTER(TrainPartials), C.POINTER(TrainTensors), i32, i32, i32, i32, vp, C.POINTER(TrainAdam), vp]),
+    "bz_train_optim_partials": (i32, []),
+    "bz_train_optim_hyper": (i32, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    "bz_train_optim_step": (i32, [C.POINTER(TrainTensors), C.POINTER(TrainOptim), i32, i32, i32, vp]),
     "bz_profile_enable": (i32, [i32]),
     "bz_profile_reserve": (i32, [i32, i64]),
     "bz_profile_read": (i32, [i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]),

@@ -581,6 +581,110 @@ __global__ __launch_bounds__(256) void k_train_adam(AdamArgs A) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The extended optimiser (bz_train_optim_step): AdamW with decoupled weight decay, a clip of the global gradient norm and an
+// exponential moving average of the parameters, as two launches over the job table and 1024-element blocks of k_train_adam.
+//   k_train_gnorm: sum of g^2 over all 14 gradient tensors.  A FIXED grid of kGnormGroups workgroups; workgroup w takes the
+//     blocks w, w + kGnormGroups, ... in that order, a thread the elements 256 e + tid (e = 0..3) of each as ONE fmaf chain
+//     s = fmaf(g, g, s); then an LDS tree (strides 128, 64, .., 1: red[i] += red[i + stride]) and one float per workgroup
+//     into partials[w] -- written by EVERY workgroup on every launch, 0 where it had no block: nothing is ever zeroed by a
+//     memset and there is no atomic, so the same gradients give the same bits whatever the scheduling.  Workgroup 0 also
+//     advances the step counter, one launch ahead of its reader (the reason above k_train_adam).
+//   k_train_optim: every workgroup sums the partials by the same tree, norm = sqrtf(sum), and updates its 1024 elements (or
+//     none of them: a norm that is not < +inf -- a NaN or an infinity among the gradients, or a square that overflowed --
+//     skips the step as a whole; the counter has advanced all the same, it counts ATTEMPTED steps).
+// hyper (device, 32 bytes): {lr, t, warm-up steps, weight decay, max norm, EMA decay, 0, 0} (bz_train_optim_hyper lays it out).
+// stats (device, 16 bytes): {norm before the clip, scale applied (0: skipped), steps skipped, steps clipped}; the last two
+// accumulate until the caller zeroes them, like the error word of k_train_finish.
+constexpr int kGnormGroups = 256;
+struct OptimJob { float *p, *m, *v, *ema; const float* g; int count, block0, decay; };
+struct OptimArgs {
+    float* hyper;
+    float* stats;
+    float* partials;
+    float beta1, beta2, eps;
+    int n_jobs, n_blocks;
+    OptimJob job[14];
+};
+// red[0] = the sum of red[0..255] in the fixed tree order (all 256 threads call it)
+__device__ __forceinline__ float tree_sum_256(float* red, int tid) {
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+__global__ __launch_bounds__(256) void k_train_gnorm(OptimArgs A) {
+    __shared__ float red[256];
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0 && tid == 0) A.hyper[1] += 1.0f;
+    float s = 0.0f;
+    int j = 0;
+    for (int b = blockIdx.x; b < A.n_blocks; b += kGnormGroups) {
+        while (j + 1 < A.n_jobs && b >= A.job[j + 1].block0) ++j;
+        const float* __restrict__ g = A.job[j].g;
+        const int base = (b - A.job[j].block0) * 1024, count = A.job[j].count;
+        float x[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {                      // (the four loads first: in flight together)
+            const int o = base + 256 * e + tid;
+            x[e] = o < count ? g[o] : 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(x[e], x[e], s);   // (an element past the tensor's end adds +0: s unchanged)
+    }
+    red[tid] = s;
+    const float total = tree_sum_256(red, tid);
+    if (tid == 0) A.partials[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(256) void k_train_optim(OptimArgs A) {
+    __shared__ float red[256];
+    static_assert(kGnormGroups == 256, "one partial per thread");
+    const int tid = threadIdx.x;
+    red[tid] = A.partials[tid];
+    const float norm = sqrtf(tree_sum_256(red, tid));
+    const bool skip = !(norm < INFINITY);
+    const float t = A.hyper[1], warm = A.hyper[2], wd = A.hyper[3], max_norm = A.hyper[4], ema_keep = A.hyper[5];
+    const float scale = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;   // torch.nn.utils.clip_grad_norm_
+    if (blockIdx.x == 0 && tid == 0) {
+        A.stats[0] = norm;
+        A.stats[1] = skip ? 0.0f : scale;
+        if (skip) A.stats[2] += 1.0f;
+        else if (scale < 1.0f) A.stats[3] += 1.0f;
+    }
+    if (skip) return;
+    AdamScalars ad;
+    ad.lr = warm > 0.0f ? A.hyper[0] * fminf(1.0f, t / warm) : A.hyper[0];
+    ad.beta1 = A.beta1; ad.beta2 = A.beta2; ad.eps = A.eps;
+    ad.bc1 = 1.0f - powf(A.beta1, t);
+    ad.bc2_rsqrt = 1.0f / sqrtf(1.0f - powf(A.beta2, t));
+    int j = 0;
+    while (j + 1 < A.n_jobs && (int)blockIdx.x >= A.job[j + 1].block0) ++j;
+    const OptimJob J = A.job[j];
+    const float keep = 1.0f - ad.lr * (J.decay ? wd : 0.0f);   // torch.optim.AdamW: the decoupled decay first (1 exactly without)
+    const float ema_in = 1.0f - ema_keep;
+    const int base = ((int)blockIdx.x - J.block0) * 1024;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int o = base + 256 * e + tid;
+        if (o < J.count) {
+            const float g = J.g[o] * scale;
+            const float mn = fmaf(ad.beta1, J.m[o], (1.0f - ad.beta1) * g);      // adam_update's arithmetic from here on
+            const float vn = fmaf(ad.beta2, J.v[o], (1.0f - ad.beta2) * g * g);
+            J.m[o] = mn;
+            J.v[o] = vn;
+            const float pn = J.p[o] * keep - (ad.lr / ad.bc1) * mn / (sqrtf(vn) * ad.bc2_rsqrt + ad.eps);
+            J.p[o] = pn;
+            if (J.ema) {
+                const float a = J.ema[o];
+                J.ema[o] = fmaf(ema_in, pn - a, a);       // a == pn stays a exactly
+            }
+        }
+    }
+}
+
 bool ends_shape_ok(int C, int n) { return (C == 64 || C == 128) && n >= 4 && n % 4 == 0; }
 int stem_blocks(int n) { const int g = (n + 1) / 2; return g < 512 ? g : 512; }   // k_train_stem_wgrad: 4 half-positions per workgroup pass
 int heads_blocks(int n) { const int g = n / 4; return g < 256 ? g : 256; }
@@ -746,5 +850,56 @@ BZ_EXPORT int32_t bz_train_finish(const bz_train_partials* Q, const bz_train_ten
         hipLaunchKernelGGL(k_train_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
         BZ_LAUNCH_CHECK("k_train_adam");
     }
+    return BZ_OK;
+}
+
+/* floats of the caller-owned partials buffer of bz_train_optim_step: one per workgroup of k_train_gnorm's fixed grid */
+BZ_EXPORT int32_t bz_train_optim_partials(void) { return kGnormGroups; }
+
+/* the 32-byte hyper block of bz_train_optim, laid out (and checked) in HOST memory: the caller copies it to the device */
+BZ_EXPORT int32_t bz_train_optim_hyper(float lr, float steps_done, float warmup_steps, float weight_decay, float max_norm, float ema_decay,
+                                       float* block8) {
+    BZ_REQUIRE(block8, "bz_train_optim_hyper: the block pointer is null");
+    BZ_REQUIRE(lr >= 0.0f && lr < INFINITY && steps_done >= 0.0f && steps_done < INFINITY && warmup_steps >= 0.0f && warmup_steps < INFINITY,
+               "bz_train_optim_hyper: the rate, the step count and the warm-up must be finite and >= 0");
+    BZ_REQUIRE(weight_decay >= 0.0f && weight_decay < INFINITY, "bz_train_optim_hyper: weight_decay must be finite and >= 0");
+    BZ_REQUIRE(max_norm >= 0.0f && max_norm < INFINITY, "bz_train_optim_hyper: max_norm must be finite and >= 0 (0: no clipping)");
+    BZ_REQUIRE(ema_decay >= 0.0f && ema_decay < 1.0f, "bz_train_optim_hyper: ema_decay must lie in [0, 1)");
+    block8[0] = lr; block8[1] = steps_done; block8[2] = warmup_steps; block8[3] = weight_decay;
+    block8[4] = max_norm; block8[5] = ema_decay; block8[6] = 0.0f; block8[7] = 0.0f;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_train_optim_step(const bz_train_tensors* G, const bz_train_optim* opt, int32_t C, int32_t n_layers, int32_t VH, void* stream) {
+    BZ_REQUIRE(G && opt, "bz_train_optim_step: a null argument");
+    BZ_REQUIRE((C == 64 || C == 128) && n_layers >= 2 && n_layers <= 1024 && VH >= 1 && VH <= 64,
+               "bz_train_optim_step: bad shape (C = 64 or 128, 2 <= conv layers <= 1024, value_hidden <= 64)");
+    BZ_REQUIRE(all_set(G), "bz_train_optim_step: a gradient pointer is null");
+    BZ_REQUIRE(opt->hyper && opt->stats && opt->partials && all_set(&opt->p) && all_set(&opt->m) && all_set(&opt->v) && (!opt->ema || all_set(opt->ema)),
+               "bz_train_optim_step: the optimiser block has a null pointer");
+    BZ_REQUIRE(opt->beta1 >= 0.0f && opt->beta1 < 1.0f && opt->beta2 >= 0.0f && opt->beta2 < 1.0f && opt->eps > 0.0f,
+               "bz_train_optim_step: Adam needs 0 <= beta < 1 and eps > 0");
+    if (bz_device_count() <= 0) { set_error("bz_train_optim_step: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    OptimArgs A;
+    A.hyper = opt->hyper; A.stats = opt->stats; A.partials = opt->partials;
+    A.beta1 = opt->beta1; A.beta2 = opt->beta2; A.eps = opt->eps; A.n_jobs = 0;
+    int blocks = 0;
+    typedef bz_train_tensors T;
+    auto job = [&](float* bz_train_tensors::*field, int count, bool weight) {
+        OptimJob& J = A.job[A.n_jobs++];
+        J.p = opt->p.*field; J.m = opt->m.*field; J.v = opt->v.*field; J.ema = opt->ema ? opt->ema->*field : nullptr; J.g = G->*field;
+        J.count = count; J.block0 = blocks; J.decay = (weight || opt->decay_biases) ? 1 : 0;
+        blocks += (count + 1023) / 1024;
+    };
+    // k_train_adam's job order and blocks
+    job(&T::tower_w, n_layers * C * C * 9, true); job(&T::tower_b, n_layers * C, false); job(&T::stem_w, C * 18, true); job(&T::stem_b, C, false);
+    job(&T::pol_w, 2 * C, true); job(&T::pol_b, 2, false); job(&T::polfc_w, 65 * 128, true); job(&T::polfc_b, 65, false);
+    job(&T::val_w, C, true); job(&T::val_b, 1, false); job(&T::v1_w, VH * 64, true); job(&T::v1_b, VH, false);
+    job(&T::v2_w, VH, true); job(&T::v2_b, 1, false);
+    A.n_blocks = blocks;
+    hipLaunchKernelGGL(k_train_gnorm, dim3(kGnormGroups), dim3(256), 0, (hipStream_t)stream, A);
+    BZ_LAUNCH_CHECK("k_train_gnorm");
+    hipLaunchKernelGGL(k_train_optim, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
+    BZ_LAUNCH_CHECK("k_train_optim");
     return BZ_OK;
 }

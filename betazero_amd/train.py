@@ -116,7 +116,15 @@ class GraphedTrainStep:
     The forms of the step that go through torch autograd run eagerly unless capture_autograd=True (see __init__)."""
 
     def __init__(self, module, lr=1e-4, batch=1024, na=65, device="cuda:0", autocast=True, tower_kernels=None, lr_warmup_steps=0,
-                 step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False):
+                 step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False, weight_decay=0.0, clip_norm=0.0,
+                 ema_decay=None, decay_biases=False):
+        # weight_decay / clip_norm / ema_decay / decay_biases: the extended optimiser of the all-kernel step (StepPlan.enable_adam:
+        # AdamW's decoupled decay, a clip of the global gradient norm, non-finite steps skipped, an averaged copy of the weights
+        # for ema_module()).  It exists only as kernels: any other form of the step refuses the options, before a device is touched.
+        self._optim_opts = dict(weight_decay=weight_decay, clip_norm=clip_norm, ema_decay=ema_decay, decay_biases=decay_biases)
+        self.extended = bool(weight_decay) or bool(clip_norm) or ema_decay is not None or bool(decay_biases)
+        if self.extended and (fused_adam is False or step_kernels is False or not getattr(module, "fused_tower", False)):
+            raise ValueError("weight_decay / clip_norm / ema_decay / decay_biases need fused_adam (the all-kernel step)")
         # value_targets (DESIGN.md 3.18): the value loss is against the examples' fp32 `vt` instead of z -- on the all-kernel
         # step through k_train_heads_vt (the graph is captured once with that kernel), on the autograd forms as the MSE target
         self.value_targets = bool(value_targets)
@@ -157,9 +165,11 @@ class GraphedTrainStep:
         if self.fused_adam:
             if self.step_plan is None:
                 raise ValueError("fused_adam needs step_kernels")
-            self.step_plan.enable_adam(self.lr, warmup_steps=self.warmup)
+            self.step_plan.enable_adam(self.lr, warmup_steps=self.warmup, **(self._optim_opts if self.extended else {}))
             self.optimizer = None
         else:
+            if self.extended:
+                raise ValueError("weight_decay / clip_norm / ema_decay / decay_biases need fused_adam (the all-kernel step)")
             self.optimizer = torch.optim.Adam(module.parameters(), lr=self.lr_t, capturable=True, fused=True)
         # capture_autograd: a step that goes through torch autograd (step_kernels=False, or a module without the fused tower) is
         # NOT captured into a HIP graph unless asked for -- it runs eagerly, same arithmetic.  Captured autograd steps returned
@@ -248,6 +258,26 @@ class GraphedTrainStep:
         self.graph.replay()
         self.steps_done += 1
         return self.out[:3].clone()
+
+    def set_lr(self, lr):
+        """change the (peak) learning rate from the next step on; the fused optimiser reads it from device memory, so the
+        captured graph is not recaptured (moments, step count and warm-up stay)"""
+        self.lr = float(lr)
+        if self.fused_adam:
+            self.step_plan.set_lr(self.lr)
+
+    def optim_stats(self, reset=True):
+        """{grad_norm, scale, skipped, clipped} of the extended optimiser (StepPlan.optim_stats; synchronises)"""
+        if not self.extended:
+            raise RuntimeError("GraphedTrainStep: optim_stats() needs weight_decay / clip_norm / ema_decay")
+        return self.step_plan.optim_stats(reset=reset)
+
+    def ema_module(self):
+        """a deep copy of the module holding the EMA weights (ema_decay=...): what refresh_device_net takes in place of the
+        module, and its non-finite check then covers the averaged net"""
+        if not self.extended or self.step_plan.ema is None:
+            raise RuntimeError("GraphedTrainStep: ema_module() needs ema_decay")
+        return self.step_plan.ema_module()
 
     def check(self):
         """raise IndexError if a step since the last check was handed a row index outside the data set (the all-kernel step

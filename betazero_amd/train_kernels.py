@@ -145,6 +145,13 @@ class StepPlan(TowerPlan):
 
     NAMES = ("stem_w", "stem_b", "tower_w", "tower_b", "pol_w", "pol_b", "polfc_w", "polfc_b", "val_w", "val_b", "v1_w", "v1_b", "v2_w", "v2_b")
 
+    @staticmethod
+    def _named(module):
+        return {"stem_w": module.stem.weight, "stem_b": module.stem.bias, "tower_w": module.tower_w, "tower_b": module.tower_b,
+                "pol_w": module.pol.weight, "pol_b": module.pol.bias, "polfc_w": module.polfc.weight, "polfc_b": module.polfc.bias,
+                "val_w": module.val.weight, "val_b": module.val.bias, "v1_w": module.v1.weight, "v1_b": module.v1.bias,
+                "v2_w": module.v2.weight, "v2_b": module.v2.bias}
+
     def __init__(self, module, batch, device="cuda:0", value_targets=False):
         """value_targets: the head kernel reads a float value target per row (set_batch(..., vt=...)) in place
         of z, through k_train_heads_vt; everything else of the step is the same"""
@@ -155,10 +162,7 @@ class StepPlan(TowerPlan):
         super().__init__(module.C, 2 * module.NB, batch, device)
         L, dev = _lib.lib(), self.device
         self.module, self.VH = module, module.VH
-        named = {"stem_w": module.stem.weight, "stem_b": module.stem.bias, "tower_w": module.tower_w, "tower_b": module.tower_b,
-                 "pol_w": module.pol.weight, "pol_b": module.pol.bias, "polfc_w": module.polfc.weight, "polfc_b": module.polfc.bias,
-                 "val_w": module.val.weight, "val_b": module.val.bias, "v1_w": module.v1.weight, "v1_b": module.v1.bias,
-                 "v2_w": module.v2.weight, "v2_b": module.v2.bias}
+        named = self._named(module)
         for k, p in named.items():
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError(f"StepPlan: parameter {k} must be a contiguous fp32 tensor on {dev}")
@@ -181,6 +185,7 @@ class StepPlan(TowerPlan):
         self.vt_slot = torch.zeros(1, dtype=torch.int64, device=dev)
         self._vt_ref = None
         self._adam, self.adam_m, self.adam_v, self.hyper = None, None, None, None
+        self._optim, self.ema, self.stats, self.optim_partials = None, None, None, None   # the extended optimiser (enable_adam)
 
     # ---- the batch
     def set_batch(self, own, opp, pi, z, idx=None, vt=None):
@@ -220,23 +225,59 @@ class StepPlan(TowerPlan):
             self._vt_ref = vt
 
     # ---- the optimiser as the step's tenth launch
-    def enable_adam(self, lr, betas=(0.9, 0.999), eps=1e-8, warmup_steps=0):
+    def enable_adam(self, lr, betas=(0.9, 0.999), eps=1e-8, warmup_steps=0, weight_decay=0.0, clip_norm=0.0, ema_decay=None,
+                    decay_biases=False, extended=None):
         """Adam (torch.optim.Adam's arithmetic, no weight decay / amsgrad: what the reference constructs, train.py:87) applied
         by k_train_adam right behind k_train_finish (one coalesced pass over all 14 tensors).  State: adam_m / adam_v (dicts of tensors like the parameters) and
         the device block `hyper` = {lr, steps done, warm-up steps, 0}: the kernel advances the step count itself and ramps
-        the rate over the first warmup_steps steps (lr * min(1, t / warmup_steps)), so consecutive steps need no host write."""
+        the rate over the first warmup_steps steps (lr * min(1, t / warmup_steps)), so consecutive steps need no host write.
+
+        weight_decay / clip_norm / ema_decay / decay_biases, or extended=True, select the extended optimiser instead
+        (bz_train_optim_step, bz_abi.h: AdamW's decoupled decay -- of the weights, and of the biases only with decay_biases --, a
+        clip of the global gradient norm at clip_norm, a step with a non-finite norm skipped as a whole, and with ema_decay an
+        averaged copy of the parameters in `ema`): two launches behind k_train_finish, eleven in all.  `hyper` is then the
+        32-byte block {lr, steps attempted, warm-up, weight decay, max norm, EMA decay, 0, 0}, `stats` the kernels' 16 bytes
+        (optim_stats()).  With every option off the extended step leaves the bits of the plain one."""
+        if extended is None:
+            extended = bool(weight_decay) or bool(clip_norm) or ema_decay is not None or bool(decay_biases)
+        elif not extended and (weight_decay or clip_norm or ema_decay is not None or decay_biases):
+            raise ValueError("enable_adam: weight_decay / clip_norm / ema_decay / decay_biases need the extended optimiser")
         self.adam_m = {k: torch.zeros_like(p) for k, p in self.params.items()}
         self.adam_v = {k: torch.zeros_like(p) for k, p in self.params.items()}
-        self.hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
         T = _lib.TrainTensors
-        self._adam = _lib.TrainAdam(hyper=self.hyper.data_ptr(), beta1=betas[0], beta2=betas[1], eps=eps,
-                                    p=T(**{k: self.params[k].data_ptr() for k in self.NAMES}),
-                                    m=T(**{k: self.adam_m[k].data_ptr() for k in self.NAMES}),
-                                    v=T(**{k: self.adam_v[k].data_ptr() for k in self.NAMES}))
+        tensors = lambda d: T(**{k: d[k].data_ptr() for k in self.NAMES})  # noqa: E731
+        self._adam, self._optim, self.ema, self.stats, self.optim_partials = None, None, None, None, None
+        if not extended:
+            self.hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self._adam = _lib.TrainAdam(hyper=self.hyper.data_ptr(), beta1=betas[0], beta2=betas[1], eps=eps,
+                                        p=tensors(self.params), m=tensors(self.adam_m), v=tensors(self.adam_v))
+        else:
+            self.weight_decay, self.clip_norm = float(weight_decay), float(clip_norm)
+            self.ema_decay = 0.0 if ema_decay is None else float(ema_decay)
+            self.lr, self.warmup = float(lr), int(warmup_steps)
+            self._hyper_block()   # (refuses a bad value before anything is allocated)
+            self.hyper = torch.zeros(8, dtype=torch.float32, device=self.device)
+            self.stats = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self.optim_partials = torch.zeros(_lib.lib().bz_train_optim_partials(), dtype=torch.float32, device=self.device)
+            if ema_decay is not None:
+                self.ema = {k: p.detach().clone() for k, p in self.params.items()}
+                self._ema_set = tensors(self.ema)
+            self._optim = _lib.TrainOptim(hyper=self.hyper.data_ptr(), stats=self.stats.data_ptr(), partials=self.optim_partials.data_ptr(),
+                                          beta1=betas[0], beta2=betas[1], eps=eps, decay_biases=int(bool(decay_biases)),
+                                          p=tensors(self.params), m=tensors(self.adam_m), v=tensors(self.adam_v),
+                                          ema=ct.pointer(self._ema_set) if self.ema is not None else None)
         self.reset_adam(lr, warmup_steps)
 
+    def _hyper_block(self, steps_done=0):
+        """the extended optimiser's hyper block as a host tensor, laid out and checked by the library"""
+        blk = (ct.c_float * 8)()
+        _lib.check(_lib.lib().bz_train_optim_hyper(self.lr, float(steps_done), float(self.warmup), self.weight_decay, self.clip_norm,
+                                                   self.ema_decay, blk))
+        return torch.tensor(list(blk), dtype=torch.float32)
+
     def reset_adam(self, lr=None, warmup_steps=None, steps_done=0):
-        """zero moments, step count `steps_done`, (new) rate / warm-up"""
+        """zero moments, step count `steps_done`, (new) rate / warm-up; the extended optimiser's EMA becomes a copy of the
+        parameters again and its statistics are zeroed"""
         if lr is not None:
             self.lr = float(lr)
         if warmup_steps is not None:
@@ -245,13 +286,50 @@ class StepPlan(TowerPlan):
             for t in d.values():
                 t.zero_()
         with torch.cuda.device(self.device):
-            self.hyper.copy_(torch.tensor([self.lr, float(steps_done), float(self.warmup), 0.0], dtype=torch.float32))
+            if self._optim is None:
+                self.hyper.copy_(torch.tensor([self.lr, float(steps_done), float(self.warmup), 0.0], dtype=torch.float32))
+                return
+            self.hyper.copy_(self._hyper_block(steps_done))
+            self.stats.zero_()
+            if self.ema is not None:
+                for k, t in self.ema.items():
+                    t.copy_(self.params[k].detach())
 
     def set_lr(self, lr):
         """change the (peak) learning rate; moments and step count stay"""
         self.lr = float(lr)
         with torch.cuda.device(self.device):
             self.hyper[0:1].copy_(torch.tensor([self.lr], dtype=torch.float32))
+
+    def optim_step(self):
+        """the extended optimiser's two launches alone (k_train_gnorm, k_train_optim) on whatever the .grad tensors hold"""
+        if self._optim is None:
+            raise RuntimeError("StepPlan: enable_adam(..., extended=True) (or one of its options) first")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bz_train_optim_step(ct.byref(self._grads), ct.byref(self._optim), self.C, self.L, self.VH, self._stream()))
+
+    def optim_stats(self, reset=True):
+        """{grad_norm, scale, skipped, clipped} of the extended optimiser: the last step's gradient norm before the clip and the
+        scale it applied (0.0: the step was skipped), and how many steps since the last reset were skipped (non-finite norm)
+        / clipped.  One read of the device (synchronises); call it where the losses are looked at."""
+        if self._optim is None:
+            raise RuntimeError("StepPlan: enable_adam(..., extended=True) (or one of its options) first")
+        norm, scale, skipped, clipped = self.stats.tolist()
+        if reset and (skipped or clipped):
+            self.stats[2:4].zero_()
+        return {"grad_norm": norm, "scale": scale, "skipped": int(skipped), "clipped": int(clipped)}
+
+    def ema_module(self):
+        """a deep copy of the module holding the averaged weights (enable_adam(..., ema_decay=...))"""
+        import copy
+        if self.ema is None:
+            raise RuntimeError("StepPlan: enable_adam(..., ema_decay=...) first")
+        m = copy.deepcopy(self.module)
+        with torch.no_grad():
+            for k, p in self._named(m).items():
+                p.copy_(self.ema[k])
+                p.grad = None
+        return m
 
     @property
     def adam_t(self):
@@ -260,11 +338,12 @@ class StepPlan(TowerPlan):
 
     # ---- the launches
     def launch(self, adam=False):
-        """the 9 (adam: 10) launches of one step on the current stream (no host work besides: this is what a HIP graph captures)"""
+        """the 9 (adam: 10, or 11 with the extended optimiser) launches of one step on the current stream (no host work besides:
+        this is what a HIP graph captures)"""
         L, p, n, Cc, Ly = _lib.lib(), self.params, self.n, self.C, self.L
         if self._batch_refs is None:
             raise RuntimeError("StepPlan: set_batch() first")
-        if adam and self._adam is None:
+        if adam and self._adam is None and self._optim is None:
             raise RuntimeError("StepPlan: enable_adam() first")
         for k, t in p.items():   # (an optimiser that swapped a gradient tensor out would leave the kernels writing into a dead one)
             assert t.grad is not None and t.grad.data_ptr() == getattr(self._grads, k), f"the .grad of {k} was replaced"
@@ -291,7 +370,9 @@ class StepPlan(TowerPlan):
             chk(L.bz_train_stem_wgrad(bd, self.acts[0].data_ptr(), self.gs[0].data_ptr(), n, Cc, self.stem_partial.data_ptr(), st))
             chk(L.bz_train_heads_wgrad(self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(), n, self.VH, self.heads_w_partial.data_ptr(), st))
             chk(L.bz_train_finish(ct.byref(self._partials), ct.byref(self._grads), Cc, Ly, self.VH, n, self.losses.data_ptr(),
-                                  ct.byref(self._adam) if adam else None, st))
+                                  ct.byref(self._adam) if adam and self._optim is None else None, st))
+        if adam and self._optim is not None:
+            self.optim_step()
         return self.losses
 
     def bad_rows(self, reset=True):
@@ -319,7 +400,7 @@ class StepPlan(TowerPlan):
         return self.launch(adam=False)
 
     def step(self):
-        """grads() and the Adam update: 10 launches (enable_adam() first)"""
+        """grads() and the Adam update: 10 launches, 11 with the extended optimiser (enable_adam() first)"""
         return self.launch(adam=True)
 
 

@@ -821,6 +821,7 @@ int32_t bz_train_wgrad(const void* acts, const void* gs, int32_t C, int32_t n_la
 /* (10 with the optimiser):                                                   */
 /*   stem_fwd, pack_weights, tower_fwd, heads, tower_bwd, wgrad, stem_wgrad, */
 /*   heads_wgrad, finish (+ the Adam update as a tenth launch).  The net is     */
+/* (bz_train_optim_step, the extended optimiser: two launches in its place.)  */
 /* betazero_amd/net.py's (SURVEY 8(d) "net"): every pointer below is one of   */
 /* its parameter tensors (fp32, torch layout) or the gradient of one.         */
 /* n = batch, a multiple of 4 (and of bz_train_positions_per_workgroup(C)).   */
@@ -890,6 +891,41 @@ int32_t bz_train_heads_wgrad(const float* hv, const float* dl, const float* dv1,
  * opt != NULL: followed by the Adam update of every parameter (a second launch) */
 int32_t bz_train_finish(const bz_train_partials* Q, const bz_train_tensors* G, int32_t C, int32_t n_layers, int32_t VH, int32_t n,
                         float* losses, const bz_train_adam* opt, void* stream);
+/* The extended optimiser: AdamW with decoupled weight decay (torch.optim.AdamW's arithmetic, two parameter groups), a clip of
+ * the GLOBAL gradient norm (torch.nn.utils.clip_grad_norm_'s rule), a refusal of non-finite steps and an exponential moving
+ * average of the parameters.  Called AFTER bz_train_finish(..., opt = NULL, ...) on the gradients G it left: two more launches
+ * (k_train_gnorm, k_train_optim), so the extended step is eleven.  With weight decay 0, max norm 0, no EMA tensors and finite
+ * gradients the update is bit for bit the one of bz_train_finish(..., opt != NULL).
+ *   hyper: 32 bytes of DEVICE memory {lr; steps ATTEMPTED so far t; warm-up steps; weight decay; max norm (0: no clip); EMA
+ *     decay d; 0; 0}, read at launch time (a captured graph follows a host write).  bz_train_optim_hyper lays the block out in
+ *     host memory and refuses (BZ_EINVAL) a negative or non-finite lr / t / warm-up / weight decay / max norm and an EMA decay
+ *     outside [0, 1); the caller copies it to the device.  k_train_gnorm advances t by one, whether or not the update follows.
+ *   norm = sqrtf(sum of g^2 over all 14 tensors), a fixed-order fp32 sum with no atomics and no zeroed buffer;
+ *     partials: bz_train_optim_partials() floats of DEVICE scratch, every one rewritten by every step.
+ *   skip  = !(norm < +inf): a NaN or an infinity anywhere among the gradients, or a square that overflowed (|g| > 1.8e19):
+ *     NOTHING of p, m, v, ema is written by that step (t has advanced all the same).
+ *   scale = max norm > 0 ? fminf(1, max norm / (norm + 1e-6f)) : 1;   g' = g * scale;   lr_t, bc1, bc2_rsqrt as in bz_train_adam
+ *   m' = fmaf(beta1, m, (1 - beta1) g');  v' = fmaf(beta2, v, (1 - beta2) g' g')
+ *   p' = p * (1 - lr_t * wd_j) - (lr_t / bc1) * m' / (sqrtf(v') * bc2_rsqrt + eps)
+ *     wd_j = the weight decay for the seven *_w tensors, and for the seven *_b tensors only with decay_biases != 0 (else 0)
+ *   ema' = fmaf(1 - d, p' - ema, ema)   (only with ema != NULL; the caller starts ema at a copy of p)
+ *   stats: 16 bytes of DEVICE memory {norm of the last step before the clip; scale it applied (0: skipped); steps skipped;
+ *     steps clipped (scale < 1)}: the two counts accumulate until the caller zeroes them, like losses[3]. */
+typedef struct bz_train_optim {
+    float* hyper;
+    float* stats;
+    float* partials;
+    float beta1, beta2, eps;
+    int32_t decay_biases;
+    bz_train_tensors p, m, v;           /* as in bz_train_adam */
+    const bz_train_tensors* ema;        /* the averaged parameters (updated in place), or NULL */
+} bz_train_optim;
+int32_t bz_train_optim_partials(void);
+int32_t bz_train_optim_hyper(float lr, float steps_done, float warmup_steps, float weight_decay, float max_norm, float ema_decay,
+                             float* block8_host);
+/* BZ_EINVAL (with a message) for a null pointer in G / opt (ema alone may be NULL), betas outside [0, 1), eps <= 0, C other than
+ * 64 / 128, n_layers < 2 or VH outside 1..64; BZ_ENOGPU without a device */
+int32_t bz_train_optim_step(const bz_train_tensors* G, const bz_train_optim* opt, int32_t C, int32_t n_layers, int32_t VH, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* In-library kernel timers: HIP events recorded on the launch stream around  */

@@ -103,6 +103,13 @@ def main():
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupled weight decay on the weights (not the biases) of "
+                    "the all-kernel step (GraphedTrainStep.weight_decay)")
+    ap.add_argument("--clip-norm", type=float, default=0.0, help="clip the global gradient norm of every step at this value (0: off)")
+    ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the weights with this decay; the "
+                    "net that is validated, gated and pushed to the engine is then the averaged one")
+    ap.add_argument("--lr-decay", type=float, default=1.0, help="the learning rate is multiplied by this after every iteration "
+                    "(GraphedTrainStep.set_lr: no recapture)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -111,6 +118,9 @@ def main():
     args = ap.parse_args()
     if args.gumbel_interior and not args.gumbel:
         ap.error("--gumbel-interior takes effect only with --gumbel")
+    extended = bool(args.weight_decay or args.clip_norm or args.ema_decay is not None)
+    if (extended or args.lr_decay != 1.0) and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
+        ap.error("--weight-decay / --clip-norm / --ema-decay / --lr-decay need the all-kernel training step")
 
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
@@ -120,7 +130,8 @@ def main():
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
-                                                                  value_targets=use_vt)
+                                                                  value_targets=use_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
+                                                                  ema_decay=args.ema_decay)
     bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
@@ -200,10 +211,20 @@ def main():
         losses = torch.stack(losses).cpu().numpy()  # one transfer per iteration, after the last step
         if graphed is not None:
             graphed.check()                         # an out-of-range row index in any step of the iteration raises here
+        optim = {}
+        if extended:  # a skipped step (non-finite gradient norm) left the weights as they were: reported, not fatal
+            optim = {"optim": {**{k: (round(v, 5) if isinstance(v, float) else v) for k, v in graphed.optim_stats().items()},
+                               "lr": graphed.lr}}
+        bad = ~np.isfinite(losses).all(1)
+        if extended and 0 < int(bad.sum()) <= optim["optim"]["skipped"]:   # the steps the optimiser refused: out of the means
+            losses = losses[~bad] if not bad.all() else losses
         if not np.isfinite(losses).all():
             raise RuntimeError(f"training diverged in iteration {it}: first non-finite loss at step "
                                f"{int(np.argmax(~np.isfinite(losses).all(1)))} of {steps}")
-        refresh_device_net(cand, module)
+        trained = graphed.ema_module() if args.ema_decay is not None else module   # the net that is validated, gated and played
+        refresh_device_net(cand, trained)
+        if args.lr_decay != 1.0:
+            graphed.set_lr(graphed.lr * args.lr_decay)
         t_train = time.time() - t1
         val_after = validate(cand, val)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
         val_mean = {"after_mean_of_8": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in validate(cand, val, symmetry="mean").items()
@@ -217,7 +238,7 @@ def main():
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
             if g["promoted"]:
-                refresh_device_net(dnet, module)
+                refresh_device_net(dnet, trained)
             gate = {"gate": g}
         head, tail = np.mean(losses[: max(1, steps // 10)], axis=0), np.mean(losses[-max(1, steps // 10):], axis=0)
         emit({"what": "iteration", "iter": it, "games": args.games, "plies": plies, "examples": int(len(ex)),
@@ -231,7 +252,7 @@ def main():
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
-              **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}),
+              **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),

@@ -2,7 +2,11 @@
 """Where a training step's time goes: ms per Adam step of the az_loop net (64 channels, 4 blocks,
 batch 1024) with the residual tower on the hand-written HIP kernels (csrc/bz_train.hip) against stock PyTorch-ROCm
 autograd (MIOpen) -- eager / HIP-graph replay, fp32 / bf16 autocast, default / benchmarked MIOpen solvers, NCHW /
-channels-last -- plus the three tower kernels on their own.  python tools/bench_train.py [channels] [blocks] [batch] [--quick | --kernels-only]"""
+channels-last -- plus the three tower kernels on their own.  python tools/bench_train.py [channels] [blocks] [batch] [--quick | --kernels-only]
+
+--optim: only the cost of the extended optimiser: the graphed all-kernel step with the plain Adam launch, with
+the extended optimiser and every option off, with the clip, clip + decay, clip + decay + EMA -- one process, the
+configurations interleaved, medians of --repeats R (default 7) timings of 200 replays each; one JSON line per configuration."""
 import os
 import sys
 import time
@@ -122,6 +126,51 @@ def ends_only():
         print(f"  {name:20s} {e0.elapsed_time(e1) / 50 * 1e3:8.1f} us", flush=True)
 
 
+def optim_mode():
+    import json
+    repeats = next((int(a.split("=")[1]) for a in sys.argv if a.startswith("--repeats=")), 7)
+    configs = [("plain", {}), ("extended, every option off", {"extended": True}), ("clip", {"clip_norm": 1.0}),
+               ("clip + decay", {"clip_norm": 1.0, "weight_decay": 1e-4}),
+               ("clip + decay + EMA", {"clip_norm": 1.0, "weight_decay": 1e-4, "ema_decay": 0.99})]
+    idx = [torch.randint(0, n, (B,), device="cuda:0") for _ in range(8)]
+    steps = {}
+    for name, opts in configs:
+        torch.manual_seed(0)
+        m = PolicyValueNet(C, NB, 64, fused_tower=True).cuda()
+        g = GraphedTrainStep(m, lr=1e-3, batch=B, **{k: v for k, v in opts.items() if k != "extended"})
+        if opts.get("extended"):   # the new launches with nothing for them to do (GraphedTrainStep itself never asks for that)
+            g.step_plan.enable_adam(g.lr, warmup_steps=g.warmup, extended=True)
+            g.extended = True
+        for i in range(30):        # the capture and a warm-up
+            g(ex, idx[i % 8])
+        steps[name] = g
+    torch.cuda.synchronize()
+    K, ms = 200, {name: [] for name in steps}
+    for _ in range(repeats):
+        for name, g in steps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(K):
+                g(ex, idx[i % 8])
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / K)
+    base = float(np.median(ms["plain"]))
+    for name, g in steps.items():
+        t = ms[name]
+        med = float(np.median(t))
+        line = {"what": "train_optim", "channels": C, "blocks": NB, "batch": B, "config": name, "replays_per_repeat": K,
+                "ms_per_step_median": round(med, 5), "ms_per_step_min": round(min(t), 5), "ms_per_step_max": round(max(t), 5),
+                "delta_vs_plain_pct": round(100 * (med - base) / base, 2), "spread_pct": round(100 * (max(t) - min(t)) / med, 2),
+                "repeats_ms": [round(x, 5) for x in t]}
+        if g.extended:
+            line["optim_stats"] = g.optim_stats()
+        print(json.dumps(line), flush=True)
+
+
+if "--optim" in sys.argv:
+    optim_mode()
+    sys.exit(0)
 print(f"net {C} channels x {NB} blocks, batch {B}")
 print("tower kernels alone (csrc/bz_train.hip):")
 tower_only()
