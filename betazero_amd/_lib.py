@@ -87,6 +87,15 @@ class TrainPartials(C.Structure):     # bz_train_partials
     _fields_ = [(n, vp) for n in ("tower", "tower_b", "stem", "heads", "heads_w")] + [("splits", i32)]
 
 
+class TrainOwn(C.Structure):          # bz_train_own: the ownership head of a step
+    _fields_ = [("w", vp), ("b", vp), ("targets", vp), ("weight", C.c_float), ("partial", vp)]
+
+
+class TrainOwnAdam(C.Structure):      # bz_train_own_adam
+    _fields_ = [("hyper", vp), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)] + \
+               [(n, vp) for n in ("pw", "pb", "mw", "mb", "vw", "vb")]
+
+
 _SIGS = {
     "bz_abi_version": (i32, []),
     "bz_last_error": (C.c_char_p, []),
@@ -185,6 +194,10 @@ _SIGS = {
     "bz_root_value": (i32, [vp, vp, i32, vp]),
     "bz_value_targets": (i32, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp]),
     "bz_value_targets_segment": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
+    "bz_engine_ownership_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_ownership": (i32, [vp, vp, i64, vp]),
+    "bz_engine_pack_ownership": (i32, [vp, vp, vp, i64, i32, vp]),
+    "bz_ownership_row": (i32, [u64, u64, i32, vp, vp]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),
@@ -220,6 +233,9 @@ _SIGS = {
     "bz_train_stem_wgrad": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "bz_train_heads": (i32, [vp, vp, i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
     "bz_train_heads_vt": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
+    "bz_train_heads_own": (i32, [vp, vp, C.POINTER(TrainOwn), i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
+    "bz_train_heads_own_vt": (i32, [vp, vp, vp, C.POINTER(TrainOwn), i32, i32, i32, C.POINTER(TrainHeadParams), vp, vp, vp, vp, vp, vp]),
+    "bz_train_own_finish": (i32, [C.POINTER(TrainOwn), i32, i32, vp, vp, vp, vp, C.POINTER(TrainOwnAdam), vp]),
     "bz_train_heads_wgrad": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "bz_train_finish": (i32, [C.POINTER(TrainPartials), C.POINTER(TrainTensors), i32, i32, i32, i32, vp, C.POINTER(TrainAdam), vp]),
     "bz_train_optim_partials": (i32, []),

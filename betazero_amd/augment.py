@@ -54,7 +54,9 @@ def _first_occurrences(key8, own8, opp8, pi8):
 def augment_examples(ex, dedupe=True, device="cuda:0"):
     """Examples / DeviceExamples (n rows) -> the same type (<= 8n rows, row 8*i+t = transform t of row i before dedupe).
     z, mover and game carry over; `act` is permuted with the board; `ply` is kept; `kl` (policy surprise, when present) is the
-    source row's: the eight copies share it, and the dedupe keeps the first occurrence's; `q` and `vt` likewise."""
+    source row's: the eight copies share it, and the dedupe keeps the first occurrence's; `q` and `vt` likewise.
+    `fown` / `fopp` (the ownership target) are boards: they go through the same kernel, so every copy's target is
+    transformed by the symmetry of its position; the dedupe key does not see them and keeps the first occurrence's."""
     _lib.require_gpu()
     host_in = isinstance(ex, Examples)
     if host_in:
@@ -72,9 +74,19 @@ def augment_examples(ex, dedupe=True, device="cuda:0"):
     act8 = torch.empty((8 * n, na), dtype=torch.float32, device=dev)
     scr_a = torch.empty(8 * n, dtype=torch.int64, device=dev)  # two distinct buffers: the kernel's outputs
     scr_b = torch.empty(8 * n, dtype=torch.int64, device=dev)  # are __restrict__
+    has_own = ex.fown is not None and ex.fopp is not None
+    if (ex.fown is None) != (ex.fopp is None):
+        raise ValueError("augment_examples: the examples must carry both fown and fopp (ownership target), or neither")
+    fown8 = fopp8 = None
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
         L = _lib.lib()
+        if has_own:  # (its policy output lands in pi8, which the next call overwrites: the stream orders them)
+            fown, fopp = ex.fown.contiguous(), ex.fopp.contiguous()
+            fown8 = torch.empty(8 * n, dtype=torch.int64, device=dev)
+            fopp8 = torch.empty(8 * n, dtype=torch.int64, device=dev)
+            _lib.check(L.bz_augment_d4_batch(fown.data_ptr(), fopp.data_ptr(), pi.data_ptr(), n, size, na, fown8.data_ptr(),
+                                             fopp8.data_ptr(), pi8.data_ptr(), None, st))
         _lib.check(L.bz_augment_d4_batch(own.data_ptr(), opp.data_ptr(), pi.data_ptr(), n, size, na, own8.data_ptr(),
                                          opp8.data_ptr(), pi8.data_ptr(), key8.data_ptr(), st))
         _lib.check(L.bz_augment_d4_batch(own.data_ptr(), opp.data_ptr(), act1.data_ptr(), n, size, na,
@@ -84,5 +96,6 @@ def augment_examples(ex, dedupe=True, device="cuda:0"):
     out = DeviceExamples(own=own8[keep], opp=opp8[keep], pi=pi8[keep], z=ex.z[src], mover=ex.mover[src],
                          act=act8[keep].argmax(1).to(torch.uint8), game=ex.game[src], ply=ex.ply[src], size=size,
                          kl=None if ex.kl is None else ex.kl[src], q=None if ex.q is None else ex.q[src],
-                         vt=None if ex.vt is None else ex.vt[src])
+                         vt=None if ex.vt is None else ex.vt[src], fown=None if fown8 is None else fown8[keep],
+                         fopp=None if fopp8 is None else fopp8[keep])
     return out.cpu() if host_in else out

@@ -42,6 +42,7 @@
 #include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
+#include "bz_ownership.h"
 
 using namespace bz;
 
@@ -223,6 +224,10 @@ struct FpuSel { float r, r_root, Wr; };
 // the value every node of the current search was expanded with, f32 [B][ncap] indexed like the nodes.  A kernel argument of
 // k_gfull_step only.
 struct GumbelInDev { float* node_v; };
+// Ownership targets (fin_x = nullptr: off), set by bz_engine_set_ownership in the caller's buffer: every finished
+// game's final board in absolute colours, u64 [rounds][B] each, indexed like ex_len, and the scratch the root-policy kernel
+// writes in front of the play kernel (pi [B][NA], act [B]).  A kernel argument of the two ownership kernels only.
+struct OwnDev { u64 *fin_x, *fin_o; float* pi; int32_t* act; };
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -2314,6 +2319,49 @@ __global__ void __launch_bounds__(256) k_pack_q(EngineDev E, ValueDev V, float* 
     for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = V.ex_q[src + t];
 }
 
+// ---- ownership targets: in front of the play kernel, behind k_root_policy / k_forced_root_policy, which left
+// the action the play kernel is about to play in O.act (the same choice by the same functions).  One lane per
+// game applies it to the root, repeats dev_play_tail's terminal test and stores a finished game's final board in absolute
+// colours.  The play kernel's own refusal (a row to record and no room for it) is repeated too: such a game is not finished.
+// (budget: the playout cap's, or null -- a fast search records no row, and finishes its game all the same)
+template <class G>
+__global__ void __launch_bounds__(256) k_own_final(EngineDev E, OwnDev O, const u32* budget) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    const int a = O.act[g];
+    if (a < 0 || a >= G::NA) return;  // (no search has expanded this slot's root)
+    const bool record = !(budget && budget[g] < (u32)E.sims);
+    if (record && E.g_nex[g] >= E.t_max) return;
+    const int round = E.g_round[g];
+    if (round < 0 || round >= E.rounds) return;
+    const Node root = E.nodes[(size_t)g * E.ncap];
+    u64 own, opp;
+    G::apply(root.own, root.opp, a, &own, &opp);
+    const int tm = -(int)E.g_to_move[g];
+    const u64 lg = G::legal(own, opp);
+    int tv;
+    if (!G::terminal(own, opp, tm, lg, &tv)) return;
+    const size_t i = (size_t)round * E.B + g;
+    O.fin_x[i] = tm == 1 ? own : opp;
+    O.fin_o[i] = tm == 1 ? opp : own;
+}
+// the rows' target boards in the packed block's row order (k_pack_q's walk over the pack_off k_pack_scan left): every row of
+// a game gets its game's final board in the row's own side-to-move frame
+__global__ void __launch_bounds__(256) k_pack_own(EngineDev E, OwnDev O, u64* fown, u64* fopp, int64_t cap) {
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= E.rounds * E.B) return;
+    const int off = E.pack_off[i];
+    if (off < 0) return;
+    const int len = E.ex_len[i];
+    const size_t src = (size_t)i * E.t_max;
+    const u64 fx = O.fin_x[i], fo = O.fin_o[i];
+    for (int t = lane; t < len && t < E.t_max && (int64_t)off + t < cap; t += 64) {
+        u64 a, b;
+        ownership_row(fx, fo, (int)E.ex_mover[src + t], &a, &b);
+        fown[(size_t)off + t] = a; fopp[(size_t)off + t] = b;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2340,6 +2388,7 @@ struct bz_engine {
     FpuDev fpu;        // first-play urgency reduction (bz_engine_set_fpu); fpu.root_w = nullptr: off
     int fpu_done;      // ... simulations selected so far in the current search: what an expand-only step has backed up when it is done
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
+    OwnDev own;        // ownership targets (bz_engine_set_ownership); own.fin_x = nullptr: off
     // hashed evaluation symmetry (bz_engine_set_eval_symmetry); on the engine, not on the net: two pipelines
     // and two match players share one bz_net
     int sym_on;
@@ -2486,6 +2535,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->forced = ForcedDev{};
     e->surp = SurpDev{};
     e->value = ValueDev{};
+    e->own = OwnDev{};
     e->fpu = FpuDev{}; e->fpu_done = 0;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
@@ -2613,6 +2663,9 @@ BZ_EXPORT int32_t bz_engine_sum_counters(bz_engine* e, void* stream) {
 BZ_EXPORT int32_t bz_engine_reset_games(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     BZ_DISPATCH(e, k_reset_games, stream, e->dev);
+    if (e->own.fin_x)  //  no game is finished: every final board 0 (fin_x and fin_o are one range)
+        BZ_HIP(hipMemsetAsync(e->own.fin_x, 0, (size_t)(reinterpret_cast<char*>(e->own.pi) - reinterpret_cast<char*>(e->own.fin_x)),
+                              (hipStream_t)stream));
     return BZ_OK;
 }
 
@@ -3156,6 +3209,64 @@ BZ_EXPORT int32_t bz_engine_pack_search_value(bz_engine* e, float* out, int64_t 
     return BZ_OK;
 }
 
+/* ---- ownership targets */
+namespace {
+struct OwnOffsets { int64_t fin_x, fin_o, pi, act, total; };
+OwnOffsets own_carve(const bz_engine_cfg& c) {
+    OwnOffsets o{};
+    Carver k;
+    const int64_t B = c.n_games, na = c.game == BZ_GAME_TTT ? TicTacToe::NA : Reversi::NA;
+    o.fin_x = k.take((int64_t)c.rounds * B * 8);
+    o.fin_o = k.take((int64_t)c.rounds * B * 8);
+    o.pi = k.take(B * na * 4);
+    o.act = k.take(B * 4);
+    o.total = k.off;
+    return o;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_ownership_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_ownership_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_ownership_bytes: %s", kBadCfg); return -1; }
+    return own_carve(*cfg).total;
+}
+
+BZ_EXPORT int32_t bz_engine_set_ownership(bz_engine* e, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_ownership: null engine");
+    if (!buf) {  // off: no extra launch
+        e->own = OwnDev{};
+        return BZ_OK;
+    }
+    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_ownership: the buffer must be 256-byte aligned");
+    const OwnOffsets o = own_carve(e->cfg);
+    if (bytes < o.total) { set_error("bz_engine_set_ownership: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no final board; (act 0 is never read before k_root_policy wrote it)
+    e->own.fin_x = at<u64>(buf, o.fin_x); e->own.fin_o = at<u64>(buf, o.fin_o);
+    e->own.pi = at<float>(buf, o.pi); e->own.act = at<int32_t>(buf, o.act);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uint64_t* fopp_out, int64_t cap_rows, int32_t append_rows,
+                                           void* stream) {
+    BZ_REQUIRE(e && fown_out && fopp_out, "bz_engine_pack_ownership: null pointer");
+    BZ_REQUIRE(e->own.fin_x, "bz_engine_pack_ownership: the final boards are not recorded (bz_engine_set_ownership)");
+    BZ_REQUIRE(cap_rows >= 1 && cap_rows <= (int64_t(1) << 31) - 1 && append_rows >= 0 && append_rows <= cap_rows,
+               "bz_engine_pack_ownership: bad capacity or append_rows");
+    const int n = e->dev.rounds * e->dev.B;
+    hipLaunchKernelGGL(k_pack_own, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->own,
+                       reinterpret_cast<u64*>(fown_out), reinterpret_cast<u64*>(fopp_out), cap_rows);
+    BZ_LAUNCH_CHECK("k_pack_own");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_ownership_row(uint64_t fin_x, uint64_t fin_o, int32_t mover, uint64_t* t_own, uint64_t* t_opp) {
+    BZ_REQUIRE(t_own && t_opp && (mover == 1 || mover == -1), "bz_ownership_row: null pointer or mover not +1 / -1");
+    u64 a, b;
+    ownership_row((u64)fin_x, (u64)fin_o, (int)mover, &a, &b);
+    *t_own = a; *t_opp = b;
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_root_value(const uint32_t* N, const float* W, int32_t n, float* q) {
     BZ_REQUIRE(N && W && q && n >= 1 && n <= 255, "bz_root_value: null pointer or n outside 1 .. 255");
     *q = root_value(n, [N](int i) { return N[i]; }, [W](int i) { return W[i]; });
@@ -3186,6 +3297,11 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         hipLaunchKernelGGL(k_root_q, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->value,
                            e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
         BZ_LAUNCH_CHECK("k_root_q");
+    }
+    if (e->own.fin_x) {  //  the final board of every game this play ends, while the root it plays from is in place
+        int32_t rc = bz_engine_root_policy(e, e->own.pi, e->own.act, stream);
+        if (rc != BZ_OK) return rc;
+        BZ_DISPATCH(e, k_own_final, stream, e->dev, e->own, e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
     }
     {
         ProfScope ps(BZ_PROF_PLAY, stream);

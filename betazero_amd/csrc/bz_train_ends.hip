@@ -216,20 +216,32 @@ struct HeadArgs {
 };
 // the partial vector: [0, 3C) d hw (pol.weight [2][C], then val.weight [C]) | 3: d hb | 65: d polfc.bias | 64: d v1.bias |
 // 64: d v2.weight | 1: d v2.bias | 3: loss, CE, MSE | 1: batch positions whose row index was out of range (the error word)
-template <int C> struct Hd {
+// the ownership head of a step (bz_train_own, bz_abi.h): a kernel argument of the _own kernels only
+struct OwnArgs {
+    const float *w, *b;                            // Conv2d(C, 1, 1): weight [C], bias [1]
+    const unsigned long long* const* targets;      // device slot of two pointers: fown [rows], fopp [rows]
+    float weight;                                  // own_weight
+    float* partial;                                // [gridDim.x][C + 2]: d ow [C] | d ob | L_own
+};
+// (kOwn: a fourth row of hwS, the ownership head's weights; everything else of the layout is shared)
+template <int C, bool kOwn = false> struct Hd {
     static constexpr int XS = C + 8;                         // bf16 per LDS row of x (16 bytes of padding: conflict-free 16-byte reads down a column)
-    static constexpr int WT = 0, V1T = 128 * 65, HWS = V1T + 64 * 65, SHARED = HWS + 3 * C;   // floats
+    static constexpr int WT = 0, V1T = 128 * 65, HWS = V1T + 64 * 65, SHARED = HWS + (kOwn ? 4 : 3) * C;   // floats
     static constexpr int W_X = 0, W_HV = 64 * XS / 2, W_DP = W_HV + 192, W_DL = W_DP + 256, W_DV1 = W_DL + 68, W_FLOATS = W_DV1 + 64;
     static constexpr int LDS = (SHARED + 4 * W_FLOATS) * 4;
     static constexpr int O_HB = 3 * C, O_PFB = O_HB + 3, O_V1B = O_PFB + 65, O_V2W = O_V1B + 64, O_V2B = O_V2W + 64, O_LOSS = O_V2B + 1,
                          NP = O_LOSS + 4;
+    static constexpr int NPO = C + 2;                        // the ownership head's partial vector (kOwn)
 };
 
 // (kVT: the value target of a position is vt[row], an fp32 array whose address is read from the device word *vt_slot at launch
 // time -- bz_train_heads_vt, DESIGN.md 3.18 -- instead of (float)z[row]; nothing else differs between the two kernels)
-template <int C, bool kVT>
-__device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A, const float* const* vt_slot) {
-    typedef Hd<C> H;
+// (kOwn: the ownership head, DESIGN.md 12.2 -- a fourth 1x1 plane o = tanh(ob + sum_c x ow[c]) without a ReLU, trained on the
+// cells of the row's target boards; its d (pre-activation), dp3, rides in the fourth slot of dpS through steps D, E and F, where
+// it is added LAST: with own_weight = 0 everything the other kernels produce keeps its value)
+template <int C, bool kVT, bool kOwn = false>
+__device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A, const float* const* vt_slot, const OwnArgs* __restrict__ O = nullptr) {
+    typedef Hd<C, kOwn> H;
     constexpr int ZC = C / 8, CPL = C / 64;
     extern __shared__ float lds[];
     float* Wt = lds + H::WT;      // [i][a], 65 floats per row: polfc.weight transposed
@@ -271,8 +283,15 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
         for (int u = 0; u < 8; ++u) { const int i = i0 + 256 * u + tid; V1t[(i & 63) * 65 + (i >> 6)] = v[u]; }
     }
     for (int i = tid; i < 3 * C; i += 256) hwS[i] = i < 2 * C ? A.pol_w[i] : A.val_w[i - 2 * C];
+    if constexpr (kOwn)
+        for (int i = tid; i < C; i += 256) hwS[3 * C + i] = O->w[i];
     const bz_train_batch B = *A.batch;
     const float* vt = kVT ? *vt_slot : nullptr;
+    const unsigned long long *fown = nullptr, *fopp = nullptr;
+    float ob = 0.0f, acc_ow[CPL], acc_ob = 0.0f, acc_lown = 0.0f;
+    if constexpr (kOwn) { fown = O->targets[0]; fopp = O->targets[1]; ob = O->b[0]; }
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) acc_ow[q] = 0.0f;
     const float hb[3] = {A.pol_b[0], A.pol_b[1], A.val_b[0]};
     const float pfb = A.polfc_b[lane], pfb64 = A.polfc_b[64], v2b = A.v2_b[0];
     const float v1b = lane < A.VH ? A.v1_b[lane] : 0.0f, v2w = lane < A.VH ? A.v2_w[lane] : 0.0f;
@@ -290,15 +309,17 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
         acc_bad += batch_row_bad(B, pos) ? 1.0f : 0.0f;
         // (the targets are needed in steps B and C: asked for now, they arrive under step A)
         const float pa = B.pi[(size_t)row * 65 + lane], p64 = B.pi[(size_t)row * 65 + 64], zf = kVT ? vt[row] : (float)B.z[row];
+        float tgt = 0.0f;   // (kOwn) the cell's ownership target: bit_cell(fown) - bit_cell(fopp)
+        if constexpr (kOwn) tgt = (float)((int)((fown[row] >> lane) & 1ull) - (int)((fopp[row] >> lane) & 1ull));
         __syncthreads();   // the previous pass's copy-out has read xs; (first pass: the weight tables are in place)
 #pragma unroll
         for (int k = 0; k < ZC; ++k) { const int i = lane + 64 * k; *reinterpret_cast<u32x4*>(xs + (i / ZC) * H::XS + (i % ZC) * 8) = xr[k]; }
         if ((grp + (int)gridDim.x) * 4 < A.n) fetch_x((grp + gridDim.x) * 4 + wv);
         __syncthreads();
         // ---- A: the three 1x1 convolutions, lane = cell
-        float hvv[3];
+        float hvv[3], dp3 = 0.0f;
         {
-            float d0 = hb[0], d1 = hb[1], d2 = hb[2];
+            float d0 = hb[0], d1 = hb[1], d2 = hb[2], d3 = ob;
 #pragma unroll 2
             for (int k = 0; k < ZC; ++k) {
                 const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + lane * H::XS + 8 * k);
@@ -309,9 +330,15 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
                     d0 = fmaf(lo, hwS[c], d0);         d0 = fmaf(hi, hwS[c + 1], d0);
                     d1 = fmaf(lo, hwS[C + c], d1);     d1 = fmaf(hi, hwS[C + c + 1], d1);
                     d2 = fmaf(lo, hwS[2 * C + c], d2); d2 = fmaf(hi, hwS[2 * C + c + 1], d2);
+                    if constexpr (kOwn) { d3 = fmaf(lo, hwS[3 * C + c], d3); d3 = fmaf(hi, hwS[3 * C + c + 1], d3); }
                 }
             }
             hvv[0] = relu(d0); hvv[1] = relu(d1); hvv[2] = relu(d2);
+            if constexpr (kOwn) {   // L_own = mean over positions and all 64 cells of (o - t)^2; no ReLU: dp3 is d3's gradient
+                const float o = tanhf(d3), diff = o - tgt, inv = A.inv_n * (1.0f / 64.0f);
+                dp3 = O->weight * 2.0f * diff * (1.0f - o * o) * inv;
+                acc_lown = fmaf(diff * diff, inv, acc_lown);
+            }
 #pragma unroll
             for (int j = 0; j < 3; ++j) { hvS[64 * j + lane] = hvv[j]; A.hv[(size_t)pos * 192 + 64 * j + lane] = hvv[j]; }
         }
@@ -358,9 +385,10 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
 #pragma unroll 8
             for (int h = 0; h < 64; ++h) a2 = fmaf(dv1S[h], V1t[lane * 65 + h], a2);
             dp[0] = hvv[0] > 0.0f ? a0 : 0.0f; dp[1] = hvv[1] > 0.0f ? a1 : 0.0f; dp[2] = hvv[2] > 0.0f ? a2 : 0.0f;
-            *reinterpret_cast<f32x4*>(dpS + 4 * lane) = (f32x4){dp[0], dp[1], dp[2], 0.0f};
+            *reinterpret_cast<f32x4*>(dpS + 4 * lane) = (f32x4){dp[0], dp[1], dp[2], kOwn ? dp3 : 0.0f};
 #pragma unroll
             for (int j = 0; j < 3; ++j) acc_hb[j] += dp[j];
+            if constexpr (kOwn) acc_ob += dp3;
         }
         __syncthreads();
         // ---- E: d hw[j][c] += sum_cell dp[cell][j] x[cell][c], lane = channel (c = lane + 64 q)
@@ -373,6 +401,7 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
                 acc_hw[0][q] = fmaf(d[0], xv, acc_hw[0][q]);
                 acc_hw[1][q] = fmaf(d[1], xv, acc_hw[1][q]);
                 acc_hw[2][q] = fmaf(d[2], xv, acc_hw[2][q]);
+                if constexpr (kOwn) acc_ow[q] = fmaf(d[3], xv, acc_ow[q]);
             }
         }
         __syncthreads();
@@ -385,8 +414,9 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int c = 8 * k + 2 * e;
-                const float glo = fmaf(dp[0], hwS[c], fmaf(dp[1], hwS[C + c], dp[2] * hwS[2 * C + c]));
-                const float ghi = fmaf(dp[0], hwS[c + 1], fmaf(dp[1], hwS[C + c + 1], dp[2] * hwS[2 * C + c + 1]));
+                float glo = fmaf(dp[0], hwS[c], fmaf(dp[1], hwS[C + c], dp[2] * hwS[2 * C + c]));
+                float ghi = fmaf(dp[0], hwS[c + 1], fmaf(dp[1], hwS[C + c + 1], dp[2] * hwS[2 * C + c + 1]));
+                if constexpr (kOwn) { glo = fmaf(dp3, hwS[3 * C + c], glo); ghi = fmaf(dp3, hwS[3 * C + c + 1], ghi); }
                 o[e] = pack2(bf_pos_lo(xv[e]) ? glo : 0.0f, bf_pos_hi(xv[e]) ? ghi : 0.0f);
             }
             *at = o;
@@ -417,15 +447,31 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
         red[H::O_LOSS] = acc_ce + acc_mse; red[H::O_LOSS + 1] = acc_ce; red[H::O_LOSS + 2] = acc_mse;
         red[H::O_LOSS + 3] = acc_bad;   // (wave-uniform: one position per wave and pass)
     }
+    float* redo = lds + 4 * H::NP;   // (kOwn) the four waves' ownership vectors, behind the others
+    if constexpr (kOwn) {
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) redo[wv * H::NPO + lane + 64 * q] = acc_ow[q];
+        const float sb = wave_sum(acc_ob), sl = wave_sum(acc_lown);
+        if (lane == 0) { redo[wv * H::NPO + C] = sb; redo[wv * H::NPO + C + 1] = sl; }
+    }
     __syncthreads();
     for (int o = tid; o < H::NP; o += 256)
         A.partial[(size_t)blockIdx.x * H::NP + o] = (lds[o] + lds[H::NP + o]) + (lds[2 * H::NP + o] + lds[3 * H::NP + o]);
+    if constexpr (kOwn)
+        for (int o = tid; o < H::NPO; o += 256)
+            O->partial[(size_t)blockIdx.x * H::NPO + o] = (redo[o] + redo[H::NPO + o]) + (redo[2 * H::NPO + o] + redo[3 * H::NPO + o]);
 }
 
 template <int C>
 __global__ __launch_bounds__(256) void k_train_heads(HeadArgs A) { train_heads_body<C, false>(A, nullptr); }
 template <int C>
 __global__ __launch_bounds__(256) void k_train_heads_vt(HeadArgs A, const float* const* vt_slot) { train_heads_body<C, true>(A, vt_slot); }
+template <int C>
+__global__ __launch_bounds__(256) void k_train_heads_own(HeadArgs A, OwnArgs O) { train_heads_body<C, false, true>(A, nullptr, &O); }
+template <int C>
+__global__ __launch_bounds__(256) void k_train_heads_own_vt(HeadArgs A, const float* const* vt_slot, OwnArgs O) {
+    train_heads_body<C, true, true>(A, vt_slot, &O);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the FC weight gradients that reduce over the batch:  d polfc.weight[a][i] = sum_pos dl[pos][a] h[pos][i]  (65 x 128),
@@ -582,6 +628,47 @@ __global__ __launch_bounds__(256) void k_train_adam(AdamArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// the ownership head's own end of the step, one workgroup behind k_train_finish (or the extended optimiser),
+// which has advanced the step counter: thread o < C + 2 sums entry o of the workgroups' ownership partials in strided_sum's fixed
+// order (no atomic, nothing zeroed by a memset) -> d ow [C], d ob, L_own; losses[0] += own_weight * L_own (k_train_finish stored
+// CE + MSE there in this step); then plain Adam (adam_update) on the head's C + 1 parameters with the rate, warm-up and t of the
+// step's hyper block -- unless one of the C + 1 gradients is not finite: the parameters and moments then stay as they are.
+struct OwnFinishArgs {
+    const float* partial;
+    int parts, C;
+    float weight;
+    float *grad_w, *grad_b, *own_loss, *losses;
+    const float* hyper;            // null: no update
+    float beta1, beta2, eps;
+    float *pw, *pb, *mw, *mb, *vw, *vb;
+};
+__global__ __launch_bounds__(256) void k_train_own_finish(OwnFinishArgs F) {
+    __shared__ int bad;
+    const int o = threadIdx.x, C = F.C;
+    if (o == 0) bad = 0;
+    __syncthreads();
+    float g = 0.0f;
+    if (o < C + 2) g = strided_sum(F.partial + o, F.parts, (size_t)(C + 2));
+    if (o < C) F.grad_w[o] = g;
+    else if (o == C) F.grad_b[0] = g;
+    else if (o == C + 1) {
+        F.own_loss[0] = g;
+        if (F.losses) F.losses[0] += F.weight * g;
+    }
+    if (o < C + 1 && !(fabsf(g) < INFINITY)) bad = 1;   // (every writer writes the same value)
+    __syncthreads();
+    if (!F.hyper || bad || o >= C + 1) return;
+    const float t = F.hyper[1], warm = F.hyper[2];
+    AdamScalars ad;
+    ad.lr = warm > 0.0f ? F.hyper[0] * fminf(1.0f, t / warm) : F.hyper[0];
+    ad.beta1 = F.beta1; ad.beta2 = F.beta2; ad.eps = F.eps;
+    ad.bc1 = 1.0f - powf(F.beta1, t);
+    ad.bc2_rsqrt = 1.0f / sqrtf(1.0f - powf(F.beta2, t));
+    if (o < C) adam_update(g, F.pw, F.mw, F.vw, (size_t)o, ad);
+    else adam_update(g, F.pb, F.mb, F.vb, 0, ad);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // The extended optimiser (bz_train_optim_step): AdamW with decoupled weight decay, a clip of the global gradient norm and an
 // exponential moving average of the parameters, as two launches over the job table and 1024-element blocks of k_train_adam.
 //   k_train_gnorm: sum of g^2 over all 14 gradient tensors.  A FIXED grid of kGnormGroups workgroups; workgroup w takes the
@@ -725,12 +812,17 @@ BZ_EXPORT int32_t bz_train_stem_wgrad(const bz_train_batch* batch_dev, const voi
 
 namespace {
 // bz_train_heads (vt_slot == nullptr, `who` names the entry point in messages) and bz_train_heads_vt
+// (own != nullptr: bz_train_heads_own / bz_train_heads_own_vt, the kernels with the ownership head)
 int32_t launch_heads(const char* who, const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot, bool with_vt,
                      int32_t n, int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
-                     float* partial, void* stream) {
+                     float* partial, void* stream, const bz_train_own* own = nullptr, bool with_own = false) {
     if (!(act_top && batch_dev && (vt_slot || !with_vt) && P && g_top && hv && dl && dv1 && partial && ends_shape_ok(C, n) && VH >= 1 && VH <= 64)) {
         set_error("%s: bad arguments (C = 64 or 128, n a multiple of 4, value_hidden <= 64)", who);
         return BZ_EINVAL;
+    }
+    if (with_own) {
+        if (!(own && own->w && own->b && own->targets && own->partial)) { set_error("%s: the ownership block is null or has a null pointer", who); return BZ_EINVAL; }
+        if (!(own->weight >= 0.0f && own->weight < INFINITY)) { set_error("%s: own_weight must be finite and >= 0", who); return BZ_EINVAL; }
     }
     if (!(P->pol_w && P->pol_b && P->polfc_w && P->polfc_b && P->val_w && P->val_b && P->v1_w && P->v1_b && P->v2_w && P->v2_b)) {
         set_error("%s: a head parameter pointer is null", who);
@@ -744,6 +836,31 @@ int32_t launch_heads(const char* who, const void* act_top, const bz_train_batch*
     A.g_top = static_cast<__bf16*>(g_top); A.hv = hv; A.dl = dl; A.dv1 = dv1; A.partial = partial;
     const dim3 grid(heads_blocks(n));
     hipStream_t s = (hipStream_t)stream;
+    if (with_own) {
+        constexpr int kLdsOwn64 = Hd<64, true>::LDS, kLdsOwn128 = Hd<128, true>::LDS;   // (a comma inside a macro argument splits it)
+        OwnArgs O;
+        O.w = own->w; O.b = own->b; O.targets = reinterpret_cast<const unsigned long long* const*>(own->targets); O.weight = own->weight;
+        O.partial = own->partial;
+        if (!with_vt && C == 64) {
+            static unsigned done = 0;
+            if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_own<64>), kLdsOwn64, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_own)");
+            hipLaunchKernelGGL(k_train_heads_own<64>, grid, dim3(256), kLdsOwn64, s, A, O);
+        } else if (!with_vt) {
+            static unsigned done = 0;
+            if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_own<128>), kLdsOwn128, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_own)");
+            hipLaunchKernelGGL(k_train_heads_own<128>, grid, dim3(256), kLdsOwn128, s, A, O);
+        } else if (C == 64) {
+            static unsigned done = 0;
+            if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_own_vt<64>), kLdsOwn64, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_own_vt)");
+            hipLaunchKernelGGL(k_train_heads_own_vt<64>, grid, dim3(256), kLdsOwn64, s, A, vt_slot, O);
+        } else {
+            static unsigned done = 0;
+            if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads_own_vt<128>), kLdsOwn128, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads_own_vt)");
+            hipLaunchKernelGGL(k_train_heads_own_vt<128>, grid, dim3(256), kLdsOwn128, s, A, vt_slot, O);
+        }
+        BZ_LAUNCH_CHECK(with_vt ? "k_train_heads_own_vt" : "k_train_heads_own");
+        return BZ_OK;
+    }
     if (!with_vt && C == 64) {
         static unsigned done = 0;
         if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_train_heads<64>), Hd<64>::LDS, &done); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_train_heads)");
@@ -775,6 +892,40 @@ BZ_EXPORT int32_t bz_train_heads_vt(const void* act_top, const bz_train_batch* b
                                     int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
                                     float* partial, void* stream) {
     return launch_heads("bz_train_heads_vt", act_top, batch_dev, vt_slot_dev, true, n, C, VH, P, g_top, hv, dl, dv1, partial, stream);
+}
+
+BZ_EXPORT int32_t bz_train_heads_own(const void* act_top, const bz_train_batch* batch_dev, const bz_train_own* own, int32_t n, int32_t C,
+                                     int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1, float* partial,
+                                     void* stream) {
+    return launch_heads("bz_train_heads_own", act_top, batch_dev, nullptr, false, n, C, VH, P, g_top, hv, dl, dv1, partial, stream, own, true);
+}
+
+BZ_EXPORT int32_t bz_train_heads_own_vt(const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot_dev,
+                                        const bz_train_own* own, int32_t n, int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top,
+                                        float* hv, float* dl, float* dv1, float* partial, void* stream) {
+    return launch_heads("bz_train_heads_own_vt", act_top, batch_dev, vt_slot_dev, true, n, C, VH, P, g_top, hv, dl, dv1, partial, stream, own, true);
+}
+
+BZ_EXPORT int32_t bz_train_own_finish(const bz_train_own* own, int32_t C, int32_t n, float* grad_w, float* grad_b, float* own_loss, float* losses,
+                                      const bz_train_own_adam* opt, void* stream) {
+    BZ_REQUIRE(own && own->partial && grad_w && grad_b && own_loss && ends_shape_ok(C, n), "bz_train_own_finish: bad arguments");
+    BZ_REQUIRE(own->weight >= 0.0f && own->weight < INFINITY, "bz_train_own_finish: own_weight must be finite and >= 0");
+    if (opt) {
+        BZ_REQUIRE(opt->hyper && opt->pw && opt->pb && opt->mw && opt->mb && opt->vw && opt->vb, "bz_train_own_finish: the optimiser block has a null pointer");
+        BZ_REQUIRE(opt->beta1 >= 0.0f && opt->beta1 < 1.0f && opt->beta2 >= 0.0f && opt->beta2 < 1.0f && opt->eps > 0.0f,
+                   "bz_train_own_finish: Adam needs 0 <= beta < 1 and eps > 0");
+    }
+    if (bz_device_count() <= 0) { set_error("bz_train_own_finish: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    OwnFinishArgs F{};
+    F.partial = own->partial; F.parts = heads_blocks(n); F.C = C; F.weight = own->weight;
+    F.grad_w = grad_w; F.grad_b = grad_b; F.own_loss = own_loss; F.losses = losses;
+    if (opt) {
+        F.hyper = opt->hyper; F.beta1 = opt->beta1; F.beta2 = opt->beta2; F.eps = opt->eps;
+        F.pw = opt->pw; F.pb = opt->pb; F.mw = opt->mw; F.mb = opt->mb; F.vw = opt->vw; F.vb = opt->vb;
+    }
+    hipLaunchKernelGGL(k_train_own_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, F);
+    BZ_LAUNCH_CHECK("k_train_own_finish");
+    return BZ_OK;
 }
 
 BZ_EXPORT int32_t bz_train_heads_wgrad(const float* hv, const float* dl, const float* dv1, int32_t n, int32_t VH, float* partial, void* stream) {

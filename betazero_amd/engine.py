@@ -47,6 +47,10 @@ class Examples:
     kl: np.ndarray = None  # policy surprise: KL(pi || raw prior) per row, f32 [n]; None = not recorded
     q: np.ndarray = None   # search value: the root's sum W / sum N for the mover, f32 [n]; None = not recorded
     vt: np.ndarray = None  # value target (betazero_amd.value_targets), f32 [n]; None = train on z
+    # ownership target: the final board of the row's game in the row's side-to-move frame, uint64 [n] each --
+    # cell i is worth bit_i(fown) - bit_i(fopp); None = not recorded
+    fown: np.ndarray = None
+    fopp: np.ndarray = None
 
     def __len__(self):
         return self.own.shape[0]
@@ -78,6 +82,8 @@ class DeviceExamples:
     kl: torch.Tensor = None  # policy surprise: f32 [n], or None = not recorded
     q: torch.Tensor = None   # search value: f32 [n], or None = not recorded
     vt: torch.Tensor = None  # value target: f32 [n], or None = train on z
+    fown: torch.Tensor = None  # ownership target: int64 [n] holding the uint64 bit patterns, or None = not recorded
+    fopp: torch.Tensor = None
 
     def __len__(self):
         return int(self.own.shape[0])
@@ -88,7 +94,9 @@ class DeviceExamples:
         return Examples(own=n(self.own).view(np.uint64), opp=n(self.opp).view(np.uint64), pi=n(self.pi), z=n(self.z),
                         mover=n(self.mover), act=n(self.act), game=n(self.game), ply=n(self.ply).astype(np.int32), size=self.size,
                         kl=None if self.kl is None else n(self.kl), q=None if self.q is None else n(self.q),
-                        vt=None if self.vt is None else n(self.vt))
+                        vt=None if self.vt is None else n(self.vt),
+                        fown=None if self.fown is None else n(self.fown).view(np.uint64),
+                        fopp=None if self.fopp is None else n(self.fopp).view(np.uint64))
 
     @staticmethod
     def from_host(ex, device="cuda:0"):
@@ -98,7 +106,9 @@ class DeviceExamples:
                               game=t(np.asarray(ex.game, np.int64)), ply=t(np.asarray(ex.ply, np.int32)), size=ex.size,
                               kl=None if ex.kl is None else t(np.asarray(ex.kl, np.float32)),
                               q=None if ex.q is None else t(np.asarray(ex.q, np.float32)),
-                              vt=None if ex.vt is None else t(np.asarray(ex.vt, np.float32)))
+                              vt=None if ex.vt is None else t(np.asarray(ex.vt, np.float32)),
+                              fown=None if ex.fown is None else t(np.asarray(ex.fown, np.uint64).view(np.int64)),
+                              fopp=None if ex.fopp is None else t(np.asarray(ex.fopp, np.uint64).view(np.int64)))
 
     def states(self):
         """canonical boards [n, size, size] int8 on the device: +1 = side to move, -1 = opponent"""
@@ -110,7 +120,8 @@ class DeviceExamples:
         return a - b
 
 
-_OPTIONAL_FIELDS = (("kl", "policy surprise"), ("q", "search value"), ("vt", "value target"))
+_OPTIONAL_FIELDS = (("kl", "policy surprise"), ("q", "search value"), ("vt", "value target"), ("fown", "ownership target"),
+                    ("fopp", "ownership target"))
 
 
 def _all_or_none(parts, field, what):
@@ -321,12 +332,19 @@ def check_search_value(search_value):
     return bool(search_value)
 
 
+def check_ownership(ownership):
+    """ownership targets: a bool, anything else is refused (ValueError, before any device is touched)"""
+    if not isinstance(ownership, (bool, np.bool_)):
+        raise ValueError(f"ownership must be a bool (got {ownership!r})")
+    return bool(ownership)
+
+
 class SelfPlayEngine:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, c_puct=1.5, temp_moves=0, openings=0,
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None):
+                 eval_symmetry=None, fpu=None, ownership=False):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -379,7 +397,13 @@ class SelfPlayEngine:
         Fpu(reduction, root_reduction) = first-play urgency reduction at every level of every walk.  root_stats(), pi, the
         move choice and the rows follow the usual rules on the tree this search builds.  Combines with Dirichlet noise,
         playout_cap, forced_playouts, surprise, search_value, eval_symmetry, every evaluator and eval_cache mode; set_fpu()
-        changes it between searches.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel."""
+        changes it between searches.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel.
+
+        ownership: False = off (the default, unchanged); True = the final board of every finished game is kept
+        (ownership_rows()), and examples() / device_examples() carry every row's ownership target `fown`, `fopp`: that board in
+        the row's side-to-move frame.  Searches, moves and rows are what they are without it; it combines with everything the
+        engine accepts."""
+        self.ownership = check_ownership(ownership)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
@@ -469,6 +493,13 @@ class SelfPlayEngine:
             self.vws = torch.zeros(vbytes + 256, dtype=torch.uint8, device=self.device)
             self._vpad = (-self.vws.data_ptr()) & 255
             self._call(L.bz_engine_set_search_value, self.vws.data_ptr() + self._vpad, vbytes)
+        if self.ownership:  # the engine's final-board buffer (caller-owned, like the workspace)
+            obytes = L.bz_engine_ownership_bytes(C.byref(self.cfg))
+            if obytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.ows = torch.zeros(obytes + 256, dtype=torch.uint8, device=self.device)
+            self._opad = (-self.ows.data_ptr()) & 255
+            self._call(L.bz_engine_set_ownership, self.ows.data_ptr() + self._opad, obytes)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -729,6 +760,35 @@ class SelfPlayEngine:
         self.pack_examples(cap_rows=cap)
         return self.pack_search_value(cap_rows=cap)[:n_rows]
 
+    def ownership_rows(self):
+        """ownership targets: the finished games' final boards in absolute colours, (fin_x, fin_o), int64
+        [rounds, B] views of the ownership buffer holding the uint64 bit patterns, indexed like example_tensors()["len"] (valid
+        where len >= 0, 0 elsewhere)"""
+        if not self.ownership:
+            raise RuntimeError("ownership_rows(): the engine was built without ownership=True")
+        n = self.rounds * self.B * 8
+        step = (n + 255) & ~255  # fin_x and fin_o are the buffer's first two arrays
+        return tuple(self.ows[self._opad + k * step:self._opad + k * step + n].view(torch.int64).view(self.rounds, self.B)
+                     for k in (0, 1))
+
+    def pack_ownership(self, out=None, cap_rows=None, append=False):
+        """the finished games' rows' ownership targets in the row order of the packed block the preceding pack_examples() (same
+        cap_rows, same stream) filled: (fown, fopp), int64 [cap_rows] on the device, rows [0, n_rows) valid"""
+        cap = int(cap_rows or self.rounds * self.B * self.t_max)
+        if out is None:
+            assert not append
+            out = (torch.zeros(cap, dtype=torch.int64, device=self.device), torch.zeros(cap, dtype=torch.int64, device=self.device))
+        self._call(_lib.lib().bz_engine_pack_ownership, out[0].data_ptr(), out[1].data_ptr(), cap, int(append))
+        return out
+
+    def _packed_own(self, n_rows):
+        """the ownership targets of the finished games' rows in (round, slot, ply) order -- the order of examples() and
+        device_examples()"""
+        cap = self.rounds * self.B * self.t_max
+        self.pack_examples(cap_rows=cap)
+        fown, fopp = self.pack_ownership(cap_rows=cap)
+        return fown[:n_rows], fopp[:n_rows]
+
     def examples(self):
         """finished games' rows, compacted on the device; only the valid rows cross PCIe"""
         ex = unpack_example_block(self.example_block())
@@ -736,6 +796,8 @@ class SelfPlayEngine:
             ex.kl = self._packed_kl(len(ex)).cpu().numpy()
         if self.search_value:
             ex.q = self._packed_q(len(ex)).cpu().numpy()
+        if self.ownership:
+            ex.fown, ex.fopp = (_u64(t) for t in self._packed_own(len(ex)))
         return ex
 
     def block_geometry(self):
@@ -754,6 +816,8 @@ class SelfPlayEngine:
             ex.kl = self._packed_kl(len(ex))
         if self.search_value:
             ex.q = self._packed_q(len(ex))
+        if self.ownership:
+            ex.fown, ex.fopp = self._packed_own(len(ex))
         return ex
 
     def winners(self):
@@ -1031,8 +1095,10 @@ class PipelinedSelfPlay:
 
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
-                 forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, **engine_kwargs):
+                 forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False,
+                 **engine_kwargs):
         assert 1 <= pipelines <= n_games
+        check_ownership(ownership)
         # every pipeline gets the same seed, so the same position has the same orientation in all of them
         eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
         check_search_value(search_value)
@@ -1053,9 +1119,10 @@ class PipelinedSelfPlay:
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
                                        playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                                       search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, **engine_kwargs)
+                                       search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership,
+                                       **engine_kwargs)
                         for i in range(pipelines)]
-        self.surprise, self.search_value = bool(surprise), bool(search_value)
+        self.surprise, self.search_value, self.ownership = bool(surprise), bool(search_value), bool(ownership)
         e0 = self.engines[0]
         self.B, self.sims, self.na, self.t_max, self.rounds, self.size, self.game = n_games, sims, e0.na, e0.t_max, e0.rounds, e0.size, e0.game
 
@@ -1153,14 +1220,16 @@ class PipelinedSelfPlay:
         return out
 
     def _pack_with_extras(self, out=None, cap_rows=None):
-        """pack_examples() plus the per-row arrays the engines record next to the block: (block, kl or None, q or None), each
-        array a float32 [cap_rows] device tensor in the block's row order.  Each engine's arrays are packed right behind its
-        rows, while the row offsets its pack left are current."""
+        """pack_examples() plus the per-row arrays the engines record next to the block: (block, kl or None, q or None, (fown,
+        fopp) or None), kl and q float32 [cap_rows] device tensors in the block's row order, the ownership targets (DESIGN.md
+        3.22) int64 [cap_rows].  Each engine's arrays are packed right behind its rows, while the row offsets its pack left are
+        current."""
         cap = int(cap_rows or self.packed_capacity())
         if out is None:
             out = alloc_packed_block(self.na, cap, self.device)
         kl = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.surprise else None
         q = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.search_value else None
+        own = tuple(torch.zeros(cap, dtype=torch.int64, device=self.device) for _ in range(2)) if self.ownership else None
         self.join()
         for i, e in enumerate(self.engines):
             e.pack_examples(out, cap, append=i > 0)
@@ -1168,7 +1237,17 @@ class PipelinedSelfPlay:
                 e.pack_surprise(kl, cap, append=i > 0)
             if q is not None:
                 e.pack_search_value(q, cap, append=i > 0)
-        return out, kl, q
+            if own is not None:
+                e.pack_ownership(own, cap, append=i > 0)
+        return out, kl, q, own
+
+    def pack_examples_with_ownership(self, out=None, cap_rows=None):
+        """pack_examples() plus the rows' ownership targets (ownership=True): (block, fown, fopp), int64 [cap_rows] device
+        tensors in the block's row order"""
+        if not self.ownership:
+            raise RuntimeError("pack_examples_with_ownership(): built without ownership=True")
+        blk, _, _, own = self._pack_with_extras(out, cap_rows)
+        return blk, own[0], own[1]
 
     def pack_examples_with_surprise(self, out=None, cap_rows=None):
         """pack_examples() plus the rows' kl (surprise=True): (block, float32 [cap_rows] device tensor in the block's row
@@ -1182,22 +1261,35 @@ class PipelinedSelfPlay:
         order)"""
         if not self.search_value:
             raise RuntimeError("pack_examples_with_search_value(): built without search_value=True")
-        blk, _, q = self._pack_with_extras(out, cap_rows)
+        blk, _, q, _ = self._pack_with_extras(out, cap_rows)
         return blk, q
 
     def device_examples(self):
-        blk, kl, q = self._pack_with_extras()
+        blk, kl, q, own = self._pack_with_extras()
         ex = unpack_packed_block_device(blk)
         ex.kl = None if kl is None else kl[:len(ex)]
         ex.q = None if q is None else q[:len(ex)]
+        if own is not None:
+            ex.fown, ex.fopp = own[0][:len(ex)], own[1][:len(ex)]
         return ex
 
     def examples(self):
-        blk, kl, q = self._pack_with_extras()
+        blk, kl, q, own = self._pack_with_extras()
         ex = unpack_packed_block(blk)
         ex.kl = None if kl is None else kl[:len(ex)].cpu().numpy()
         ex.q = None if q is None else q[:len(ex)].cpu().numpy()
+        if own is not None:
+            ex.fown, ex.fopp = _u64(own[0][:len(ex)]), _u64(own[1][:len(ex)])
         return ex
+
+    def ownership_rows(self):
+        """the final boards of all pipelines, slots in pipeline order: (fin_x, fin_o), int64 [rounds, B] device tensors
+        (SelfPlayEngine.ownership_rows)"""
+        if not self.ownership:
+            raise RuntimeError("ownership_rows(): built without ownership=True")
+        self.join()
+        r = [e.ownership_rows() for e in self.engines]
+        return torch.cat([a for a, _ in r], dim=1), torch.cat([b for _, b in r], dim=1)
 
     def winners(self):
         self.join()
@@ -1214,7 +1306,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False, search_value=False, eval_symmetry=None, fpu=None):
+              surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1225,7 +1317,9 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     then the pruned policy target.  surprise: SelfPlayEngine -- the Examples then carry `kl`.
     search_value: SelfPlayEngine -- the Examples then carry `q`.  eval_symmetry: SelfPlayEngine (DESIGN.md
     3.19) -- every leaf is evaluated under a hashed board symmetry (True: seeded by `seed`).  fpu: SelfPlayEngine (DESIGN.md
-    3.20) -- first-play urgency reduction in the select rule."""
+    3.20) -- first-play urgency reduction in the select rule.  ownership: SelfPlayEngine -- the Examples then
+    carry `fown`, `fopp`."""
+    check_ownership(ownership)
     check_search_value(search_value)
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
@@ -1243,7 +1337,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
                            gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu)
+                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

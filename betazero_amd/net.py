@@ -17,6 +17,20 @@ from . import _lib
 _NBHD = {}  # device -> gather table of the stem's 3x3 neighbourhoods (PolicyValueNet._forward_kernels)
 
 
+class OwnershipHead(nn.Module):
+    """The ownership head (KataGo, Wu 2019, section 5): Conv2d(C, 1, 1) on the trunk's output, tanh -- per cell,
+    who owns it when the game ends, +1 = the side to move.  A module of its own next to PolicyValueNet: an auxiliary training
+    target that only shapes the trunk.  Its C + 1 parameters are in no flat_params(), no bz_net and no state_dict of the net."""
+
+    def __init__(self, channels=128):
+        super().__init__()
+        self.C = channels
+        self.conv = nn.Conv2d(channels, 1, 1)
+
+    def forward(self, x):  # the trunk's output [B, C, 8, 8] -> ownership [B, 64] in (-1, 1), cell = 8 * row + col
+        return torch.tanh(self.conv(x)).flatten(1)
+
+
 class PolicyValueNet(nn.Module):
     """fused_tower=True keeps the 2 x blocks conv3x3 layers of the residual tower as TWO stacked parameters (tower_w
     [L, C, C, 3, 3], tower_b [L, C]; same initial values, same flat_params() order as the per-layer modules) -- the form
@@ -40,8 +54,10 @@ class PolicyValueNet(nn.Module):
         self.v1 = nn.Linear(64, value_hidden)
         self.v2 = nn.Linear(value_hidden, 1)
 
-    def forward(self, planes, plan=None):  # [B,2,8,8] float (own, opp) -> logits [B,65], value [B]
+    def forward(self, planes, plan=None, trunk=False):  # [B,2,8,8] float (own, opp) -> logits [B,65], value [B]
+        # (trunk=True: also the tower's output [B, C, 8, 8], what an OwnershipHead takes; the stock layers only)
         if self.fused_tower and plan is not None:
+            assert not trunk, "trunk=True needs the stock layers (plan=None)"
             return self._forward_kernels(planes, plan)
         x = F.relu(self.stem(planes))
         if self.fused_tower:
@@ -54,7 +70,7 @@ class PolicyValueNet(nn.Module):
                 x = F.relu(b(F.relu(a(x))) + x)
         p = self.polfc(F.relu(self.pol(x)).flatten(1))
         v = torch.tanh(self.v2(F.relu(self.v1(F.relu(self.val(x)).flatten(1))))).squeeze(-1)
-        return p, v
+        return (p, v, x) if trunk else (p, v)
 
     def _forward_kernels(self, planes, plan):
         """the training forward around the HIP tower kernels (train_kernels.tower_apply_nhwc), everything in the

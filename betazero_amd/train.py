@@ -30,14 +30,31 @@ def make_optimizer(module, lr=1e-4):
     return torch.optim.Adam(module.parameters(), lr=lr)  # train.py:87,192
 
 
-def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False):
+def ownership_targets(fown, fopp):
+    """int64 tensors holding the uint64 target boards [n] -> the cells' targets, float [n, 64] in {+1, 0, -1}:
+    bit_i(fown) - bit_i(fopp)"""
+    dev = fown.device
+    sh = _SHIFTS.get(dev)
+    if sh is None:
+        sh = _SHIFTS[dev] = torch.arange(64, dtype=torch.int64, device=dev)
+    return (((fown[:, None] >> sh) & 1) - ((fopp[:, None] >> sh) & 1)).to(torch.float32)
+
+
+def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False, ownership=None, own_weight=1.0):
     """one Adam step on the rows `idx` of ex (Reversi 8x8 net).  ex: DeviceExamples (stays on the GPU; idx a device
     index tensor or None = all rows) or host Examples (uploaded first).  Returns (loss, policy CE, value MSE) as
-    detached device scalars.  value_targets: the value MSE is against ex.vt (fp32) instead of z."""
+    detached device scalars.  value_targets: the value MSE is against ex.vt (fp32) instead of z.
+    ownership: an OwnershipHead on the trunk's output, trained on ex.fown / ex.fopp -- the loss gains
+    own_weight * L_own, L_own = the mean over positions and all 64 cells of (o - t)^2, and a fourth value, L_own, is returned.
+    The optimizer must then hold the head's parameters too."""
+    from .train_kernels import check_own_weight
+    own_weight = check_own_weight(own_weight)
     if isinstance(ex, Examples):
         ex = DeviceExamples.from_host(ex, device)
     if value_targets and ex.vt is None:
         raise ValueError("train_step: value_targets=True needs examples with vt (betazero_amd.value_targets.value_targets)")
+    if ownership is not None and (ex.fown is None or ex.fopp is None):
+        raise ValueError("train_step: ownership= needs examples with fown / fopp (self-play with ownership=True records them)")
     dev = ex.own.device
     if next(module.parameters()).device != dev:
         module.to(dev)
@@ -49,14 +66,24 @@ def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, 
         own, opp, pi, z = ex.own[idx], ex.opp[idx], ex.pi[idx], (ex.vt if value_targets else ex.z)[idx]
     x = planes_from_bits(own, opp)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-        logits, v = module(x)
+        if ownership is None:
+            logits, v = module(x)
+        else:
+            logits, v, trunk = module(x, trunk=True)
+            o = ownership.to(dev)(trunk)
     logits, v = logits.float(), v.float()
     ce = -(pi * F.log_softmax(logits, dim=1)).sum(1).mean()
     mse = F.mse_loss(v, z.to(torch.float32))
     loss = ce + mse
+    if ownership is not None:
+        t = ownership_targets(ex.fown, ex.fopp) if idx is None else ownership_targets(ex.fown[idx], ex.fopp[idx])
+        l_own = F.mse_loss(o.float(), t)
+        loss = loss + own_weight * l_own
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
+    if ownership is not None:
+        return loss.detach(), ce.detach(), mse.detach(), l_own.detach()
     return loss.detach(), ce.detach(), mse.detach()
 
 
@@ -72,7 +99,8 @@ def select_rows(ex, idx):
     """DeviceExamples holding the rows `idx` (a device index tensor) of ex"""
     return DeviceExamples(own=ex.own[idx], opp=ex.opp[idx], pi=ex.pi[idx], z=ex.z[idx], mover=ex.mover[idx], act=ex.act[idx],
                           game=ex.game[idx], ply=ex.ply[idx], size=ex.size, kl=None if ex.kl is None else ex.kl[idx],
-                          q=None if ex.q is None else ex.q[idx], vt=None if ex.vt is None else ex.vt[idx])
+                          q=None if ex.q is None else ex.q[idx], vt=None if ex.vt is None else ex.vt[idx],
+                          fown=None if ex.fown is None else ex.fown[idx], fopp=None if ex.fopp is None else ex.fopp[idx])
 
 
 @torch.no_grad()
@@ -117,7 +145,14 @@ class GraphedTrainStep:
 
     def __init__(self, module, lr=1e-4, batch=1024, na=65, device="cuda:0", autocast=True, tower_kernels=None, lr_warmup_steps=0,
                  step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False, weight_decay=0.0, clip_norm=0.0,
-                 ema_decay=None, decay_biases=False):
+                 ema_decay=None, decay_biases=False, ownership=None, own_weight=1.0):
+        # ownership: an OwnershipHead trained next to the net on the examples' fown / fopp, inside the all-kernel
+        # step (StepPlan(ownership=...): k_train_heads_own and one more launch, k_train_own_finish, in the same graph); the loss
+        # is CE + MSE + own_weight * L_own and __call__ returns L_own as a fourth value.  Any other form of the step refuses it.
+        from .train_kernels import check_own_weight
+        self.ownership, self.own_weight = ownership, check_own_weight(own_weight)
+        if ownership is not None and (step_kernels is False or fused_adam is False or not getattr(module, "fused_tower", False)):
+            raise ValueError("ownership= needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels, fused_adam)")
         # weight_decay / clip_norm / ema_decay / decay_biases: the extended optimiser of the all-kernel step (StepPlan.enable_adam:
         # AdamW's decoupled decay, a clip of the global gradient norm, non-finite steps skipped, an averaged copy of the weights
         # for ema_module()).  It exists only as kernels: any other form of the step refuses the options, before a device is touched.
@@ -147,10 +182,15 @@ class GraphedTrainStep:
             if not getattr(module, "fused_tower", False):
                 raise ValueError("tower_kernels / step_kernels need PolicyValueNet(..., fused_tower=True)")
             if step_kernels:
-                self.step_plan = self.plan = StepPlan(self.module, batch, device, value_targets=self.value_targets)
+                if ownership is not None:
+                    ownership.to(device)
+                self.step_plan = self.plan = StepPlan(self.module, batch, device, value_targets=self.value_targets, ownership=ownership,
+                                                      own_weight=self.own_weight)
                 self.idx = torch.zeros(batch, dtype=torch.int64, device=self.dev)   # the batch's rows: the kernels gather them themselves
             else:
                 self.plan = TowerPlan(module.C, 2 * module.NB, batch, device)
+        if ownership is not None and self.step_plan is None:
+            raise ValueError("ownership= needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels, fused_adam)")
         # lr_warmup_steps > 0: the learning rate ramps linearly from lr / warmup to lr over the first steps.  Adam's first
         # updates move every weight by ~lr whatever the gradient's size; at the loop demo's lr = 2e-3 that kills the
         # single-channel value head's ReLU (and in 2 of 4 seeds every head ReLU, i.e. the whole net) within the first
@@ -237,9 +277,12 @@ class GraphedTrainStep:
         assert idx.numel() == self.batch, "GraphedTrainStep replays a fixed batch size"
         if self.value_targets and ex.vt is None:
             raise ValueError("GraphedTrainStep(value_targets=True) needs examples with vt (betazero_amd.value_targets.value_targets)")
+        if self.ownership is not None and (ex.fown is None or ex.fopp is None):
+            raise ValueError("GraphedTrainStep(ownership=...) needs examples with fown / fopp (self-play with ownership=True)")
         if self.step_plan is not None:   # the kernels read rows idx of the data set themselves: one 8-byte-per-row copy, no gathers
             self.idx.copy_(idx)
-            self.step_plan.set_batch(ex.own, ex.opp, ex.pi, ex.z, self.idx, vt=ex.vt if self.value_targets else None)
+            own_kw = dict(fown=ex.fown, fopp=ex.fopp) if self.ownership is not None else {}
+            self.step_plan.set_batch(ex.own, ex.opp, ex.pi, ex.z, self.idx, vt=ex.vt if self.value_targets else None, **own_kw)
         else:
             torch.index_select(ex.own, 0, idx, out=self.own)
             torch.index_select(ex.opp, 0, idx, out=self.opp)
@@ -257,6 +300,8 @@ class GraphedTrainStep:
             self.lr_t.fill_(self._lr_at(self.steps_done))
         self.graph.replay()
         self.steps_done += 1
+        if self.ownership is not None:   # loss (with own_weight * L_own), CE, MSE, L_own
+            return torch.cat([self.out[:3], self.step_plan.own_loss])
         return self.out[:3].clone()
 
     def set_lr(self, lr):

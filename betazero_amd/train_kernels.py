@@ -127,6 +127,15 @@ class _RowsLinear(torch.autograd.Function):
         return gx, gW.to(ctx.dts[1]), gb.to(ctx.dts[2])
 
 
+def check_own_weight(own_weight):
+    """the ownership loss's weight: a finite number >= 0, anything else is refused (ValueError, before any
+    device is touched)"""
+    w = own_weight
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w < float("inf"):   # (NaN fails)
+        raise ValueError(f"own_weight must be a finite number >= 0 (got {w!r})")
+    return float(w)
+
+
 class StepPlan(TowerPlan):
     """forward + losses + backward (+ Adam) of one training step of `module` (PolicyValueNet(fused_tower=True), on the
     device) at a fixed batch size, entirely on the HIP kernels:
@@ -152,9 +161,19 @@ class StepPlan(TowerPlan):
                 "val_w": module.val.weight, "val_b": module.val.bias, "v1_w": module.v1.weight, "v1_b": module.v1.bias,
                 "v2_w": module.v2.weight, "v2_b": module.v2.bias}
 
-    def __init__(self, module, batch, device="cuda:0", value_targets=False):
+    def __init__(self, module, batch, device="cuda:0", value_targets=False, ownership=None, own_weight=1.0):
         """value_targets: the head kernel reads a float value target per row (set_batch(..., vt=...)) in place
-        of z, through k_train_heads_vt; everything else of the step is the same"""
+        of z, through k_train_heads_vt; everything else of the step is the same.
+
+        ownership: an OwnershipHead(C) -- the head kernel becomes k_train_heads_own (or its _vt form), which
+        also computes the head on act[L], its loss L_own against the rows' ownership targets (set_batch(..., fown=, fopp=)) and
+        its gradients; the step's loss is CE + MSE + own_weight * L_own, and one more small launch (k_train_own_finish) ends the
+        step: the head's .grad, own_loss[0] = L_own and, with enable_adam(), plain Adam on the head's own C + 1 parameters."""
+        own_weight = check_own_weight(own_weight)
+        if ownership is not None:
+            from .net import OwnershipHead
+            if not isinstance(ownership, OwnershipHead) or ownership.C != getattr(module, "C", None):
+                raise ValueError("StepPlan: ownership must be an OwnershipHead of the module's channel count")
         if not getattr(module, "fused_tower", False):
             raise ValueError("StepPlan needs PolicyValueNet(..., fused_tower=True)")
         if module.VH > 64:
@@ -185,13 +204,28 @@ class StepPlan(TowerPlan):
         self.vt_slot = torch.zeros(1, dtype=torch.int64, device=dev)
         self._vt_ref = None
         self._adam, self.adam_m, self.adam_v, self.hyper = None, None, None, None
+        # the ownership head: its parameters (outside `params`: no bz_train_tensors has them), its partial sums, the device slot
+        # with the addresses of the data set's two target arrays, and L_own
+        self.ownership, self.own_weight = ownership, own_weight
+        self._own, self._own_adam, self._own_ref = None, None, None
+        if ownership is not None:
+            self.own_params = {"w": ownership.conv.weight, "b": ownership.conv.bias}
+            for k, t in self.own_params.items():
+                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"StepPlan: the ownership head's parameter {k} must be a contiguous fp32 tensor on {dev}")
+                t.grad = torch.zeros_like(t)
+            self.own_partial, self.own_loss = f32(sizes[2], self.C + 2), f32(1)
+            self.own_slot = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._own = _lib.TrainOwn(w=self.own_params["w"].data_ptr(), b=self.own_params["b"].data_ptr(), targets=self.own_slot.data_ptr(),
+                                      weight=own_weight, partial=self.own_partial.data_ptr())
         self._optim, self.ema, self.stats, self.optim_partials = None, None, None, None   # the extended optimiser (enable_adam)
 
     # ---- the batch
-    def set_batch(self, own, opp, pi, z, idx=None, vt=None):
+    def set_batch(self, own, opp, pi, z, idx=None, vt=None, fown=None, fopp=None):
         """point the step at rows `idx` (int64 [batch], on the device; None: rows 0..batch-1) of the data set (own, opp, pi,
         z).  Asynchronous on the current stream; the tensors are kept alive until the next call.  vt: the data set's value
-        targets, fp32 [rows] (a plan built with value_targets=True needs them; they are gathered by the same idx)."""
+        targets, fp32 [rows] (a plan built with value_targets=True needs them; they are gathered by the same idx).  fown /
+        fopp: the data set's ownership targets, int64 [rows] (a plan built with ownership= needs them; gathered by idx too)."""
         n, dev = self.n, self.device
         rows = int(own.shape[0])
         if rows < 1:
@@ -206,6 +240,12 @@ class StepPlan(TowerPlan):
                 raise ValueError("set_batch: a plan with value_targets=True needs vt fp32 [rows], contiguous, on the plan's device")
         elif vt is not None:
             raise ValueError("set_batch: vt given, but the plan was built without value_targets=True")
+        if self._own is not None:
+            if fown is None or fopp is None or not all(t.dtype == torch.int64 and t.shape == (rows,) and t.is_contiguous() and t.device == dev
+                                                       for t in (fown, fopp)):
+                raise ValueError("set_batch: a plan with ownership= needs fown / fopp int64 [rows], contiguous, on the plan's device")
+        elif fown is not None or fopp is not None:
+            raise ValueError("set_batch: fown / fopp given, but the plan was built without ownership=")
         if idx is None:
             if rows < n:
                 raise ValueError(f"set_batch: the data set has {rows} rows, the batch needs {n}")
@@ -223,6 +263,11 @@ class StepPlan(TowerPlan):
                 with torch.cuda.device(dev):
                     self.vt_slot.copy_(torch.tensor([vt.data_ptr()], dtype=torch.int64))
             self._vt_ref = vt
+        if self._own is not None:
+            if self._own_ref is None or (self._own_ref[0].data_ptr(), self._own_ref[1].data_ptr()) != (fown.data_ptr(), fopp.data_ptr()):
+                with torch.cuda.device(dev):
+                    self.own_slot.copy_(torch.tensor([fown.data_ptr(), fopp.data_ptr()], dtype=torch.int64))
+            self._own_ref = (fown, fopp)
 
     # ---- the optimiser as the step's tenth launch
     def enable_adam(self, lr, betas=(0.9, 0.999), eps=1e-8, warmup_steps=0, weight_decay=0.0, clip_norm=0.0, ema_decay=None,
@@ -266,6 +311,13 @@ class StepPlan(TowerPlan):
                                           beta1=betas[0], beta2=betas[1], eps=eps, decay_biases=int(bool(decay_biases)),
                                           p=tensors(self.params), m=tensors(self.adam_m), v=tensors(self.adam_v),
                                           ema=ct.pointer(self._ema_set) if self.ema is not None else None)
+        if self._own is not None:   # the head's own Adam state; it reads the rate, the step count and the warm-up of `hyper`
+            self.own_m = {k: torch.zeros_like(t) for k, t in self.own_params.items()}
+            self.own_v = {k: torch.zeros_like(t) for k, t in self.own_params.items()}
+            self._own_adam = _lib.TrainOwnAdam(hyper=self.hyper.data_ptr(), beta1=betas[0], beta2=betas[1], eps=eps,
+                                               pw=self.own_params["w"].data_ptr(), pb=self.own_params["b"].data_ptr(),
+                                               mw=self.own_m["w"].data_ptr(), mb=self.own_m["b"].data_ptr(),
+                                               vw=self.own_v["w"].data_ptr(), vb=self.own_v["b"].data_ptr())
         self.reset_adam(lr, warmup_steps)
 
     def _hyper_block(self, steps_done=0):
@@ -282,7 +334,7 @@ class StepPlan(TowerPlan):
             self.lr = float(lr)
         if warmup_steps is not None:
             self.warmup = int(warmup_steps)
-        for d in (self.adam_m, self.adam_v):
+        for d in (self.adam_m, self.adam_v) + ((self.own_m, self.own_v) if self._own_adam is not None else ()):
             for t in d.values():
                 t.zero_()
         with torch.cuda.device(self.device):
@@ -339,7 +391,7 @@ class StepPlan(TowerPlan):
     # ---- the launches
     def launch(self, adam=False):
         """the 9 (adam: 10, or 11 with the extended optimiser) launches of one step on the current stream (no host work besides:
-        this is what a HIP graph captures)"""
+        this is what a HIP graph captures); with the ownership head one more, k_train_own_finish, at the end"""
         L, p, n, Cc, Ly = _lib.lib(), self.params, self.n, self.C, self.L
         if self._batch_refs is None:
             raise RuntimeError("StepPlan: set_batch() first")
@@ -354,9 +406,22 @@ class StepPlan(TowerPlan):
             chk(L.bz_train_pack_weights(p["tower_w"].data_ptr(), Cc, Ly, self.wf_fwd.data_ptr(), self.wf_bwd.data_ptr(), st))
             chk(L.bz_train_tower_fwd(self.acts[0].data_ptr(), self.wf_fwd.data_ptr(), p["tower_b"].data_ptr(), Cc, Ly, n, self.acts[1].data_ptr(),
                                      self.masks.data_ptr(), st))
-            if self.value_targets:
-                if self._vt_ref is None:
-                    raise RuntimeError("StepPlan: set_batch(..., vt=...) first")
+            if self._own is not None and self._own_ref is None:
+                raise RuntimeError("StepPlan: set_batch(..., fown=..., fopp=...) first")
+            if self.value_targets and self._vt_ref is None:
+                raise RuntimeError("StepPlan: set_batch(..., vt=...) first")
+            if self._own is not None:
+                for k, t in self.own_params.items():
+                    assert t.grad is not None, f"the .grad of the ownership head's {k} was replaced"
+                if self.value_targets:
+                    chk(L.bz_train_heads_own_vt(self.acts[Ly].data_ptr(), bd, self.vt_slot.data_ptr(), ct.byref(self._own), n, Cc, self.VH,
+                                                ct.byref(self._head), self.gs[Ly].data_ptr(), self.hv.data_ptr(), self.dl.data_ptr(),
+                                                self.dv1.data_ptr(), self.heads_partial.data_ptr(), st))
+                else:
+                    chk(L.bz_train_heads_own(self.acts[Ly].data_ptr(), bd, ct.byref(self._own), n, Cc, self.VH, ct.byref(self._head),
+                                             self.gs[Ly].data_ptr(), self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(),
+                                             self.heads_partial.data_ptr(), st))
+            elif self.value_targets:
                 chk(L.bz_train_heads_vt(self.acts[Ly].data_ptr(), bd, self.vt_slot.data_ptr(), n, Cc, self.VH, ct.byref(self._head),
                                         self.gs[Ly].data_ptr(), self.hv.data_ptr(), self.dl.data_ptr(), self.dv1.data_ptr(),
                                         self.heads_partial.data_ptr(), st))
@@ -373,6 +438,11 @@ class StepPlan(TowerPlan):
                                   ct.byref(self._adam) if adam and self._optim is None else None, st))
         if adam and self._optim is not None:
             self.optim_step()
+        if self._own is not None:   # behind the launch that advanced the step counter
+            with torch.cuda.device(self.device):
+                w, b = self.own_params["w"], self.own_params["b"]
+                _lib.check(L.bz_train_own_finish(ct.byref(self._own), Cc, n, w.grad.data_ptr(), b.grad.data_ptr(), self.own_loss.data_ptr(),
+                                                 self.losses.data_ptr(), ct.byref(self._own_adam) if adam else None, self._stream()))
         return self.losses
 
     def bad_rows(self, reset=True):
@@ -392,11 +462,12 @@ class StepPlan(TowerPlan):
             raise IndexError(f"StepPlan: {n} batch position(s) had a row index outside the data set since the last check; "
                              "the kernels clamp instead of faulting, so those steps trained on the wrong rows")
 
-    def grads(self, own=None, opp=None, pi=None, z=None, idx=None, vt=None):
+    def grads(self, own=None, opp=None, pi=None, z=None, idx=None, vt=None, fown=None, fopp=None):
         """forward, losses, backward: every parameter's .grad is set; returns the static [loss, CE, MSE, error word] tensor.
-        (own, opp, pi, z[, idx][, vt]) given: set_batch() first."""
+        (own, opp, pi, z[, idx][, vt][, fown, fopp]) given: set_batch() first.  With the ownership head the loss includes
+        own_weight * L_own, and own_loss[0] is L_own."""
         if own is not None:
-            self.set_batch(own, opp, pi, z, idx, vt=vt)
+            self.set_batch(own, opp, pi, z, idx, vt=vt, fown=fown, fopp=fopp)
         return self.launch(adam=False)
 
     def step(self):

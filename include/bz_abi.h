@@ -638,6 +638,27 @@ int32_t bz_value_targets(const float* q, const int8_t* z, const int8_t* mover, c
                          float lam, float q_mix, float* vt, uint64_t* status_dev, void* stream);
 /* one segment, the function the kernel runs: q, z, mover, vt [T], T in 1 .. 1024.  Host only. */
 int32_t bz_value_targets_segment(const float* q, const int8_t* z, const int8_t* mover, int32_t T, float lam, float q_mix, float* vt);
+/* Ownership targets (KataGo, Wu 2019, section 5), opt-in per engine.  When a move of bz_engine_play ends a
+ * game, the position that move produced is kept in absolute colours: fin_x = the stones of X (the side that moves with
+ * to_move = +1), fin_o = O's, u64 [rounds][n_games] each, indexed like ex_len, in the engine's bit layout.  Valid iff
+ * ex_len >= 0, 0 otherwise (bz_engine_reset_games zeroes them).  A game that records no row (every search fast under the
+ * playout cap) still records its final board.  The feature observes: bz_engine_play launches the kernel behind
+ * bz_engine_root_policy (into scratch inside the buffer) and one one-lane-per-game kernel in front of its play kernel, while
+ * the searched tree is in place -- searches, rows, counters and bz_engine_layout are what they are without it. */
+/* bytes of the caller-owned buffer: fin_x, fin_o u64 [rounds][n_games], then the scratch pi f32 [n_games][NA] and act i32
+ * [n_games], each 256-byte aligned.  Needs no GPU; -1 (bz_last_error says why) for a bad config. */
+int64_t bz_engine_ownership_bytes(const bz_engine_cfg* cfg);
+/* switch the mode on (buf: device memory of >= bz_engine_ownership_bytes bytes, 256-byte aligned, owned by the caller and
+ * kept alive while the mode is on; zeroed on `stream`) or off (buf == NULL), between searches. */
+int32_t bz_engine_set_ownership(bz_engine* e, void* buf, int64_t bytes, void* stream);
+/* the rows' target boards in the packed block's row order, two u64 per row (bz_ownership_row of the row's game and the row's
+ * ex_mover): bz_engine_pack_surprise's contract (after bz_engine_pack_examples, same stream, same cap_rows; append_rows: the
+ * rows already in the arrays). */
+int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uint64_t* fopp_out, int64_t cap_rows, int32_t append_rows,
+                                 void* stream);
+/* a row's target boards, the function the kernel runs: *t_own = mover == +1 ? fin_x : fin_o, *t_opp = the other board; the
+ * target of cell i is bit_i(t_own) - bit_i(t_opp) in {+1, 0, -1}.  mover: +1 or -1.  Host only. */
+int32_t bz_ownership_row(uint64_t fin_x, uint64_t fin_o, int32_t mover, uint64_t* t_own, uint64_t* t_opp);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
@@ -882,6 +903,43 @@ int32_t bz_train_heads(const void* act_top, const bz_train_batch* batch_dev, int
 int32_t bz_train_heads_vt(const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot_dev, int32_t n,
                           int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1,
                           float* partial, void* stream);
+/* The ownership head in the step (KataGo, Wu 2019, section 5): a fourth 1x1 plane on act[L], Conv2d(C, 1, 1)
+ * with a tanh, trained on every row's ownership target.  Its C + 1 parameters belong to no bz_train_tensors:
+ * the net the engine plays with does not have them.  Per position, lane = cell, fp32 on the bf16 act[L]:
+ *   d3 = ob + sum_c x[cell][c] ow[c]  (one fmaf chain, c ascending);  o = tanhf(d3);  t = bit_cell(fown[row]) - bit_cell(fopp[row])
+ *   L_own = mean over positions and all 64 cells of (o - t)^2;  dp3 = own_weight * 2 (o - t)(1 - o^2) * (1 / n) / 64
+ * dp3 joins bz_train_heads' backward: d ob += dp3, d ow[c] += sum_cell dp3 x, and g_top gains fmaf(dp3, ow[c], .) as its LAST
+ * term -- with weight = 0 every output of bz_train_heads keeps its value.  The rows are gathered by the batch's idx, with the
+ * same clamping and the same error word. */
+typedef struct bz_train_own {
+    const float *w, *b;                /* the head's parameters: weight [C], bias [1] (device) */
+    const uint64_t* const* targets;    /* DEVICE slot of two pointers: fown [rows], fopp [rows] -- a device slot for the reason
+                                          vt_slot_dev is one: a captured step survives a new data set */
+    float weight;                      /* own_weight: finite, >= 0 */
+    float* partial;                    /* [sizes[2]][C + 2] (bz_train_ends_sizes): per workgroup d ow [C], d ob, L_own */
+} bz_train_own;
+/* bz_train_heads / bz_train_heads_vt with the ownership head (k_train_heads_own / k_train_heads_own_vt): every output of
+ * theirs, plus own->partial */
+int32_t bz_train_heads_own(const void* act_top, const bz_train_batch* batch_dev, const bz_train_own* own, int32_t n, int32_t C,
+                           int32_t VH, const bz_train_head_params* P, void* g_top, float* hv, float* dl, float* dv1, float* partial,
+                           void* stream);
+int32_t bz_train_heads_own_vt(const void* act_top, const bz_train_batch* batch_dev, const float* const* vt_slot_dev,
+                              const bz_train_own* own, int32_t n, int32_t C, int32_t VH, const bz_train_head_params* P, void* g_top,
+                              float* hv, float* dl, float* dv1, float* partial, void* stream);
+/* The head's own end of the step, one launch of one workgroup behind bz_train_finish (and bz_train_optim_step), which have
+ * advanced the step counter: own->partial summed in a fixed order (no atomics, no memset) -> grad_w [C], grad_b [1],
+ * own_loss[0] = L_own; losses (may be null) [0] += own_weight * L_own -- bz_train_finish stored CE + MSE there in this step.
+ * opt (may be null): plain Adam (bz_train_finish's arithmetic) on the C + 1 parameters, with the rate, the step number and the
+ * warm-up of `hyper` = the step's optimiser's hyper block; when one of the C + 1 gradients is not finite, parameters and
+ * moments stay as they are.  Under the extended optimiser the head's parameters are outside its norm, decay and EMA (the engine
+ * never reads them); their gradient's way into the trunk, g_top, is inside. */
+typedef struct bz_train_own_adam {
+    const float* hyper;
+    float beta1, beta2, eps;
+    float *pw, *pb, *mw, *mb, *vw, *vb;   /* parameters and the two Adam moments: weight [C], bias [1] */
+} bz_train_own_adam;
+int32_t bz_train_own_finish(const bz_train_own* own, int32_t C, int32_t n, float* grad_w, float* grad_b, float* own_loss, float* losses,
+                            const bz_train_own_adam* opt, void* stream);
 /* partial [sizes[4]][sizes[5]] */
 int32_t bz_train_heads_wgrad(const float* hv, const float* dl, const float* dv1, int32_t n, int32_t VH, float* partial, void* stream);
 /* every partial sum -> the gradient tensors G (torch layouts); losses[4] = loss, policy CE, value MSE of the batch, and the

@@ -37,7 +37,7 @@ from betazero_amd.augment import augment_examples  # noqa: E402
 from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
                                  check_playout_cap, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
-from betazero_amd.net import DeviceNet, PolicyValueNet  # noqa: E402
+from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
 from betazero_amd.value_targets import value_targets  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
@@ -110,6 +110,10 @@ def main():
                     "net that is validated, gated and pushed to the engine is then the averaged one")
     ap.add_argument("--lr-decay", type=float, default=1.0, help="the learning rate is multiplied by this after every iteration "
                     "(GraphedTrainStep.set_lr: no recapture)")
+    ap.add_argument("--ownership", action="store_true", help="ownership targets (DESIGN.md 3.22, 12.2; KataGo): self-play keeps every "
+                    "game's final board, and an auxiliary head next to the net learns, per cell, who owns it at the end; the head "
+                    "only shapes the trunk, the engine's net does not have it.  Needs the all-kernel training step")
+    ap.add_argument("--own-weight", type=float, default=1.0, help="the weight of the ownership loss in the step's loss (untuned)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -121,6 +125,10 @@ def main():
     extended = bool(args.weight_decay or args.clip_norm or args.ema_decay is not None)
     if (extended or args.lr_decay != 1.0) and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
         ap.error("--weight-decay / --clip-norm / --ema-decay / --lr-decay need the all-kernel training step")
+    if args.ownership and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
+        ap.error("--ownership needs the all-kernel training step")
+    if not (0.0 <= args.own_weight < float("inf")):
+        ap.error("--own-weight must be finite and >= 0")
 
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
@@ -128,10 +136,11 @@ def main():
     v_lam, v_mix = 1.0 if args.value_lambda is None else args.value_lambda, 0.0 if args.value_q_mix is None else args.value_q_mix
     kernels = not (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256)
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
+    own_head = OwnershipHead(args.channels) if args.ownership else None
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
                                                                   value_targets=use_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
-                                                                  ema_decay=args.ema_decay)
+                                                                  ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight)
     bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
@@ -169,7 +178,7 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, search_value=use_vt, fpu=fpu,
+                               surprise=args.surprise, search_value=use_vt, fpu=fpu, ownership=args.ownership,
                                eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
@@ -254,6 +263,9 @@ def main():
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
               **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
+              # the ownership loss L_own over the last (and the first) tenth of the steps
+              **({"own": round(float(tail[3]), 4), "own_first_tenth": round(float(head[3]), 4), "own_weight": args.own_weight}
+                 if args.ownership else {}),
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
