@@ -416,7 +416,9 @@ __device__ __forceinline__ void train_heads_body(const HeadArgs& __restrict__ A,
                 const int c = 8 * k + 2 * e;
                 float glo = fmaf(dp[0], hwS[c], fmaf(dp[1], hwS[C + c], dp[2] * hwS[2 * C + c]));
                 float ghi = fmaf(dp[0], hwS[c + 1], fmaf(dp[1], hwS[C + c + 1], dp[2] * hwS[2 * C + c + 1]));
-                if constexpr (kOwn) { glo = fmaf(dp3, hwS[3 * C + c], glo); ghi = fmaf(dp3, hwS[3 * C + c + 1], ghi); }
+                // (a zero dp3 -- own_weight = 0, o == t, a saturated tanh -- adds nothing, and is not added: fmaf(+-0, ow, -0) is +0
+                // unless the product is -0 too, which turned a -0 of the other planes into +0; a NaN dp3 is != 0 and is added)
+                if constexpr (kOwn) if (dp3 != 0.0f) { glo = fmaf(dp3, hwS[3 * C + c], glo); ghi = fmaf(dp3, hwS[3 * C + c + 1], ghi); }
                 o[e] = pack2(bf_pos_lo(xv[e]) ? glo : 0.0f, bf_pos_hi(xv[e]) ? ghi : 0.0f);
             }
             *at = o;

@@ -322,12 +322,17 @@ def dot(x, W, dim_terms):
     return matsum(x, W, dim_terms)
 
 
-def heads_ref(x, P, pi, z):
+def heads_ref(x, P, pi, z, own=None):
     """the heads and losses of k_train_heads / k_train_heads_wgrad / k_train_finish on act[L] x [n, 64, C] (float64 values
     of the stored bf16) with parameters P (torch tensors, fp64 values of the fp32 parameters), in the kernels' operation
     order.  Requires exact 1x1 convolutions and FC pre-activations (asserted through `exact_units`): then the ReLU masks are
     exact and only exp / log / tanh and what follows round.  Returns {name: B} for the three losses, g[L] (before its bf16
-    rounding) and the ten head gradients."""
+    rounding) and the ten head gradients.
+
+    own (k_train_heads_own / k_train_heads_own_vt and k_train_own_finish): a dict of the ownership head's
+    `ow` [C] and `ob` (float64 values of the fp32 parameters), the rows' target boards `fown` / `fopp` (int64 tensors [n] holding
+    the uint64 bits) and `own_weight`.  Adds own_w [1, C, 1, 1], own_b [1], l_own, the plane's o [n, 64] (B) and d3 (exact),
+    and replaces loss (CE + MSE + own_weight L_own) and g_top (the head's term added last); the rest is what it is without."""
     n, _, C = x.shape
     inv_n = B.rnd(torch.tensor(1.0 / n), torch.tensor(0.0))     # 1.0f / n: one rounding
     hw = torch.cat([P["pol_w"].reshape(2, C), P["val_w"].reshape(1, C)])          # [3, C]
@@ -391,7 +396,38 @@ def heads_ref(x, P, pi, z):
            "polfc_w": g_polfc_w, "polfc_b": da.sum(0), "v1_w": g_v1_w, "v1_b": dv1.sum(0),
            "v2_w": B(g_v2_w.v.reshape(1, -1), g_v2_w.e.reshape(1, -1)), "v2_b": B(dpre2.sum(0).v.reshape(1), dpre2.sum(0).e.reshape(1)),
            "h": h, "s": s, "t": t}
+    if own is not None:
+        out.update(_own_plane_ref(x, own, inv_n, both, matsum(dps, hw, 3)))
     return out
+
+
+def _own_plane_ref(x, own, inv_n, both, three):
+    """the fourth plane of train_heads_body<C, kVT, true> and k_train_own_finish's sums, in their operation order.  both: CE + MSE
+    as k_train_finish stores it; three: the three-term expression of g_top before its mask.  The plane has no ReLU and no mask:
+    all 64 cells of every position count."""
+    n, _, C = x.shape
+    ow = torch.as_tensor(own["ow"], dtype=torch.float64, device=x.device).reshape(C)
+    ob = torch.as_tensor(own["ob"], dtype=torch.float64, device=x.device).reshape(())
+    w = float(np.float32(own["own_weight"]))                      # (the kernel argument is a float)
+    d3 = x @ ow + ob                                              # [n, 64]: one ascending fmaf chain from ob
+    exact_units(x.abs() @ ow.abs() + ob.abs(), "ownership 1x1")
+    sh = torch.arange(64, dtype=torch.int64, device=x.device)
+    bit = lambda b: (torch.as_tensor(b, dtype=torch.int64, device=x.device)[:, None] >> sh) & 1  # noqa: E731  (arithmetic shift: & 1 keeps bit 63)
+    tgt = (bit(own["fown"]) - bit(own["fopp"])).double()          # [n, 64] in {-1, 0, 1}
+    o = B(d3).tanh()
+    diff = o - B(tgt)
+    inv = B(inv_n.v * 2.0 ** -6, inv_n.e * 2.0 ** -6)             # inv_n * (1.0f / 64.0f): a scaling by a power of two, exact
+    dp3 = (((B(w) * 2.0) * diff) * (1.0 - o * o)) * inv           # [n, 64]
+    lo_t = fma(diff * diff, inv, B(torch.zeros_like(d3)))
+    flat = lambda a: B(a.v.reshape(-1), a.e.reshape(-1))          # noqa: E731
+    l_own = flat(lo_t).sum(0)
+    d_ob = flat(dp3).sum(0)
+    f = flat(dp3)
+    d_ow = matsum(B(f.v[None, :], f.e[None, :]), x.reshape(-1, C), 64 * n)[0]
+    g_top = fma(B(dp3.v[:, :, None], dp3.e[:, :, None]), B(ow.expand(n, 64, C)), three).where(x > 0)
+    loss = both + B(w) * l_own                                    # losses[0] + weight * L_own: two roundings
+    return {"own_w": B(d_ow.v.reshape(1, C, 1, 1), d_ow.e.reshape(1, C, 1, 1)), "own_b": B(d_ob.v.reshape(1), d_ob.e.reshape(1)),
+            "l_own": l_own, "loss": loss, "g_top": g_top, "o": o, "d3": d3, "own_t": tgt, "dp3": dp3}
 
 
 def _bcol(a):   # B [n] -> B [n, 1]
@@ -410,7 +446,18 @@ def exact_units(terms, what, unit=None):
 
 # the grid of each exact head sum for exact_head_net's parameters (powers of two): x and the 1x1 weights integers,
 # polfc / v1 weights multiples of 2^-6, v2 multiples of 2^-8
-HEAD_UNIT = {"1x1 convolutions": 1.0, "policy FC": 2.0 ** -6, "value FC 1": 2.0 ** -6, "value FC 2": 2.0 ** -14}
+HEAD_UNIT = {"1x1 convolutions": 1.0, "policy FC": 2.0 ** -6, "value FC 1": 2.0 ** -6, "value FC 2": 2.0 ** -14,
+             "ownership 1x1": 2.0 ** -4}   # (exact_own_params: x integers, ow and ob multiples of 2^-4)
+
+
+def exact_own_params(C, seed, density=0.25):
+    """the ownership head's (ow [C], ob) on which its pre-activation is exact on integer activations: ow multiples of 2^-4 in
+    [-4, 4] / 16 at `density`, ob a multiple of 2^-4 in [-1/2, 1/2] -- on _heads_case's activations the plane then has cells
+    with |o| < 0.5, cells where tanhf saturates to +-1 exactly and cells with d3 = 0 exactly (the callers assert which)"""
+    g = torch.Generator().manual_seed(seed)
+    ow = torch.randint(-4, 5, (C,), generator=g).double() * 2.0 ** -4 * (torch.rand(C, generator=g) < density)
+    ob = torch.randint(-8, 9, (1,), generator=g).double() * 2.0 ** -4
+    return ow, ob
 
 
 def exact_head_params(C, VH, seed, saturate=False):
