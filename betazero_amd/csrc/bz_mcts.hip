@@ -2362,6 +2362,204 @@ __global__ void __launch_bounds__(256) k_pack_own(EngineDev E, OwnDev O, u64* fo
     }
 }
 
+// ---- the root store (S = 0: off), set by bz_engine_set_root_store in the caller's buffer: finished searches of
+// roots at most D - 1 plies behind a game's start, keyed by the root's position, S entries behind an open-addressed index of
+// n_idx >= 2 S words (entry + 1; 0 = empty).  An entry is one slot's arena image -- nodes, edges, node_v and the slot's table
+// entries of that search -- and every index inside it (edge0, child ids, the table's node ids) is relative to the slot's own
+// region, so an image moves between slots and the store by plain copies.  k_store_save files the trees of a finished search,
+// k_store_seed lays a stored tree of a slot's next root where k_root_begin takes the slot's previous tree from: the carry-over
+// then does what it does with a slot's own previous search.  A kernel argument of these two kernels only.
+struct __attribute__((aligned(64))) StoreHdr { u64 own, opp, epoch; u32 n_nodes, n_edges, ready, pad[7]; };
+static_assert(sizeof(StoreHdr) == 64, "layout");
+struct StoreDev {
+    int S, D, n_idx, base;  // base: the plies a game starts with (the fixed two-ply openings)
+    u32* n_used;            // entries claimed so far
+    u32* idx;               // [n_idx]
+    StoreHdr* hdr;          // [S]
+    u32* mark;              // [B]: the generation a slot was last seeded under (what its search then sees as the previous one)
+    Node* nodes; Edge* edges; float* node_v; u64* tt;  // [S][ncap], [S][ecap], [S][ncap], [S][tt_buckets * 16]
+};
+constexpr int kCntSeededEvals = 11, kCntSeededSearches = 12, kCntStoreSaves = 13;  // counters[] words, written like kCntCollisions
+
+__device__ __forceinline__ u32 store_home(const StoreDev& St, u64 own, u64 opp) { return (u32)(hash_pos(own, opp) >> 20) & (u32)(St.n_idx - 1); }
+// the entry holding (own, opp) under `epoch`, or -1; *at: the index word the probe stopped at (an empty one on a miss)
+__device__ __forceinline__ int store_find(const StoreDev& St, u64 own, u64 opp, u64 epoch, u32* at) {
+    u32 p = store_home(St, own, opp);
+    for (int k = 0; k < St.n_idx; ++k, p = (p + 1u) & (u32)(St.n_idx - 1)) {
+        const u32 w = St.idx[p];
+        if (w == 0u || w > (u32)St.S) { *at = p; return -1; }
+        const StoreHdr& h = St.hdr[w - 1u];
+        if (h.own == own && h.opp == opp && h.epoch == epoch) { *at = p; return (int)(w - 1u); }
+    }
+    *at = ~0u;
+    return -1;
+}
+__device__ __forceinline__ bool store_depth_ok(const EngineDev& E, const StoreDev& St, int g) {
+    const int d = E.g_moves[g] - St.base;
+    return E.g_state[g] == 0 && d >= 0 && d < St.D;
+}
+__device__ __forceinline__ u32 tt_gen_before(u32 gen) { return gen == 1u ? kTtGenMax - 1u : gen - 1u; }
+
+// what tt_lookup_insert answered when node `i` of slot g's finished search was created: true iff it took its evaluation from
+// the previous search's arena.  The table only ever gains entries during a search (free slots are filled, live ones stay), and
+// an entry's node id says when: the entries below i are the table that lookup saw.
+__device__ __forceinline__ bool tt_replay_from_prev(const EngineDev& E, int g, u32 i, u32 gen, u32 prev_nodes) {
+    const Node nd = E.nodes[(size_t)g * E.ncap + i];
+    if (nd.info & kTerm) return false;  // (terminal children are never looked up)
+#ifdef BZ_EXP_TT_WEAK_HASH
+    const u64 h = hash_pos(nd.own, nd.opp) & 1u;
+#else
+    const u64 h = hash_pos(nd.own, nd.opp);
+#endif
+    const u32 tag = (u32)(h >> 32), gen_prev = tt_gen_before(gen);
+    const u64* bucket = E.tt + ((size_t)g * (size_t)E.tt_buckets + (size_t)(h & (u64)(E.tt_buckets - 1))) * 16;
+    u32 hit = ~0u;
+    for (int s = 0; s < 16; ++s) {
+        const u64 e = bucket[s];
+        const u32 meta = (u32)(e >> 32), egen = meta >> kChildBits;
+        const bool cur = egen == gen && (meta & kChildMask) < i, prv = prev_nodes != 0u && egen == gen_prev;
+        if ((cur || prv) && (u32)e == tag) {
+            const u32 key = ((prv ? 1u : 0u) << 20) | ((u32)s << 16) | (meta & kChildMask);
+            hit = key < hit ? key : hit;
+        }
+    }
+    if (hit == ~0u || (hit >> 20) == 0u) return false;
+    const u32 x = hit & kChildMask;
+    if (x == 0u || x >= prev_nodes) return false;
+    const Node xn = E.nodes_alt[(size_t)g * E.ncap + x];
+    return xn.own == nd.own && xn.opp == nd.opp && !(xn.info & kTerm) && (xn.info & 0xFFu) != 0u;
+}
+
+// Behind the last tree step of search `gen`, in front of the play kernel.  Blocks 0 .. B - 1: slot b, if this search was seeded
+// for it, counts the evaluations it took from the seeded tree (counters[11]).  Block B files the finished trees: slots in
+// ascending order, 256 at a time -- every lane looks its slot's root up, lane 0 then claims entries for the roots still
+// missing (first come = lowest slot: which tree a root gets does not depend on timing), and the block copies them in.  A full
+// store files nothing more.  budget: the playout cap's, or null -- a fast search's small tree is not worth an entry.
+__global__ void __launch_bounds__(256) k_store_save(EngineDev E, StoreDev St, u32 gen, u64 epoch, const u32* budget) {
+    __shared__ int claim[256];
+    __shared__ u32 part[256];
+    const int t = threadIdx.x;
+    if ((int)blockIdx.x < E.B) {
+        const int g = blockIdx.x;
+        const GameHot& hot = E.hot[g];
+        if (E.g_state[g] != 0 || hot.tt_gen != gen || hot.last_gen != gen || hot.prev_nodes == 0u || St.mark[g] != tt_gen_before(gen)) return;
+        const u32 n = hot.n_nodes < (u32)E.ncap ? hot.n_nodes : (u32)E.ncap;
+        u32 mine = 0;
+        for (u32 i = 1u + (u32)t; i < n; i += 256u) mine += tt_replay_from_prev(E, g, i, gen, hot.prev_nodes) ? 1u : 0u;
+        part[t] = mine;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if (t < o) part[t] += part[t + o]; __syncthreads(); }
+        if (t == 0 && part[0]) atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntSeededEvals, (unsigned long long)part[0]);
+        return;
+    }
+    const size_t ttn = (size_t)E.tt_buckets * 16;
+    for (int g0 = 0; g0 < E.B; g0 += 256) {
+        const int g = g0 + t;
+        int c = -1;  // -2: a root to file
+        if (g < E.B && store_depth_ok(E, St, g) && E.hot[g].last_gen == gen && E.hot[g].tt_gen == gen && E.hot[g].n_nodes > 1u &&
+            E.hot[g].n_nodes <= (u32)E.ncap && E.hot[g].n_edges <= (u32)E.ecap && !(budget && budget[g] < (u32)E.sims)) {
+            const Node r = E.nodes[(size_t)g * E.ncap];
+            u32 at;
+            if (store_find(St, r.own, r.opp, epoch, &at) < 0) c = -2;
+        }
+        claim[t] = c;
+        __syncthreads();
+        if (t == 0) {
+            for (int j = 0; j < 256; ++j) {
+                if (claim[j] != -2) continue;
+                claim[j] = -1;
+                const u32 used = *St.n_used;
+                if (used >= (u32)St.S) continue;
+                const int gj = g0 + j;
+                const Node r = E.nodes[(size_t)gj * E.ncap];
+                u32 at;
+                if (store_find(St, r.own, r.opp, epoch, &at) >= 0 || at == ~0u) continue;  // (a lower slot of this launch filed this root)
+                StoreHdr h{};
+                h.own = r.own; h.opp = r.opp; h.epoch = epoch; h.n_nodes = E.hot[gj].n_nodes; h.n_edges = E.hot[gj].n_edges; h.ready = 0u;
+                St.hdr[used] = h;
+                St.idx[at] = used + 1u;
+                *St.n_used = used + 1u;
+                __threadfence();
+                claim[j] = (int)used;
+            }
+        }
+        __syncthreads();
+        for (int j = 0; j < 256; ++j) {
+            const int en = claim[j];
+            if (en < 0) continue;
+            const int gj = g0 + j;
+            const u32 nn = St.hdr[en].n_nodes, ne = St.hdr[en].n_edges;
+            const uint4* sn = reinterpret_cast<const uint4*>(E.nodes + (size_t)gj * E.ncap);
+            uint4* dn = reinterpret_cast<uint4*>(St.nodes + (size_t)en * E.ncap);
+            for (u32 k = t; k < nn * 2u; k += 256u) dn[k] = sn[k];
+            const uint4* se = reinterpret_cast<const uint4*>(E.edges + (size_t)gj * E.ecap);
+            uint4* de = reinterpret_cast<uint4*>(St.edges + (size_t)en * E.ecap);
+            for (u32 k = t; k < ne; k += 256u) de[k] = se[k];
+            const float* sv = E.node_v + (size_t)gj * E.ncap;
+            float* dv = St.node_v + (size_t)en * E.ncap;
+            for (u32 k = t; k < nn; k += 256u) dv[k] = sv[k];
+            const u64* st = E.tt + (size_t)gj * ttn;
+            u64* dt = St.tt + (size_t)en * ttn;
+            for (size_t k = t; k < ttn; k += 256) {  // this search's entries only; the rest of the image is empty
+                const u64 e = st[k];
+                dt[k] = ((u32)(e >> 32) >> kChildBits) == gen ? e : 0ULL;
+            }
+        }
+        __syncthreads();
+        if (t == 0)
+            for (int j = 0; j < 256; ++j)
+                if (claim[j] >= 0) {
+                    St.hdr[claim[j]].ready = 1u;
+                    atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntStoreSaves, 1ULL);
+                }
+        __syncthreads();
+    }
+}
+
+// In front of k_root_begin, on the arena the search of generation `gen` just ran in -- the one the host is about to make the
+// previous one.  Block g: if slot g's next root is stored, the entry replaces the slot's tree there, its table entries take
+// generation `gen`, and the slot's n_nodes / last_gen say "my previous search, `gen`, left n_nodes nodes": k_root_begin and
+// tt_lookup_insert read nothing else.  The slot's table holds nothing but the image afterwards (its older entries would be
+// dead from the next search on anyway).
+__global__ void __launch_bounds__(256) k_store_seed(EngineDev E, StoreDev St, u32 gen, u64 epoch) {
+    __shared__ int found;
+    const int g = blockIdx.x, t = threadIdx.x;
+    if (t == 0) {
+        int en = -1;
+        if (store_depth_ok(E, St, g)) {
+            u32 at;
+            en = store_find(St, E.g_own[g], E.g_opp[g], epoch, &at);
+            if (en >= 0 && (St.hdr[en].ready == 0u || St.hdr[en].n_nodes > (u32)E.ncap || St.hdr[en].n_edges > (u32)E.ecap)) en = -1;
+        }
+        found = en;
+    }
+    __syncthreads();
+    const int en = found;
+    if (en < 0) return;
+    const u32 nn = St.hdr[en].n_nodes, ne = St.hdr[en].n_edges;
+    const uint4* sn = reinterpret_cast<const uint4*>(St.nodes + (size_t)en * E.ncap);
+    uint4* dn = reinterpret_cast<uint4*>(E.nodes + (size_t)g * E.ncap);
+    for (u32 k = t; k < nn * 2u; k += 256u) dn[k] = sn[k];
+    const uint4* se = reinterpret_cast<const uint4*>(St.edges + (size_t)en * E.ecap);
+    uint4* de = reinterpret_cast<uint4*>(E.edges + (size_t)g * E.ecap);
+    for (u32 k = t; k < ne; k += 256u) de[k] = se[k];
+    const float* sv = St.node_v + (size_t)en * E.ncap;
+    float* dv = E.node_v + (size_t)g * E.ncap;
+    for (u32 k = t; k < nn; k += 256u) dv[k] = sv[k];
+    const size_t ttn = (size_t)E.tt_buckets * 16;
+    const u64* st = St.tt + (size_t)en * ttn;
+    u64* dt = E.tt + (size_t)g * ttn;
+    for (size_t k = t; k < ttn; k += 256) {
+        const u64 e = st[k];
+        dt[k] = e ? ((e & 0xFFFFFFFFULL) | ((u64)((gen << kChildBits) | ((u32)(e >> 32) & kChildMask)) << 32)) : 0ULL;
+    }
+    if (t == 0) {
+        E.hot[g].n_nodes = nn; E.hot[g].last_gen = gen;
+        St.mark[g] = gen;
+        atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntSeededSearches, 1ULL);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2389,6 +2587,8 @@ struct bz_engine {
     int fpu_done;      // ... simulations selected so far in the current search: what an expand-only step has backed up when it is done
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
     OwnDev own;        // ownership targets (bz_engine_set_ownership); own.fin_x = nullptr: off
+    StoreDev store;    // the root store (bz_engine_set_root_store); store.S = 0: off
+    int64_t store_index_bytes;  // ... its front part (fill count, index, entry headers): zeroing it empties the store
     // hashed evaluation symmetry (bz_engine_set_eval_symmetry); on the engine, not on the net: two pipelines
     // and two match players share one bz_net
     int sym_on;
@@ -2536,6 +2736,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->surp = SurpDev{};
     e->value = ValueDev{};
     e->own = OwnDev{};
+    e->store = StoreDev{}; e->store_index_bytes = 0;
     e->fpu = FpuDev{}; e->fpu_done = 0;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
@@ -2679,17 +2880,24 @@ BZ_EXPORT int32_t bz_engine_set_roots(bz_engine* e, const uint64_t* own, const u
 
 BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    // evaluations of the previous search are this search's only under the same weights (bz_net_update / bz_engine_set_net between
+    // two searches of a live engine: nothing is carried over, exactly as if the slot had sat the previous search out)
+    const uint64_t epoch = bz_net_epoch(e->net);
+    const int carry_ok = epoch == e->eval_epoch;
+    e->eval_epoch = epoch;
+    if (e->store.S > 0) {  //  the root store lives and dies with the carry-over: another evaluator, an empty store
+        if (!carry_ok) BZ_HIP(hipMemsetAsync(e->store.n_used, 0, (size_t)e->store_index_bytes, (hipStream_t)stream));
+        else if (e->search_seq != 0u) {  // ... else the stored trees of the next roots, in the arena that is about to become the previous one
+            hipLaunchKernelGGL(k_store_seed, dim3(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->store, e->search_seq, epoch);
+            BZ_LAUNCH_CHECK("k_store_seed");
+        }
+    }
     e->search_seq = e->search_seq % (kTtGenMax - 1u) + 1u;  // 1 .. 2^19 - 2 (0 = never written)
     if (e->dev.ecache == 2) {  // the tree just searched stays intact in the other arena while the new one grows in this one
         Node* tn = e->dev.nodes; e->dev.nodes = e->dev.nodes_alt; e->dev.nodes_alt = tn;
         Edge* te = e->dev.edges; e->dev.edges = e->dev.edges_alt; e->dev.edges_alt = te;
         float* tv = e->dev.node_v; e->dev.node_v = e->dev.node_v_alt; e->dev.node_v_alt = tv;
     }
-    // evaluations of the previous search are this search's only under the same weights (bz_net_update / bz_engine_set_net between
-    // two searches of a live engine: nothing is carried over, exactly as if the slot had sat the previous search out)
-    const uint64_t epoch = bz_net_epoch(e->net);
-    const int carry_ok = epoch == e->eval_epoch;
-    e->eval_epoch = epoch;
     BZ_DISPATCH(e, k_root_begin, stream, e->dev, e->search_seq, carry_ok);
     if (e->cap.fast > 0) {  // this search's budgets
         hipLaunchKernelGGL(k_cap_budget, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->cap);
@@ -2789,6 +2997,15 @@ BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
 // the roots are expanded on their own and bz_engine_root_noise runs before the first walk: Dirichlet noise, Gumbel root search
 static bool root_prep(const bz_engine* e) { return e->dev.dir_eps > 0.0f || e->gumbel.m > 0; }
 
+//  behind the last tree step of a stepwise search: the finished trees of early roots go to the root store
+static int32_t store_save(bz_engine* e, void* stream) {
+    if (e->store.S == 0) return BZ_OK;
+    hipLaunchKernelGGL(k_store_save, dim3(e->dev.B + 1), dim3(256), 0, (hipStream_t)stream, e->dev, e->store, e->search_seq, e->eval_epoch,
+                       e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+    BZ_LAUNCH_CHECK("k_store_save");
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     BZ_REQUIRE(e, "null engine");
     int ek = e->cfg.eval_kind;
@@ -2832,7 +3049,8 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
         if ((rc = tree_step(e, (noise && s == 0) ? 0 : 1, 1, (uint32_t)s, stream)) != BZ_OK) return rc;
         if ((rc = bz_engine_evaluate(e, stream)) != BZ_OK) return rc;
     }
-    return tree_step(e, 1, 0, 0, stream);
+    if ((rc = tree_step(e, 1, 0, 0, stream)) != BZ_OK) return rc;
+    return store_save(e, stream);
 }
 
 BZ_EXPORT int32_t bz_engine_root_stats(bz_engine* e, void* stream) {
@@ -3259,6 +3477,54 @@ BZ_EXPORT int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uin
     return BZ_OK;
 }
 
+namespace {
+struct StoreOffsets { int64_t n_used, idx, hdr, mark, nodes, edges, node_v, tt, total; int n_idx; };
+StoreOffsets store_carve(const bz_engine_cfg& c, int64_t S) {
+    const Offsets w = carve(c);
+    StoreOffsets o{};
+    Carver k;
+    o.n_idx = 16;
+    while ((int64_t)o.n_idx < 2 * S) o.n_idx *= 2;
+    o.n_used = k.take(256); o.idx = k.take((int64_t)o.n_idx * 4); o.hdr = k.take(S * (int64_t)sizeof(StoreHdr));
+    o.mark = k.take((int64_t)c.n_games * 4);
+    o.nodes = k.take(S * w.ncap * (int64_t)sizeof(Node)); o.edges = k.take(S * w.ecap * (int64_t)sizeof(Edge));
+    o.node_v = k.take(S * w.ncap * 4); o.tt = k.take(S * w.tt_buckets * 16 * 8);
+    o.total = k.off;
+    return o;
+}
+inline bool store_args_ok(int32_t S, int32_t D) { return S >= 1 && S <= 65536 && D >= 1 && D <= 64; }
+}  // namespace
+
+/* The root store: bytes of the buffer for `entries` stored searches; 0 for a config whose engine does not run
+ * the carry-over cache (the store is off there) */
+BZ_EXPORT int64_t bz_engine_root_store_bytes(const bz_engine_cfg* cfg, int32_t entries, int32_t plies) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_root_store_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_root_store_bytes: %s", kBadCfg); return -1; }
+    if (!store_args_ok(entries, plies)) { set_error("bz_engine_root_store_bytes: 1 <= entries <= 65536, 1 <= plies <= 64"); return -1; }
+    if (carve(*cfg).ecache != 2) return 0;
+    return store_carve(*cfg, entries).total;
+}
+
+BZ_EXPORT int32_t bz_engine_set_root_store(bz_engine* e, void* buf, int64_t bytes, int32_t entries, int32_t plies, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_root_store: null engine");
+    if (!buf || e->dev.ecache != 2) {  // off: no extra launch
+        e->store = StoreDev{}; e->store_index_bytes = 0;
+        return BZ_OK;
+    }
+    BZ_REQUIRE(store_args_ok(entries, plies), "bz_engine_set_root_store: 1 <= entries <= 65536, 1 <= plies <= 64");
+    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_root_store: the buffer must be 256-byte aligned");
+    const StoreOffsets o = store_carve(e->cfg, entries);
+    if (bytes < o.total) { set_error("bz_engine_set_root_store: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.nodes, (hipStream_t)stream));  // an empty store, no slot seeded
+    StoreDev& s = e->store;
+    s.S = entries; s.D = plies; s.n_idx = o.n_idx;
+    s.base = (e->cfg.game == BZ_GAME_REVERSI && e->cfg.openings) ? 2 : 0;
+    s.n_used = at<u32>(buf, o.n_used); s.idx = at<u32>(buf, o.idx); s.hdr = at<StoreHdr>(buf, o.hdr); s.mark = at<u32>(buf, o.mark);
+    s.nodes = at<Node>(buf, o.nodes); s.edges = at<Edge>(buf, o.edges); s.node_v = at<float>(buf, o.node_v); s.tt = at<u64>(buf, o.tt);
+    e->store_index_bytes = o.mark;
+    return BZ_OK;
+}
+
 BZ_EXPORT int32_t bz_ownership_row(uint64_t fin_x, uint64_t fin_o, int32_t mover, uint64_t* t_own, uint64_t* t_opp) {
     BZ_REQUIRE(t_own && t_opp && (mover == 1 || mover == -1), "bz_ownership_row: null pointer or mover not +1 / -1");
     u64 a, b;
@@ -3461,6 +3727,7 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
         bz_engine* e = engines[i];
         if (!e || search_is_fused(e)) continue;
         if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
+        if ((rc = store_save(e, streams[i])) != BZ_OK) return rc;
         if (play && (rc = bz_engine_play(e, restart, streams[i])) != BZ_OK) return rc;
     }
     return BZ_OK;

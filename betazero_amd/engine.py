@@ -173,6 +173,25 @@ def check_eval_cache(eval_cache):
     return eval_cache
 
 
+ROOT_STORE_DEFAULT = (256, 3)  # (entries, plies) of the root store an engine with the carry-over cache gets
+
+
+def check_root_store(root_store, eval_cache=True):
+    """None: ROOT_STORE_DEFAULT with eval_cache True / "carry", else off; False: off; (entries, plies): 1 <= entries <= 65536,
+    1 <= plies <= 64.  Returns the pair or None; anything else is refused with ValueError, before any device is touched."""
+    carry = eval_cache is True or (isinstance(eval_cache, str) and eval_cache == "carry")
+    if root_store is None:
+        return ROOT_STORE_DEFAULT if carry else None
+    if root_store is False:
+        return None
+    ok = (isinstance(root_store, (tuple, list)) and len(root_store) == 2 and
+          all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in root_store) and
+          1 <= root_store[0] <= 65536 and 1 <= root_store[1] <= 64)
+    if not ok:
+        raise ValueError(f"root_store must be None, False or (entries in 1..65536, plies in 1..64) (got {root_store!r})")
+    return (int(root_store[0]), int(root_store[1])) if carry else None
+
+
 MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
 
 
@@ -344,7 +363,7 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None, ownership=False):
+                 eval_symmetry=None, fpu=None, ownership=False, root_store=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -402,7 +421,14 @@ class SelfPlayEngine:
         ownership: False = off (the default, unchanged); True = the final board of every finished game is kept
         (ownership_rows()), and examples() / device_examples() carry every row's ownership target `fown`, `fopp`: that board in
         the row's side-to-move frame.  Searches, moves and rows are what they are without it; it combines with everything the
-        engine accepts."""
+        engine accepts.
+
+        root_store: None = the default for the cache mode -- ROOT_STORE_DEFAULT = (entries, plies) with
+        eval_cache True / "carry", off otherwise; False = off; (entries, plies) = a store of that size.  Finished searches of
+        roots fewer than `plies` moves behind a game's start are kept, and a slot whose next root is on file starts from that
+        tree's evaluations.  Results are unchanged; root_store_counters() says how often it fired.  Ignored where the engine
+        does not run the carry-over cache."""
+        self.root_store = check_root_store(root_store, eval_cache)
         self.ownership = check_ownership(ownership)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
@@ -493,6 +519,17 @@ class SelfPlayEngine:
             self.vws = torch.zeros(vbytes + 256, dtype=torch.uint8, device=self.device)
             self._vpad = (-self.vws.data_ptr()) & 255
             self._call(L.bz_engine_set_search_value, self.vws.data_ptr() + self._vpad, vbytes)
+        if self.root_store is not None:  # the engine's root store (caller-owned, like the workspace)
+            S, D = self.root_store
+            rbytes = L.bz_engine_root_store_bytes(C.byref(self.cfg), S, D)
+            if rbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            if rbytes == 0:  # no carry-over cache in this engine (synthetic evaluator, reuse_subtree, leaves_per_step > 1)
+                self.root_store = None
+            else:  # (empty, not zeros: the setter clears the index, and nothing reads an entry the index does not name)
+                self.rws = torch.empty(rbytes + 256, dtype=torch.uint8, device=self.device)
+                rpad = (-self.rws.data_ptr()) & 255
+                self._call(L.bz_engine_set_root_store, self.rws.data_ptr() + rpad, rbytes, S, D)
         if self.ownership:  # the engine's final-board buffer (caller-owned, like the workspace)
             obytes = L.bz_engine_ownership_bytes(C.byref(self.cfg))
             if obytes < 0:
@@ -676,6 +713,13 @@ class SelfPlayEngine:
         # what it was before leaves_per_step existed
         names = _lib.COUNTER_NAMES if self.K > 1 else _lib.COUNTER_NAMES[:_lib.COUNTER_NAMES.index("n_collisions")]
         return dict(zip(names, (int(v) for v in c[:len(names)])))
+
+    def root_store_counters(self):
+        """the root store's counters: n_seeded_evals -- evaluations taken from a seeded tree (part of
+        counters()["n_cache_hits_prev"]) --, n_seeded_searches and n_root_saves (trees filed; at most `entries` per evaluator)"""
+        self._call(_lib.lib().bz_engine_sum_counters)
+        c = self._view(self.lay.counters, torch.int64, (24,)).cpu().numpy()
+        return {"n_seeded_evals": int(c[11]), "n_seeded_searches": int(c[12]), "n_root_saves": int(c[13])}
 
     # leaf buffers for BZ_EVAL_EXTERNAL callers (torch tensors aliasing the workspace): K*B rows, row g*K + j = walk j of game g
     def leaf_buffers(self):
@@ -1108,6 +1152,7 @@ class PipelinedSelfPlay:
         check_forced_playouts(forced_playouts, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_fpu(fpu, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
         check_eval_cache(engine_kwargs.get("eval_cache", True))
+        check_root_store(engine_kwargs.get("root_store"), engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
         # 2 cores per rank against 0.18 -- profiles/r04_host_run_ahead.txt)
         self.run_ahead = run_ahead
@@ -1190,6 +1235,13 @@ class PipelinedSelfPlay:
         """the last search's budgets of all pipelines, in slot order (SelfPlayEngine.budgets)"""
         self.sync()
         return np.concatenate([e.budgets() for e in self.engines])
+
+    def root_store_counters(self):
+        tot = {}
+        for c in self._each(lambda e: e.root_store_counters()):
+            for k, v in c.items():
+                tot[k] = tot.get(k, 0) + v
+        return tot
 
     def counters(self):
         tot = {}

@@ -659,6 +659,25 @@ int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uint64_t* fop
 /* a row's target boards, the function the kernel runs: *t_own = mover == +1 ? fin_x : fin_o, *t_opp = the other board; the
  * target of cell i is bit_i(t_own) - bit_i(t_opp) in {+1, 0, -1}.  mover: +1 or -1.  Host only. */
 int32_t bz_ownership_row(uint64_t fin_x, uint64_t fin_o, int32_t mover, uint64_t* t_own, uint64_t* t_opp);
+/* The root store, opt-in per engine, active only where the engine runs the carry-over cache
+ * (BZ_ENGINE_EVAL_CACHE | BZ_ENGINE_EVAL_CACHE_CARRY with a net evaluator, one leaf per step, no subtree reuse).  The first
+ * searches of a game repeat searches other games of the engine already ran: a finished search whose root lies fewer than
+ * `plies` moves behind the game's start (the two fixed opening plies not counted) is filed under its root position, `entries`
+ * of them at most, and a slot whose next root is on file gets that tree as its "previous search" before bz_engine_root_begin
+ * -- the carry-over then shares its evaluations exactly as it shares those of the slot's own previous search, each hit
+ * confirmed against the stored position.  Results are bit for bit those without the store; counters[7] drops, counters[8] and
+ * [9] rise by as much.  counters[11] = evaluations taken from a seeded tree (part of counters[9]), counters[12] = searches
+ * that were seeded, counters[13] = trees filed.  A change of evaluator (bz_net_update, bz_engine_set_net,
+ * bz_engine_set_eval_symmetry) empties the store at the next search.
+ * Bytes: 256 + 4 x n_idx (n_idx = the power of two >= max(16, 2 x entries)) + 64 x entries + 4 x n_games, then per entry one
+ * slot's arenas: nodes 32 x (sims + 2), edges 16 x (sims + 2) x MAXCH (34 on the Reversi boards), node values 4 x (sims + 2)
+ * and the slot's table 128 x buckets (buckets = the power of two >= max(16, (sims + 2) / 4)), each array 256-byte aligned --
+ * 0.50 MB per entry at 800 simulations.  0 when the config does not run the carry-over cache; -1 for a bad config. */
+int64_t bz_engine_root_store_bytes(const bz_engine_cfg* cfg, int32_t entries, int32_t plies);
+/* on (buf: device memory of >= bz_engine_root_store_bytes bytes, 256-byte aligned, owned by the caller and kept alive while
+ * the store is on; its index is zeroed on `stream`) or off (buf == NULL), between searches.  On an engine without the
+ * carry-over cache the call succeeds and the store stays off. */
+int32_t bz_engine_set_root_store(bz_engine* e, void* buf, int64_t bytes, int32_t entries, int32_t plies, void* stream);
 /* the pi and the action bz_engine_play would write and play, for every slot, after a search: device arrays pi f32
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
@@ -716,7 +735,8 @@ int32_t bz_selfplay_run(bz_engine* e, int32_t restart, void* stream);
 int32_t bz_engines_step(bz_engine* const* engines, void* const* streams, int32_t n, int32_t restart,
                         int32_t run_ahead_sims);
 int32_t bz_engine_reset_counters(bz_engine* e, void* stream);
-/* fold the kernels' per-wave counter slots into the layout's counters[16] array (async) */
+/* fold the kernels' per-wave counter slots into the layout's counters array (async): words 0..9.  Words 10 (n_collisions) and
+ * 11..13 (the root store's) are added to in place by their kernels; 14 and 15 are unused, 16..23 belong to diagnostic builds */
 int32_t bz_engine_sum_counters(bz_engine* e, void* stream);
 
 /* ------------------------------------------------------------------------ */
