@@ -181,6 +181,12 @@ _SIGS = {
     "bz_engine_set_fpu": (i32, [vp, i32, C.c_float, C.c_float, vp, i64, vp]),
     "bz_fpu_mass": (u32, [vp, vp, i32]),
     "bz_fpu_value": (C.c_float, [vp, vp, i32, C.c_float, C.c_float]),
+    "bz_engine_solver_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_solver_check": (i32, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_solver": (i32, [vp, i32, vp, i64, vp]),
+    "bz_engine_root_proven": (i32, [vp, vp, vp, vp, vp]),
+    "bz_solver_node": (i32, [vp, i32]),
+    "bz_solver_pick": (i32, [vp, vp, i32, i32, C.c_uint64]),
     "bz_engine_surprise_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_set_surprise": (i32, [vp, vp, i64, vp]),
     "bz_engine_pack_surprise": (i32, [vp, vp, i64, i32, vp]),

@@ -21,6 +21,7 @@
 // noise (k_root_noise) and subtree reuse (two arenas, dev_reroot) -- DESIGN.md 3.9, 3.10; leaf-parallel search with virtual
 // loss (K walks per game per step, k_leaf_step) -- DESIGN.md 3.12.
 // First-play urgency reduction in the select rule (k_fpu_step and its cap / forced variants, csrc/bz_fpu.h) -- DESIGN.md 3.20.
+// Proven wins, losses and draws (k_solve_step / k_solve_cap_step, the proof pass behind their backup, csrc/bz_solver.h) -- DESIGN.md 3.23.
 // The Gumbel interior rule below the root of a Gumbel search (k_gfull_step, csrc/bz_gumbel_interior.h) -- DESIGN.md 3.21.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
@@ -39,6 +40,7 @@
 #include "bz_math.h"
 #include "bz_rules.h"
 #include "bz_fpu.h"
+#include "bz_solver.h"
 #include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
@@ -60,6 +62,12 @@ __host__ __device__ __forceinline__ int e_action(u32 w0) { return (int)((w0 >> k
 __host__ __device__ __forceinline__ int e_nch(u32 w0) { return (int)((w0 >> kNchShift) & 0x3Fu); }
 __host__ __device__ __forceinline__ bool e_term(u32 w0) { return ((w0 >> kTermShift) & 1u) != 0; }
 __host__ __device__ __forceinline__ int e_val(u32 w0) { return (int)((w0 >> kValShift) & 3u) - 1; }
+//  bit 30 of w0: the edge is PROVEN -- its child is decided with the value in the kValShift bits, for the mover at
+// the child like a terminal child's.  Only the proof pass of the solver kernels sets it; every fresh or copied edge has it clear.
+constexpr int kProvenShift = 30;
+constexpr u32 kProven = 1u << kProvenShift, kDecidedMask = kProven | (1u << kTermShift);
+__host__ __device__ __forceinline__ bool e_decided(u32 w0) { return (w0 & kDecidedMask) != 0; }
+__host__ __device__ __forceinline__ int e_cval(u32 w0) { return e_decided(w0) ? e_val(w0) : kSolverUndecided; }
 __host__ __device__ __forceinline__ u32 e_child(u32 w3) { return w3 & kChildMask; }
 __host__ __device__ __forceinline__ u32 e_edge0(u32 w3) { return w3 >> kChildBits; }
 
@@ -229,6 +237,11 @@ struct GumbelInDev { float* node_v; };
 // writes in front of the play kernel (pi [B][NA], act [B]).  A kernel argument of the two ownership kernels only.
 struct OwnDev { u64 *fin_x, *fin_o; float* pi; int32_t* act; };
 
+// Proven wins, losses and draws (root = nullptr: off), set by bz_engine_set_solver in the caller's buffer: every
+// root's proven value + 2 (0 = undecided) i32 [B] and the two counts of the current search -- nodes newly decided, walks that
+// ended at a proven edge that is not terminal.  bz_engine_root_begin zeroes all of it.  A kernel argument of the solver kernels only.
+struct SolveDev { int32_t* root; u32* counts; };
+
 struct Cnt { u32 v[CNT_N]; };
 
 // Diagnostic build only (betazero_amd.build.build_variant("treestamps", ["-DBZ_EXP_TREE_STAMPS"]), tools/exp_tree_stamps.py):
@@ -336,6 +349,16 @@ __device__ __forceinline__ u32 group_sum_u32(u32 x) {
     if (kGW > 2) x += xchg<2>(x);
     if (kGW > 4) x += xchg<4>(x);
     if (kGW > 8) x += xchg<8>(x);
+    return x;
+}
+
+// OR over the kGW lanes of a group (the solver's node rule)
+template <int kGW>
+__device__ __forceinline__ u32 group_or_u32(u32 x) {
+    if (kGW > 1) x |= xchg<1>(x);
+    if (kGW > 2) x |= xchg<2>(x);
+    if (kGW > 4) x |= xchg<4>(x);
+    if (kGW > 8) x |= xchg<8>(x);
     return x;
 }
 
@@ -643,7 +666,11 @@ __device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const Gumbel
 // loaded together into registers, and the node's own value v_X (gnv, this game's row of the interior buffer) is loaded beside
 // its position: still ONE dependent load per level.  Per-edge terms are computed one edge per lane; max / min are group
 // reductions; the three sums run in ascending edge order (group_seq_sum), so the bits are those of gi_pick_serial.
-template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false, bool kGfull = false>
+// kSolve (k_solve_step / k_solve_cap_step; the plain PUCT branch only): a decided edge (terminal or proven) with
+// c = -1 scores +inf, with c = +1 -inf, with c = 0 takes q = 0; when every edge scores -inf the walk takes edge 0; a walk that
+// takes a decided edge ends there with the edge's value, as at a terminal edge.
+template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false, bool kGfull = false,
+          bool kSolve = false>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
                                            Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f,
@@ -783,11 +810,14 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
                 float u = E.c_puct * e.P;
                 u = u * sq;
                 u = fdiv(u, 1.0f + (float)N);
+                if (kSolve && e_decided(e.w0) && e_val(e.w0) == 0) q = 0.0f;
                 cd.sc = q + u; cd.w0 = e.w0; cd.w3 = e.w3; cd.W = e.W;
+                if (kSolve && e_decided(e.w0) && e_val(e.w0) != 0) cd.sc = e_val(e.w0) < 0 ? __builtin_inff() : -__builtin_inff();
                 if (kForced && depth == 0 && fk > 0.0f && N > 0 && (float)N < forced_nf(fk, e.P, sumN)) cd.sc = __builtin_inff();
             }
             group_argmax<kGW>(cd);
-            if (cd.sc > bests) { bests = cd.sc; best = cd.i; bestw0 = cd.w0; bestw3 = cd.w3; bestW = cd.W; }
+            // (kSolve: the first chunk's winner stands in until a higher score comes -- edge 0 when every edge scores -inf)
+            if (cd.sc > bests || (kSolve && base == 0)) { bests = cd.sc; best = cd.i; bestw0 = cd.w0; bestw3 = cd.w3; bestW = cd.W; }
         }
         if (lead) c.v[CNT_CHILD_SCORED] += (u32)n;
         const u32 eidx = e0 + (u32)best;
@@ -797,7 +827,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
             if (depth < E.maxd) sink.put(depth, sub, eidx, bestw0, bestW);
             else if (lead) atomicOr(&E.flags[FLAG_ERR], ERR_DEPTH);
             depth++;
-            if (e_term(bestw0)) { kind = LEAF_TERMINAL; leaf = child; tval = (float)e_val(bestw0); break; }
+            if (kSolve ? e_decided(bestw0) : e_term(bestw0)) { kind = LEAF_TERMINAL; leaf = child; tval = (float)e_val(bestw0); break; }
             // leaf-parallel: a non-terminal child without edges was created by an earlier walk of this step
             if (kLeafPar && e_nch(bestw0) == 0) { kind = LEAF_COLLIDE; leaf = child; tval = 0.0f; break; }
             // children's visits of X == visits of the edge into X minus the creating one
@@ -1002,6 +1032,50 @@ __device__ __forceinline__ void dev_backup(const EngineDev& E, int g, int sub, i
         backup_edge(edges, pe, val, d == depth - 1, leaf, exp_e0, exp_n);
     }
     if (sub == 0) c.v[CNT_EDGES_BACKED] += (u32)dmax;
+}
+
+// The proof pass behind the backup of a walk that ended in a terminal or proven leaf: upwards from the deepest
+// path edge, the node rule over the block of edges the path edge lies in -- lanes over edges, one OR across the group.  A decided
+// parent marks the path edge into it (behind the backup's own store of that edge) and the pass goes on one level up; it stops
+// at the first undecided parent and at the root, whose value goes to the solver buffer.  Path entries hold no w3: the block of
+// path edge d is the root's (edge 0, root_n) or comes from the words of path edge d - 1.  A truncated path (depth > maxd, ERR_DEPTH)
+// proves nothing.  re0: the caller's register copy of root edge `sub`.
+template <class G>
+__device__ __forceinline__ void dev_prove(const EngineDev& E, const SolveDev& Sv, int g, int sub, const PathEnt* path, int depth,
+                                          int root_n, Edge& re0) {
+    constexpr int kGW = G::GW;
+    if (depth < 1 || depth > E.maxd) return;
+    Edge* edges = E.edges + (size_t)g * E.ecap;
+    const int root_rec = Sv.root[g];
+    u32 n_new = 0;
+    int d = depth - 1;
+    PathEnt pe = path[d];
+    const bool at_proven = !e_term(pe.w0);  // the walk stopped at a proven edge that is not terminal
+    for (;;) {
+        group_fence();  // the backup's stores and the mark below are read here
+        u32 b0 = 0; int n = root_n;
+        PathEnt up = pe;
+        if (d > 0) { up = path[d - 1]; b0 = e_edge0(edges[up.eidx].w3); n = e_nch(up.w0); }
+        if (b0 + (u32)n > (u32)E.ecap) break;  // (never: the walk scored these edges)
+        u32 bits = 0;
+        for (int i = sub; i < n; i += kGW) bits |= solver_edge_bits(e_cval(edges[b0 + i].w0));
+        bits = group_or_u32<kGW>(bits);
+        const int pv = solver_node_value(bits, n);
+        if (pv == kSolverUndecided) break;
+        if (d == 0) {  // the root
+            if (root_rec == 0) { n_new++; if (sub == 0) Sv.root[g] = pv + 2; }
+            break;
+        }
+        n_new++;
+        const u32 w0n = ((up.w0 + 1u) & ~(3u << kValShift)) | ((u32)(pv + 1) << kValShift) | kProven;  // (up.w0 + 1: what the backup stored)
+        if (sub == 0) edges[up.eidx].w0 = w0n;
+        if (d == 1 && (u32)sub == up.eidx) re0.w0 = w0n;
+        --d; pe = up;
+    }
+    if (sub == 0) {
+        if (n_new) atomicAdd(&Sv.counts[0], n_new);
+        if (at_proven) atomicAdd(&Sv.counts[1], 1u);
+    }
 }
 
 template <class G>
@@ -1240,10 +1314,12 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 // simulation 0 starts Wr from 0, so no search needs a reset.
 // kGfull (with kGumbel): the Gumbel interior rule at every level below the root, and every expanded node's value
 // stored in the interior buffer with its expansion, on the EVAL and on the COPY path.
-template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false, bool kGfull = false>
+// kSolve: decided edges in the walk's scores, and the proof pass behind the backup of a terminal or proven leaf; the
+// backup of an evaluated or copied leaf stays the pure-store path it is.
+template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false, bool kGfull = false, bool kSolve = false>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
                                                const u32* budget = nullptr, float fk = 0.0f, const FpuDev* fd = nullptr,
-                                               const GumbelInDev* gi = nullptr) {
+                                               const GumbelInDev* gi = nullptr, const SolveDev* sv = nullptr) {
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1328,6 +1404,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                     if (depth0 == 1 && n > 0) re0.w3 = leaf | (e0 << kChildBits);
                 }
             }
+            if constexpr (kSolve) if (kind == LEAF_TERMINAL) dev_prove<G>(E, *sv, g, sub, path, depth0, root_n, re0);
         }
         st.mark(2);
         if (do_select) {
@@ -1347,7 +1424,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                     dev_select<G, PathHbm<kGW>, false, true, false, false, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, 0.0f, nullptr,
                                                                                  gi->node_v + (size_t)g * E.ncap);
                 } else
-                dev_select<G, PathHbm<kGW>, false, kGumbel, kForced>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
+                dev_select<G, PathHbm<kGW>, false, kGumbel, kForced, false, false, kSolve>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
                 sink.flush(sub, depth);
                 if (sub == 0) {
                     E.hot[g].n_nodes = nn; E.hot[g].leaf_node = leaf2; E.hot[g].depth = (u32)depth;
@@ -1446,6 +1523,19 @@ __global__ void __launch_bounds__(256) k_fpu_forced_cap_step(EngineDev E, CapDev
                                                              u32 sim_idx) {
     const GumbelDev none{};
     tree_step_body<G, false, true, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k, &Fp);
+}
+
+// The tree steps with proven wins, losses and draws: k_tree_step / k_cap_step with the solver's select rule and
+// the proof pass behind the backup.  Sv travels as a kernel argument.
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_step(EngineDev E, SolveDev Sv, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, false, false, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, 0.0f, nullptr, nullptr, &Sv);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_cap_step(EngineDev E, CapDev Cp, SolveDev Sv, int do_expand, int do_select, u32 sim_idx) {
+    const GumbelDev none{};
+    tree_step_body<G, false, true, false, false, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, 0.0f, nullptr, nullptr, &Sv);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -2029,6 +2119,62 @@ __global__ void __launch_bounds__(256) k_cap_play(EngineDev E, CapDev Cp, int re
     dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
 }
 
+// The move of a search with proven edges, shared by k_solve_play, k_solve_cap_play and k_root_policy: pi stays
+// N / sum N (dev_puct_choice writes it), the played edge is solver_pick's
+template <class G, bool kPi = true>
+__device__ __forceinline__ int dev_solver_choice(const EngineDev& E, int g, const Edge* ed, int n, u32 sumN, int made, int round,
+                                                 float* pi) {
+    const int plain = dev_puct_choice<G, kPi>(E, g, ed, n, sumN, made, round, pi);
+    bool any = false;
+    for (int i = 0; i < n; ++i) any = any || e_decided(ed[i].w0);
+    if (!any) return plain;
+    const bool tau1 = made < E.temp_moves;
+    const u64 gid = E.id_base + (u64)round * E.id_stride + (u64)g;
+    return solver_pick(n, [ed](int i) { return (u64)e_N(ed[i].w0); }, [ed](int i) { return e_cval(ed[i].w0); }, tau1,
+                       tau1 ? rng_draw(E.seed, gid, (u64)made) : 0ULL);
+}
+
+// M5 with the solver's move rule: k_play / k_cap_play with dev_solver_choice
+template <class G, bool kCap>
+__device__ __forceinline__ void solve_play_body(const EngineDev& E, const u32* budget, int restart) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    Node root = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+    int n = (int)(root.info & 0xFFu);
+    u32 sumN = 0;
+    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
+    const bool full = kCap ? budget[g] >= (u32)E.sims : true;
+    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
+    if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
+    size_t row = rowbase + nex;
+    const int pick = full ? dev_solver_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
+                          : dev_solver_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
+    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_play(EngineDev E, int restart) { solve_play_body<G, false>(E, nullptr, restart); }
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_cap_play(EngineDev E, CapDev Cp, int restart) { solve_play_body<G, true>(E, Cp.budget, restart); }
+
+// the proof state of every slot's root: edge_out [B][NA] the decided value of the edge of every action (2:
+// undecided or no such edge), root_out [B] the root's recorded value (2: undecided; idle slots: all 2)
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_read(EngineDev E, SolveDev Sv, int8_t* edge_out, int8_t* root_out) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B) return;
+    int8_t* eo = edge_out + (size_t)g * G::NA;
+    for (int a = 0; a < G::NA; ++a) eo[a] = (int8_t)kSolverUndecided;
+    root_out[g] = (int8_t)kSolverUndecided;
+    if (E.g_state[g] != 0) return;
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    for (int i = 0; i < (int)(r.info & 0xFFu); ++i) { const u32 w0 = ed[i].w0; eo[e_action(w0)] = (int8_t)e_cval(w0); }
+    const int rec = Sv.root[g];
+    if (rec != 0) root_out[g] = (int8_t)(rec - 2);
+}
+
 // The move and the pi of a search with forced playouts: the DESIGN.md 3.7 choice over the raw N; pi from the
 // pruned N' (F.prune) or the raw N.  pi = nullptr: the choice alone.
 template <class G>
@@ -2102,7 +2248,7 @@ __global__ void __launch_bounds__(256) k_forced_root_policy(EngineDev E, CapDev 
 
 // the pi and the action bz_engine_play would write and play, into pi [B][NA] / action [B] (idle or finished slots: zeros, -1)
 template <class G>
-__global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, float* pi_out, int32_t* act_out) {
+__global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, int solve, float* pi_out, int32_t* act_out) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.B) return;
     float* pi = pi_out + (size_t)g * G::NA;
@@ -2120,7 +2266,8 @@ __global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, 
     } else {
         u32 sumN = 0;
         for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
-        pick = dev_puct_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+        pick = solve ? dev_solver_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi)  // 
+                     : dev_puct_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
     }
     act_out[g] = e_action(ed[pick].w0);
 }
@@ -2585,6 +2732,8 @@ struct bz_engine {
     SurpDev surp;      // policy surprise weighting (bz_engine_set_surprise); surp.prior = nullptr: off
     FpuDev fpu;        // first-play urgency reduction (bz_engine_set_fpu); fpu.root_w = nullptr: off
     int fpu_done;      // ... simulations selected so far in the current search: what an expand-only step has backed up when it is done
+    SolveDev solve;    // proven wins, losses and draws (bz_engine_set_solver); solve.root = nullptr: off
+    int64_t solve_bytes;  // ... the bytes bz_engine_root_begin zeroes in its buffer
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
     OwnDev own;        // ownership targets (bz_engine_set_ownership); own.fin_x = nullptr: off
     StoreDev store;    // the root store (bz_engine_set_root_store); store.S = 0: off
@@ -2738,6 +2887,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->own = OwnDev{};
     e->store = StoreDev{}; e->store_index_bytes = 0;
     e->fpu = FpuDev{}; e->fpu_done = 0;
+    e->solve = SolveDev{}; e->solve_bytes = 0;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2905,6 +3055,8 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     }
     e->pack_parity = 1;
     e->fpu_done = 0;
+    if (e->solve.root)  //  no root is decided, both counts 0
+        BZ_HIP(hipMemsetAsync(e->solve.root, 0, (size_t)e->solve_bytes, (hipStream_t)stream));
     return BZ_OK;
 }
 
@@ -2922,6 +3074,12 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
         else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_fpu_cap_step, stream, e->dev, e->cap, e->fpu, do_expand, do_select, sim_idx);
         else BZ_DISPATCH_G(e, k_fpu_step, stream, e->dev, e->fpu, do_expand, do_select, sim_idx);
         if (do_select) { e->pack_parity = (int)(sim_idx & 1u); e->fpu_done = (int)sim_idx + 1; }
+        return BZ_OK;
+    }
+    if (e->solve.root) {  //  the step kernels with the solver's select rule and proof pass
+        if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_solve_cap_step, stream, e->dev, e->cap, e->solve, do_expand, do_select, sim_idx);
+        else BZ_DISPATCH_G(e, k_solve_step, stream, e->dev, e->solve, do_expand, do_select, sim_idx);
+        if (do_select) e->pack_parity = (int)(sim_idx & 1u);
         return BZ_OK;
     }
     if (e->gumbel.m > 0 && e->gin.node_v) BZ_DISPATCH_G(e, k_gfull_step, stream, e->dev, e->gumbel, e->gin, do_expand, do_select, sim_idx);  // 
@@ -3012,9 +3170,9 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
     const bool noise = root_prep(e);
     // (playout cap randomisation: per-slot budgets live in the step kernels only; forced playouts: the forced root rule too)
-    // (first-play urgency reduction: the rule lives in the step kernels only)
+    // (first-play urgency reduction, the solver: the rule lives in the step kernels only)
     if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f) &&
-        !e->fpu.root_w) {
+        !e->fpu.root_w && !e->solve.root) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -3136,6 +3294,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
     BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_gumbel: Gumbel root search does not combine with forced playouts (bz_engine_set_forced_playouts)");
     BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_gumbel: Gumbel root search does not combine with first-play urgency reduction (bz_engine_set_fpu)");
+    BZ_REQUIRE(!e->solve.root, "bz_engine_set_gumbel: Gumbel root search does not combine with the solver (bz_engine_set_solver)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
     const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
     if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -3266,6 +3425,7 @@ BZ_EXPORT int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t p
     }
     if (const char* why = forced_refusal(e->cfg, k)) { set_error("bz_engine_set_forced_playouts: %s", why); return BZ_EINVAL; }
     BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_forced_playouts: forced playouts do not combine with Gumbel root search (bz_engine_set_gumbel)");
+    BZ_REQUIRE(!(k > 0.0f && e->solve.root), "bz_engine_set_forced_playouts: forced playouts do not combine with the solver (bz_engine_set_solver)");
     e->forced.k = k; e->forced.prune = prune ? 1 : 0;
     return BZ_OK;
 }
@@ -3320,6 +3480,7 @@ BZ_EXPORT int32_t bz_engine_set_fpu(bz_engine* e, int32_t on, float reduction, f
     BZ_REQUIRE(fpu_red_ok(reduction) && fpu_red_ok(root_reduction),
                "bz_engine_set_fpu: first-play urgency reduction: reduction and root_reduction must be finite and >= 0");
     BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_fpu: first-play urgency reduction does not combine with Gumbel root search (bz_engine_set_gumbel)");
+    BZ_REQUIRE(!e->solve.root, "bz_engine_set_fpu: first-play urgency reduction does not combine with the solver (bz_engine_set_solver)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_fpu: the buffer must be non-null and 256-byte aligned");
     const int64_t need = fpu_bytes(e->cfg);
     if (bytes < need) { set_error("bz_engine_set_fpu: buffer too small (%lld < %lld)", (long long)bytes, (long long)need); return BZ_ENOMEM; }
@@ -3339,6 +3500,78 @@ BZ_EXPORT float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float
     const uint32_t S = bz_fpu_mass(N, P, n);
     if (S == 0xFFFFFFFFu) return __builtin_nanf("");
     return fpu_value(S, q_node, reduction);
+}
+
+/* ---- proven wins, losses and draws */
+namespace {
+// what the solver refuses in a config (nullptr: nothing)
+const char* solver_refusal(const bz_engine_cfg& c) {
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "the solver does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "the solver does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*): concurrent walks race on proofs";
+    return nullptr;
+}
+struct SolveOffsets { int64_t root, counts, total; };
+inline SolveOffsets solver_carve(const bz_engine_cfg& c) {
+    Carver k; SolveOffsets o;
+    o.root = k.take((int64_t)c.n_games * 4); o.counts = k.take(8); o.total = k.off;
+    return o;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_solver_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_solver_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_solver_bytes: %s", kBadCfg); return -1; }
+    if (const char* why = solver_refusal(*cfg)) { set_error("bz_engine_solver_bytes: %s", why); return -1; }
+    return solver_carve(*cfg).total;
+}
+
+BZ_EXPORT int32_t bz_engine_solver_check(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_solver_check: %s", kBadFlags); return BZ_EINVAL; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_solver_check: %s", kBadCfg); return BZ_EINVAL; }
+    if (const char* why = solver_refusal(*cfg)) { set_error("bz_engine_solver_check: %s", why); return BZ_EINVAL; }
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_set_solver(bz_engine* e, int32_t on, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_solver: null engine");
+    if (!on) {  // off: the plain (the cap's) kernels again
+        e->solve = SolveDev{}; e->solve_bytes = 0;
+        return BZ_OK;
+    }
+    if (const char* why = solver_refusal(e->cfg)) { set_error("bz_engine_set_solver: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_solver: the solver does not combine with Gumbel root search (bz_engine_set_gumbel)");
+    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_solver: the solver does not combine with forced playouts (bz_engine_set_forced_playouts): both score +inf");
+    BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_solver: the solver does not combine with first-play urgency reduction (bz_engine_set_fpu)");
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_solver: the buffer must be non-null and 256-byte aligned");
+    const SolveOffsets o = solver_carve(e->cfg);
+    if (bytes < o.total) { set_error("bz_engine_set_solver: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));
+    char* b = static_cast<char*>(buf);
+    e->solve.root = reinterpret_cast<int32_t*>(b + o.root); e->solve.counts = reinterpret_cast<u32*>(b + o.counts);
+    e->solve_bytes = o.total;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_root_proven(bz_engine* e, int8_t* edge_out, int8_t* root_out, uint32_t* counts_out, void* stream) {
+    BZ_REQUIRE(e && edge_out && root_out && counts_out, "bz_engine_root_proven: null pointer");
+    BZ_REQUIRE(e->solve.root, "bz_engine_root_proven: the solver is off (bz_engine_set_solver)");
+    BZ_DISPATCH(e, k_solve_read, stream, e->dev, e->solve, edge_out, root_out);
+    BZ_HIP(hipMemcpyAsync(counts_out, e->solve.counts, 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_solver_node(const int8_t* vals, int32_t n) {
+    if (!(vals && n >= 1 && n <= 255)) { set_error("bz_solver_node: null pointer or n outside 1 .. 255"); return -128; }
+    for (int i = 0; i < n; ++i)
+        if (vals[i] < -1 || vals[i] > 2) { set_error("bz_solver_node: vals[%d] = %d is none of -1, 0, +1, 2 (undecided)", i, (int)vals[i]); return -128; }
+    return solver_node(n, [vals](int i) { return (int)vals[i]; });
+}
+
+BZ_EXPORT int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t n, int32_t tau1, uint64_t draw) {
+    if (!(N && vals && n >= 1 && n <= 255)) { set_error("bz_solver_pick: null pointer or n outside 1 .. 255"); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (vals[i] < -1 || vals[i] > 2) { set_error("bz_solver_pick: vals[%d] = %d is none of -1, 0, +1, 2 (undecided)", i, (int)vals[i]); return -1; }
+    return solver_pick(n, [N](int i) { return (u64)N[i]; }, [vals](int i) { return (int)vals[i]; }, tau1 != 0, (u64)draw);
 }
 
 /* ---- policy surprise weighting */
@@ -3545,7 +3778,7 @@ BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action
         BZ_DISPATCH(e, k_forced_root_policy, stream, e->dev, e->cap, e->forced, pi, action);
         return BZ_OK;
     }
-    BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, pi, action);
+    BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, e->solve.root ? 1 : 0, pi, action);
     return BZ_OK;
 }
 
@@ -3574,6 +3807,8 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
         else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH(e, k_forced_cap_play, stream, e->dev, e->cap, e->forced, (int)restart);
         else if (e->forced.k > 0.0f) BZ_DISPATCH(e, k_forced_play, stream, e->dev, e->forced, (int)restart);  // 
+        else if (e->solve.root && e->cap.fast > 0) BZ_DISPATCH(e, k_solve_cap_play, stream, e->dev, e->cap, (int)restart);  // 
+        else if (e->solve.root) BZ_DISPATCH(e, k_solve_play, stream, e->dev, (int)restart);
         else if (e->cap.fast > 0) BZ_DISPATCH(e, k_cap_play, stream, e->dev, e->cap, (int)restart);  // 
         else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
@@ -3678,7 +3913,7 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
 static bool search_is_fused(const bz_engine* e) {
     const int ek = e->cfg.eval_kind;
     return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && e->dev.K == 1 &&
-           e->cap.fast == 0 && !(e->forced.k > 0.0f) && !e->fpu.root_w;
+           e->cap.fast == 0 && !(e->forced.k > 0.0f) && !e->fpu.root_w && !e->solve.root;
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree

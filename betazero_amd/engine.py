@@ -344,6 +344,28 @@ def check_fpu(fpu, reuse_subtree=False, leaves_per_step=1, gumbel=None):
     return Fpu(*out)
 
 
+def check_solver(solver, reuse_subtree=False, leaves_per_step=1, gumbel=None, forced_playouts=None, fpu=None):
+    """proven wins, losses and draws: a bool; True is refused with subtree reuse, leaves_per_step > 1, Gumbel
+    root search, forced playouts and first-play urgency reduction (ValueError, before any device is touched)"""
+    if solver is None:
+        return False
+    if not isinstance(solver, (bool, np.bool_)):
+        raise ValueError(f"solver must be a bool (got {solver!r})")
+    if not solver:
+        return False
+    if reuse_subtree:
+        raise ValueError("solver: proofs do not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("solver: proofs do not combine with leaves_per_step > 1 (concurrent walks race on proofs)")
+    if gumbel is not None and gumbel is not False:
+        raise ValueError("solver: proofs do not combine with Gumbel root search (gumbel)")
+    if forced_playouts is not None and forced_playouts is not False:
+        raise ValueError("solver: proofs do not combine with forced_playouts (both score +inf)")
+    if fpu is not None and fpu is not False:
+        raise ValueError("solver: proofs do not combine with first-play urgency reduction (fpu)")
+    return True
+
+
 def check_search_value(search_value):
     """search-value targets: a bool, anything else is refused (ValueError, before any device is touched)"""
     if not isinstance(search_value, (bool, np.bool_)):
@@ -363,7 +385,7 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None, ownership=False, root_store=None):
+                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -427,7 +449,14 @@ class SelfPlayEngine:
         eval_cache True / "carry", off otherwise; False = off; (entries, plies) = a store of that size.  Finished searches of
         roots fewer than `plies` moves behind a game's start are kept, and a slot whose next root is on file starts from that
         tree's evaluations.  Results are unchanged; root_store_counters() says how often it fired.  Ignored where the engine
-        does not run the carry-over cache."""
+        does not run the carry-over cache.
+
+        solver: False = off (the default, unchanged); True = the search books proven wins, losses and draws:
+        an edge whose child is decided is marked, the mark travels up the path with the backup, the select rule never
+        walks through a decided edge, and play() / root_policy() play the lowest winning move and avoid lost ones.  pi stays
+        N / sum N.  proven() reads the proof state; set_solver() changes it between searches.  Combines with Dirichlet
+        noise, playout_cap, surprise, search_value, ownership, eval_symmetry, every evaluator, eval_cache mode and the root
+        store.  Refused with reuse_subtree, leaves_per_step > 1, gumbel, forced_playouts and fpu."""
         self.root_store = check_root_store(root_store, eval_cache)
         self.ownership = check_ownership(ownership)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
@@ -443,6 +472,7 @@ class SelfPlayEngine:
         self.forced_playouts = check_forced_playouts(forced_playouts, reuse_subtree, self.K, gumbel)
         self.fpu = check_fpu(fpu, reuse_subtree, self.K, gumbel)
         self._reuse = bool(reuse_subtree)
+        self.solver = check_solver(solver, reuse_subtree, self.K, gumbel, forced_playouts, fpu)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -502,6 +532,8 @@ class SelfPlayEngine:
             self._call(L.bz_engine_set_forced_playouts, self.forced_playouts.k, int(self.forced_playouts.prune))
         if self.fpu is not None:
             self._set_fpu(self.fpu)
+        if self.solver:
+            self._set_solver(True)
         if self.surprise:  # the engine's surprise buffer (caller-owned, like the workspace)
             sbytes = L.bz_engine_surprise_bytes(C.byref(self.cfg))
             if sbytes < 0:
@@ -618,6 +650,41 @@ class SelfPlayEngine:
         self.drain()
         self._set_fpu(fp)
         self.fpu = fp
+
+    def _set_solver(self, on):
+        L = _lib.lib()
+        if not on:
+            self._call(L.bz_engine_set_solver, 0, None, 0)
+            return
+        if getattr(self, "pws", None) is None:  # the engine's proof buffer (caller-owned, like the workspace)
+            pbytes = L.bz_engine_solver_bytes(C.byref(self.cfg))
+            if pbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.pws = torch.zeros(pbytes + 256, dtype=torch.uint8, device=self.device)
+            self._ppad, self._pbytes = (-self.pws.data_ptr()) & 255, pbytes
+        self._call(L.bz_engine_set_solver, 1, self.pws.data_ptr() + self._ppad, self._pbytes)
+
+    def set_solver(self, solver):
+        """switch the solver on or off, between searches"""
+        on = check_solver(solver, self._reuse, self.K, self.gumbel, self.forced_playouts, self.fpu)
+        self.drain()
+        self._set_solver(on)
+        self.solver = on
+
+    def proven(self):
+        """after a search with the solver on: (root, edges, counts) -- root: per slot the root's proven value
+        for its mover (-1, 0, +1) or None; edges: int8 [B, NA], the decided value of the root edge of every action for the
+        mover AFTER it (-1: the move wins), 2 where undecided or no such edge; counts: {"n_decided": nodes newly decided in
+        the last search, "n_proven_stops": walks that ended at a decided edge that is not terminal}"""
+        if not self.solver:
+            raise RuntimeError("proven(): the solver is off")
+        edge = torch.empty((self.B, self.na), dtype=torch.int8, device=self.device)
+        root = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        cnt = torch.empty(2, dtype=torch.int32, device=self.device)
+        self._call(_lib.lib().bz_engine_root_proven, edge.data_ptr(), root.data_ptr(), cnt.data_ptr())
+        r, c = root.cpu().numpy(), cnt.cpu().numpy().view(np.uint32)
+        return ([None if v == 2 else int(v) for v in r], edge.cpu().numpy(),
+                {"n_decided": int(c[0]), "n_proven_stops": int(c[1])})
 
     def search(self):
         self._call(_lib.lib().bz_engine_search)
@@ -1140,9 +1207,10 @@ class PipelinedSelfPlay:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
                  forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False,
-                 **engine_kwargs):
+                 solver=False, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_ownership(ownership)
+        check_solver(solver, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel, forced_playouts, fpu)
         # every pipeline gets the same seed, so the same position has the same orientation in all of them
         eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
         check_search_value(search_value)
@@ -1164,7 +1232,7 @@ class PipelinedSelfPlay:
         self.engines = [SelfPlayEngine(game, self.sizes[i], sims, evaluator, net, game_id_base=game_id_base + sum(self.sizes[:i]),
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
                                        playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                                       search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership,
+                                       search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership, solver=solver,
                                        **engine_kwargs)
                         for i in range(pipelines)]
         self.surprise, self.search_value, self.ownership = bool(surprise), bool(search_value), bool(ownership)
@@ -1358,7 +1426,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False):
+              surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False, solver=False):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1378,6 +1446,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
     check_forced_playouts(forced_playouts, reuse_subtree, leaves_per_step, gumbel)
     check_fpu(fpu, reuse_subtree, leaves_per_step, gumbel)
+    check_solver(solver, reuse_subtree, leaves_per_step, gumbel, forced_playouts, fpu)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"
@@ -1389,7 +1458,7 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
                            gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership)
+                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership, solver=solver)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import check_eval_cache, check_fpu, check_gumbel, check_leaves_per_step, check_sims
+from .engine import check_eval_cache, check_fpu, check_gumbel, check_leaves_per_step, check_sims, check_solver
 
 
 @dataclass
@@ -26,7 +26,8 @@ class MatchPlayer:
     eval_symmetry (True or a symmetry.EvalSymmetry): DESIGN.md 3.19, the side evaluates every leaf under a hashed board
     symmetry (True: seed 0) -- a match stays a pure function of its arguments.  fpu (True or an engine.Fpu): DESIGN.md 3.20,
     the side searches with first-play urgency reduction (not with gumbel or leaves_per_step > 1).  Each side has its own
-    GumbelConfig.interior ("puct" or "gumbel")."""
+    GumbelConfig.interior ("puct" or "gumbel").  solver=True: DESIGN.md 3.23, the side books proven wins, losses and
+    draws and plays the solver's move (not with gumbel, fpu or leaves_per_step > 1)."""
     sims: int = 800
     net: object = None
     evaluator: str = None
@@ -36,6 +37,7 @@ class MatchPlayer:
     eval_cache: object = True
     eval_symmetry: object = None
     fpu: object = None
+    solver: bool = False
 
     def checked(self, game, n_games, side):
         """-> (evaluator name, GumbelConfig or None); ValueError for anything a match cannot play, before any device is touched"""
@@ -44,6 +46,7 @@ class MatchPlayer:
         gumbel = check_gumbel(self.gumbel, leaves_per_step=k)
         check_eval_cache(self.eval_cache)
         check_fpu(self.fpu, False, k, self.gumbel)
+        check_solver(self.solver, False, k, self.gumbel, None, self.fpu)
         is_mlp = type(self.net).__name__ == "DeviceMLP"
         ev = self.evaluator or (("mlp_f32" if is_mlp else "net_bf16") if self.net is not None else "uniform")
         if not isinstance(ev, str) or ev not in ("uniform", "hash", "net_f32", "net_bf16", "net_fp8", "mlp_f32", "mlp_bf16"):
@@ -226,7 +229,7 @@ def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cud
     dev = torch.device(device)
     B = int(n_games)
     engs = [SelfPlayEngine(ename, B, p.sims, ev, p.net, p.c_puct, device=device, eval_cache=p.eval_cache,
-                           leaves_per_step=p.leaves_per_step, gumbel=gum, eval_symmetry=p.eval_symmetry, fpu=p.fpu)
+                           leaves_per_step=p.leaves_per_step, gumbel=gum, eval_symmetry=p.eval_symmetry, fpu=p.fpu, solver=bool(p.solver))
             for p, ev, gum in ((a, ev_a, gum_a), (b, ev_b, gum_b))]
     m = Match(ename, B, device)
     streams = pipeline_streams(dev, 2)

@@ -153,15 +153,20 @@ class MCTSPlayer(Player):
     so it is deterministic.  eval_symmetry (True or a symmetry.EvalSymmetry): every leaf is evaluated under a hashed board
     symmetry (True: seed 0); net evaluators on Reversi only.  fpu (True or an engine.Fpu): first-play urgency
     reduction in the select rule; not with gumbel or leaves_per_step > 1.  GumbelConfig(interior="gumbel"):
-    the Gumbel interior rule below the root instead of PUCT."""
+    the Gumbel interior rule below the root instead of PUCT.  solver=True: the search books proven wins,
+    losses and draws and the move is the solver's (SelfPlayEngine.root_policy): the lowest proven win, never
+    a proven loss while another move is left; last_proven is then the root's proven value for the mover or None; not with
+    gumbel, fpu or leaves_per_step > 1."""
 
     def __init__(self, symbol, sims=800, net=None, evaluator=None, c_puct=1.5, device="cuda:0", leaves_per_step=1,
-                 gumbel=None, eval_symmetry=None, fpu=None):
-        from .engine import check_fpu, check_gumbel, check_leaves_per_step, check_sims
+                 gumbel=None, eval_symmetry=None, fpu=None, solver=False):
+        from .engine import check_fpu, check_gumbel, check_leaves_per_step, check_sims, check_solver
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
         self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step (DESIGN.md 3.12)
         self.gumbel = check_gumbel(gumbel, leaves_per_step=self.leaves_per_step)
         self.fpu = check_fpu(fpu, False, self.leaves_per_step, gumbel)
+        self.solver = check_solver(solver, False, self.leaves_per_step, gumbel, None, fpu)
+        self.last_proven = None  # solver mode: the root's proven value of the last search (-1, 0, +1) or None
         self.symbol, self.sims, self.net, self.c_puct, self.device = symbol, sims, net, c_puct, device
         # evaluator: "uniform" | "hash" | "net_bf16" | "net_f32" | "net_fp8", or a callable (own, opp, kind) -> (logits, value)
         # on CUDA tensors (SelfPlayEngine.search_external): any torch module, e.g. an MLP for tic-tac-toe
@@ -182,7 +187,7 @@ class MCTSPlayer(Player):
         if game not in self._eng:
             self._eng[game] = SelfPlayEngine(game, 1, self.sims, self.evaluator, self.net, self.c_puct,
                                              device=self.device, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel,
-                                             eval_symmetry=self.eval_symmetry, fpu=self.fpu)
+                                             eval_symmetry=self.eval_symmetry, fpu=self.fpu, solver=self.solver)
         return self._eng[game]
 
     def get_move(self, board):
@@ -204,7 +209,9 @@ class MCTSPlayer(Player):
         N, _, _ = eng.root_stats()
         eng.status()  # raises on engine error flags (e.g. terminal root)
         self.last_visits = N[0]
-        if self.gumbel is not None:
+        if self.solver:
+            self.last_proven = eng.proven()[0][0]
+        if self.gumbel is not None or self.solver:
             pi, act = eng.root_policy()
             self.last_policy = pi[0]
             a = int(act[0])

@@ -558,6 +558,50 @@ uint32_t bz_fpu_mass(const uint32_t* N, const float* P, int32_t n);
 /* f of that node for a node value q_node and a reduction: fpu_value(S, q_node, reduction) as the kernels compute it; NaN for
  * bad arguments.  Host only. */
 float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float q_node, float reduction);
+/* Proven wins, losses and draws (MCTS-Solver, Winands et al. 2008; LC0's "certainty propagation"), opt-in per
+ * engine.  It runs no second search: it books what the walks of the search already find.
+ * State: the edge into a child X is DECIDED with a value c in {-1, 0, +1} for the mover at X -- the convention of the terminal
+ *   value an edge already stores.  An edge into a terminal child is decided from its creation; another edge becomes decided by
+ *   the proof pass (bit 30 of the edge's word 0, the value in the bits of the terminal value).  An edge without a child, and
+ *   every edge an expansion, an evaluation-cache copy or the root store writes, is undecided: a cached evaluation carries priors
+ *   and a value, never a proof.
+ * Node rule, for a node X with n edges of decided values c_i: X is decided +1 as soon as some c_i = -1; otherwise X is decided
+ *   only when all n edges are decided, with max over i of -c_i.  The colours alternate on every edge, passes included: a pass
+ *   node (n = 1) is decided exactly when its child is.  All of it is integer: bz_solver_node is the function the kernels run.
+ * Backup: when the leaf of a backup was terminal or a decided edge, the node rule runs on the block of edges the deepest path edge
+ *   lies in; a decided parent marks the path edge into it and the pass goes on one level up; it stops at the first undecided
+ *   parent, at the root -- whose value is recorded per game in the caller's buffer -- and proves nothing on a path longer than
+ *   the engine's depth limit.  The backup of an evaluated leaf is untouched.
+ * Select: the scores of DESIGN.md 3.3 with (a) an edge decided c = -1 (the move wins) scoring +inf, (b) an edge decided c = +1
+ *   scoring -inf -- edge 0 when every edge does -- and (c) an edge decided c = 0 taking q = 0 exactly, its u unchanged; ascending
+ *   order and the strict first maximum as before.  A walk that takes a decided edge ends there with value c and needs no
+ *   evaluator row: no walk passes a decided edge, and the root's visits still sum to the simulations.
+ * Move (bz_engine_play, bz_engine_root_policy; bz_solver_pick is the function): the lowest root edge decided c = -1 at every
+ *   temperature; otherwise the rule of DESIGN.md 3.7 over the edges not decided c = +1 (sampling: the draw modulo THEIR visit
+ *   sum); when every edge is decided +1 or the remaining visit sum is 0, over all edges.  The recorded pi stays N / sum N.
+ * Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step, Gumbel root search, forced playouts,
+ * first-play urgency reduction (the setters refuse each other).  Dirichlet noise, the playout cap, surprise, search value,
+ * ownership, evaluation symmetry, every evaluator (the external one through the step API), every evaluation-cache mode and
+ * the root store work unchanged.  Searches go through the step kernels. */
+/* bytes of the caller-owned buffer: the roots' values i32 [n_games] and two u32 counts, each rounded up to 256 bytes.  Needs no
+ * GPU; -1 (bz_last_error says why) for a bad config or a refused combination. */
+int64_t bz_engine_solver_bytes(const bz_engine_cfg* cfg);
+/* BZ_OK when an engine of this config accepts bz_engine_set_solver(e, 1, ...), else BZ_EINVAL.  Needs no GPU. */
+int32_t bz_engine_solver_check(const bz_engine_cfg* cfg);
+/* switch the solver on (on != 0) or off (on == 0: the plain kernels again), between searches.  buf: device memory of >=
+ * bz_engine_solver_bytes bytes, 256-byte aligned, owned by the caller and kept alive while the mode is on; zeroed on `stream`
+ * here and by every bz_engine_root_begin. */
+int32_t bz_engine_set_solver(bz_engine* e, int32_t on, void* buf, int64_t bytes, void* stream);
+/* the proof state after a search, into device memory: edge_out int8 [n_games][NA], the decided value of the root edge of every
+ * action (2: undecided, or no such edge); root_out int8 [n_games], the root's recorded value (2: undecided); counts_out
+ * uint32 [2]: nodes newly decided in this search (roots included), walks that ended at a decided edge that is not terminal. */
+int32_t bz_engine_root_proven(bz_engine* e, int8_t* edge_out, int8_t* root_out, uint32_t* counts_out, void* stream);
+/* the node rule: vals [n] in {-1, 0, +1, 2 = undecided}, n in 1 .. 255; returns the node's value or 2; -128 for bad arguments.
+ * Host only. */
+int32_t bz_solver_node(const int8_t* vals, int32_t n);
+/* the move rule: N, vals [n] the root edges' visits and decided values, tau1 != 0: sampling with the 64-bit draw, else the
+ * first maximum; returns the edge index; -1 for bad arguments.  Host only. */
+int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t n, int32_t tau1, uint64_t draw);
 /* Policy surprise weighting (KataGo, Wu 2019, section 3.3), opt-in per engine.  Every row bz_engine_play
  * records gets kl = sum over the root's edges in ascending action order with pi_a > 0 of pi_a * (logf(pi_a) - logf(max(P_a,
  * FLT_MIN))), every operation one binary32 operation, then kl > 0 ? kl : 0 (a rounding negative or a NaN: 0).

@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
 from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
-                                 check_playout_cap, concat_device_examples)
+                                 check_playout_cap, check_solver, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
@@ -100,6 +100,8 @@ def main():
                     "with 0, in self-play, for both players of the gate and for the arena's search player; not given = off (0 is a "
                     "reduction).  Not with --gumbel")
     ap.add_argument("--fpu-root-reduction", type=float, default=0.1, help="the reduction at the root under --fpu-reduction (KataGo's 0.1)")
+    ap.add_argument("--solver", action="store_true", help="proven wins, losses and draws (DESIGN.md 3.23) in self-play, for both players "
+                    "of the gate and for the arena's search player.  Not with --gumbel, --forced-k or --fpu-reduction")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -149,6 +151,7 @@ def main():
     cap = check_playout_cap(PlayoutCap(args.fast_sims, args.full_prob) if args.fast_sims else None, args.sims, gumbel=gumbel)
     forced = check_forced_playouts(ForcedPlayouts(args.forced_k, not args.no_prune) if args.forced_k else None, gumbel=gumbel)
     fpu = check_fpu(Fpu(args.fpu_reduction, args.fpu_root_reduction) if args.fpu_reduction is not None else None, gumbel=gumbel)
+    solver = check_solver(args.solver, gumbel=gumbel, forced_playouts=forced, fpu=fpu)
     lines = []
 
     def emit(d):
@@ -159,7 +162,7 @@ def main():
         t0 = time.time()
         try:
             res = play_arena("reversi", args.arena_games, args.arena_sims, opponent_depth=depth or args.depth, evaluator=evaluator,
-                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel, fpu=fpu)
+                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel, fpu=fpu, solver=solver)
         except RuntimeError:  # keep the weights that were in play for a post-mortem
             if args.out:
                 np.save(args.out + ".failed_params.npy", module.flat_params())
@@ -178,7 +181,7 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, search_value=use_vt, fpu=fpu, ownership=args.ownership,
+                               surprise=args.surprise, search_value=use_vt, fpu=fpu, solver=solver, ownership=args.ownership,
                                eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
@@ -241,8 +244,8 @@ def main():
         gate = {}
         if args.gate_games:  # the candidate (A) against the net self-play uses (B)
             t2 = time.time()
-            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu),
-                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu), opening_plies=args.opening_plies,
+            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu, solver=solver),
+                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu, solver=solver), opening_plies=args.opening_plies,
                              seed=args.seed * 1000 + it)
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
@@ -261,7 +264,7 @@ def main():
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
               **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
-              **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **optim,
+              **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **({"solver": True} if solver else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               # the ownership loss L_own over the last (and the first) tenth of the steps
               **({"own": round(float(tail[3]), 4), "own_first_tenth": round(float(head[3]), 4), "own_weight": args.own_weight}
