@@ -13,7 +13,7 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "Player", "ReversiPlayer", "RandomPlayer", "ReversiRandomPlayer", "MCTSPlayer",
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
            "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
-           "MatchPlayer", "MatchResult", "play_match"]
+           "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -23,4 +23,7 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
     if name in ("MatchPlayer", "MatchResult", "play_match"):  # head-to-head matches
         from . import match
         return getattr(match, name)
+    if name in ("Resign", "check_resign"):  # resignation in self-play
+        from . import engine
+        return getattr(engine, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

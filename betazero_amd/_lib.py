@@ -204,6 +204,11 @@ _SIGS = {
     "bz_engine_set_ownership": (i32, [vp, vp, i64, vp]),
     "bz_engine_pack_ownership": (i32, [vp, vp, vp, i64, i32, vp]),
     "bz_ownership_row": (i32, [u64, u64, i32, vp, vp]),
+    "bz_engine_resign_bytes": (i64, [C.POINTER(EngineCfg)]),
+    "bz_engine_set_resign": (i32, [vp, C.c_float, i32, u32, vp, i64, vp]),
+    "bz_engine_resign_rows": (i32, [vp, vp, vp, vp, vp, vp]),
+    "bz_resign_step": (i32, [C.c_float, C.c_float, i32, i32, vp]),
+    "bz_resign_playout": (i32, [u64, u64, u32]),
     "bz_engine_root_store_bytes": (i64, [C.POINTER(EngineCfg), i32, i32]),
     "bz_engine_set_root_store": (i32, [vp, vp, i64, i32, i32, vp]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),

@@ -23,6 +23,7 @@
 // First-play urgency reduction in the select rule (k_fpu_step and its cap / forced variants, csrc/bz_fpu.h) -- DESIGN.md 3.20.
 // Proven wins, losses and draws (k_solve_step / k_solve_cap_step, the proof pass behind their backup, csrc/bz_solver.h) -- DESIGN.md 3.23.
 // The Gumbel interior rule below the root of a Gumbel search (k_gfull_step, csrc/bz_gumbel_interior.h) -- DESIGN.md 3.21.
+// Resignation in self-play (k_resign_note in front of the play kernel, k_resign_finish behind it, csrc/bz_resign.h) -- DESIGN.md 3.24.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -45,6 +46,7 @@
 #include "bz_surprise.h"
 #include "bz_value.h"
 #include "bz_ownership.h"
+#include "bz_resign.h"
 
 using namespace bz;
 
@@ -241,6 +243,15 @@ struct OwnDev { u64 *fin_x, *fin_o; float* pi; int32_t* act; };
 // root's proven value + 2 (0 = undecided) i32 [B] and the two counts of the current search -- nodes newly decided, walks that
 // ended at a proven edge that is not terminal.  bz_engine_root_begin zeroes all of it.  A kernel argument of the solver kernels only.
 struct SolveDev { int32_t* root; u32* counts; };
+
+// Resignation (streak = nullptr: off), set by bz_engine_set_resign in the caller's buffer: every game's two
+// streaks u8 [rounds][B][2] (side +1, side -1) and its record -- the side that fired first i8 (0: none), the moves made and the
+// root value at that search, and whether the game is played out u8 -- [rounds][B] each, indexed like ex_len.  A kernel argument
+// of the two resignation kernels only.
+struct ResignDev { float threshold; int consecutive; u32 playout_q; uint8_t* streak; int8_t* side; int32_t* move; float* q; uint8_t* played_out; };
+// g_state of a slot k_resign_note has ended and k_resign_finish has not yet restarted or retired: like every value but 0 it
+// makes the kernels between the two skip the slot
+constexpr uint8_t kStateResigned = 2;
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -2492,6 +2503,54 @@ __global__ void __launch_bounds__(256) k_own_final(EngineDev E, OwnDev O, const 
     O.fin_x[i] = tm == 1 ? own : opp;
     O.fin_o[i] = tm == 1 ? opp : own;
 }
+// ---- resignation: one lane per game around the play kernel.  k_resign_note, the first launch of
+// bz_engine_play: the root value of the search that has just ended (k_root_q's expression on the same raw statistics) goes
+// through the mover's streak (a full search only: budget is the playout cap's, or null); the first fire of a game is recorded;
+// a game that is not played out ends there -- no row, no move, the other side wins, z back-filled over the rows so far as
+// dev_play_tail does at a terminal position -- and its slot leaves g_state == 0, so that every kernel up to k_resign_finish
+// skips it and dev_pending_row answers 0 for it.
+template <class G>
+__global__ void __launch_bounds__(256) k_resign_note(EngineDev E, ResignDev R, const u32* budget) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != 0) return;
+    const int round = E.g_round[g];
+    if (round < 0 || round >= E.rounds) return;
+    const size_t i = (size_t)round * E.B + g;
+    const bool out = resign_played_out(E.seed, E.id_base + (u64)round * E.id_stride + (u64)g, R.playout_q);
+    R.played_out[i] = out ? 1 : 0;
+    if (budget && budget[g] < (u32)E.sims) return;  // a fast search: the threshold is calibrated on full ones
+    const Node r = E.nodes[(size_t)g * E.ncap];
+    const int n = (int)(r.info & 0xFFu);
+    if (n == 0) return;  // (no search has expanded this slot's root)
+    const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
+    const float q = root_value(n, [ed](int k) { return e_N(ed[k].w0); }, [ed](int k) { return ed[k].W; });
+    const int tm = E.g_to_move[g];
+    uint8_t* st = R.streak + i * 2 + (tm == 1 ? 0 : 1);
+    int s;
+    const bool fire = resign_step(q, R.threshold, R.consecutive, (int)*st, &s);
+    *st = (uint8_t)s;
+    if (!fire) return;
+    if (R.side[i] == 0) { R.side[i] = (int8_t)tm; R.move[i] = E.g_moves[g]; R.q[i] = q; }
+    if (out) return;
+    const int nex = E.g_nex[g] < E.t_max ? E.g_nex[g] : E.t_max, w = -tm;
+    const size_t rowbase = i * E.t_max;
+    for (int t = 0; t < nex; ++t) E.ex_z[rowbase + t] = (int8_t)(w * E.ex_mover[rowbase + t]);
+    E.ex_len[i] = nex;
+    E.ex_winner[i] = (int8_t)w;
+    atomicAdd(&E.flags[FLAG_FINISHED], 1u);
+    E.g_state[g] = kStateResigned;
+}
+// behind the play kernel and k_surp_kl: a resigned slot starts its next game (restart and a round left) or stays finished.
+// (Not in k_resign_note: the play kernel would play the fresh game's first move from the tree of the resigned one.)
+template <class G>
+__global__ void __launch_bounds__(256) k_resign_finish(EngineDev E, int restart) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.B || E.g_state[g] != kStateResigned) return;
+    const int round = E.g_round[g];
+    if (restart && round + 1 < E.rounds) { dev_start_game<G>(E, g, round + 1); return; }
+    E.g_state[g] = 1;
+}
+
 // the rows' target boards in the packed block's row order (k_pack_q's walk over the pack_off k_pack_scan left): every row of
 // a game gets its game's final board in the row's own side-to-move frame
 __global__ void __launch_bounds__(256) k_pack_own(EngineDev E, OwnDev O, u64* fown, u64* fopp, int64_t cap) {
@@ -2736,6 +2795,8 @@ struct bz_engine {
     int64_t solve_bytes;  // ... the bytes bz_engine_root_begin zeroes in its buffer
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
     OwnDev own;        // ownership targets (bz_engine_set_ownership); own.fin_x = nullptr: off
+    ResignDev resign;  // resignation (bz_engine_set_resign); resign.streak = nullptr: off
+    int64_t resign_bytes;  // ... the bytes bz_engine_reset_games zeroes in its buffer
     StoreDev store;    // the root store (bz_engine_set_root_store); store.S = 0: off
     int64_t store_index_bytes;  // ... its front part (fill count, index, entry headers): zeroing it empties the store
     // hashed evaluation symmetry (bz_engine_set_eval_symmetry); on the engine, not on the net: two pipelines
@@ -2885,6 +2946,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->surp = SurpDev{};
     e->value = ValueDev{};
     e->own = OwnDev{};
+    e->resign = ResignDev{}; e->resign_bytes = 0;
     e->store = StoreDev{}; e->store_index_bytes = 0;
     e->fpu = FpuDev{}; e->fpu_done = 0;
     e->solve = SolveDev{}; e->solve_bytes = 0;
@@ -3017,6 +3079,8 @@ BZ_EXPORT int32_t bz_engine_reset_games(bz_engine* e, void* stream) {
     if (e->own.fin_x)  //  no game is finished: every final board 0 (fin_x and fin_o are one range)
         BZ_HIP(hipMemsetAsync(e->own.fin_x, 0, (size_t)(reinterpret_cast<char*>(e->own.pi) - reinterpret_cast<char*>(e->own.fin_x)),
                               (hipStream_t)stream));
+    if (e->resign.streak)  //  no streak, no record
+        BZ_HIP(hipMemsetAsync(e->resign.streak, 0, (size_t)e->resign_bytes, (hipStream_t)stream));
     return BZ_OK;
 }
 
@@ -3688,6 +3752,7 @@ BZ_EXPORT int32_t bz_engine_set_ownership(bz_engine* e, void* buf, int64_t bytes
         e->own = OwnDev{};
         return BZ_OK;
     }
+    BZ_REQUIRE(!e->resign.streak, "bz_engine_set_ownership: ownership targets do not combine with resignation (bz_engine_set_resign): a resigned game has no final board");
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_ownership: the buffer must be 256-byte aligned");
     const OwnOffsets o = own_carve(e->cfg);
     if (bytes < o.total) { set_error("bz_engine_set_ownership: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -3708,6 +3773,79 @@ BZ_EXPORT int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uin
                        reinterpret_cast<u64*>(fown_out), reinterpret_cast<u64*>(fopp_out), cap_rows);
     BZ_LAUNCH_CHECK("k_pack_own");
     return BZ_OK;
+}
+
+/* ---- resignation */
+namespace {
+struct ResignOffsets { int64_t streak, side, move, q, played_out, total; };
+ResignOffsets resign_carve(const bz_engine_cfg& c) {
+    ResignOffsets o{};
+    Carver k;
+    const int64_t n = (int64_t)c.rounds * c.n_games;
+    o.streak = k.take(n * 2); o.side = k.take(n); o.move = k.take(n * 4); o.q = k.take(n * 4); o.played_out = k.take(n);
+    o.total = k.off;
+    return o;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_resign_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_resign_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_resign_bytes: %s", kBadCfg); return -1; }
+    return resign_carve(*cfg).total;
+}
+
+BZ_EXPORT int32_t bz_engine_set_resign(bz_engine* e, float threshold, int32_t consecutive, uint32_t playout_q, void* buf, int64_t bytes,
+                                       void* stream) {
+    if (buf) {  // (what needs no engine first: these refusals can be had without a GPU)
+        BZ_REQUIRE(threshold >= -1.0f && threshold <= 1.0f, "bz_engine_set_resign: threshold must be a finite number in [-1, 1]");  // (NaN fails)
+        BZ_REQUIRE(consecutive >= 1 && consecutive <= kResignMaxStreak, "bz_engine_set_resign: consecutive must be in 1 .. 255");
+        BZ_REQUIRE(playout_q <= 65536u, "bz_engine_set_resign: playout_q must be in 0 .. 65536 (the share of played-out games in units of 2^-16)");
+        BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_resign: the buffer must be 256-byte aligned");
+    }
+    BZ_REQUIRE(e, "bz_engine_set_resign: null engine");
+    if (!buf) {  // off: no extra launch
+        e->resign = ResignDev{}; e->resign_bytes = 0;
+        return BZ_OK;
+    }
+    BZ_REQUIRE(!e->own.fin_x, "bz_engine_set_resign: resignation does not combine with ownership targets (bz_engine_set_ownership): a resigned game has no final board");
+    const ResignOffsets o = resign_carve(e->cfg);
+    if (bytes < o.total) { set_error("bz_engine_set_resign: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_EINVAL; }
+    // the buffer the engine already records in: only the rule changes, streaks and records stay
+    if (at<uint8_t>(buf, o.streak) != e->resign.streak) BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));
+    ResignDev& r = e->resign;
+    r.threshold = threshold; r.consecutive = consecutive; r.playout_q = playout_q;
+    r.streak = at<uint8_t>(buf, o.streak); r.side = at<int8_t>(buf, o.side); r.move = at<int32_t>(buf, o.move);
+    r.q = at<float>(buf, o.q); r.played_out = at<uint8_t>(buf, o.played_out);
+    e->resign_bytes = o.total;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_resign_rows(bz_engine* e, int8_t* side, int32_t* move, float* q, uint8_t* played_out, void* stream) {
+    BZ_REQUIRE(e && side && move && q && played_out, "bz_engine_resign_rows: null pointer");
+    BZ_REQUIRE(e->resign.streak, "bz_engine_resign_rows: resignation is off (bz_engine_set_resign)");
+    const size_t n = (size_t)e->dev.rounds * e->dev.B;
+    hipStream_t s = (hipStream_t)stream;
+    BZ_HIP(hipMemcpyAsync(side, e->resign.side, n, hipMemcpyDeviceToDevice, s));
+    BZ_HIP(hipMemcpyAsync(move, e->resign.move, n * 4, hipMemcpyDeviceToDevice, s));
+    BZ_HIP(hipMemcpyAsync(q, e->resign.q, n * 4, hipMemcpyDeviceToDevice, s));
+    BZ_HIP(hipMemcpyAsync(played_out, e->resign.played_out, n, hipMemcpyDeviceToDevice, s));
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_resign_step(float q, float threshold, int32_t consecutive, int32_t streak_in, int32_t* streak_out) {
+    if (!(streak_out && consecutive >= 1 && consecutive <= kResignMaxStreak && streak_in >= 0 && streak_in <= kResignMaxStreak)) {
+        set_error("bz_resign_step: null pointer, consecutive outside 1 .. 255 or streak_in outside 0 .. 255");
+        return -1;
+    }
+    int s;
+    const bool fire = resign_step(q, threshold, (int)consecutive, (int)streak_in, &s);
+    *streak_out = s;
+    return fire ? 1 : 0;
+}
+
+BZ_EXPORT int32_t bz_resign_playout(uint64_t seed, uint64_t gid, uint32_t playout_q) {
+    if (playout_q > 65536u) { set_error("bz_resign_playout: playout_q must be in 0 .. 65536"); return -1; }
+    return resign_played_out((u64)seed, (u64)gid, playout_q) ? 1 : 0;
 }
 
 namespace {
@@ -3784,6 +3922,8 @@ BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action
 
 BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     BZ_REQUIRE(e, "null engine");
+    if (e->resign.streak)  //  first: a slot that resigns here is out of every kernel below
+        BZ_DISPATCH(e, k_resign_note, stream, e->dev, e->resign, e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
     if (e->surp.prior) {  //  the row this play is about to write
         // without Dirichlet noise the searched root still holds its raw priors (only the noise ever rewrites a prior): saved here,
         // whichever way the search ran -- fused, step kernels, the step API
@@ -3813,6 +3953,7 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
     }
     if (e->surp.prior) BZ_DISPATCH(e, k_surp_kl, stream, e->dev, e->surp);  // ... and its kl (before the arenas swap below)
+    if (e->resign.streak) BZ_DISPATCH(e, k_resign_finish, stream, e->dev, (int)restart);  // 
     if (e->dev.reuse) {  // the tree just searched becomes the source of the next root_begin's subtree copy
         Node* tn = e->dev.nodes; e->dev.nodes = e->dev.nodes_alt; e->dev.nodes_alt = tn;
         Edge* te = e->dev.edges; e->dev.edges = e->dev.edges_alt; e->dev.edges_alt = te;

@@ -277,6 +277,67 @@ def check_playout_cap(playout_cap, sims=None, reuse_subtree=False, leaves_per_st
 
 
 @dataclass(frozen=True)
+class Resign:
+    """Resignation in self-play (AlphaGo Zero): a side whose root value q = sum W / sum N stayed below
+    `threshold` (strict, float32) for `consecutive` full searches in a row (1..255) resigns -- the game ends there, the other
+    side wins, the firing search records no row.  A seeded share `playout_frac` of the games (applied in units of 2^-16,
+    drawn per global game id) never resigns and only records where it would have: their real outcomes give the
+    false-positive rate (SelfPlayEngine.resign_stats)."""
+    threshold: float = -0.9
+    consecutive: int = 2
+    playout_frac: float = 0.1
+
+    @property
+    def playout_q(self):
+        """the share of played-out games in units of 2^-16 (what the engine compares 16 random bits with)"""
+        return int(round(float(self.playout_frac) * 65536))
+
+
+def check_resign(resign, ownership=False):
+    """None / False: off (None returned); True: Resign(); or a Resign -- validated in float32, and refused with ownership
+    targets: a resigned game has no final board (ValueError, before any device is touched)"""
+    if resign is None or resign is False:
+        return None
+    cfg = Resign() if resign is True else resign
+    if not isinstance(cfg, Resign):
+        raise ValueError(f"resign must be None, False, True or a Resign (got {resign!r})")
+    t = cfg.threshold
+    with np.errstate(over="ignore", under="ignore"):
+        ok = not isinstance(t, (bool, np.bool_)) and isinstance(t, (int, float, np.integer, np.floating))
+        t32 = float(np.float32(t)) if ok else 2.0
+    if not -1.0 <= t32 <= 1.0:  # (NaN fails)
+        raise ValueError(f"resign: threshold must be a finite number in [-1, 1] in float32 (got {t!r})")
+    n = cfg.consecutive
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 255:
+        raise ValueError(f"resign: consecutive must be an int in 1..255 (got {n!r})")
+    f = cfg.playout_frac
+    if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, float, np.integer, np.floating)) or not 0.0 <= f <= 1.0:  # (NaN fails)
+        raise ValueError(f"resign: playout_frac must be a number in [0, 1] (got {f!r})")
+    if ownership is not None and ownership is not False:
+        raise ValueError("resign: resignation does not combine with ownership targets (ownership): a resigned game has no final board")
+    return Resign(t32, int(n), float(f))
+
+
+def resign_stats(side, played_out, winner, length):
+    """the calibration figures of DESIGN.md 3.24 from resign_rows() and winners(): arrays of one shape, one element per game
+    (length < 0: the game is not finished).  A false positive is a finished played-out game with a record whose recorded
+    side did not lose -- it won or drew."""
+    side, out, winner = np.asarray(side), np.asarray(played_out).astype(bool), np.asarray(winner)
+    fin = np.asarray(length) >= 0
+    would = fin & out & (side != 0)
+    fp = would & (winner.astype(np.int64) != -side.astype(np.int64))
+    n_would, n_fp = int(would.sum()), int(fp.sum())
+    return {"n_finished": int(fin.sum()), "n_resigned": int((fin & ~out & (side != 0)).sum()), "n_played_out": int((fin & out).sum()),
+            "n_would_resign": n_would, "n_false_positive": n_fp, "false_positive_rate": n_fp / n_would if n_would else None}
+
+
+def _sum_resign_stats(parts):
+    tot = {k: sum(p[k] for p in parts) for k in ("n_finished", "n_resigned", "n_played_out", "n_would_resign", "n_false_positive")}
+    tot["false_positive_rate"] = tot["n_false_positive"] / tot["n_would_resign"] if tot["n_would_resign"] else None
+    return tot
+
+
+@dataclass(frozen=True)
 class ForcedPlayouts:
     """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2): every visited root child
     is searched until it has sqrt(k P sum N) visits (P the prior after the Dirichlet noise); the recorded pi then drops
@@ -385,7 +446,7 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False):
+                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False, resign=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -456,9 +517,17 @@ class SelfPlayEngine:
         walks through a decided edge, and play() / root_policy() play the lowest winning move and avoid lost ones.  pi stays
         N / sum N.  proven() reads the proof state; set_solver() changes it between searches.  Combines with Dirichlet
         noise, playout_cap, surprise, search_value, ownership, eval_symmetry, every evaluator, eval_cache mode and the root
-        store.  Refused with reuse_subtree, leaves_per_step > 1, gumbel, forced_playouts and fpu."""
+        store.  Refused with reuse_subtree, leaves_per_step > 1, gumbel, forced_playouts and fpu.
+
+        resign: None / False = every game is played to the end (the default, unchanged); True or a
+        Resign(threshold, consecutive, playout_frac) = a side whose root value stayed below the threshold for `consecutive`
+        full searches in a row resigns; a seeded share of the games is played out and only records where it would have
+        resigned.  resign_rows() reads the records, resign_stats() the false-positive rate; set_resign() changes the rule
+        between searches.  Searches, and the rows of games that do not resign, are what they are without it; it combines with
+        everything the engine accepts but ownership."""
         self.root_store = check_root_store(root_store, eval_cache)
         self.ownership = check_ownership(ownership)
+        self.resign = check_resign(resign, self.ownership)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
@@ -569,6 +638,8 @@ class SelfPlayEngine:
             self.ows = torch.zeros(obytes + 256, dtype=torch.uint8, device=self.device)
             self._opad = (-self.ows.data_ptr()) & 255
             self._call(L.bz_engine_set_ownership, self.ows.data_ptr() + self._opad, obytes)
+        if self.resign is not None:
+            self._set_resign(self.resign)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -670,6 +741,51 @@ class SelfPlayEngine:
         self.drain()
         self._set_solver(on)
         self.solver = on
+
+    def _set_resign(self, rs):
+        L = _lib.lib()
+        if rs is None:
+            self._call(L.bz_engine_set_resign, 0.0, 0, 0, None, 0)
+            return
+        if getattr(self, "zws", None) is None:  # the engine's resignation buffer (caller-owned, like the workspace)
+            zbytes = L.bz_engine_resign_bytes(C.byref(self.cfg))
+            if zbytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.zws = torch.zeros(zbytes + 256, dtype=torch.uint8, device=self.device)
+            self._zpad, self._zbytes = (-self.zws.data_ptr()) & 255, zbytes
+        self._call(L.bz_engine_set_resign, rs.threshold, rs.consecutive, rs.playout_q, self.zws.data_ptr() + self._zpad, self._zbytes)
+
+    def set_resign(self, resign):
+        """switch resignation on, off or to another rule, between searches: None / False, True (the defaults)
+        or a Resign.  While it stays on, streaks and records are kept; switching it off and on again clears them."""
+        rs = check_resign(resign, self.ownership)
+        self.drain()
+        self._set_resign(rs)
+        self.resign = rs
+
+    def resign_rows(self):
+        """resignation: every game's record, numpy [rounds, B] each -- side int8 (the side that fired first,
+        +1 / -1; 0 = none), move int32 (moves made at that search), q float32 (its root value) and played_out bool (the game
+        never resigns; known once the game has had a play)"""
+        if self.resign is None:
+            raise RuntimeError("resign_rows(): resignation is off (resign=)")
+        n = self.rounds * self.B
+        side = torch.empty(n, dtype=torch.int8, device=self.device)
+        move = torch.empty(n, dtype=torch.int32, device=self.device)
+        q = torch.empty(n, dtype=torch.float32, device=self.device)
+        out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self._call(_lib.lib().bz_engine_resign_rows, side.data_ptr(), move.data_ptr(), q.data_ptr(), out.data_ptr())
+        shp = (self.rounds, self.B)
+        return (side.cpu().numpy().reshape(shp), move.cpu().numpy().reshape(shp), q.cpu().numpy().reshape(shp),
+                out.cpu().numpy().astype(bool).reshape(shp))
+
+    def resign_stats(self):
+        """the calibration figures over the games finished so far: n_finished, n_resigned, n_played_out
+        (finished and played out), n_would_resign (of those, with a record), n_false_positive (of those, the recorded side won
+        or drew) and false_positive_rate (None when n_would_resign == 0)"""
+        side, _, _, out = self.resign_rows()
+        winner, length = self.winners()
+        return resign_stats(side, out, winner, length)
 
     def proven(self):
         """after a search with the solver on: (root, edges, counts) -- root: per slot the root's proven value
@@ -1207,9 +1323,10 @@ class PipelinedSelfPlay:
     def __init__(self, game, n_games, sims, evaluator="uniform", net=None, pipelines=2, streams=None, game_id_base=0,
                  game_id_stride=None, device="cuda:0", run_ahead=16, leaves_per_step=1, gumbel=None, playout_cap=None,
                  forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False,
-                 solver=False, **engine_kwargs):
+                 solver=False, resign=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
         check_ownership(ownership)
+        check_resign(resign, ownership)
         check_solver(solver, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel, forced_playouts, fpu)
         # every pipeline gets the same seed, so the same position has the same orientation in all of them
         eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
@@ -1233,7 +1350,7 @@ class PipelinedSelfPlay:
                                        game_id_stride=stride, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
                                        playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
                                        search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership, solver=solver,
-                                       **engine_kwargs)
+                                       resign=resign, **engine_kwargs)
                         for i in range(pipelines)]
         self.surprise, self.search_value, self.ownership = bool(surprise), bool(search_value), bool(ownership)
         e0 = self.engines[0]
@@ -1411,6 +1528,24 @@ class PipelinedSelfPlay:
         r = [e.ownership_rows() for e in self.engines]
         return torch.cat([a for a, _ in r], dim=1), torch.cat([b for _, b in r], dim=1)
 
+    def set_resign(self, resign):
+        """SelfPlayEngine.set_resign on every pipeline, between searches"""
+        rs = check_resign(resign, self.ownership)
+        self.sync()
+        self._each(lambda e: e.set_resign(rs))
+
+    def resign_rows(self):
+        """the resignation records of all pipelines in global game order: (side, move, q, played_out), numpy [rounds, B]
+        (SelfPlayEngine.resign_rows)"""
+        self.join()
+        r = self._each(lambda e: e.resign_rows())
+        return tuple(np.concatenate([p[k] for p in r], axis=1) for k in range(4))
+
+    def resign_stats(self):
+        """SelfPlayEngine.resign_stats summed over the pipelines"""
+        self.join()
+        return _sum_resign_stats(self._each(lambda e: e.resign_stats()))
+
     def winners(self):
         self.join()
         w = [e.winners() for e in self.engines]
@@ -1426,7 +1561,7 @@ class PipelinedSelfPlay:
 def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=0, openings=0, c_puct=1.5,
               device="cuda:0", game_id_base=0, game_id_stride=None, dirichlet_alpha=0.0, dirichlet_eps=0.0,
               reuse_subtree=False, pipelines=None, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
-              surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False, solver=False):
+              surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False, solver=False, resign=None):
     """Play n_games concurrent self-play games to the end on one GPU and return
     (s, pi, z): canonical states int8 [n, size, size], visit-count policies
     f32 [n, NA], outcomes for the mover int8 [n] -- plus the Examples object.
@@ -1438,8 +1573,10 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     search_value: SelfPlayEngine -- the Examples then carry `q`.  eval_symmetry: SelfPlayEngine (DESIGN.md
     3.19) -- every leaf is evaluated under a hashed board symmetry (True: seeded by `seed`).  fpu: SelfPlayEngine (DESIGN.md
     3.20) -- first-play urgency reduction in the select rule.  ownership: SelfPlayEngine -- the Examples then
-    carry `fown`, `fopp`."""
+    carry `fown`, `fopp`.  resign: SelfPlayEngine -- decided games end early; a resigned game's rows are the
+    first rows of the game it would have been."""
     check_ownership(ownership)
+    check_resign(resign, ownership)
     check_search_value(search_value)
     check_leaves_per_step(leaves_per_step)
     check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
@@ -1458,7 +1595,8 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
                            openings=openings, seed=seed, rounds=1, dirichlet_alpha=dirichlet_alpha,
                            dirichlet_eps=dirichlet_eps, reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step,
                            gumbel=gumbel, playout_cap=playout_cap, forced_playouts=forced_playouts, surprise=surprise,
-                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership, solver=solver)
+                           search_value=search_value, eval_symmetry=eval_symmetry, fpu=fpu, ownership=ownership, solver=solver,
+                           resign=resign)
     sp.run_iteration()
     ex = sp.examples()
     return ex.states(), ex.pi, ex.z, ex

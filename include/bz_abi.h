@@ -703,6 +703,43 @@ int32_t bz_engine_pack_ownership(bz_engine* e, uint64_t* fown_out, uint64_t* fop
 /* a row's target boards, the function the kernel runs: *t_own = mover == +1 ? fin_x : fin_o, *t_opp = the other board; the
  * target of cell i is bit_i(t_own) - bit_i(t_opp) in {+1, 0, -1}.  mover: +1 or -1.  Host only. */
 int32_t bz_ownership_row(uint64_t fin_x, uint64_t fin_o, int32_t mover, uint64_t* t_own, uint64_t* t_opp);
+/* Resignation in self-play (AlphaGo Zero, Silver et al. 2017, "Self-play"), opt-in per engine.  After a search
+ * and before its move, q = the root's sum W / sum N for the mover (bz_root_value on the raw statistics bz_engine_root_stats
+ * reports, whatever the search mode: the bits of 3.18's ex_q).  Every game keeps one streak per side, 0 at its start: a FULL
+ * search (under playout cap randomisation a fast one touches nothing) sets the mover's streak to min(streak + 1, 255) if
+ * q < threshold (strict, binary32; a NaN q is not below it) and to 0 otherwise, and the side FIRES when its streak has
+ * reached `consecutive`.  A pass is no search and touches nothing.  The first fire of a game writes its record: the side
+ * (+1 / -1), the moves made and q.  A game is PLAYED OUT iff
+ *     (rng_draw(seed ^ BZ_RESIGN_KEY, gid, 0) & 0xFFFF) < playout_q,   gid = game_id_base + round x game_id_stride + slot
+ * -- a function of (seed, gid) alone -- and then goes on as if nothing had happened: the record is the only trace, and the
+ * game's real outcome says whether the resignation would have been right.  Any other game ends at its first fire: the firing
+ * search records no row and plays no move, the other side wins, z is back-filled over the rows recorded so far, ex_len,
+ * ex_winner and the finished-games count follow, and with `restart` and a round left the slot starts its next game.  Such a
+ * game's rows are a prefix of the rows it has without resignation; a game may end with ex_len = 0.
+ * bz_engine_play then launches k_resign_note first (one lane per game: q, the streak, the record, a resigning game's end; the
+ * slot leaves the active state, so every later kernel of the play skips it by the test it already makes) and k_resign_finish
+ * last (restart or retire the resigned slots).  Off (the default) launches nothing and changes no bit. */
+#define BZ_RESIGN_KEY 0x72657369676E6564ULL /* "resigned" */
+/* bytes of the caller-owned buffer: streaks u8 [rounds][n_games][2] (side +1, side -1), then per game [rounds][n_games],
+ * indexed like ex_len: side i8 (0 = no record), moves made i32, q f32, played out u8 -- each array 256-byte aligned.  Needs no
+ * GPU; -1 (bz_last_error says why) for a bad config. */
+int64_t bz_engine_resign_bytes(const bz_engine_cfg* cfg);
+/* on (buf: device memory of >= bz_engine_resign_bytes bytes, 256-byte aligned, owned by the caller and kept alive while the
+ * mode is on; zeroed on `stream`, as bz_engine_reset_games does) or off (buf == NULL: no extra launch), between searches.
+ * Called again with the buffer the engine already uses it only changes threshold, consecutive and playout_q: streaks and
+ * records stay.  threshold: finite, in [-1, 1]; consecutive in 1 .. 255; playout_q in 0 .. 65536.  Refused (BZ_EINVAL,
+ * bz_last_error names this function) for a null engine, an unaligned or too small buffer, a bad argument, and together with
+ * ownership targets -- in either order of the two setters: a resigned game has no final board. */
+int32_t bz_engine_set_resign(bz_engine* e, float threshold, int32_t consecutive, uint32_t playout_q, void* buf, int64_t bytes,
+                             void* stream);
+/* copies of the records into device arrays of [rounds][n_games] elements each: side i8, moves made i32, q f32, played out u8
+ * (written for every game that has had a play) */
+int32_t bz_engine_resign_rows(bz_engine* e, int8_t* side, int32_t* move, float* q, uint8_t* played_out, void* stream);
+/* the streak rule, the function the kernel runs: *streak_out = the streak behind a full search with root value q; returns 1
+ * if the side fires, 0 if not, -1 for a null pointer, consecutive outside 1 .. 255 or streak_in outside 0 .. 255.  Host only. */
+int32_t bz_resign_step(float q, float threshold, int32_t consecutive, int32_t streak_in, int32_t* streak_out);
+/* 1 if the game with global id gid is played out, 0 if not, -1 for playout_q > 65536: the draw the kernel makes.  Host only. */
+int32_t bz_resign_playout(uint64_t seed, uint64_t gid, uint32_t playout_q);
 /* The root store, opt-in per engine, active only where the engine runs the carry-over cache
  * (BZ_ENGINE_EVAL_CACHE | BZ_ENGINE_EVAL_CACHE_CARRY with a net evaluator, one leaf per step, no subtree reuse).  The first
  * searches of a game repeat searches other games of the engine already ran: a finished search whose root lies fewer than

@@ -34,14 +34,30 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
-from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, check_forced_playouts, check_fpu,  # noqa: E402
-                                 check_playout_cap, check_solver, concat_device_examples)
+from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, Resign, check_forced_playouts,  # noqa: E402
+                                 check_fpu, check_playout_cap, check_resign, check_solver, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
 from betazero_amd.value_targets import value_targets  # noqa: E402
 from betazero_amd.train import (GraphedTrainStep, holdout_split, make_optimizer, refresh_device_net, select_rows,  # noqa: E402
                                 train_step, validate)
+
+
+# how --resign-threshold moves between iterations (untuned): down fast when resignations turn out wrong, up slowly when they are safe
+RESIGN_STEP_DOWN, RESIGN_STEP_UP, RESIGN_T_MIN, RESIGN_T_MAX = 0.05, 0.01, -0.99, -0.5
+
+
+def next_resign_threshold(threshold, stats, fp_target):
+    """the threshold of the next iteration from this one's resign_stats()"""
+    rate = stats["false_positive_rate"]
+    if rate is None:  # no played-out game would have resigned: nothing was measured
+        return threshold
+    if rate > fp_target:
+        threshold -= RESIGN_STEP_DOWN
+    elif rate < fp_target / 2:
+        threshold += RESIGN_STEP_UP
+    return min(max(threshold, RESIGN_T_MIN), RESIGN_T_MAX)
 
 
 def main():
@@ -116,6 +132,16 @@ def main():
                     "game's final board, and an auxiliary head next to the net learns, per cell, who owns it at the end; the head "
                     "only shapes the trunk, the engine's net does not have it.  Needs the all-kernel training step")
     ap.add_argument("--own-weight", type=float, default=1.0, help="the weight of the ownership loss in the step's loss (untuned)")
+    ap.add_argument("--resign-threshold", type=float, default=None, help="resignation in self-play (DESIGN.md 3.24; AlphaGo Zero): a side "
+                    "whose root value stayed below T for --resign-consecutive full searches in a row resigns; not given = every game is "
+                    "played to the end.  After an iteration with played-out games that would have resigned, T moves down by "
+                    f"{RESIGN_STEP_DOWN} when their false-positive rate is above --resign-fp-target and up by {RESIGN_STEP_UP} when it "
+                    f"is below half of it, inside [{RESIGN_T_MIN}, {RESIGN_T_MAX}] (the two steps are untuned).  Not with --ownership")
+    ap.add_argument("--resign-consecutive", type=int, default=2, help="full searches in a row below the threshold before a side resigns")
+    ap.add_argument("--resign-playout-frac", type=float, default=0.1, help="the share of the games that never resigns and records where "
+                    "it would have (AlphaGo Zero's 10 %%): the false-positive rate is measured on them")
+    ap.add_argument("--resign-fp-target", type=float, default=0.05, help="the false-positive rate the threshold is steered to stay "
+                    "under (AlphaGo Zero's 5 %%)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -129,6 +155,10 @@ def main():
         ap.error("--weight-decay / --clip-norm / --ema-decay / --lr-decay need the all-kernel training step")
     if args.ownership and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
         ap.error("--ownership needs the all-kernel training step")
+    if args.resign_threshold is not None and args.ownership:
+        ap.error("--resign-threshold does not combine with --ownership: a resigned game has no final board")
+    if not (0.0 <= args.resign_fp_target <= 1.0):
+        ap.error("--resign-fp-target must be in [0, 1]")
     if not (0.0 <= args.own_weight < float("inf")):
         ap.error("--own-weight must be finite and >= 0")
 
@@ -152,6 +182,8 @@ def main():
     forced = check_forced_playouts(ForcedPlayouts(args.forced_k, not args.no_prune) if args.forced_k else None, gumbel=gumbel)
     fpu = check_fpu(Fpu(args.fpu_reduction, args.fpu_root_reduction) if args.fpu_reduction is not None else None, gumbel=gumbel)
     solver = check_solver(args.solver, gumbel=gumbel, forced_playouts=forced, fpu=fpu)
+    resign = check_resign(Resign(args.resign_threshold, args.resign_consecutive, args.resign_playout_frac)
+                          if args.resign_threshold is not None else None, ownership=args.ownership)
     lines = []
 
     def emit(d):
@@ -181,7 +213,7 @@ def main():
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
-                               surprise=args.surprise, search_value=use_vt, fpu=fpu, solver=solver, ownership=args.ownership,
+                               surprise=args.surprise, search_value=use_vt, fpu=fpu, solver=solver, ownership=args.ownership, resign=resign,
                                eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
         plies = sp.run_iteration()
         ex = sp.device_examples()    # finished games' rows, packed on the device
@@ -192,6 +224,13 @@ def main():
                                          "mean_abs_vt_minus_z": round(float((ex.vt - ex.z.to(torch.float32)).abs().mean()), 5)}}
         winners, _ = sp.winners()
         cnt = sp.counters()
+        resign_info = {}
+        if resign is not None:  # this iteration's figures, then the next iteration's threshold
+            st = sp.resign_stats()
+            nxt = next_resign_threshold(resign.threshold, st, args.resign_fp_target)
+            resign_info = {"resign": {"threshold": round(resign.threshold, 4), "consecutive": resign.consecutive,
+                                      "playout_frac": resign.playout_frac, **st, "next_threshold": round(nxt, 4)}}
+            resign = check_resign(Resign(nxt, resign.consecutive, resign.playout_frac))
         torch.cuda.synchronize()
         t_play = time.time() - t0
         t1 = time.time()
@@ -263,7 +302,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
-              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info,
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info, **resign_info,
               **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **({"solver": True} if solver else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               # the ownership loss L_own over the last (and the first) tenth of the steps
