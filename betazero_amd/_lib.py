@@ -135,6 +135,7 @@ _SIGS = {
     "bz_net_forward_counted": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, vp]),
     "bz_net_set_adaptive_shape": (i32, [vp, i32]),
     "bz_net_shape_tally": (i32, [vp, vp, vp]),
+    "bz_net_set_tile_map": (i32, [vp, i32]),
     "bz_mlp_param_count": (i64, [i32]),
     "bz_mlp_workspace_bytes": (i64, [i32, i32]),
     "bz_mlp_create": (i32, [i32, i32, vp, vp, i64, vp, C.POINTER(vp)]),

@@ -58,6 +58,7 @@ struct bz_net {
     hipEvent_t f32_done;
     bool f32_used;
     int adaptive;                    // bz_net_set_adaptive_shape: 0 off, 1 on (default), 2 the latency shape always
+    int tile_map;                    // bz_net_set_tile_map: 1 = the plain C = 128 throughput launches run k_edge_bf16 (default), 0 = k_tower_bf16
     uint32_t* tally;                 // [kShapes] device counters: device-count tower launches that ran, by shape
     // stamp of the parameter upload the weights came from, unique over all nets of the process: an engine's evaluation
     // cache carries nothing over from a search made with another stamp
@@ -124,6 +125,8 @@ typedef Tw<64, 2> TwS64;     // latency shapes: the smallest P whose (M-tile, po
 typedef Tw<128, 1> TwS128;
 typedef Tw<256, 1> TwS256;
 typedef Tw<128, 4, true> TwM16;  // the benchmark net's throughput shape on v_mfma_f32_16x16x32_bf16 (bz_tower.h)
+// the same on the edge-aware cell tiling (bz_tile_map.h): 126 instead of 132 N-tile-taps per layer, bit-identical outputs
+typedef Tw<128, 4, true, 1> TwEdge;
 constexpr int kSmallBatch = 256;  // one workgroup per position and per CU up to here
 // Device-count launches (the engine: the host knows max_n only, the packed-leaf count sits on the device) pick the shape
 // per launch from that count ("head of a move"): up to kAdaptT1 rows the latency shape, above it the
@@ -208,6 +211,12 @@ __device__ __forceinline__ float wave_sum(float x) {
 #undef BZ_NET_SYM
 #define BZ_NET_SYM 1
 #include "bz_net_tower_bf16_body.h"
+#undef BZ_NET_SYM
+// ... and the plain kernel once more as k_edge_bf16<G>, for the edge-aware cell tiling (TwEdge)
+#define BZ_NET_SYM 0
+#define BZ_NET_EDGE 1
+#include "bz_net_tower_bf16_body.h"
+#undef BZ_NET_EDGE
 #undef BZ_NET_SYM
 
 // ====================================================================================
@@ -674,7 +683,7 @@ BZ_EXPORT int32_t bz_net_create(int32_t C, int32_t NB, int32_t VH, int32_t max_b
     n->v1_wT = at<float>(ws, o.v1_wT); n->v1_b = at<float>(ws, o.v1_b);
     n->v2_w = at<float>(ws, o.v2_w); n->v2_b = at<float>(ws, o.v2_b);
     n->act_a = at<float>(ws, o.act_a); n->act_b = at<float>(ws, o.act_b);
-    n->tally = at<uint32_t>(ws, o.tally); n->adaptive = 1;
+    n->tally = at<uint32_t>(ws, o.tally); n->adaptive = 1; n->tile_map = 1;
 
     n->ws_base = ws;
     n->f32_used = false;
@@ -700,6 +709,8 @@ BZ_EXPORT int32_t bz_net_create(int32_t C, int32_t NB, int32_t VH, int32_t max_b
         if (C == 256) { e3 = BZ_TOWER_LDS(Tw<256>); if (e3 == hipSuccess) e3 = BZ_TOWER_LDS(TwS256); }
 #undef BZ_TOWER_LDS
         if (e3 != hipSuccess) { delete n; return hip_fail(e3, "hipFuncSetAttribute(k_sym_bf16)"); }
+        if (C == 128) e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_bf16<TwEdge>), hipFuncAttributeMaxDynamicSharedMemorySize, TwEdge::LDS);
+        if (e3 != hipSuccess) { delete n; return hip_fail(e3, "hipFuncSetAttribute(k_edge_bf16)"); }
         // the f32 parity kernels stage a whole position in LDS: above 64 KB at C = 256
         if (C == 256) {
             e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_heads<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -814,6 +825,10 @@ static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp,
         if (fp8 && Y) hipLaunchKernelGGL(f8::k_sym_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T, *Y);
         else if (fp8) hipLaunchKernelGGL(f8::k_tower_fp8, dim3((cnt + 3) / 4), dim3(256), f8::kLds, s, T);
         else if (Y) BZ_TOWER_PICK(k_sym_bf16, *Y);
+        else if (n->C == 128 && n->tile_map && !small && mode != 2) {  // the throughput launch on the edge-aware tiling
+            if (mode == 1) BZ_TOWER_LAUNCH(k_tower_bf16, TwS128, TS);
+            BZ_TOWER_LAUNCH(k_edge_bf16, TwEdge, T);
+        }
         else BZ_TOWER_PICK(k_tower_bf16);
 #undef BZ_TOWER_PICK
 #undef BZ_TOWER_LAUNCH
@@ -825,6 +840,11 @@ static int32_t forward_bf16(bz_net* n, const uint64_t* own, const uint64_t* opp,
 BZ_EXPORT int32_t bz_net_set_adaptive_shape(bz_net* n, int32_t mode) {
     BZ_REQUIRE(n && mode >= 0 && mode <= 2, "bz_net_set_adaptive_shape: null net, or mode not 0 (off), 1 (on) or 2 (latency shape always)");
     n->adaptive = mode;
+    return BZ_OK;
+}
+BZ_EXPORT int32_t bz_net_set_tile_map(bz_net* n, int32_t map) {
+    BZ_REQUIRE(n && (map == 0 || map == 1), "bz_net_set_tile_map: null net, or map not 0 (board rows) or 1 (edge-aware)");
+    n->tile_map = map;
     return BZ_OK;
 }
 BZ_EXPORT int32_t bz_net_shape_tally(bz_net* n, int64_t* counts, void* stream) {

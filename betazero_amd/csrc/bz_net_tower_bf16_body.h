@@ -1,10 +1,11 @@
-// bz_net_tower_bf16_body.h -- the fused bf16 net kernel: k_tower_bf16<G> and k_sym_bf16<G>.
-// Included twice by bz_net.hip, inside its anonymous namespace: with BZ_NET_SYM 0 it defines the plain kernel, with
+// bz_net_tower_bf16_body.h -- the fused bf16 net kernel: k_tower_bf16<G>, k_sym_bf16<G> and k_edge_bf16<G>.
+// Included three times by bz_net.hip, inside its anonymous namespace: with BZ_NET_SYM 0 it defines the plain kernel, with
 // BZ_NET_SYM 1 the form that evaluates every position under a board symmetry (bz_sym.h): the bitboards
 // are transformed in registers right after they are loaded and the policy row is stored through the inverse cell
-// permutation.  One text, two kernels -- not a shared inlined body: the plain kernel then compiles to the very
-// instructions it had before the symmetric form existed (a wrapper around a force-inlined template body moved their
-// register allocation), and the resource tests find one kernel per name.
+// permutation; with BZ_NET_SYM 0 and BZ_NET_EDGE 1 the plain kernel again under a name of its own, for the geometry on
+// the edge-aware cell tiling (Tw<128, 4, true, 1>, bz_tile_map.h).  One text, three kernels -- not a shared inlined body:
+// the plain kernel then compiles to the very instructions it had before the other forms existed (a wrapper around a
+// force-inlined template body moved their register allocation), and the resource tests find one kernel per name.
 
 // The whole net forward for P positions per workgroup: stem (MFMA, K = 18 padded to 32, fed from
 // the bitboards) -> residual tower (activations resident in LDS) -> heads (conv1x1 by MFMA, the
@@ -13,6 +14,8 @@ template <class G>
 __global__ void __launch_bounds__(256, 1)
 #if BZ_NET_SYM
 k_sym_bf16(TowerArgs T, bz_sym::Args Y) {  // (the name must not contain the plain kernel's: the resource tests look kernels up by substring)
+#elif BZ_NET_EDGE
+k_edge_bf16(TowerArgs T) {  // (likewise: neither of the other two names)
 #else
 k_tower_bf16(TowerArgs T) {
 #endif
@@ -63,7 +66,39 @@ k_tower_bf16(TowerArgs T) {
     }
 
     // ---- stem: conv3x3 2 -> C as a [C x 32] x [32 x 64] GEMM per position
-    if constexpr (G::M16) {  // K = 32 is ONE 16x16x32 MFMA per quarter: lane (c, g) feeds cell c of half b with k = 8g ..
+    if constexpr (G::EDGE) {  // as the 16x16x32 stem below, one MFMA pair per tile of bz_tile_map.h: lane column c feeds pair c
+        namespace tmap = bz_tile_map;
+        f32x16 acc[MW][G::NU];
+        Bias<G> bias;
+        const int c = lane & 15, g = lane >> 4;
+        load_bias16<G>(bias, T.stem_b, wt0, g);
+        bf16x8 sa[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) sa[a] = __builtin_bit_cast(bf16x8, T.stem_wf16[(wt0 * 2 + a) * 64 + lane]);
+        // the boards of the lane's positions: the row pattern serves two position pairs, the other patterns one position each
+        const int lp[5] = {tmap::lane_p(tmap::kRow, c), 2 + tmap::lane_p(tmap::kRow, c), tmap::lane_p(tmap::kCol, c),
+                           tmap::lane_p(tmap::kMix, c), tmap::lane_p(tmap::kIn, c)};
+        u64 own[5], opp[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            int pos = pos0 + wp0 + lp[i];
+            pos = pos < T.n ? pos : T.n - 1;
+            own[i] = T.own[pos]; opp[i] = T.opp[pos];
+        }
+#pragma unroll
+        for (int u = 0; u < G::NU; ++u) {
+            acc[0][u] = (f32x16)(0.0f);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int t = 2 * u + b, i = t < 4 ? (t & 1) : 1 + tmap::pattern(t);
+                const int cell = 8 * tmap::pair_y(t, c) + tmap::pair_x(t, c);
+                const bf16x8 f = stem_frag16(nbhd(own[i], cell), nbhd(opp[i], cell), g);
+                if (b) { mfma16_quarter<1>(acc[0][u], sa[0], f); mfma16_quarter<3>(acc[0][u], sa[1], f); }
+                else { mfma16_quarter<0>(acc[0][u], sa[0], f); mfma16_quarter<2>(acc[0][u], sa[1], f); }
+            }
+        }
+        epilogue_edge<G>(acc, bufX + wp0 * G::TILE, false, bias, wt0, lane);
+    } else if constexpr (G::M16) {  // K = 32 is ONE 16x16x32 MFMA per quarter: lane (c, g) feeds cell c of half b with k = 8g ..
         f32x16 acc[MW][G::NU];
         Bias<G> bias;
         const int c = lane & 15, g = lane >> 4;

@@ -4,6 +4,7 @@
 // __forceinline__ device function, so both translation units instantiate their own copies.
 #pragma once
 #include "bz_common.h"
+#include "bz_tile_map.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -35,7 +36,10 @@ constexpr int kTC = 128;                  // channels of the benchmark net (the 
 // shift dy = -1 then reads nothing but zero padding for the whole of unit 0 (dy = +1: unit 7), and that MFMA -- and its
 // LDS read -- is skipped: 6 of the 9 taps issue 7 MFMAs per k-step instead of 8, 8.3 % of the tower's matrix work.  The
 // skipped products are exact zeros, so every output is bit-identical to the full sum.  (Padding along x cannot be
-// skipped the same way: a 32-cell unit cannot be a board column AND a board row.)  Waves with fewer than four
+// skipped with these units: a 32-cell unit cannot be a board column AND a board row.  That is a limit of the tiling, not
+// of the convolution: MAP = 1 -- bz_tile_map.h, "the edge-aware tiling" at the end of this file -- deals the same cells
+// to 16-pair tiles so that the board's edge columns are tiles of their own, and skips those for dx = -1 / +1 too.)
+// Waves with fewer than four
 // positions keep the position-major units (lane r -> row 4 nt + (r >> 3), column r & 7 of one position).
 //
 // LDS image of a position: 8 board rows at a pitch of 9 cells -- 8 squares and one all-zero cell, which is the x = 8
@@ -44,9 +48,13 @@ constexpr int kTC = 128;                  // channels of the benchmark net (the 
 // skip them, position-major units point the affected lanes at a zero cell.
 // (Round 1 measured 2 positions x 2 workgroups per CU, a tile-major last tap and the 16x16x32 MFMA shape, round 2 the
 // MW = 2 split at C = 128: all within +-1 % because the kernel sits on the power-limited clock -- DESIGN.md 5.)
-template <int C_, int P_ = 512 / C_, bool M16_ = false> struct Tw {
+template <int C_, int P_ = 512 / C_, bool M16_ = false, int MAP_ = 0> struct Tw {
     static_assert(C_ == 64 || C_ == 128 || C_ == 256, "the MFMA tower is built for 64, 128 or 256 channels");
     static constexpr int C = C_;
+    // MAP = 1: the 16x16x32 path on the edge-aware cell tiling of bz_tile_map.h ("the edge-aware tiling" at the end of this
+    // file); MAP = 0: every geometry as it was
+    static constexpr bool EDGE = MAP_ == 1;
+    static_assert(MAP_ == 0 || (MAP_ == 1 && M16_ && C_ == 128 && P_ == 4), "the edge-aware tiling serves Tw<128, 4, true> only");
     // M16: the K-loop on v_mfma_f32_16x16x32_bf16 instead of 32x32x16 (the "16x16x32 path" at the end of this file):
     // the same LDS image, the same bytes per MAC from LDS and L2, the same cycles -- and a higher clock under load
     static constexpr bool M16 = M16_;
@@ -103,7 +111,8 @@ template <int C_, int P_ = 512 / C_, bool M16_ = false> struct Tw {
     }
     // byte offset of 16-byte chunk k of board cell c of the workgroup's position p, inside that position
     static __device__ __forceinline__ int cell_off(int p, int c, int k) {
-        if constexpr (M16) return cell_at(c >> 3, c & 7) + pos16(k, c & 7);
+        if constexpr (EDGE) return cell_at(c >> 3, c & 7) + (bz_tile_map::slot(k, p, c >> 3, c & 7) << 4);
+        else if constexpr (M16) return cell_at(c >> 3, c & 7) + pos16(k, c & 7);
         else return cell_at(c >> 3, c & 7) + ((k ^ sw(ROWT ? p : c >> 3, c & 7)) << 4);
     }
     // unit u, lane column r (0..31) -> position inside the wave and board cell
@@ -493,6 +502,120 @@ __device__ __forceinline__ void epilogue16(f32x16 (&acc)[G::MW][G::NU], char* ou
     }
 }
 
+// ------------------------------------------------------------------ the edge-aware tiling (Tw<128, 4, true, 1>)
+// The 16x16x32 path above with the wave's 256 (position, cell) pairs dealt to its 16 N-tiles by bz_tile_map.h instead of
+// (board row, position pair): tile t is quarter 2 a + (t & 1) of accumulator unit t >> 1, a sub-step (kq, hf) runs the
+// eight tiles 2 j + hf, and a tap skips the tiles that it shifts onto the halo as a whole -- rows as before, and now the
+// column tiles 4 (dx = -1) and 5 (dx = +1): 126 tile-taps per layer instead of 132, i.e. 1008 MFMAs and 504 ds_read_b128
+// instead of 1056 and 528.  Every output element still sums taps 0..8 and, inside a tap, kq = 0..3 in ascending order,
+// and what is skipped are exact zeros: the outputs are bit-identical to MAP = 0.
+// Addresses: lane column c of a tile reads  lane part (register) + tile and tap part (immediate).  The chunk's slot
+// depends on the row, so a tile's slot is its pattern's rotated by a compile-time amount (bz_tile_map::slot_rot): the
+// lane keeps one offset per (pattern, rotation) -- at most 4 x 8 registers, computed once per layer, whatever the tap.
+namespace tmap = bz_tile_map;
+struct EdgeOff { int o[tmap::kPatterns][8]; };
+// sub = the odd part of the chunk index that the lane adds (K-loop: its k-group g; epilogue: g >> 1), rot0 = a wave-uniform
+// rotation on top of the compile-time one, extra = bytes added to every offset
+template <class G>
+__device__ __forceinline__ void edge_offsets(EdgeOff& E, int c, int sub, int rot0, int extra) {
+#pragma unroll
+    for (int pat = 0; pat < tmap::kPatterns; ++pat)
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            E.o[pat][u] = tmap::lane_cells(pat, c) * G::CELL + (tmap::lane_slot(pat, c, sub, (u + rot0) & 7) << 4) + extra;
+}
+// activation fragments of sub-step (kq, hf) of tap TAP: b[j] = tile 2 j + hf
+template <class G, int TAP>
+__device__ __forceinline__ void load_b_edge(bf16x8 (&b)[G::NU], const char* in, const EdgeOff& E, int kq, int hf) {
+#pragma unroll
+    for (int j = 0; j < G::NU; ++j) {
+        const int t = 2 * j + hf;
+        if (!tmap::skip(TAP, t))
+            b[j] = *reinterpret_cast<const bf16x8*>(in + E.o[tmap::pattern(t)][tmap::slot_rot(t, TAP, 4 * kq)] +
+                                                    (tmap::tile_cells(t) + tmap::tap_cells(TAP)) * G::CELL);
+    }
+}
+template <class G, int TAP, int HF>
+__device__ __forceinline__ void mfma_edge(f32x16 (&acc)[G::MW][G::NU], const bf16x8 (&a)[2], const bf16x8 (&b)[G::NU]) {
+#pragma unroll
+    for (int j = 0; j < G::NU; ++j)
+        if (!tmap::skip(TAP, 2 * j + HF)) {  // tile-major: consecutive MFMAs share the activation operand, as mfma_units16
+            mfma16_quarter<HF>(acc[0][j], a[0], b[j]);
+            mfma16_quarter<2 + HF>(acc[0][j], a[1], b[j]);
+        }
+}
+// one conv tap, as tap_step16: 2 KQ sub-steps, the (2 MFMA, 1 DS read) groups counted in the tiles each sub-step runs
+template <int S, int TAP, class G>
+__device__ __forceinline__ void tap_step_edge(f32x16 (&acc)[G::MW][G::NU], WSets16<G>& WS, const uint4*& ap, const char* in,
+                                              const EdgeOff& E, int lane, bf16x8 (&B)[2][G::NU]) {
+    constexpr bool last = TAP == 8;
+    constexpr int TAP_N = last ? TAP : TAP + 1;
+    bf16x8 (&use)[G::KQ][2] = WS.s[S];
+    bf16x8 (&nxt)[G::KQ][2] = WS.s[S ^ 1];
+#pragma unroll
+    for (int kq = 0; kq < G::KQ; ++kq)
+#pragma unroll
+        for (int a = 0; a < 2; ++a) nxt[kq][a] = __builtin_bit_cast(bf16x8, ap[(kq * G::MT * 2 + a) * 64 + (unsigned)lane]);
+    ap += G::KQ * G::MT * 2 * 64;
+    constexpr int NS = 2 * G::KQ;
+#pragma unroll
+    for (int ss = 0; ss < NS; ++ss) {
+        if (ss + 1 < NS) load_b_edge<G, TAP>(B[(ss + 1) & 1], in, E, (ss + 1) >> 1, (ss + 1) & 1);
+        else if constexpr (!last) load_b_edge<G, TAP_N>(B[0], in, E, 0, 0);  // first sub-step of the next tap
+        if (ss & 1) mfma_edge<G, TAP, 1>(acc, use[ss >> 1], B[1]);
+        else mfma_edge<G, TAP, 0>(acc, use[ss >> 1], B[0]);
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int nm = tmap::tiles_of_half(TAP, i & 1);  // tiles whose MFMAs run in sub-step i / whose reads it issues
+        const int nr = i + 1 < NS ? tmap::tiles_of_half(TAP, (i + 1) & 1) : last ? 0 : tmap::tiles_of_half(TAP_N, 0);
+#pragma unroll
+        for (int j = 0; j < G::NU; ++j) {
+            if (j < nm) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // the tile's 2 MFMAs
+            if (j < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 DS read
+        }
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                  // 1 VMEM read (weight prefetch)
+    }
+    __builtin_amdgcn_sched_barrier(0);  // one tap per scheduling region
+}
+template <int S0, int TAP, class G>
+__device__ __forceinline__ void run_taps_edge(f32x16 (&acc)[G::MW][G::NU], WSets16<G>& WS, const uint4*& ap, const char* in,
+                                              const EdgeOff& E, int lane, bf16x8 (&B)[2][G::NU]) {
+    if constexpr (TAP < 9) {
+        tap_step_edge<(S0 + TAP) & 1, TAP, G>(acc, WS, ap, in, E, lane, B);
+        run_taps_edge<S0, TAP + 1, G>(acc, WS, ap, in, E, lane, B);
+    }
+}
+// +bias (+skip) -> ReLU -> bf16 -> LDS, as epilogue16: lane (c, g) holds channels 32 wt + 16 a + 4 g + i of pair c of tile t,
+// i.e. the (g & 1) half of chunk 4 wt + 2 a + (g >> 1) of that cell
+template <class G>
+__device__ __forceinline__ void epilogue_edge(f32x16 (&acc)[G::MW][G::NU], char* out, bool second, const Bias<G>& bias, int wt,
+                                              int lane) {
+    const int c = lane & 15, g = lane >> 4;
+    EdgeOff E;
+    edge_offsets<G>(E, c, g >> 1, 2 * wt, 8 * (g & 1));
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const f32x4 bq = bias.q[0][a];
+#pragma unroll
+        for (int t = 0; t < tmap::kTiles; ++t) {
+            const int off = E.o[tmap::pattern(t)][tmap::slot_rot(t, tmap::kCentre, 2 * a)] + tmap::tile_cells(t) * G::CELL;
+            const int q = 2 * a + (t & 1), u = t >> 1;
+            f32x4 v = {acc[0][u][4 * q], acc[0][u][4 * q + 1], acc[0][u][4 * q + 2], acc[0][u][4 * q + 3]};
+            v = v + bq;
+            if (second) {
+                bf16x4 sk = *reinterpret_cast<const bf16x4*>(out + off);
+                v = v + __builtin_convertvector(sk, f32x4);
+            }
+            v = relu_f32x4(v);
+            f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
+            s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
+            s16x2 hi = __builtin_bit_cast(s16x2, __builtin_convertvector(vhi, bf16x2));
+            *reinterpret_cast<uint2*>(out + off) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
+        }
+    }
+}
+
 // One conv3x3 layer over the resident positions: LDS -> MFMA -> (+bias, +skip, ReLU) -> LDS.
 // S0 = register set that holds chunk 0's weight fragments on entry; on exit it is set (S0 + NCH) % DEPTH.
 // What happens to a layer's accumulators is a policy: EpInfer = the inference epilogue above; the training kernels
@@ -500,13 +623,14 @@ __device__ __forceinline__ void epilogue16(f32x16 (&acc)[G::MW][G::NU], char* ou
 template <class G> struct EpInfer {
     __device__ __forceinline__ void operator()(f32x16 (&acc)[G::MW][G::NU], char* out, bool second, const Bias<G>& bias, int wt0,
                                                int r, int h) const {
-        if constexpr (G::M16) epilogue16<G>(acc, out, second, bias, wt0, 32 * h + r);
+        if constexpr (G::EDGE) epilogue_edge<G>(acc, out, second, bias, wt0, 32 * h + r);
+        else if constexpr (G::M16) epilogue16<G>(acc, out, second, bias, wt0, 32 * h + r);
         else epilogue<G>(acc, out, second, bias, wt0, r, h);
     }
 };
 // the weight-fragment register sets of a geometry
 template <class G> struct WSetsOf { typedef WSets<G> type; };
-template <int C_, int P_> struct WSetsOf<Tw<C_, P_, true>> { typedef WSets16<Tw<C_, P_, true>> type; };
+template <int C_, int P_, int MAP_> struct WSetsOf<Tw<C_, P_, true, MAP_>> { typedef WSets16<Tw<C_, P_, true, MAP_>> type; };
 template <int S0, class G, class EP = EpInfer<G>>
 __device__ __forceinline__ void conv_layer(const char* in, char* out, bool second, const float* __restrict__ bl,
                                            typename WSetsOf<G>::type& WS, const uint4*& ap, int w, int r, int h,
@@ -524,7 +648,15 @@ __device__ __forceinline__ void conv_layer(const char* in, char* out, bool secon
     if constexpr (G::M16) load_bias16<G>(bias, bl, G::wt0(w), (32 * h + r) >> 4);
     else load_bias<G>(bias, bl, G::wt0(w), h);
     int boff[2];
-    if constexpr (G::M16) {
+    if constexpr (G::EDGE) {
+        bf16x8 B[2][G::NU];
+        const int lane = 32 * h + r;
+        EdgeOff E;
+        edge_offsets<G>(E, lane & 15, lane >> 4, 0, 0);
+        load_b_edge<G, 0>(B[0], in, E, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        run_taps_edge<S0, 0, G>(acc, WS, ap, in, E, lane, B);
+    } else if constexpr (G::M16) {
         static_assert(G::ROWT && G::MW == 1 && G::C == 128, "the 16x16x32 path serves the row-tile shape of the 128-channel net");
         bf16x8 B[2][G::NU];
         const int lane = 32 * h + r;

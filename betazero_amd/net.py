@@ -222,6 +222,11 @@ class DeviceNet:
         are bit for bit the same in every mode."""
         _lib.check(_lib.lib().bz_net_set_adaptive_shape(self.h, int(mode)))
 
+    def set_tile_map(self, edge=True):
+        """the 128-channel throughput shape of the plain bf16 forward: True / 1 = the edge-aware cell tiling (k_edge_bf16,
+        the default), False / 0 = board-row tiles (k_tower_bf16).  Results are bit for bit the same under both."""
+        _lib.check(_lib.lib().bz_net_set_tile_map(self.h, int(edge)))
+
     def shape_tally(self):
         """{shape: device-count tower launches that did work since the last call}; waits for the current stream"""
         c = (C.c_int64 * 3)()

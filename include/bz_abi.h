@@ -214,6 +214,12 @@ int32_t bz_net_forward_counted(bz_net* net, int32_t kind, const uint64_t* own, c
                                const uint32_t* n_dev, float* logits, float* value, void* stream);
 int32_t bz_net_set_adaptive_shape(bz_net* net, int32_t mode);
 int32_t bz_net_shape_tally(bz_net* net, int64_t* counts /* [3] */, void* stream);
+/* bz_net_set_tile_map (an addition to ABI 7): which kernel runs the throughput shape of the plain bf16 forward
+ *   at C == 128, with a host count or a device count (the adaptive pair's high window included): 1 = k_edge_bf16 on the
+ *   edge-aware cell tiling (csrc/bz_tile_map.h; the default), 0 = k_tower_bf16 on board-row tiles.  Every row is bit for bit
+ *   the same under both; both count in the throughput slot of bz_net_shape_tally.  The symmetric forward, the latency
+ *   shape, the other widths and fp8 do not depend on it.  Takes effect for the launches issued after it. */
+int32_t bz_net_set_tile_map(bz_net* net, int32_t map);
 
 /* ---- the forward under a board symmetry ----
  * Eight elements s = 0..7 on the size x size corner of the 8x8 planes: 0..6 are bz_augment_d4_batch's transforms 0..6

@@ -4,7 +4,10 @@
 (DeviceNet.set_adaptive_shape: 2 = latency, 0 = throughput, 1 = the adaptive pair, which adds the empty launch), in two
 configurations: `alone`, and `two_streams` = the same launch running on a second stream at the same time, which is what
 the head of a move looks like with two pipelines.  us = wall time of `reps` back-to-back launches per stream / reps.
-usage: python tools/bench_tower_shapes.py [out.jsonl] [--reps N]"""
+--rows / --max-n / --modes time other counts, buffers and shapes (e.g. the engine's 1300 and 4096 rows on the throughput
+shape alone); --tile-map 0|1 picks the throughput shape's kernel (DeviceNet.set_tile_map: board-row tiles / edge-aware).
+usage: python tools/bench_tower_shapes.py [out.jsonl] [--reps N] [--rows A,B,..] [--max-n N] [--modes latency,throughput,adaptive]
+       [--tile-map 0|1]"""
 import json
 import os
 import sys
@@ -22,11 +25,18 @@ MODES = (("latency", 2), ("throughput", 0), ("adaptive", 1))
 
 def main():
     args = sys.argv[1:]
-    reps = int(args[args.index("--reps") + 1]) if "--reps" in args else 200
+    opt = lambda k, d: args[args.index(k) + 1] if k in args else d  # noqa: E731
+    reps = int(opt("--reps", 200))
+    ROWS = tuple(int(v) for v in opt("--rows", ",".join(map(str, globals()["ROWS"]))).split(","))
+    MAX_N = int(opt("--max-n", max(globals()["MAX_N"], max(ROWS))))
+    MODES = tuple(m for m in globals()["MODES"] if m[0] in opt("--modes", "latency,throughput,adaptive").split(","))
+    tile_map = opt("--tile-map", None)
     out = open(args[0], "w") if args and not args[0].startswith("--") else None
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     net = DeviceNet.from_module(PolicyValueNet(128, 6, 64).round_to_bf16_(), MAX_N, dev)
+    if tile_map is not None:
+        net.set_tile_map(int(tile_map))
     d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "reversi_random_games.npz"))["rows"]
     d = d[d[:, 1] == 8]
     idx = np.arange(MAX_N) % len(d)
@@ -49,6 +59,8 @@ def main():
         for name, mode in MODES:
             net.set_adaptive_shape(mode)
             rec = {"shape": name, "rows": rows, "max_n": MAX_N, "reps": reps}
+            if tile_map is not None:
+                rec["tile_map"] = int(tile_map)
             for cfg, ns in (("alone", 1), ("two_streams", 2)):
                 run(ns, 10)
                 torch.cuda.synchronize(dev)
