@@ -2,7 +2,9 @@
 k_solve_play / k_solve_cap_play, the solver branch of k_root_policy and the reader kernel against the solver twin of
 tests/test_solver_cpu.py.  "Equal" = bit for bit: root N / W / P, the proof state of every root edge and of the root, the two
 counts, the played move, and in self-play every row, winner and length.  Every proof the engine reports on the tic-tac-toe and
-4x4 sets is also held to the negamax value directly."""
+4x4 sets is also held to the negamax value directly.  The second half runs self-play with a net in the loop -- every evaluation
+cache mode, so that a slot's previous arena and the root store's trees hold proven edges --, the step API, two pipelines and
+the observing options against the same twin."""
 import ctypes as C
 
 import numpy as np
@@ -13,10 +15,12 @@ import betazero_amd as bz
 from betazero_amd import _lib
 from betazero_amd.engine import PlayoutCap, SelfPlayEngine
 from betazero_amd.match import MatchPlayer, play_match
+from oracle import py_twin
 from oracle.py_twin import Twin
 from test_gpu_playout_cap import _bits, _run, _same_rows
-from test_solver_cpu import (S_COMPLETE, SolverTwin, boards, forced_win_fixtures, negamax, rev4_positions, rev4_roots, ttt5_roots,
-                             ttt_positions)
+from test_solver_cpu import (NET_CAP, NET_CAP_BASE, NET_CASE, OBSERVER_CASE, S_COMPLETE, SolverTwin, boards, exact_bf16_net, forced_win_fixtures, negamax,
+                             net_case_store, net_case_twins, observer_case_twins, rev4_positions, rev4_roots, solver_twins, ttt5_roots, ttt_positions,
+                             twin_figures)
 
 pytestmark = pytest.mark.gpu
 NOISE = dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)
@@ -266,3 +270,200 @@ def test_arena_with_the_solver_plays_its_games_to_the_end():
     from betazero_amd.arena import play_arena
     s = play_arena("ttt", 16, 64, evaluator="uniform", solver=True, opening_plies=1, seed=1).summary()
     assert s["games"] == 16 and s["wins"] + s["draws"] + s["losses"] == 16, s
+
+
+# ---------------------------------------------------------------- self-play with the net in the loop, the step API, observers
+def _case(game, n, sims, ev, twins, cap=None, external=None, base=0, noise=False, **kw):
+    """n games to the end against their twins, search by search as in the noise-and-cap test above: N, W, P, the proof of every
+    root edge and of the root, pi, the action, both counts, under the cap the budgets; then rows, winners, lengths and
+    n_sims.  The previous search of a slot is a solver search: what the carry-over cache (and the root store) copy from holds
+    proven edges.  Returns (engine, counters, searches with a decided root, decided root edges)."""
+    eng = SelfPlayEngine(game, n, sims, "external" if external else ev, solver=True, game_id_base=base,
+                         playout_cap=PlayoutCap(cap[0], cap[1] / 65536) if cap else None, **(NOISE if noise else {}), **kw)
+    eng.reset_counters()
+    eng.reset_games()
+    step = roots = edges_dec = 0
+    while True:
+        if external:
+            eng.search_external(external)
+        else:
+            eng.search()
+        if cap:
+            want = [tw.budgets[step] if step < len(tw.budgets) else 0 for tw, _, _ in twins]
+            assert np.array_equal(eng.budgets(), np.array(want, np.uint32)), step
+        N, W, P = eng.root_stats()
+        pi, act = eng.root_policy()
+        proven, edges, counts = eng.proven()
+        nd = ns = 0
+        for g, (tw, _, _) in enumerate(twins):
+            if step >= len(tw.log):
+                assert act[g] == -1 and proven[g] is None and (edges[g] == 2).all() and not pi[g].any(), (step, g)
+                continue
+            lg = tw.log[step]
+            a = lg["a"]
+            assert np.array_equal(N[g, a], np.array(lg["N"], np.uint32)) and int(N[g].sum()) == lg["budget"], (step, g, N[g, a], lg["N"])
+            assert np.array_equal(_bits(W[g, a]), _bits(lg["W"])) and np.array_equal(_bits(P[g, a]), _bits(lg["P"])), (step, g)
+            assert [None if v == 2 else int(v) for v in edges[g, a]] == lg["c"] and proven[g] == lg["proven"], (step, g, edges[g, a], lg["c"])
+            assert int((edges[g] != 2).sum()) == sum(c is not None for c in lg["c"]), (step, g)
+            assert act[g] == lg["act"] and np.array_equal(_bits(pi[g]), _bits(lg["pi"])), (step, g)
+            nd, ns = nd + lg["n_decided"], ns + lg["n_stops"]
+            roots += lg["proven"] is not None
+            edges_dec += sum(c is not None for c in lg["c"])
+        assert counts == {"n_decided": nd, "n_proven_stops": ns}, (step, counts, nd, ns)
+        eng.play(False)
+        step += 1
+        if eng.status()[0] == 0:
+            break
+        assert step < 200
+    ex = eng.examples()
+    winners, lens = eng.winners()
+    cnt = eng.counters()
+    for g, (tw, rows, w) in enumerate(twins):
+        assert lens[0, g] == len(rows) and winners[0, g] == w, (g, lens[0, g], len(rows), winners[0, g], w)
+        _same_rows(ex, base + g, rows, w)
+    assert len(ex) == sum(len(r) for _, r, _ in twins)
+    assert cnt["n_sims"] == sum(b for tw, _, _ in twins for b in tw.budgets)
+    assert roots > 0 and edges_dec > 0  # the run holds decided roots and decided edges
+    return eng, cnt, roots, edges_dec
+
+
+def _net_case(cache, capped):
+    from test_gpu_search_net import _dn
+    Pn, _ = exact_bf16_net()
+    twins = net_case_twins(capped)
+    kw = dict(NET_CASE)
+    eng, cnt, _, _ = _case(kw.pop("game"), kw.pop("n"), kw.pop("sims"), "net_bf16", twins, cap=NET_CAP if capped else None, noise=capped,
+                           base=NET_CAP_BASE if capped else 0, net=_dn(Pn, NET_CASE["n"]), eval_cache=cache, **kw)
+    assert cnt["n_net_leaves"] + cnt["n_cache_hits"] == sum(tw.n_evals for tw, _, _ in twins), cnt
+    assert (cnt["n_cache_hits"] > 0) == (cache is not False), cnt
+    assert (cnt["n_cache_hits_prev"] > 0) == (cache is True), cnt
+    r = eng.root_store_counters()
+    print("cache", cache, "capped", capped, cnt, r)
+    if cache is True:  # the default engine: the carry-over and the root store copy from trees that hold proven edges
+        assert eng.root_store == (256, 3) and r["n_seeded_searches"] > 0 and r["n_seeded_evals"] > 0 and r["n_root_saves"] > 0, r
+        assert (r["n_root_saves"], r["n_seeded_searches"]) == net_case_store(capped), r  # ... exactly where the games say it does
+    else:
+        assert eng.root_store is None and r == {"n_seeded_evals": 0, "n_seeded_searches": 0, "n_root_saves": 0}, r
+    return twins
+
+
+@pytest.mark.parametrize("cache", [False, "search", True])
+def test_selfplay_with_the_exact_bf16_net_equals_the_twin_in_every_cache_mode(cache):
+    """the search-grade exact bf16 net (tests/test_search_net_cpu.py), the twin's evaluator the oracle's bf16 forward.  From the
+    second move on a slot's previous arena is a solver tree: the carry-over re-creates its nodes from edges that carry proofs,
+    and the staggered pool brings roots back that the store holds -- n_net_leaves + n_cache_hits stays the twin's evaluation
+    count in every mode"""
+    twins = _net_case(cache, False)
+    assert {b for tw, _, _ in twins for b in tw.budgets} == {NET_CASE["sims"]}
+
+
+def test_selfplay_with_the_exact_bf16_net_under_the_cap_with_noise_equals_the_twin():
+    twins = _net_case(True, True)
+    assert {b for tw, _, _ in twins for b in tw.budgets} == {NET_CASE["sims"], NET_CAP[0]}
+
+
+def test_net_f32_selfplay_equals_the_twin_with_the_per_position_forward():
+    from test_gpu_leaf_parallel import _net32, _net_fn
+    dn = _net32()
+    kw = dict(temp_moves=8, openings=1, seed=3)
+    twins = solver_twins("reversi", "net", 4, 16, eval_fn=_net_fn(dn), **kw)
+    _case("reversi", 4, 16, "net_f32", twins, net=dn, **kw)
+
+
+@pytest.mark.parametrize("cap", [None, (8, 32768)], ids=["plain", "cap"])
+def test_external_evaluator_through_the_step_api_equals_the_twin(cap):
+    """select / expand_backup as separate launches: every proof pass runs in an expand-only step, behind a backup whose walk
+    an earlier launch selected"""
+    na = 65
+
+    def external(own, opp, kind):
+        o = own.cpu().numpy().view(np.uint64)
+        q = opp.cpu().numpy().view(np.uint64)
+        k = kind.cpu().numpy()
+        lg = np.zeros((len(o), na), np.float32)
+        v = np.zeros(len(o), np.float32)
+        for i in np.nonzero(k == 1)[0]:
+            lg[i], v[i] = py_twin.eval_hash(int(o[i]), int(q[i]), na)
+        return torch.from_numpy(lg).cuda(), torch.from_numpy(v).cuda()
+    kw = dict(temp_moves=3, seed=8)
+    twins = solver_twins("reversi4", "hash", 6, 32, cap=cap, noise=True, **kw)
+    _case("reversi4", 6, 32, "hash", twins, cap=cap, external=external, noise=True, **kw)
+    assert {b for tw, _, _ in twins for b in tw.budgets} == ({32, 8} if cap else {32})
+    assert sum(lg["n_stops"] for tw, _, _ in twins for lg in tw.log) > 0
+
+
+def test_two_pipelines_equal_the_twin():
+    from betazero_amd.engine import PipelinedSelfPlay
+    n, sims = 12, 32
+    kw = dict(temp_moves=4, seed=9)
+    sp = PipelinedSelfPlay("reversi4", n, sims, "hash", pipelines=2, solver=True, game_id_base=100, **kw, **NOISE)
+    sp.reset_counters()
+    sp.run_iteration()
+    assert sp.status()[0] == 0
+    ex, (winners, lens), cnt = sp.examples(), sp.winners(), sp.counters()
+    # the two engines hold slots 0..5 of games 100..105 and 106..111: every draw is keyed by the global game id
+    twins = solver_twins("reversi4", "hash", 6, sims, base=100, noise=True, **kw) + \
+        solver_twins("reversi4", "hash", 6, sims, base=100, noise=True, slot0=6, **kw)
+    for g, (tw, rows, w) in enumerate(twins):
+        assert lens[0, g] == len(rows) and winners[0, g] == w, g
+        _same_rows(ex, 100 + g, rows, w)
+    assert cnt["n_sims"] == sum(b for tw, _, _ in twins for b in tw.budgets) and len(ex) == sum(len(r) for _, r, _ in twins)
+    f = twin_figures(twins)
+    assert f["decided_roots"] > 0 and f["n_stops"] > 0, f
+
+
+def test_surprise_search_value_and_ownership_columns_equal_the_twins():
+    """q is the value of the RAW visits of its root -- sum W / sum N -- also where the root is decided: a proven win still reads
+    what the walks backed up, not +1 (tests/test_solver_cpu.py holds that this case has such rows)"""
+    from test_ownership_cpu import ownership_row
+    twins = observer_case_twins()
+    kw = dict(OBSERVER_CASE)
+    eng, _, _, _ = _case(kw.pop("game"), kw.pop("n"), kw.pop("sims"), "hash", twins, noise=True, surprise=True, search_value=True,
+                         ownership=True, **kw)
+    ex = eng.examples()
+    for g, (tw, rows, w) in enumerate(twins):
+        msk = ex.game == g
+        assert np.array_equal(_bits(ex.kl[msk]), _bits(tw.kl_rows(rows))), g
+        assert np.array_equal(_bits(ex.q[msk]), _bits(tw.q_rows(rows))), g
+        fx, fo = tw.final_bits()
+        want = ownership_row(np.full(len(rows), fx, np.uint64), np.full(len(rows), fo, np.uint64), np.array([r[3] for r in rows]))
+        assert np.array_equal(ex.fown[msk], want[0]) and np.array_equal(ex.fopp[msk], want[1]), g
+    assert (ex.kl > 0).any() and (ex.q != 0).any() and len(np.unique(ex.fown)) > 1
+
+
+def test_eval_symmetry_with_the_solver_plays_the_games_of_a_second_identical_engine_and_every_proof_is_the_negamax_value():
+    """(the symmetry changes the evaluator, not the rule: pinned product against product, as tests/test_gpu_symmetry.py does;
+    a proof does not depend on the evaluator at all, so every reported one is still held to negamax)"""
+    from betazero_amd.engine import EvalSymmetry
+    from test_gpu_leaf_parallel import _net32
+    dn = _net32()
+    kw = dict(net=dn, temp_moves=4, seed=6, solver=True)
+
+    def run(**more):
+        eng = SelfPlayEngine("reversi4", 8, 32, "net_f32", **kw, **more)
+        eng.reset_counters(); eng.reset_games()
+        pos, roots, edges, acts = [], [], [], []
+        for step in range(64):
+            eng.search()
+            own, opp, tm, st = eng.positions()
+            pr = eng.proven()
+            _, act = eng.root_policy()
+            for g in np.nonzero(st == 0)[0]:
+                x, o = (own[g], opp[g]) if tm[g] == 1 else (opp[g], own[g])
+                pos.append((bz.ReversiBoard.from_bits(int(x), int(o), 4), int(tm[g])))
+                roots.append(pr[0][g]); edges.append(pr[1][g])
+            acts.append(act.copy())
+            eng.play(False)
+            if eng.status()[0] == 0:
+                break
+        else:
+            raise AssertionError("the games did not end")
+        return eng.examples(), eng.winners(), np.array(acts), (pos, roots, np.array(edges))
+    a, (wa, la), aa, (pos, roots, edges) = run(eval_symmetry=EvalSymmetry(11))
+    b, (wb, lb), ab, _ = run(eval_symmetry=EvalSymmetry(11))
+    assert len(a) == len(b) > 0 and np.array_equal(wa, wb) and np.array_equal(la, lb) and np.array_equal(aa, ab)
+    assert np.array_equal(a.act, b.act) and np.array_equal(_bits(a.pi), _bits(b.pi)) and np.array_equal(a.own, b.own)
+    c, _, ac, _ = run()
+    assert c.pi.shape != a.pi.shape or not np.array_equal(_bits(c.pi), _bits(a.pi))  # not the games without the symmetry
+    n = _sound("reversi4", pos, (roots, edges, None))
+    assert n > 0 and sum(r is not None for r in roots) > 0, n

@@ -13,7 +13,10 @@ import betazero_amd as bz
 from betazero_amd import _lib
 from oracle.py_twin import Twin, f32, rng_draw
 from test_forced_playouts_cpu import _score
+from test_ownership_cpu import OwnTwin, winner_of
 from test_playout_cap_cpu import CapTwin, _cfg, boards, cap_budget
+from test_surprise_cpu import _Surprise
+from test_value_targets_cpu import _Value
 
 UND = 2  # "undecided" at the ABI
 TTT_GW = 4  # lanes per tic-tac-toe game in the tree kernels (csrc/bz_rules.h)
@@ -447,6 +450,135 @@ def test_selfplay_twin_under_the_cap_with_noise_records_full_searches_only_and_a
                 assert c != 1
             lost += c == 1
     assert decided > 0
+
+
+# ---------------------------------------------------------------- the twin runs behind the net / observer cases of the GPU file
+NOISE_TWIN = dict(dir_alpha=0.3, dir_eps=0.25)
+
+
+def solver_twins(game, ev, n, sims, cap=None, temp_moves=0, openings=0, seed=0, base=0, stagger=0, eval_fn=None, noise=False, slot0=0,
+                 cls=SolverTwin):
+    """every game's solver twin, played to the end: [(twin, rows, winner)]; a twin keeps its own game's log and budgets"""
+    out = []
+    for g in range(n):
+        tw = cls(game, ev, cap=cap, eval_fn=eval_fn, boards=boards(), **(NOISE_TWIN if noise else {}))
+        rows, w, _ = tw.selfplay(base + slot0 + g, sims, temp_moves, openings, seed, slot=g, stagger=stagger)
+        out.append((tw, rows, w))
+    return out
+
+
+def twin_figures(twins):
+    """what keeps a case from passing vacuously: searches with a decided root, decided root edges, nodes decided, walks that
+    stopped at a proven edge, the budgets drawn"""
+    logs = [lg for tw, _, _ in twins for lg in tw.log]
+    return {"decided_roots": sum(lg["proven"] is not None for lg in logs), "decided_edges": sum(c is not None for lg in logs for c in lg["c"]),
+            "n_decided": sum(lg["n_decided"] for lg in logs), "n_stops": sum(lg["n_stops"] for lg in logs),
+            "budgets": {b for tw, _, _ in twins for b in tw.budgets}, "searches": len(logs)}
+
+
+@functools.lru_cache(maxsize=None)
+def exact_bf16_net():
+    """(P, oracle net): the search-grade exact bf16 net of tests/test_search_net_cpu.py, 64 channels x 1 block"""
+    from test_search_net_cpu import SEED, VH, oracle_net, search_net
+    P = search_net(64, 1, VH, "bf16", SEED)
+    return P, oracle_net(P, "bf16")
+
+
+def store_figures(twins, base, seed, stagger, sims, plies=3):
+    """what the root store of an engine playing these games once, in lockstep, does: (trees filed, searches
+    seeded).  Behind every search the roots fewer than `plies` moves into their game that are not on file are filed -- full
+    searches only, one tree per position, the lowest slot's -- and a search whose root is on file by then is seeded."""
+    made0 = [tw.start(g, base + g, 0, seed, stagger)[2] for g, (tw, _, _) in enumerate(twins)]
+    filed, seeds = set(), 0
+    for s in range(max(len(tw.log) for tw, _, _ in twins)):
+        new = set()
+        for g, (tw, _, _) in enumerate(twins):
+            if s < len(tw.log) and made0[g] + s < plies:
+                key = tw.bits(tw.log[s]["b"], tw.log[s]["p"])
+                if key in filed:
+                    seeds += 1
+                elif tw.log[s]["budget"] == sims:
+                    new.add(key)
+        filed |= new
+    return len(filed), seeds
+
+
+NET_CASE = dict(game="reversi6", n=8, sims=32, temp_moves=4, seed=2, stagger=3)
+NET_CAP = (8, 16384)  # PlayoutCap(8, 0.25)
+# game id base of the capped run.  The games are played once, so a search is seeded only where the stagger brings a slot to a
+# root another slot's full search filed; under the cap with noise that is rare -- base 0: 4 trees filed, none met again;
+# base 72: 6 filed, 4 searches seeded (store_figures)
+NET_CAP_BASE = 72
+
+
+@functools.lru_cache(maxsize=None)
+def net_case_twins(capped):
+    """the twins of the exact-bf16-net case of tests/test_gpu_solver.py (every cache mode compares with this one run), and of
+    the same case under the cap with Dirichlet noise; the evaluator is the oracle's bf16 forward"""
+    from test_search_net_cpu import oracle_eval_fn
+    kw = dict(NET_CASE)
+    return solver_twins(kw.pop("game"), "net", kw.pop("n"), kw.pop("sims"), cap=NET_CAP if capped else None,
+                        eval_fn=oracle_eval_fn(exact_bf16_net()[1], "bf16"), noise=capped, base=NET_CAP_BASE if capped else 0, **kw)
+
+
+def net_case_store(capped):
+    return store_figures(net_case_twins(capped), NET_CAP_BASE if capped else 0, NET_CASE["seed"], NET_CASE["stagger"], NET_CASE["sims"])
+
+
+class ObserverTwin(OwnTwin(SolverTwin)):
+    """SolverTwin with the three observers: each mix-in keeps its own view of every searched root, _Own the final board"""
+    kl_rows, row_kl, q_rows, row_q = _Surprise.kl_rows, _Surprise.row_kl, _Value.q_rows, _Value.row_q
+
+    def root_noise(self, root):
+        _Surprise._keep(self, root)
+        _Value._keep(self, root)
+        super().root_noise(root)
+
+
+OBSERVER_CASE = dict(game="reversi4", n=8, sims=32, temp_moves=3, seed=5)
+
+
+@functools.lru_cache(maxsize=None)
+def observer_case_twins():
+    kw = dict(OBSERVER_CASE)
+    return solver_twins(kw.pop("game"), "hash", kw.pop("n"), kw.pop("sims"), noise=True, cls=ObserverTwin, **kw)
+
+
+@pytest.mark.parametrize("capped", [False, True])
+def test_the_net_case_of_the_gpu_file_holds_decided_roots_proven_stops_and_under_the_cap_both_budgets(capped):
+    """a seed that makes the GPU case vacuous fails here first"""
+    twins = net_case_twins(capped)
+    f = twin_figures(twins)
+    print("capped" if capped else "plain", f, "evaluations", sum(tw.n_evals for tw, _, _ in twins))
+    assert f["decided_roots"] > 0 and f["decided_edges"] > 0 and f["n_decided"] > 0 and f["n_stops"] > 0, f
+    assert f["budgets"] == ({NET_CASE["sims"], NET_CAP[0]} if capped else {NET_CASE["sims"]}), f
+    for tw, rows, _ in twins:
+        assert [sum(lg["N"]) for lg in tw.log] == tw.budgets and len(rows) == sum(b == NET_CASE["sims"] for b in tw.budgets)
+    saves, seeds = net_case_store(capped)
+    print("the root store: trees filed", saves, "searches seeded", seeds)
+    assert (saves, seeds) == ((6, 4) if capped else (8, 2))  # the store fires in the default engine's run
+
+
+def test_the_observer_case_of_the_gpu_file_holds_decided_roots_and_columns_that_are_not_constant():
+    twins = observer_case_twins()
+    f = twin_figures(twins)
+    print(f)
+    assert f["decided_roots"] > 0 and f["decided_edges"] > 0 and f["n_decided"] > 0 and f["n_stops"] > 0, f
+    kl = np.concatenate([tw.kl_rows(rows) for tw, rows, _ in twins])
+    q = np.concatenate([tw.q_rows(rows) for tw, rows, _ in twins])
+    assert (kl > 0).any() and len(np.unique(q)) > 2
+    # q is the value of the raw visits -- also at a decided root, whose proven value it need not equal
+    n_dec = n_off = 0
+    for tw, rows, _ in twins:
+        lg = {tw.bits(x["b"], x["p"]): x for x in tw.log}
+        for r, qq in zip(rows, tw.q_rows(rows)):
+            x = lg[(r[0], r[1])]
+            if x["proven"] is not None:
+                n_dec += 1
+                n_off += float(qq) != float(x["proven"])
+    assert n_dec > 0 and n_off > 0, (n_dec, n_off)
+    for tw, rows, w in twins:  # the final board gives the winner the game had
+        assert winner_of(OBSERVER_CASE["game"], *tw.final_bits()) == (True, w)
 
 
 # ---------------------------------------------------------------- the ABI
