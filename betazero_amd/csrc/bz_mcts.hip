@@ -228,8 +228,6 @@ struct ValueDev { float* ex_q; };
 // First-play urgency reduction (root_w = nullptr: off), set by bz_engine_set_fpu: the two reductions and every
 // root's running value sum Wr f32 [B] in the caller's buffer.  A kernel argument of the FPU kernels only.
 struct FpuDev { float reduction, root_reduction; float* root_w; };
-// what the FPU walk takes along: the reductions and the root's Wr as of this walk
-struct FpuSel { float r, r_root, Wr; };
 // Gumbel interior selection (node_v = nullptr: off), set by bz_engine_set_gumbel_interior in the caller's buffer:
 // the value every node of the current search was expanded with, f32 [B][ncap] indexed like the nodes.  A kernel argument of
 // k_gfull_step only.
@@ -252,6 +250,64 @@ struct ResignDev { float threshold; int consecutive; u32 playout_q; uint8_t* str
 // g_state of a slot k_resign_note has ended and k_resign_finish has not yet restarted or retired: like every value but 0 it
 // makes the kernels between the two skip the slot
 constexpr uint8_t kStateResigned = 2;
+
+// ---- The search mode: which rules the walk (dev_select), the tree step around it (tree_step_body) and the move (play_body, which
+// says what each bit does to the move) run under.  One bit per rule, one compile-time mask M per kernel; the host derives the same
+// mask from the engine (engine_mode) and switches over it.  With no bit set the code is k_tree_step's / k_play's exactly.
+enum : unsigned {
+    // kModeLeaf (k_leaf_step): K > 1 walks per game per step.  In the walk, a non-terminal child without edges was
+    // created by an earlier walk of this step and ends the walk as LEAF_COLLIDE; the evaluation cache is not consulted.
+    kModeLeaf = 1u << 0,
+    // kModeGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead of PUCT (every deeper
+    // level is PUCT), and v_root is stored with the root's expansion.
+    kModeGumbel = 1u << 1,
+    // kModeCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget.
+    kModeCap = 1u << 2,
+    // kModeForced (k_forced_step / k_forced_cap_step): at the root an edge with 0 < N < fsqrt(fk P sumN) scores +inf
+    // (fk = 0: this slot does not force -- under kModeCap the full searches only force); every deeper level is PUCT.
+    kModeForced = 1u << 3,
+    // kModeFpu (k_fpu_*_step): at every level an edge with N == 0 takes q = the node's own value minus a reduction
+    // that grows with the prior mass of the node's visited edges, instead of 0.  The mass needs all of the node's edges before any
+    // is scored: its <= kCH chunks are loaded together into registers (still ONE dependent load per level), summed as integers
+    // across the group, then scored from the registers.  The root's running value sum Wr is loaded with the per-game words,
+    // advanced by what this step's backup adds to the path's root edge and stored beside it.  sim_idx is the number of simulations
+    // backed up once this step's backup is done (an expand-only step gets it from the host too): the backup of simulation 0 starts
+    // Wr from 0, so no search needs a reset.
+    kModeFpu = 1u << 4,
+    // kModeGfull (k_gfull_step; with kModeGumbel): every level below the root takes the edge whose visit share lags
+    // the node's improved policy softmax(logf(P~) + sigma(completed Q)) the most, in place of PUCT.  Like kModeFpu the node's <= kCH
+    // edge chunks are loaded together into registers, and the node's own value v_X (this game's row of the interior buffer) is
+    // loaded beside its position: still ONE dependent load per level.  Per-edge terms are computed one edge per lane; max / min are
+    // group reductions; the three sums run in ascending edge order (group_seq_sum), so the bits are those of gi_pick_serial.  Every
+    // expanded node's value is stored in the interior buffer with its expansion, on the EVAL and on the COPY path.
+    kModeGfull = 1u << 5,
+    // kModeSolve (k_solve_step / k_solve_cap_step; the plain PUCT branch of the walk only): a decided edge (terminal
+    // or proven) with c = -1 scores +inf, with c = +1 -inf, with c = 0 takes q = 0; when every edge scores -inf the walk takes edge
+    // 0; a walk that takes a decided edge ends there with the edge's value, as at a terminal edge.  The proof pass runs behind the
+    // backup of a terminal or proven leaf; the backup of an evaluated or copied leaf stays the pure-store path it is.
+    kModeSolve = 1u << 6,
+};
+// the mask's bits by name, and the combinations no code serves: the setters (bz_engine_set_*) refuse the same ones at run time
+template <unsigned M>
+struct Mode {
+    static constexpr bool leaf = (M & kModeLeaf) != 0, gumbel = (M & kModeGumbel) != 0, cap = (M & kModeCap) != 0,
+                          forced = (M & kModeForced) != 0, fpu = (M & kModeFpu) != 0, gfull = (M & kModeGfull) != 0,
+                          solve = (M & kModeSolve) != 0;
+    static_assert(!gfull || gumbel, "search mode: the Gumbel interior rule needs Gumbel root search");
+    static_assert(!gumbel || !(cap || forced || fpu || solve),
+                  "search mode: Gumbel root search combines with none of playout cap, forced playouts, FPU reduction and the solver");
+    static_assert(!solve || !(forced || fpu), "search mode: the solver combines with neither forced playouts nor FPU reduction");
+    static_assert(!leaf || M == kModeLeaf, "search mode: leaf-parallel search combines with nothing");
+};
+// what the modes' kernels get beside EngineDev: each pointer is read only under its bit and stays null otherwise
+struct ModeArgs {
+    const GumbelDev* gm = nullptr;    // kModeGumbel
+    const u32* budget = nullptr;      // kModeCap: b_g [B]
+    const ForcedDev* fo = nullptr;    // kModeForced
+    const FpuDev* fp = nullptr;       // kModeFpu
+    const GumbelInDev* gi = nullptr;  // kModeGfull
+    const SolveDev* sv = nullptr;     // kModeSolve
+};
 
 struct Cnt { u32 v[CNT_N]; };
 
@@ -664,34 +720,23 @@ __device__ __forceinline__ int gumbel_root_pick(const EngineDev& E, const Gumbel
 }
 
 // M2: PUCT walk from the root; creates the child node behind the chosen unexpanded edge (env step:
-// apply + legal + terminal).  All lanes of the group return the same values.
-// kGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead; every deeper level is PUCT.
-// kForced (k_forced_step / k_forced_cap_step): at the root an edge with 0 < N < fsqrt(fk P sumN) scores +inf
-// (fk = 0: this slot does not force); every deeper level is PUCT.
-// kFpu (k_fpu_*_step): at every level an edge with N == 0 takes q = the node's own value minus a reduction that
-// grows with the prior mass of the node's visited edges, instead of 0.  The mass needs all of the node's edges before any is
-// scored: its <= kCH chunks are loaded together into registers (still ONE dependent load per level), summed as integers across
-// the group, then scored from the registers.
-// kGfull (k_gfull_step; with kGumbel): every level below the root takes the edge whose visit share lags the node's
-// improved policy softmax(logf(P~) + sigma(completed Q)) the most, in place of PUCT.  Like kFpu the node's <= kCH edge chunks are
-// loaded together into registers, and the node's own value v_X (gnv, this game's row of the interior buffer) is loaded beside
-// its position: still ONE dependent load per level.  Per-edge terms are computed one edge per lane; max / min are group
-// reductions; the three sums run in ascending edge order (group_seq_sum), so the bits are those of gi_pick_serial.
-// kSolve (k_solve_step / k_solve_cap_step; the plain PUCT branch only): a decided edge (terminal or proven) with
-// c = -1 scores +inf, with c = +1 -inf, with c = 0 takes q = 0; when every edge scores -inf the walk takes edge 0; a walk that
-// takes a decided edge ends there with the edge's value, as at a terminal edge.
-template <class G, class Sink, bool kLeafPar = false, bool kGumbel = false, bool kForced = false, bool kFpu = false, bool kGfull = false,
-          bool kSolve = false>
+// apply + legal + terminal).  All lanes of the group return the same values.  M: the search mode (Mode, above); beside A the
+// two values that differ walk by walk: fk, the slot's forced parameter in this search (kModeForced; 0 = it does not force), and
+// Wr, the root's running value sum as of this walk (kModeFpu).
+template <class G, unsigned M, class Sink>
 __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, const RootRef& root, u32& n_nodes_g,
                                            u32& leaf, int& kind, int& depth_out, float& tval, Cnt& c,
-                                           Sink& sink, LeafPos& lp, Stamps& st, const GumbelDev* gm = nullptr, float fk = 0.0f,
-                                           const FpuSel* fp = nullptr, const float* gnv = nullptr) {
+                                           Sink& sink, LeafPos& lp, Stamps& st, const ModeArgs& A, float fk, float Wr) {
+    constexpr bool kLeafPar = Mode<M>::leaf, kGumbel = Mode<M>::gumbel, kForced = Mode<M>::forced, kFpu = Mode<M>::fpu,
+                   kGfull = Mode<M>::gfull, kSolve = Mode<M>::solve;
     constexpr int kGW = G::GW;
     constexpr int kCH = (G::MAXCH + kGW - 1) / kGW;
-    [[maybe_unused]] float vx = 0.0f;  // kGfull: v_X of the node whose edges are being scored (depth >= 1)
+    [[maybe_unused]] float vx = 0.0f;  // kGfull: v_X of the node whose edges are being scored (depth >= 1) ...
+    [[maybe_unused]] const float* gnv = nullptr;  // ... from this game's row of the interior buffer
+    if constexpr (kGfull) gnv = A.gi->node_v + (size_t)g * E.ncap;
     // kFpu: the value of the node whose edges are being scored -- the root's Wr / simulations so far, 0 before the first
     float qx = 0.0f;
-    if (kFpu) qx = root.sumN > 0u ? fdiv(fp->Wr, (float)root.sumN) : 0.0f;
+    if (kFpu) qx = root.sumN > 0u ? fdiv(Wr, (float)root.sumN) : 0.0f;
     Node* nodes = E.nodes + (size_t)g * E.ncap;
     Edge* edges = E.edges + (size_t)g * E.ecap;
     // sum of the root's child visits == simulations done so far (+ the visits a kept subtree came with)
@@ -705,7 +750,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
         const Edge* ed = edges + e0;
         float bests = -__builtin_inff(), bestW = 0.0f; int best = 0; u32 bestw0 = 0, bestw3 = 0;
         if (kGumbel && depth == 0) {  // (the root's edges start at index 0; sumN = the root's visit sum = sim_index)
-            best = gumbel_root_pick<G>(E, *gm, g, ed, n, sumN);
+            best = gumbel_root_pick<G>(E, *A.gm, g, ed, n, sumN);
             const Edge e = ed[best];
             bestw0 = e.w0; bestw3 = e.w3; bestW = e.W;
         } else if (kGfull) {  // (depth >= 1: X is expanded and not terminal)
@@ -747,7 +792,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
                     if (k * kGW + sub < n) { lo = cq[k] < lo ? cq[k] : lo; hi = cq[k] > hi ? cq[k] : hi; }
                 }
                 lo = group_min<kGW>(lo); hi = group_max<kGW>(hi);
-                const GiScale gs = gi_scale(lo, hi, nmax, gm->mvi, gm->vs);
+                const GiScale gs = gi_scale(lo, hi, nmax, A.gm->mvi, A.gm->vs);
                 // ---- the improved policy: x one edge per lane, the max by a group reduction, the sum sequentially
                 float m = -__builtin_inff();
 #pragma unroll
@@ -792,7 +837,7 @@ __device__ __forceinline__ void dev_select(const EngineDev& E, int g, int sub, c
                 }
             }
             S = group_sum_u32<kGW>(S);
-            const float f = fpu_value(S, qx, depth == 0 ? fp->r_root : fp->r);
+            const float f = fpu_value(S, qx, depth == 0 ? A.fp->root_reduction : A.fp->reduction);
             // every lane's own first maximum over its <= kCH edges (ascending index, strict >), then ONE reduction over the group:
             // the first maximum over all edges, the lowest index on ties
             Cand cd; cd.i = sub; cd.sc = -__builtin_inff(); cd.W = 0.0f; cd.w0 = 0; cd.w3 = 0;
@@ -1314,23 +1359,13 @@ __global__ void __launch_bounds__(256) k_eval_synth(EngineDev E, int eval_kind) 
 // that consume them, so they go out back to back and complete in ONE memory round trip
 template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" : "+v"(x)); }
 
-// The body of k_tree_step and of k_gumbel_step (kGumbel: the Gumbel root rule at depth 0 of the walk and v_root stored
-// with the root's expansion); with kGumbel = false it is k_tree_step's code exactly.
-// kCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget; both flags off, the code is
-// k_tree_step's / k_gumbel_step's as before.
-// kForced: forced playouts with parameter fk at the root -- under kCap in the full searches only.
-// kFpu: first-play urgency reduction at every level of the walk, and the root's running value sum Wr: loaded with
-// the per-game words, advanced by what this step's backup adds to the path's root edge and stored beside it.  sim_idx is the
-// number of simulations backed up once this step's backup is done (an expand-only step gets it from the host too): the backup of
-// simulation 0 starts Wr from 0, so no search needs a reset.
-// kGfull (with kGumbel): the Gumbel interior rule at every level below the root, and every expanded node's value
-// stored in the interior buffer with its expansion, on the EVAL and on the COPY path.
-// kSolve: decided edges in the walk's scores, and the proof pass behind the backup of a terminal or proven leaf; the
-// backup of an evaluated or copied leaf stays the pure-store path it is.
-template <class G, bool kGumbel, bool kCap = false, bool kForced = false, bool kFpu = false, bool kGfull = false, bool kSolve = false>
-__device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelDev& Gm, int do_expand, int do_select, u32 sim_idx,
-                                               const u32* budget = nullptr, float fk = 0.0f, const FpuDev* fd = nullptr,
-                                               const GumbelInDev* gi = nullptr, const SolveDev* sv = nullptr) {
+// The body of every per-step kernel but k_leaf_step, under the search mode M (Mode, above): with M = 0 it is k_tree_step's code
+// exactly, and every bit adds only what its rule needs.
+template <class G, unsigned M>
+__device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArgs& A, int do_expand, int do_select, u32 sim_idx) {
+    constexpr bool kGumbel = Mode<M>::gumbel, kCap = Mode<M>::cap, kForced = Mode<M>::forced, kFpu = Mode<M>::fpu, kGfull = Mode<M>::gfull,
+                   kSolve = Mode<M>::solve;
+    static_assert(!Mode<M>::leaf, "search mode: the leaf-parallel step is k_leaf_step's own body");
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1353,9 +1388,9 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
         u32 root_base = E.reuse ? hot.root_base : 0u;
         PathEnt pe0 = path[sub];  // (maxd >= kGW for every game)
         u32 bud = 0;
-        if (kCap) { bud = budget[g]; pin(bud); }
+        if (kCap) { bud = A.budget[g]; pin(bud); }
         [[maybe_unused]] float rw;
-        if constexpr (kFpu) { rw = fd->root_w[g]; pin(rw); }
+        if constexpr (kFpu) { rw = A.fp->root_w[g]; pin(rw); }
         // the walk's first load too: root edges 0..kGW-1 (the root's edges start at index 0; whatever this step's
         // backup / expansion changes in them is patched in registers below) -- their latency hides behind the
         // evaluator row's round trip and the softmax instead of heading the walk
@@ -1380,8 +1415,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 if (sub == 0) {
                     E.hot[g].n_edges = ne; c.v[CNT_NET_LEAVES]++; if (leaf == 0) E.hot[g].root_n = (u32)n;
                     if (E.ecache) E.node_v[(size_t)g * E.ncap + leaf] = v;  // what a later repeat of this position copies
-                    if (kGumbel && leaf == 0) Gm.vroot[g] = v;
-                    if constexpr (kGfull) gi->node_v[(size_t)g * E.ncap + leaf] = v;
+                    if (kGumbel && leaf == 0) A.gm->vroot[g] = v;
+                    if constexpr (kGfull) A.gi->node_v[(size_t)g * E.ncap + leaf] = v;
                 }
                 if (leaf == 0) { root_n = n; pre_ok = false; }  // the root's edges did not exist when re0 was fetched
             } else if (kind == LEAF_COPY) {  // ---- round trip 2: the first evaluation's edges and value (evaluation cache)
@@ -1390,8 +1425,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 n = dev_expand_copy<G>(E, g, sub, leaf, nlegal, ninfo, hot.copy_e0, from_prev, ne, c);
                 if (sub == 0) {
                     E.hot[g].n_edges = ne; E.node_v[(size_t)g * E.ncap + leaf] = v;
-                    if (kGumbel && leaf == 0) Gm.vroot[g] = v;
-                    if constexpr (kGfull) gi->node_v[(size_t)g * E.ncap + leaf] = v;
+                    if (kGumbel && leaf == 0) A.gm->vroot[g] = v;
+                    if constexpr (kGfull) A.gi->node_v[(size_t)g * E.ncap + leaf] = v;
                 }
             } else {
                 v = (float)((int)((ninfo >> 9) & 3u) - 1);
@@ -1406,7 +1441,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
             if (sub == 0) c.v[CNT_EDGES_BACKED] += (u32)dmax;
             if constexpr (kFpu) if (dmax >= 1) {  // Wr = Wr + what path entry 0 just added to its edge's W, one addition per simulation
                 rw = (sim_idx == 1u ? 0.0f : rw) + (((dmax - 1) & 1) ? v : -v);
-                if (sub == 0) fd->root_w[g] = rw;
+                if (sub == 0) A.fp->root_w[g] = rw;
             }
             if (dmax >= 1) {  // the path's root edge (lane 0 wrote it): the same words into the lane that holds it in re0
                 const u32 pe_e = (u32)__shfl((int)pe0.eidx, 0, kGW), w0n = (u32)__shfl((int)wr.x, 0, kGW), Wn = (u32)__shfl((int)wr.y, 0, kGW);
@@ -1415,7 +1450,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                     if (depth0 == 1 && n > 0) re0.w3 = leaf | (e0 << kChildBits);
                 }
             }
-            if constexpr (kSolve) if (kind == LEAF_TERMINAL) dev_prove<G>(E, *sv, g, sub, path, depth0, root_n, re0);
+            if constexpr (kSolve) if (kind == LEAF_TERMINAL) dev_prove<G>(E, *A.sv, g, sub, path, depth0, root_n, re0);
         }
         st.mark(2);
         if (do_select) {
@@ -1427,15 +1462,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
                 RootRef root; root.own = rown; root.opp = ropp; root.tm = rtm; root.n = root_n;
                 root.sumN = sim_idx + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
                 PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
-                const float fslot = (kForced && (!kCap || bud >= (u32)E.sims)) ? fk : 0.0f;
-                if constexpr (kFpu) {
-                    FpuSel fs; fs.r = fd->reduction; fs.r_root = fd->root_reduction; fs.Wr = rw;
-                    dev_select<G, PathHbm<kGW>, false, false, kForced, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, nullptr, fslot, &fs);
-                } else if constexpr (kGfull) {
-                    dev_select<G, PathHbm<kGW>, false, true, false, false, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, 0.0f, nullptr,
-                                                                                 gi->node_v + (size_t)g * E.ncap);
-                } else
-                dev_select<G, PathHbm<kGW>, false, kGumbel, kForced, false, false, kSolve>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, &Gm, fslot);  // ---- one round trip per level
+                const float fslot = (kForced && (!kCap || bud >= (u32)E.sims)) ? A.fo->k : 0.0f;
+                dev_select<G, M>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, A, fslot, kFpu ? rw : 0.0f);  // ---- one round trip per level
                 sink.flush(sub, depth);
                 if (sub == 0) {
                     E.hot[g].n_nodes = nn; E.hot[g].leaf_node = leaf2; E.hot[g].depth = (u32)depth;
@@ -1472,81 +1500,82 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const GumbelD
     st.flush(E.counters);
 }
 
+// The per-step kernels: each fills ModeArgs from its own kernel arguments (the mode's *Dev structs travel as kernel arguments, so
+// EngineDev and every other kernel's code stay what they are) and runs tree_step_body under its mode.
 template <class G>
 __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false>(E, none, do_expand, do_select, sim_idx);
+    tree_step_body<G, 0u>(E, ModeArgs{}, do_expand, do_select, sim_idx);
 }
 
 // The tree step of a Gumbel search: k_tree_step with the Gumbel root rule.  The root's statistics are read
 // afresh after this step's backup (the group fence before the walk) by a serial loop over its edges.
 template <class G>
 __global__ void __launch_bounds__(256) k_gumbel_step(EngineDev E, GumbelDev Gm, int do_expand, int do_select, u32 sim_idx) {
-    tree_step_body<G, true>(E, Gm, do_expand, do_select, sim_idx);
+    ModeArgs A; A.gm = &Gm;
+    tree_step_body<G, kModeGumbel>(E, A, do_expand, do_select, sim_idx);
 }
 
-// The tree step of a Gumbel search with the Gumbel interior rule: k_gumbel_step with the interior rule at every
-// level below the root and v_X stored with every expansion.  Gi travels as a kernel argument.
+// ... with the Gumbel interior rule at every level below the root, and v_X stored with every expansion.
 template <class G>
 __global__ void __launch_bounds__(256) k_gfull_step(EngineDev E, GumbelDev Gm, GumbelInDev Gi, int do_expand, int do_select, u32 sim_idx) {
-    tree_step_body<G, true, false, false, false, true>(E, Gm, do_expand, do_select, sim_idx, nullptr, 0.0f, nullptr, &Gi);
+    ModeArgs A; A.gm = &Gm; A.gi = &Gi;
+    tree_step_body<G, kModeGumbel | kModeGfull>(E, A, do_expand, do_select, sim_idx);
 }
 
 // The tree step under playout cap randomisation: k_tree_step, every slot walking for its own budget.
 template <class G>
 __global__ void __launch_bounds__(256) k_cap_step(EngineDev E, CapDev Cp, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget);
+    ModeArgs A; A.budget = Cp.budget;
+    tree_step_body<G, kModeCap>(E, A, do_expand, do_select, sim_idx);
 }
 
-// The tree step with forced playouts at the root: k_tree_step / k_cap_step with the forced rule in the root's
-// scores.  F.k travels as a kernel argument.
+// The tree step with forced playouts: k_tree_step / k_cap_step with the forced rule in the root's scores.
 template <class G>
 __global__ void __launch_bounds__(256) k_forced_step(EngineDev E, ForcedDev F, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, F.k);
+    ModeArgs A; A.fo = &F;
+    tree_step_body<G, kModeForced>(E, A, do_expand, do_select, sim_idx);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_forced_cap_step(EngineDev E, CapDev Cp, ForcedDev F, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k);
+    ModeArgs A; A.budget = Cp.budget; A.fo = &F;
+    tree_step_body<G, kModeForced | kModeCap>(E, A, do_expand, do_select, sim_idx);
 }
 
 // The tree steps with first-play urgency reduction: k_tree_step / k_cap_step / k_forced_step / k_forced_cap_step
-// with the FPU rule at every level of the walk.  Fp travels as a kernel argument.
+// with the FPU rule at every level of the walk.
 template <class G>
 __global__ void __launch_bounds__(256) k_fpu_step(EngineDev E, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, 0.0f, &Fp);
+    ModeArgs A; A.fp = &Fp;
+    tree_step_body<G, kModeFpu>(E, A, do_expand, do_select, sim_idx);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_fpu_cap_step(EngineDev E, CapDev Cp, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, true, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, 0.0f, &Fp);
+    ModeArgs A; A.budget = Cp.budget; A.fp = &Fp;
+    tree_step_body<G, kModeFpu | kModeCap>(E, A, do_expand, do_select, sim_idx);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_fpu_forced_step(EngineDev E, ForcedDev F, FpuDev Fp, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, false, true, true>(E, none, do_expand, do_select, sim_idx, nullptr, F.k, &Fp);
+    ModeArgs A; A.fo = &F; A.fp = &Fp;
+    tree_step_body<G, kModeFpu | kModeForced>(E, A, do_expand, do_select, sim_idx);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_fpu_forced_cap_step(EngineDev E, CapDev Cp, ForcedDev F, FpuDev Fp, int do_expand, int do_select,
                                                              u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, true, true, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, F.k, &Fp);
+    ModeArgs A; A.budget = Cp.budget; A.fo = &F; A.fp = &Fp;
+    tree_step_body<G, kModeFpu | kModeForced | kModeCap>(E, A, do_expand, do_select, sim_idx);
 }
 
 // The tree steps with proven wins, losses and draws: k_tree_step / k_cap_step with the solver's select rule and
-// the proof pass behind the backup.  Sv travels as a kernel argument.
+// the proof pass behind the backup.
 template <class G>
 __global__ void __launch_bounds__(256) k_solve_step(EngineDev E, SolveDev Sv, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, false, false, false, false, true>(E, none, do_expand, do_select, sim_idx, nullptr, 0.0f, nullptr, nullptr, &Sv);
+    ModeArgs A; A.sv = &Sv;
+    tree_step_body<G, kModeSolve>(E, A, do_expand, do_select, sim_idx);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_solve_cap_step(EngineDev E, CapDev Cp, SolveDev Sv, int do_expand, int do_select, u32 sim_idx) {
-    const GumbelDev none{};
-    tree_step_body<G, false, true, false, false, false, true>(E, none, do_expand, do_select, sim_idx, Cp.budget, 0.0f, nullptr, nullptr, &Sv);
+    ModeArgs A; A.budget = Cp.budget; A.sv = &Sv;
+    tree_step_body<G, kModeSolve | kModeCap>(E, A, do_expand, do_select, sim_idx);
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -1558,6 +1587,7 @@ __global__ void __launch_bounds__(256) k_solve_cap_step(EngineDev E, CapDev Cp, 
 template <class G>
 __global__ void __launch_bounds__(256) k_leaf_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
     constexpr int kGW = G::GW;
+    const ModeArgs none;  // (this kernel's mode reads no argument)
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
     const int K = E.K;
@@ -1645,7 +1675,7 @@ __global__ void __launch_bounds__(256) k_leaf_step(EngineDev E, int do_expand, i
                     root.tt_gen = 0; root.prev_nodes = 0;
                     PathEnt* path = path_g + (size_t)j * maxd;
                     PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
-                    dev_select<G, PathHbm<kGW>, true>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st);
+                    dev_select<G, kModeLeaf>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, none, 0.0f, 0.0f);
                     sink.flush(sub, depth);
                     group_fence();  // the walk's child-creation stores and deep path entries -> the virtual loss below
                     // virtual loss: N += 1, W -= 1 on every path edge, from the words the walk saw (nothing else wrote them since)
@@ -1720,6 +1750,7 @@ __global__ void __launch_bounds__(256) k_leaf_step(EngineDev E, int do_expand, i
 template <class G>
 __global__ void __launch_bounds__(256) k_search_fused(EngineDev E, int eval_kind) {
     constexpr int kGW = G::GW, kGPB = 256 / kGW;
+    const ModeArgs none;  // (this kernel's mode reads no argument)
     __shared__ PathEntLds s_path[kGPB][G::MAXD];
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / kGW, sub = t % kGW;
@@ -1745,7 +1776,7 @@ __global__ void __launch_bounds__(256) k_search_fused(EngineDev E, int eval_kind
                 u32 leaf; int kind, depth; float v;
                 LeafPos lp; lp.own = 0; lp.opp = 0; lp.legal = 0; lp.info = 0;
                 root.sumN = (u32)s;
-                dev_select<G>(E, g, sub, root, nn, leaf, kind, depth, v, c, sink, lp, st);
+                dev_select<G, 0u>(E, g, sub, root, nn, leaf, kind, depth, v, c, sink, lp, st, none, 0.0f, 0.0f);
                 u32 e0 = ne; int n = 0;
                 if (kind == LEAF_EVAL) {
                     ls.h = hash_pos(lp.own, lp.opp);
@@ -2074,62 +2105,6 @@ __device__ __forceinline__ void dev_play_tail(const EngineDev& E, int g, const N
     E.g_own[g] = own; E.g_opp[g] = opp; E.g_to_move[g] = (int8_t)tm; E.g_moves[g] = made; E.g_nex[g] = nex;
 }
 
-// M5 + the reference's turn loop: pi, move choice, example row, env step,
-// pass rule (reversi_terminal.py:31-35), terminal handling, z back-fill.
-template <class G>
-__global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.g_state[g] != 0) return;
-    Node root = E.nodes[(size_t)g * E.ncap];
-    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
-    int n = (int)(root.info & 0xFFu);
-    u32 sumN = 0;
-    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
-    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
-    if (nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
-    size_t row = rowbase + nex;
-    const int pick = dev_puct_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA);
-    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart);
-}
-
-// M5 of a Gumbel search: the improved policy as pi, the Gumbel move, then k_play's tail
-template <class G>
-__global__ void __launch_bounds__(256) k_gumbel_play(EngineDev E, GumbelDev Gm, int restart) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.g_state[g] != 0) return;
-    Node root = E.nodes[(size_t)g * E.ncap];
-    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
-    int n = (int)(root.info & 0xFFu);
-    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
-    if (nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
-    size_t row = rowbase + nex;
-    const int pick = dev_gumbel_choice<G>(Gm, g, ed, n, E.ex_pi + row * G::NA);
-    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart);
-}
-
-// M5 under playout cap randomisation: k_play, but only a full search (budget = sims) records its row; a fast
-// one plays its move by the same rule (tau = 1 sampling over its own visit sum included) and writes nothing
-template <class G>
-__global__ void __launch_bounds__(256) k_cap_play(EngineDev E, CapDev Cp, int restart) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.g_state[g] != 0) return;
-    Node root = E.nodes[(size_t)g * E.ncap];
-    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
-    int n = (int)(root.info & 0xFFu);
-    u32 sumN = 0;
-    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
-    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    const bool full = Cp.budget[g] >= (u32)E.sims;
-    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
-    if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
-    size_t row = rowbase + nex;
-    const int pick = full ? dev_puct_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
-                          : dev_puct_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
-    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
-}
-
 // The move of a search with proven edges, shared by k_solve_play, k_solve_cap_play and k_root_policy: pi stays
 // N / sum N (dev_puct_choice writes it), the played edge is solver_pick's
 template <class G, bool kPi = true>
@@ -2144,30 +2119,6 @@ __device__ __forceinline__ int dev_solver_choice(const EngineDev& E, int g, cons
     return solver_pick(n, [ed](int i) { return (u64)e_N(ed[i].w0); }, [ed](int i) { return e_cval(ed[i].w0); }, tau1,
                        tau1 ? rng_draw(E.seed, gid, (u64)made) : 0ULL);
 }
-
-// M5 with the solver's move rule: k_play / k_cap_play with dev_solver_choice
-template <class G, bool kCap>
-__device__ __forceinline__ void solve_play_body(const EngineDev& E, const u32* budget, int restart) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.B || E.g_state[g] != 0) return;
-    Node root = E.nodes[(size_t)g * E.ncap];
-    const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
-    int n = (int)(root.info & 0xFFu);
-    u32 sumN = 0;
-    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
-    int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    const bool full = kCap ? budget[g] >= (u32)E.sims : true;
-    size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
-    if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
-    size_t row = rowbase + nex;
-    const int pick = full ? dev_solver_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
-                          : dev_solver_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
-    dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
-}
-template <class G>
-__global__ void __launch_bounds__(256) k_solve_play(EngineDev E, int restart) { solve_play_body<G, false>(E, nullptr, restart); }
-template <class G>
-__global__ void __launch_bounds__(256) k_solve_cap_play(EngineDev E, CapDev Cp, int restart) { solve_play_body<G, true>(E, Cp.budget, restart); }
 
 // the proof state of every slot's root: edge_out [B][NA] the decided value of the edge of every action (2:
 // undecided or no such edge), root_out [B] the root's recorded value (2: undecided; idle slots: all 2)
@@ -2206,32 +2157,63 @@ __device__ __forceinline__ int dev_forced_choice(const EngineDev& E, const Force
     return pick;
 }
 
-// M5 with forced playouts: k_play / k_cap_play with the pruned pi in the recorded row; the move is theirs.
-// Under the cap (kCap) a fast search was not forced and records nothing.
-template <class G, bool kCap>
-__device__ __forceinline__ void forced_play_body(const EngineDev& E, const u32* budget, const ForcedDev& F, int restart) {
+// M5 + the reference's turn loop under the search mode M (Mode, above; kModeFpu and kModeGfull change nothing here): pi, move
+// choice, example row, env step, pass rule (reversi_terminal.py:31-35), terminal handling, z back-fill.
+// kModeGumbel: the improved policy as pi and the Gumbel move.  kModeSolve: dev_solver_choice's move.  kModeForced: the pruned pi in
+// the recorded row; the move is the plain one.  kModeCap: only a full search (budget = sims) records its row; a fast one plays its
+// move by the same rule (tau = 1 sampling over its own visit sum included; not forced) and writes nothing.
+template <class G, unsigned M>
+__device__ __forceinline__ void play_body(const EngineDev& E, const ModeArgs& A, int restart) {
+    using Md = Mode<M>;
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.B || E.g_state[g] != 0) return;
     Node root = E.nodes[(size_t)g * E.ncap];
     const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
     int n = (int)(root.info & 0xFFu);
-    u32 sumN = 0;
-    for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+    [[maybe_unused]] u32 sumN = 0;
+    if constexpr (!Md::gumbel) for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
     int round = E.g_round[g], nex = E.g_nex[g], made = E.g_moves[g], tm = E.g_to_move[g];
-    const bool full = kCap ? budget[g] >= (u32)E.sims : true;
+    const bool full = !Md::cap || A.budget[g] >= (u32)E.sims;
     size_t rowbase = ((size_t)round * E.B + g) * E.t_max;
     if (full && nex >= E.t_max) { atomicOr(&E.flags[FLAG_ERR], ERR_EXAMPLE_OVERFLOW); E.g_state[g] = 1; return; }
     size_t row = rowbase + nex;
-    const int pick = dev_forced_choice<G>(E, F, g, ed, n, sumN, made, round, full ? E.ex_pi + row * G::NA : nullptr);
+    int pick;
+    if constexpr (Md::gumbel) pick = dev_gumbel_choice<G>(*A.gm, g, ed, n, E.ex_pi + row * G::NA);
+    else if constexpr (Md::forced) pick = dev_forced_choice<G>(E, *A.fo, g, ed, n, sumN, made, round, full ? E.ex_pi + row * G::NA : nullptr);
+    else if constexpr (Md::solve) pick = full ? dev_solver_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
+                                              : dev_solver_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
+    else pick = full ? dev_puct_choice<G>(E, g, ed, n, sumN, made, round, E.ex_pi + row * G::NA)
+                     : dev_puct_choice<G, false>(E, g, ed, n, sumN, made, round, nullptr);
     dev_play_tail<G>(E, g, root, ed, pick, round, nex, made, tm, rowbase, row, restart, full);
 }
 template <class G>
+__global__ void __launch_bounds__(256) k_play(EngineDev E, int restart) { play_body<G, 0u>(E, ModeArgs{}, restart); }
+template <class G>
+__global__ void __launch_bounds__(256) k_gumbel_play(EngineDev E, GumbelDev Gm, int restart) {
+    ModeArgs A; A.gm = &Gm;
+    play_body<G, kModeGumbel>(E, A, restart);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_cap_play(EngineDev E, CapDev Cp, int restart) {
+    ModeArgs A; A.budget = Cp.budget;
+    play_body<G, kModeCap>(E, A, restart);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_play(EngineDev E, int restart) { play_body<G, kModeSolve>(E, ModeArgs{}, restart); }
+template <class G>
+__global__ void __launch_bounds__(256) k_solve_cap_play(EngineDev E, CapDev Cp, int restart) {
+    ModeArgs A; A.budget = Cp.budget;
+    play_body<G, kModeSolve | kModeCap>(E, A, restart);
+}
+template <class G>
 __global__ void __launch_bounds__(256) k_forced_play(EngineDev E, ForcedDev F, int restart) {
-    forced_play_body<G, false>(E, nullptr, F, restart);
+    ModeArgs A; A.fo = &F;
+    play_body<G, kModeForced>(E, A, restart);
 }
 template <class G>
 __global__ void __launch_bounds__(256) k_forced_cap_play(EngineDev E, CapDev Cp, ForcedDev F, int restart) {
-    forced_play_body<G, true>(E, Cp.budget, F, restart);
+    ModeArgs A; A.budget = Cp.budget; A.fo = &F;
+    play_body<G, kModeForced | kModeCap>(E, A, restart);
 }
 
 // k_root_policy with forced playouts: the pruned pi and the unchanged action; under the cap (Cp.fast > 0) a
@@ -3124,35 +3106,43 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     return BZ_OK;
 }
 
+// The engine's search mode (Mode): THE place that reads the setters' state.  The setters refuse every combination Mode refuses,
+// so what comes out is one of the masks tree_step() and bz_engine_play() switch over.
+static unsigned engine_mode(const bz_engine* e) {
+    return (e->dev.K > 1 ? kModeLeaf : 0u) | (e->gumbel.m > 0 ? kModeGumbel : 0u) | (e->cap.fast > 0 ? kModeCap : 0u) |
+           (e->forced.k > 0.0f ? kModeForced : 0u) | (e->fpu.root_w ? kModeFpu : 0u) | (e->gin.node_v ? kModeGfull : 0u) |
+           (e->solve.root ? kModeSolve : 0u);
+}
+// every slot's budget for the observers of a search: null without playout cap randomisation (every search is a full one)
+static const u32* cap_budgets(const bz_engine* e) { return e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr; }
+
 static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t sim_idx, void* stream) {
     ProfScope ps(do_select ? BZ_PROF_SELECT : BZ_PROF_EXPAND_BACKUP, stream);
-    if (e->dev.K > 1) {  // leaf-parallel: sim_idx is a multiple of K, the packed-leaf buffers alternate per step
-        BZ_DISPATCH_G(e, k_leaf_step, stream, e->dev, do_expand, do_select, sim_idx);
-        if (do_select) e->pack_parity = (int)((sim_idx / (uint32_t)e->dev.K) & 1u);
-        return BZ_OK;
+    const unsigned m = engine_mode(e);
+    //  the FPU kernels take sim_idx = simulations backed up after this step, on an expand-only step too
+    if ((m & kModeFpu) && !do_select) sim_idx = (uint32_t)e->fpu_done;
+#define BZ_STEP(KERNEL, ...) BZ_DISPATCH_G(e, KERNEL, stream, __VA_ARGS__, do_expand, do_select, sim_idx); break
+    switch (m) {
+    case 0u: BZ_STEP(k_tree_step, e->dev);
+    case kModeLeaf: BZ_STEP(k_leaf_step, e->dev);  // 
+    case kModeGumbel: BZ_STEP(k_gumbel_step, e->dev, e->gumbel);  // 
+    case kModeGumbel | kModeGfull: BZ_STEP(k_gfull_step, e->dev, e->gumbel, e->gin);  // 
+    case kModeCap: BZ_STEP(k_cap_step, e->dev, e->cap);  // 
+    case kModeForced: BZ_STEP(k_forced_step, e->dev, e->forced);  // 
+    case kModeForced | kModeCap: BZ_STEP(k_forced_cap_step, e->dev, e->cap, e->forced);
+    case kModeFpu: BZ_STEP(k_fpu_step, e->dev, e->fpu);  // 
+    case kModeFpu | kModeCap: BZ_STEP(k_fpu_cap_step, e->dev, e->cap, e->fpu);
+    case kModeFpu | kModeForced: BZ_STEP(k_fpu_forced_step, e->dev, e->forced, e->fpu);
+    case kModeFpu | kModeForced | kModeCap: BZ_STEP(k_fpu_forced_cap_step, e->dev, e->cap, e->forced, e->fpu);
+    case kModeSolve: BZ_STEP(k_solve_step, e->dev, e->solve);  // 
+    case kModeSolve | kModeCap: BZ_STEP(k_solve_cap_step, e->dev, e->cap, e->solve);
+    default: set_error("tree_step: no step kernel serves search mode 0x%x", m); return BZ_EINVAL;
     }
-    if (e->fpu.root_w) {  //  the step kernels with the FPU rule; sim_idx = simulations backed up after this step
-        if (!do_select) sim_idx = (uint32_t)e->fpu_done;
-        if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH_G(e, k_fpu_forced_cap_step, stream, e->dev, e->cap, e->forced, e->fpu, do_expand, do_select, sim_idx);
-        else if (e->forced.k > 0.0f) BZ_DISPATCH_G(e, k_fpu_forced_step, stream, e->dev, e->forced, e->fpu, do_expand, do_select, sim_idx);
-        else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_fpu_cap_step, stream, e->dev, e->cap, e->fpu, do_expand, do_select, sim_idx);
-        else BZ_DISPATCH_G(e, k_fpu_step, stream, e->dev, e->fpu, do_expand, do_select, sim_idx);
-        if (do_select) { e->pack_parity = (int)(sim_idx & 1u); e->fpu_done = (int)sim_idx + 1; }
-        return BZ_OK;
+#undef BZ_STEP
+    if (do_select) {  // leaf-parallel: sim_idx is a multiple of K, the packed-leaf buffers alternate per step
+        e->pack_parity = (int)(((m & kModeLeaf) ? sim_idx / (uint32_t)e->dev.K : sim_idx) & 1u);
+        if (m & kModeFpu) e->fpu_done = (int)sim_idx + 1;
     }
-    if (e->solve.root) {  //  the step kernels with the solver's select rule and proof pass
-        if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_solve_cap_step, stream, e->dev, e->cap, e->solve, do_expand, do_select, sim_idx);
-        else BZ_DISPATCH_G(e, k_solve_step, stream, e->dev, e->solve, do_expand, do_select, sim_idx);
-        if (do_select) e->pack_parity = (int)(sim_idx & 1u);
-        return BZ_OK;
-    }
-    if (e->gumbel.m > 0 && e->gin.node_v) BZ_DISPATCH_G(e, k_gfull_step, stream, e->dev, e->gumbel, e->gin, do_expand, do_select, sim_idx);  // 
-    else if (e->gumbel.m > 0) BZ_DISPATCH_G(e, k_gumbel_step, stream, e->dev, e->gumbel, do_expand, do_select, sim_idx);  // 
-    else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH_G(e, k_forced_cap_step, stream, e->dev, e->cap, e->forced, do_expand, do_select, sim_idx);
-    else if (e->forced.k > 0.0f) BZ_DISPATCH_G(e, k_forced_step, stream, e->dev, e->forced, do_expand, do_select, sim_idx);  // 
-    else if (e->cap.fast > 0) BZ_DISPATCH_G(e, k_cap_step, stream, e->dev, e->cap, do_expand, do_select, sim_idx);  // 
-    else BZ_DISPATCH_G(e, k_tree_step, stream, e->dev, do_expand, do_select, sim_idx);
-    if (do_select) e->pack_parity = (int)(sim_idx & 1u);
     return BZ_OK;
 }
 
@@ -3218,12 +3208,19 @@ BZ_EXPORT int32_t bz_engine_root_noise(bz_engine* e, void* stream) {
 
 // the roots are expanded on their own and bz_engine_root_noise runs before the first walk: Dirichlet noise, Gumbel root search
 static bool root_prep(const bz_engine* e) { return e->dev.dir_eps > 0.0f || e->gumbel.m > 0; }
+// an engine whose whole search is one launch (k_search_fused / k_search_fused_ttt; bz_engines_step: nothing to interleave): a
+// synthetic evaluator, no subtree reuse, no root preparation and the plain search mode -- every mode's rule lives in the step
+// kernels only
+static bool search_is_fused(const bz_engine* e) {
+    const int ek = e->cfg.eval_kind;
+    return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && engine_mode(e) == 0u;
+}
 
 //  behind the last tree step of a stepwise search: the finished trees of early roots go to the root store
 static int32_t store_save(bz_engine* e, void* stream) {
     if (e->store.S == 0) return BZ_OK;
     hipLaunchKernelGGL(k_store_save, dim3(e->dev.B + 1), dim3(256), 0, (hipStream_t)stream, e->dev, e->store, e->search_seq, e->eval_epoch,
-                       e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+                       cap_budgets(e));
     BZ_LAUNCH_CHECK("k_store_save");
     return BZ_OK;
 }
@@ -3233,10 +3230,7 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     int ek = e->cfg.eval_kind;
     // (Dirichlet noise and Gumbel root search: the roots are expanded on their own and prepared before the first walk)
     const bool noise = root_prep(e);
-    // (playout cap randomisation: per-slot budgets live in the step kernels only; forced playouts: the forced root rule too)
-    // (first-play urgency reduction, the solver: the rule lives in the step kernels only)
-    if ((ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !noise && e->dev.K == 1 && e->cap.fast == 0 && !(e->forced.k > 0.0f) &&
-        !e->fpu.root_w && !e->solve.root) {
+    if (search_is_fused(e)) {
         ProfScope ps(BZ_PROF_SEARCH_FUSED, stream);
         if (e->cfg.game == BZ_GAME_TTT && e->cfg.sims <= kTttFusedMaxSims && e->ttt_gw > 0) {
             const dim3 grid = grid_groups(e->dev.B, e->ttt_gw);
@@ -3912,45 +3906,53 @@ BZ_EXPORT int32_t bz_root_value(const uint32_t* N, const float* W, int32_t n, fl
 
 BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream) {
     BZ_REQUIRE(e && pi && action, "bz_engine_root_policy: null pointer");
-    if (e->forced.k > 0.0f) {  // 
+    const unsigned m = engine_mode(e);
+    if (m & kModeForced) {  // 
         BZ_DISPATCH(e, k_forced_root_policy, stream, e->dev, e->cap, e->forced, pi, action);
         return BZ_OK;
     }
-    BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, e->solve.root ? 1 : 0, pi, action);
+    BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, (m & kModeSolve) ? 1 : 0, pi, action);
     return BZ_OK;
 }
 
 BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
     BZ_REQUIRE(e, "null engine");
     if (e->resign.streak)  //  first: a slot that resigns here is out of every kernel below
-        BZ_DISPATCH(e, k_resign_note, stream, e->dev, e->resign, e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+        BZ_DISPATCH(e, k_resign_note, stream, e->dev, e->resign, cap_budgets(e));
     if (e->surp.prior) {  //  the row this play is about to write
         // without Dirichlet noise the searched root still holds its raw priors (only the noise ever rewrites a prior): saved here,
         // whichever way the search ran -- fused, step kernels, the step API
         if (!(e->dev.dir_eps > 0.0f)) BZ_DISPATCH(e, k_surp_save, stream, e->dev, e->surp);
         hipLaunchKernelGGL(k_surp_note, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp,
-                           e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+                           cap_budgets(e));
         BZ_LAUNCH_CHECK("k_surp_note");
     }
     if (e->value.ex_q) {  //  the root's search value of the row this play is about to write
         hipLaunchKernelGGL(k_root_q, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->value,
-                           e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+                           cap_budgets(e));
         BZ_LAUNCH_CHECK("k_root_q");
     }
     if (e->own.fin_x) {  //  the final board of every game this play ends, while the root it plays from is in place
         int32_t rc = bz_engine_root_policy(e, e->own.pi, e->own.act, stream);
         if (rc != BZ_OK) return rc;
-        BZ_DISPATCH(e, k_own_final, stream, e->dev, e->own, e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr);
+        BZ_DISPATCH(e, k_own_final, stream, e->dev, e->own, cap_budgets(e));
     }
     {
         ProfScope ps(BZ_PROF_PLAY, stream);
-        if (e->gumbel.m > 0) BZ_DISPATCH(e, k_gumbel_play, stream, e->dev, e->gumbel, (int)restart);  // 
-        else if (e->forced.k > 0.0f && e->cap.fast > 0) BZ_DISPATCH(e, k_forced_cap_play, stream, e->dev, e->cap, e->forced, (int)restart);
-        else if (e->forced.k > 0.0f) BZ_DISPATCH(e, k_forced_play, stream, e->dev, e->forced, (int)restart);  // 
-        else if (e->solve.root && e->cap.fast > 0) BZ_DISPATCH(e, k_solve_cap_play, stream, e->dev, e->cap, (int)restart);  // 
-        else if (e->solve.root) BZ_DISPATCH(e, k_solve_play, stream, e->dev, (int)restart);
-        else if (e->cap.fast > 0) BZ_DISPATCH(e, k_cap_play, stream, e->dev, e->cap, (int)restart);  // 
-        else BZ_DISPATCH(e, k_play, stream, e->dev, (int)restart);
+        // the move does not depend on how the walks ran: leaf-parallel, FPU and the interior rule play as their base mode does
+        const unsigned m = engine_mode(e) & ~(kModeLeaf | kModeFpu | kModeGfull);
+#define BZ_PLAY(KERNEL, ...) BZ_DISPATCH(e, KERNEL, stream, __VA_ARGS__, (int)restart); break
+        switch (m) {
+        case 0u: BZ_PLAY(k_play, e->dev);
+        case kModeGumbel: BZ_PLAY(k_gumbel_play, e->dev, e->gumbel);  // 
+        case kModeCap: BZ_PLAY(k_cap_play, e->dev, e->cap);  // 
+        case kModeForced: BZ_PLAY(k_forced_play, e->dev, e->forced);  // 
+        case kModeForced | kModeCap: BZ_PLAY(k_forced_cap_play, e->dev, e->cap, e->forced);
+        case kModeSolve: BZ_PLAY(k_solve_play, e->dev);  // 
+        case kModeSolve | kModeCap: BZ_PLAY(k_solve_cap_play, e->dev, e->cap);
+        default: set_error("bz_engine_play: no play kernel serves search mode 0x%x", m); return BZ_EINVAL;
+        }
+#undef BZ_PLAY
     }
     if (e->surp.prior) BZ_DISPATCH(e, k_surp_kl, stream, e->dev, e->surp);  // ... and its kl (before the arenas swap below)
     if (e->resign.streak) BZ_DISPATCH(e, k_resign_finish, stream, e->dev, (int)restart);  // 
@@ -4048,13 +4050,6 @@ static int32_t ahead_mark(bz_engine* e, int idx, hipStream_t s) {
         }
     }
     return BZ_OK;
-}
-
-// an engine whose whole search is one launch (k_search_fused / k_search_fused_ttt): nothing to interleave
-static bool search_is_fused(const bz_engine* e) {
-    const int ek = e->cfg.eval_kind;
-    return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && e->dev.K == 1 &&
-           e->cap.fast == 0 && !(e->forced.k > 0.0f) && !e->fpu.root_w && !e->solve.root;
 }
 
 // the body of bz_engines_step / bz_engines_search: one search per (non-null) engine, the stepwise ones interleaved tree
