@@ -13,7 +13,8 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "Player", "ReversiPlayer", "RandomPlayer", "ReversiRandomPlayer", "MCTSPlayer",
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
            "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
-           "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign"]
+           "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
+           "check_early_stop"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -24,6 +25,9 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
         from . import match
         return getattr(match, name)
     if name in ("Resign", "check_resign"):  # resignation in self-play
+        from . import engine
+        return getattr(engine, name)
+    if name in ("EarlyStop", "check_early_stop"):  # exact early stop of a decided search
         from . import engine
         return getattr(engine, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

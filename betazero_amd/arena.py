@@ -37,7 +37,7 @@ class ArenaResult:
 
 def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=None, c_puct=1.5, seed=0, size=8,
                device="cuda:0", max_plies=200, opening_plies=0, leaves_per_step=1, gumbel=None,
-               eval_symmetry=None, fpu=None, solver=False):
+               eval_symmetry=None, fpu=None, solver=False, early_stop=None):
     """MCTS (`sims` simulations, `evaluator`) vs minimax for n_games concurrent games; the MCTS side plays X
     (moves first) in the even-numbered games and O in the odd ones.  game: "ttt" | "reversi" (size 8, 6 or 4).
     Both players are deterministic, so without help there are only two distinct games (one per colour):
@@ -48,11 +48,14 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     rule below the root, DESIGN.md 3.21.  eval_symmetry (True or a symmetry.EvalSymmetry): the
     MCTS side evaluates every leaf under a hashed board symmetry (True: seed 0), DESIGN.md 3.19.  fpu (True or an engine.Fpu):
     the MCTS side searches with first-play urgency reduction, DESIGN.md 3.20.  solver=True: the MCTS side books proven wins,
-    losses and draws and plays the solver's move (SelfPlayEngine.root_policy), DESIGN.md 3.23."""
-    from .engine import check_fpu, check_gumbel, check_leaves_per_step, check_solver
+    losses and draws and plays the solver's move (SelfPlayEngine.root_policy), DESIGN.md 3.23.  early_stop (True or an
+    engine.EarlyStop): the MCTS side's searches stop once the simulations left cannot change the move, DESIGN.md 3.25 -- the
+    games are the games without it."""
+    from .engine import check_early_stop, check_fpu, check_gumbel, check_leaves_per_step, check_solver
     from .symmetry import check_eval_symmetry
     check_leaves_per_step(leaves_per_step)
     solver = check_solver(solver, False, leaves_per_step, gumbel, None, fpu)
+    early_stop = check_early_stop(early_stop, False, leaves_per_step, gumbel, None, None, solver)
     fpu = check_fpu(fpu, False, leaves_per_step, gumbel)
     gumbel = check_gumbel(gumbel, leaves_per_step=leaves_per_step)
     eval_symmetry = check_eval_symmetry(eval_symmetry, 0, "ttt" if game == "ttt" else "reversi", evaluator)
@@ -66,7 +69,7 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     B = n_games
     ename = "ttt" if ttt else {8: "reversi", 6: "reversi6", 4: "reversi4"}[size]
     eng = SelfPlayEngine(ename, B, sims, evaluator, net, c_puct, device=device, leaves_per_step=leaves_per_step, gumbel=gumbel,
-                         eval_symmetry=eval_symmetry, fpu=fpu, solver=solver)
+                         eval_symmetry=eval_symmetry, fpu=fpu, solver=solver, early_stop=early_stop)
     rng = np.random.default_rng(seed)
     st = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
     if ttt:

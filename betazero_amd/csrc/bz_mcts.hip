@@ -24,6 +24,7 @@
 // Proven wins, losses and draws (k_solve_step / k_solve_cap_step, the proof pass behind their backup, csrc/bz_solver.h) -- DESIGN.md 3.23.
 // The Gumbel interior rule below the root of a Gumbel search (k_gfull_step, csrc/bz_gumbel_interior.h) -- DESIGN.md 3.21.
 // Resignation in self-play (k_resign_note in front of the play kernel, k_resign_finish behind it, csrc/bz_resign.h) -- DESIGN.md 3.24.
+// Exact early stop of a search whose move is decided (k_stop_step / k_fpu_stop_step, csrc/bz_early_stop.h) -- DESIGN.md 3.25.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -42,6 +43,7 @@
 #include "bz_rules.h"
 #include "bz_fpu.h"
 #include "bz_solver.h"
+#include "bz_early_stop.h"
 #include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
@@ -250,6 +252,11 @@ struct ResignDev { float threshold; int consecutive; u32 playout_q; uint8_t* str
 // g_state of a slot k_resign_note has ended and k_resign_finish has not yet restarted or retired: like every value but 0 it
 // makes the kernels between the two skip the slot
 constexpr uint8_t kStateResigned = 2;
+// Exact early stop (stop_at = nullptr: off), set by bz_engine_set_early_stop in the caller's buffer: the simulation
+// index every slot stopped at in the current search u32 [B] (sims: it ran its whole budget; 0: it sat the search out) and one
+// word, walked = 1 + the index of the last tree step in which some slot walked.  k_stop_begin resets both behind k_root_begin.  A
+// kernel argument of the stop kernels only.
+struct StopDev { u32* stop_at; u32* walked; };
 
 // ---- The search mode: which rules the walk (dev_select), the tree step around it (tree_step_body) and the move (play_body, which
 // says what each bit does to the move) run under.  One bit per rule, one compile-time mask M per kernel; the host derives the same
@@ -286,18 +293,26 @@ enum : unsigned {
     // 0; a walk that takes a decided edge ends there with the edge's value, as at a terminal edge.  The proof pass runs behind the
     // backup of a terminal or proven leaf; the backup of an evaluated or copied leaf stays the pure-store path it is.
     kModeSolve = 1u << 6,
+    // kModeStop (k_stop_step / k_fpu_stop_step): behind the backup of the step of simulation s, a slot whose move is
+    // decided (early_stop_decided over the root's visits, s done, sims - s to go) and not sampled (moves made >= temp_moves)
+    // records stop_at = s, selects nothing and is left LEAF_NONE: idle from then on, like a slot at its playout-cap budget.  The
+    // root's first kGW edges are the ones patched in registers, the others are loaded behind the group fence; the leader and the
+    // "can still catch up" flag are two group reductions, skipped per game while early_stop_possible says the rule cannot fire.
+    kModeStop = 1u << 7,
 };
 // the mask's bits by name, and the combinations no code serves: the setters (bz_engine_set_*) refuse the same ones at run time
 template <unsigned M>
 struct Mode {
     static constexpr bool leaf = (M & kModeLeaf) != 0, gumbel = (M & kModeGumbel) != 0, cap = (M & kModeCap) != 0,
                           forced = (M & kModeForced) != 0, fpu = (M & kModeFpu) != 0, gfull = (M & kModeGfull) != 0,
-                          solve = (M & kModeSolve) != 0;
+                          solve = (M & kModeSolve) != 0, stop = (M & kModeStop) != 0;
     static_assert(!gfull || gumbel, "search mode: the Gumbel interior rule needs Gumbel root search");
     static_assert(!gumbel || !(cap || forced || fpu || solve),
                   "search mode: Gumbel root search combines with none of playout cap, forced playouts, FPU reduction and the solver");
     static_assert(!solve || !(forced || fpu), "search mode: the solver combines with neither forced playouts nor FPU reduction");
     static_assert(!leaf || M == kModeLeaf, "search mode: leaf-parallel search combines with nothing");
+    static_assert(!stop || !(leaf || gumbel || cap || forced || gfull || solve),
+                  "search mode: early stop combines with FPU reduction and with nothing else");
 };
 // what the modes' kernels get beside EngineDev: each pointer is read only under its bit and stays null otherwise
 struct ModeArgs {
@@ -307,6 +322,7 @@ struct ModeArgs {
     const FpuDev* fp = nullptr;       // kModeFpu
     const GumbelInDev* gi = nullptr;  // kModeGfull
     const SolveDev* sv = nullptr;     // kModeSolve
+    const StopDev* sp = nullptr;      // kModeStop
 };
 
 struct Cnt { u32 v[CNT_N]; };
@@ -1364,7 +1380,7 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 template <class G, unsigned M>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArgs& A, int do_expand, int do_select, u32 sim_idx) {
     constexpr bool kGumbel = Mode<M>::gumbel, kCap = Mode<M>::cap, kForced = Mode<M>::forced, kFpu = Mode<M>::fpu, kGfull = Mode<M>::gfull,
-                   kSolve = Mode<M>::solve;
+                   kSolve = Mode<M>::solve, kStop = Mode<M>::stop;
     static_assert(!Mode<M>::leaf, "search mode: the leaf-parallel step is k_leaf_step's own body");
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1391,6 +1407,8 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
         if (kCap) { bud = A.budget[g]; pin(bud); }
         [[maybe_unused]] float rw;
         if constexpr (kFpu) { rw = A.fp->root_w[g]; pin(rw); }
+        [[maybe_unused]] int made = 0;
+        if constexpr (kStop) { made = E.g_moves[g]; pin(made); }
         // the walk's first load too: root edges 0..kGW-1 (the root's edges start at index 0; whatever this step's
         // backup / expansion changes in them is patched in registers below) -- their latency hides behind the
         // evaluator row's round trip and the softmax instead of heading the walk
@@ -1402,7 +1420,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
         pin(nlegal); pin(rown); pin(ropp); pin(root_base); pin(pe0.eidx); pin(pe0.w0); pin(pe0.W);
         const bool active = state == 0 && kind != LEAF_NONE;
         // a slot at its budget expands and backs up its last leaf below, selects nothing and is left LEAF_NONE: idle from then on
-        const bool walk = kCap ? (active && sim_idx < bud) : active;
+        bool walk = kCap ? (active && sim_idx < bud) : active;
         st.mark(0);
         if (do_expand && (kind == LEAF_EVAL || kind == LEAF_TERMINAL || kind == LEAF_COPY)) {
             float v;
@@ -1451,6 +1469,39 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
                 }
             }
             if constexpr (kSolve) if (kind == LEAF_TERMINAL) dev_prove<G>(E, *A.sv, g, sub, path, depth0, root_n, re0);
+        }
+        if constexpr (kStop) {  //  sim_idx simulations are backed up: is the move decided?  (a branch per game)
+            const u32 left = (u32)E.sims - sim_idx;
+            if (do_select && walk && pre_ok && made >= E.temp_moves && early_stop_possible(root_n, sim_idx, left)) {
+                constexpr int kCH = (G::MAXCH + kGW - 1) / kGW;
+                group_fence();  // the root edge the backup above wrote is read below when it lies beyond re0
+                u32 Nk[kCH], key = 0;
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    const int i = k * kGW + sub;
+                    Nk[k] = 0;
+                    if (i < root_n) {
+                        Nk[k] = e_N(k == 0 ? re0.w0 : edges_g[i].w0);
+                        const u32 ky = early_stop_key(Nk[k], i);
+                        key = ky > key ? ky : key;
+                    }
+                }
+                key = group_max_u32<kGW>(key);
+                const u32 NL = early_stop_leader_N(key);
+                const int L = early_stop_leader(key);
+                u32 open = 0;
+#pragma unroll
+                for (int k = 0; k < kCH; ++k) {
+                    const int i = k * kGW + sub;
+                    if (i < root_n && early_stop_catches(Nk[k], i, NL, L, left)) open = 1u;
+                }
+                open = group_or_u32<kGW>(open);
+                if (!open) {
+                    walk = false;
+                    if (sub == 0) A.sp->stop_at[g] = sim_idx;
+                }
+            }
+            if (do_select && walk && sub == 0) A.sp->walked[0] = sim_idx + 1u;  // (every writer of a step stores the same word)
         }
         st.mark(2);
         if (do_select) {
@@ -1576,6 +1627,25 @@ template <class G>
 __global__ void __launch_bounds__(256) k_solve_cap_step(EngineDev E, CapDev Cp, SolveDev Sv, int do_expand, int do_select, u32 sim_idx) {
     ModeArgs A; A.budget = Cp.budget; A.sv = &Sv;
     tree_step_body<G, kModeSolve | kModeCap>(E, A, do_expand, do_select, sim_idx);
+}
+
+// The tree steps with exact early stop: k_tree_step / k_fpu_step with the stop rule between the backup and the walk.
+template <class G>
+__global__ void __launch_bounds__(256) k_stop_step(EngineDev E, StopDev Sp, int do_expand, int do_select, u32 sim_idx) {
+    ModeArgs A; A.sp = &Sp;
+    tree_step_body<G, kModeStop>(E, A, do_expand, do_select, sim_idx);
+}
+template <class G>
+__global__ void __launch_bounds__(256) k_fpu_stop_step(EngineDev E, FpuDev Fp, StopDev Sp, int do_expand, int do_select, u32 sim_idx) {
+    ModeArgs A; A.fp = &Fp; A.sp = &Sp;
+    tree_step_body<G, kModeFpu | kModeStop>(E, A, do_expand, do_select, sim_idx);
+}
+// ... and the reset of their buffer behind k_root_begin: a slot with a root to search runs its whole budget until the rule says
+// otherwise, every other slot sits the search out; no step has walked yet.
+__global__ void __launch_bounds__(256) k_stop_begin(EngineDev E, StopDev Sp) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g == 0) Sp.walked[0] = 0u;
+    if (g < E.B) Sp.stop_at[g] = E.leaf_kind[(size_t)g * E.K] != LEAF_NONE ? (u32)E.sims : 0u;
 }
 
 // Leaf-parallel tree step (K = E.K > 1 leaves per game per step with virtual loss), G::GW lanes per game as
@@ -2775,6 +2845,9 @@ struct bz_engine {
     int fpu_done;      // ... simulations selected so far in the current search: what an expand-only step has backed up when it is done
     SolveDev solve;    // proven wins, losses and draws (bz_engine_set_solver); solve.root = nullptr: off
     int64_t solve_bytes;  // ... the bytes bz_engine_root_begin zeroes in its buffer
+    StopDev stop;      // exact early stop (bz_engine_set_early_stop); stop.stop_at = nullptr: off
+    int stop_host_exit;   // ... engines_run leaves the step loop once no slot of this engine walks any more
+    uint32_t* stop_ring;  // ... pinned host words [4], one per run-ahead mark in flight: stop.walked as of that mark (created on first use)
     ValueDev value;    // search-value targets (bz_engine_set_search_value); value.ex_q = nullptr: off
     OwnDev own;        // ownership targets (bz_engine_set_ownership); own.fin_x = nullptr: off
     ResignDev resign;  // resignation (bz_engine_set_resign); resign.streak = nullptr: off
@@ -2932,6 +3005,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     e->store = StoreDev{}; e->store_index_bytes = 0;
     e->fpu = FpuDev{}; e->fpu_done = 0;
     e->solve = SolveDev{}; e->solve_bytes = 0;
+    e->stop = StopDev{}; e->stop_host_exit = 0; e->stop_ring = nullptr;
     // measured on MI355X at 65,536 games x 50 sims: round 2 (profiles/r02_bench_ttt_gw*) 2 lanes 0.185 ms, 4 lanes 0.190 ms,
     // 8 lanes 0.294 ms per launch; round 3, after the kernel became issue-bound and lost a third of its instructions
     // (profiles/r03_bench_ttt_lanes.txt): 1 lane 0.162, 2 lanes 0.137, 4 lanes 0.134, 8 lanes 0.181 ms -> 4 lanes
@@ -2990,6 +3064,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
 
 BZ_EXPORT int32_t bz_engine_destroy(bz_engine* e) {
     if (e) for (int i = 0; i < e->n_ahead; ++i) (void)hipEventDestroy(e->ahead[i]);
+    if (e && e->stop_ring) (void)hipHostFree(e->stop_ring);
     delete e;
     return BZ_OK;
 }
@@ -3103,6 +3178,10 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     e->fpu_done = 0;
     if (e->solve.root)  //  no root is decided, both counts 0
         BZ_HIP(hipMemsetAsync(e->solve.root, 0, (size_t)e->solve_bytes, (hipStream_t)stream));
+    if (e->stop.stop_at) {  //  every slot with a root: its whole budget; the others: 0; no step has walked
+        hipLaunchKernelGGL(k_stop_begin, grid_of(e->dev.B), dim3(256), 0, (hipStream_t)stream, e->dev, e->stop);
+        BZ_LAUNCH_CHECK("k_stop_begin");
+    }
     return BZ_OK;
 }
 
@@ -3111,7 +3190,7 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
 static unsigned engine_mode(const bz_engine* e) {
     return (e->dev.K > 1 ? kModeLeaf : 0u) | (e->gumbel.m > 0 ? kModeGumbel : 0u) | (e->cap.fast > 0 ? kModeCap : 0u) |
            (e->forced.k > 0.0f ? kModeForced : 0u) | (e->fpu.root_w ? kModeFpu : 0u) | (e->gin.node_v ? kModeGfull : 0u) |
-           (e->solve.root ? kModeSolve : 0u);
+           (e->solve.root ? kModeSolve : 0u) | (e->stop.stop_at ? kModeStop : 0u);
 }
 // every slot's budget for the observers of a search: null without playout cap randomisation (every search is a full one)
 static const u32* cap_budgets(const bz_engine* e) { return e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr; }
@@ -3136,6 +3215,8 @@ static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t si
     case kModeFpu | kModeForced | kModeCap: BZ_STEP(k_fpu_forced_cap_step, e->dev, e->cap, e->forced, e->fpu);
     case kModeSolve: BZ_STEP(k_solve_step, e->dev, e->solve);  // 
     case kModeSolve | kModeCap: BZ_STEP(k_solve_cap_step, e->dev, e->cap, e->solve);
+    case kModeStop: BZ_STEP(k_stop_step, e->dev, e->stop);  // 
+    case kModeFpu | kModeStop: BZ_STEP(k_fpu_stop_step, e->dev, e->fpu, e->stop);
     default: set_error("tree_step: no step kernel serves search mode 0x%x", m); return BZ_EINVAL;
     }
 #undef BZ_STEP
@@ -3349,6 +3430,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     BZ_REQUIRE(finite && gumbel_scale >= 0.0f && maxvisit_init >= 0.0f && value_scale >= 0.0f,
                "bz_engine_set_gumbel: gumbel_scale, maxvisit_init and value_scale must be finite and >= 0");
     if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_gumbel: Gumbel root search does not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
     BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_gumbel: Gumbel root search does not combine with forced playouts (bz_engine_set_forced_playouts)");
     BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_gumbel: Gumbel root search does not combine with first-play urgency reduction (bz_engine_set_fpu)");
@@ -3439,6 +3521,7 @@ BZ_EXPORT int32_t bz_engine_set_playout_cap(bz_engine* e, int32_t fast_sims, uin
     BZ_REQUIRE(fast_sims >= 1 && fast_sims < e->cfg.sims, "bz_engine_set_playout_cap: fast_sims must be 0 (off) or in 1 .. sims - 1");
     BZ_REQUIRE(full_q <= 65536u, "bz_engine_set_playout_cap: full_q must be in 0 .. 65536 (the probability of a full search in units of 2^-16)");
     if (const char* why = cap_refusal(e->cfg)) { set_error("bz_engine_set_playout_cap: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_playout_cap: playout cap randomisation does not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_playout_cap: playout cap randomisation does not combine with Gumbel root search (bz_engine_set_gumbel)");
     BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_playout_cap: the buffer must be non-null and 256-byte aligned");
     const int64_t need = cap_bytes(e->cfg);
@@ -3482,6 +3565,7 @@ BZ_EXPORT int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t p
         return BZ_OK;
     }
     if (const char* why = forced_refusal(e->cfg, k)) { set_error("bz_engine_set_forced_playouts: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_forced_playouts: forced playouts do not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_forced_playouts: forced playouts do not combine with Gumbel root search (bz_engine_set_gumbel)");
     BZ_REQUIRE(!(k > 0.0f && e->solve.root), "bz_engine_set_forced_playouts: forced playouts do not combine with the solver (bz_engine_set_solver)");
     e->forced.k = k; e->forced.prune = prune ? 1 : 0;
@@ -3597,6 +3681,7 @@ BZ_EXPORT int32_t bz_engine_set_solver(bz_engine* e, int32_t on, void* buf, int6
         return BZ_OK;
     }
     if (const char* why = solver_refusal(e->cfg)) { set_error("bz_engine_set_solver: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_solver: the solver does not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_solver: the solver does not combine with Gumbel root search (bz_engine_set_gumbel)");
     BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_solver: the solver does not combine with forced playouts (bz_engine_set_forced_playouts): both score +inf");
     BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_solver: the solver does not combine with first-play urgency reduction (bz_engine_set_fpu)");
@@ -3632,6 +3717,75 @@ BZ_EXPORT int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t 
     return solver_pick(n, [N](int i) { return (u64)N[i]; }, [vals](int i) { return (int)vals[i]; }, tau1 != 0, (u64)draw);
 }
 
+/* ---- exact early stop */
+namespace {
+// what early stop refuses in a config (nullptr: nothing)
+const char* early_stop_refusal(const bz_engine_cfg& c) {
+    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "early stop does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
+    if (leaves_per_step(c) > 1) return "early stop does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
+    return nullptr;
+}
+struct StopOffsets { int64_t stop_at, walked, total; };
+inline StopOffsets early_stop_carve(const bz_engine_cfg& c) {
+    Carver k; StopOffsets o;
+    o.stop_at = k.take((int64_t)c.n_games * 4); o.walked = k.take(4); o.total = k.off;
+    return o;
+}
+}  // namespace
+
+BZ_EXPORT int64_t bz_engine_early_stop_bytes(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_early_stop_bytes: %s", kBadFlags); return -1; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_early_stop_bytes: %s", kBadCfg); return -1; }
+    if (const char* why = early_stop_refusal(*cfg)) { set_error("bz_engine_early_stop_bytes: %s", why); return -1; }
+    return early_stop_carve(*cfg).total;
+}
+
+BZ_EXPORT int32_t bz_engine_early_stop_check(const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_early_stop_check: %s", kBadFlags); return BZ_EINVAL; }
+    if (!cfg_ok(cfg)) { set_error("bz_engine_early_stop_check: %s", kBadCfg); return BZ_EINVAL; }
+    if (const char* why = early_stop_refusal(*cfg)) { set_error("bz_engine_early_stop_check: %s", why); return BZ_EINVAL; }
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_set_early_stop(bz_engine* e, int32_t on, int32_t host_exit, void* buf, int64_t bytes, void* stream) {
+    BZ_REQUIRE(e, "bz_engine_set_early_stop: null engine");
+    if (!on) {  // off: the plain (the FPU) kernels again
+        e->stop = StopDev{}; e->stop_host_exit = 0;
+        return BZ_OK;
+    }
+    if (const char* why = early_stop_refusal(e->cfg)) { set_error("bz_engine_set_early_stop: %s", why); return BZ_EINVAL; }
+    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_early_stop: early stop does not combine with Gumbel root search (bz_engine_set_gumbel): sequential halving is its own schedule");
+    BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_early_stop: early stop does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
+    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_early_stop: early stop does not combine with forced playouts (bz_engine_set_forced_playouts)");
+    BZ_REQUIRE(!e->solve.root, "bz_engine_set_early_stop: early stop does not combine with the solver (bz_engine_set_solver)");
+    BZ_REQUIRE(e->store.S == 0, "bz_engine_set_early_stop: early stop does not combine with the root store (bz_engine_set_root_store): a shortened tree must not seed a later search");
+    BZ_REQUIRE(!e->surp.prior, "bz_engine_set_early_stop: early stop does not combine with policy surprise weighting (bz_engine_set_surprise): its targets come from complete searches");
+    BZ_REQUIRE(!e->value.ex_q, "bz_engine_set_early_stop: early stop does not combine with search-value targets (bz_engine_set_search_value): its targets come from complete searches");
+    BZ_REQUIRE(!e->own.fin_x, "bz_engine_set_early_stop: early stop does not combine with ownership targets (bz_engine_set_ownership): its targets come from complete searches");
+    BZ_REQUIRE(!e->resign.streak, "bz_engine_set_early_stop: early stop does not combine with resignation (bz_engine_set_resign): its records come from complete searches");
+    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_early_stop: the buffer must be non-null and 256-byte aligned");
+    const StopOffsets o = early_stop_carve(e->cfg);
+    if (bytes < o.total) { set_error("bz_engine_set_early_stop: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no search yet: every slot 0
+    e->stop.stop_at = at<u32>(buf, o.stop_at); e->stop.walked = at<u32>(buf, o.walked);
+    e->stop_host_exit = host_exit ? 1 : 0;
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_stopped(bz_engine* e, uint32_t* out, void* stream) {
+    BZ_REQUIRE(e && out, "bz_engine_stopped: null pointer");
+    BZ_REQUIRE(e->stop.stop_at, "bz_engine_stopped: early stop is off (bz_engine_set_early_stop)");
+    BZ_HIP(hipMemcpyAsync(out, e->stop.stop_at, (size_t)e->cfg.n_games * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_early_stop_decided(const uint32_t* N, int32_t n, uint32_t left) {
+    if (!(N && n >= 1 && n <= 255)) { set_error("bz_early_stop_decided: null pointer or n outside 1 .. 255"); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (N[i] >= (1u << 24)) { set_error("bz_early_stop_decided: N[%d] = %u is no visit count (>= 2^24)", i, N[i]); return -1; }
+    return early_stop_decided(n, left, [N](int i) { return N[i]; }) ? 1 : 0;
+}
+
 /* ---- policy surprise weighting */
 namespace {
 struct SurpOffsets { int64_t prior, pend, ex_kl, total; };
@@ -3660,6 +3814,7 @@ BZ_EXPORT int32_t bz_engine_set_surprise(bz_engine* e, void* buf, int64_t bytes,
         return BZ_OK;
     }
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_surprise: the buffer must be 256-byte aligned");
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_surprise: policy surprise weighting does not combine with early stop (bz_engine_set_early_stop)");
     const SurpOffsets o = surp_carve(e->cfg);
     if (bytes < o.total) { set_error("bz_engine_set_surprise: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no prior saved, no row pending, every kl 0
@@ -3700,6 +3855,7 @@ BZ_EXPORT int32_t bz_engine_set_search_value(bz_engine* e, void* buf, int64_t by
         return BZ_OK;
     }
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_search_value: the buffer must be 256-byte aligned");
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_search_value: search-value targets do not combine with early stop (bz_engine_set_early_stop)");
     const int64_t total = value_bytes(e->cfg);
     if (bytes < total) { set_error("bz_engine_set_search_value: buffer too small (%lld < %lld)", (long long)bytes, (long long)total); return BZ_ENOMEM; }
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)total, (hipStream_t)stream));  // every q 0
@@ -3748,6 +3904,7 @@ BZ_EXPORT int32_t bz_engine_set_ownership(bz_engine* e, void* buf, int64_t bytes
     }
     BZ_REQUIRE(!e->resign.streak, "bz_engine_set_ownership: ownership targets do not combine with resignation (bz_engine_set_resign): a resigned game has no final board");
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_ownership: the buffer must be 256-byte aligned");
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_ownership: ownership targets do not combine with early stop (bz_engine_set_early_stop)");
     const OwnOffsets o = own_carve(e->cfg);
     if (bytes < o.total) { set_error("bz_engine_set_ownership: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no final board; (act 0 is never read before k_root_policy wrote it)
@@ -3801,6 +3958,7 @@ BZ_EXPORT int32_t bz_engine_set_resign(bz_engine* e, float threshold, int32_t co
         e->resign = ResignDev{}; e->resign_bytes = 0;
         return BZ_OK;
     }
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_resign: resignation does not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE(!e->own.fin_x, "bz_engine_set_resign: resignation does not combine with ownership targets (bz_engine_set_ownership): a resigned game has no final board");
     const ResignOffsets o = resign_carve(e->cfg);
     if (bytes < o.total) { set_error("bz_engine_set_resign: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_EINVAL; }
@@ -3877,6 +4035,7 @@ BZ_EXPORT int32_t bz_engine_set_root_store(bz_engine* e, void* buf, int64_t byte
         return BZ_OK;
     }
     BZ_REQUIRE(store_args_ok(entries, plies), "bz_engine_set_root_store: 1 <= entries <= 65536, 1 <= plies <= 64");
+    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_root_store: the root store does not combine with early stop (bz_engine_set_early_stop)");
     BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_root_store: the buffer must be 256-byte aligned");
     const StoreOffsets o = store_carve(e->cfg, entries);
     if (bytes < o.total) { set_error("bz_engine_set_root_store: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -3950,6 +4109,7 @@ BZ_EXPORT int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream) {
         case kModeForced | kModeCap: BZ_PLAY(k_forced_cap_play, e->dev, e->cap, e->forced);
         case kModeSolve: BZ_PLAY(k_solve_play, e->dev);  // 
         case kModeSolve | kModeCap: BZ_PLAY(k_solve_cap_play, e->dev, e->cap);
+        case kModeStop: BZ_PLAY(k_play, e->dev);  //  a stopped search is a full search: the plain move over the tree as it stands
         default: set_error("bz_engine_play: no play kernel serves search mode 0x%x", m); return BZ_EINVAL;
         }
 #undef BZ_PLAY
@@ -4079,20 +4239,38 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
     // (K > 1: one step = K simulations; the run-ahead bound counts steps of q / K, at least one)
     const int q0 = run_ahead_sims > 0 ? (run_ahead_sims >= 2 ? run_ahead_sims / 2 : 1) : 0;
     const int q = q0 ? (q0 / Kmax > 0 ? q0 / Kmax : 1) : 0;
+    //  host exit: an engine with early stop whose slots have all stopped walking leaves the loop.  It learns that
+    // from the marks it waits on anyway: in front of every mark's event its stream copies stop.walked (1 + the last step in which
+    // a slot walked) into a pinned word, and the mark found complete -- the one after step m -- with walked <= m says step m was
+    // empty.  A slot that does not walk is left LEAF_NONE and never walks again, so every later step is empty too.
+    bool quit[16] = {};  // (n <= 16)
     for (int step = 0; step < steps; ++step) {
+        int live = 0;
         for (int i = 0; i < n; ++i) {
             bz_engine* e = engines[i];
-            if (!e || search_is_fused(e)) continue;
+            if (!e || search_is_fused(e) || quit[i]) continue;
             const int s = step * e->dev.K;
             if (s >= e->cfg.sims) continue;
+            ++live;
             const bool prep = root_prep(e);
             if ((rc = tree_step(e, (prep && s == 0) ? 0 : 1, 1, (uint32_t)s, streams[i])) != BZ_OK) return rc;
             if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
         }
+        if (!live) break;
         if (q && (step + 1) % q == 0)
-            for (int i = 0; i < n; ++i)
-                if (engines[i] && !search_is_fused(engines[i]) &&
-                    (rc = ahead_mark(engines[i], (step + 1) / q - 1, (hipStream_t)streams[i])) != BZ_OK) return rc;
+            for (int i = 0; i < n; ++i) {
+                bz_engine* e = engines[i];
+                if (!e || search_is_fused(e) || quit[i]) continue;
+                const int idx = (step + 1) / q - 1;
+                const bool watch = !play && e->stop.stop_at && e->stop_host_exit;  // (bz_engines_search only)
+                if (watch) {
+                    if (!e->stop_ring) BZ_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->stop_ring), 4 * sizeof(uint32_t), hipHostMallocDefault));
+                    BZ_HIP(hipMemcpyAsync(e->stop_ring + (idx & 3), e->stop.walked, 4, hipMemcpyDeviceToHost, (hipStream_t)streams[i]));
+                }
+                if ((rc = ahead_mark(e, idx, (hipStream_t)streams[i])) != BZ_OK) return rc;
+                // (mark idx - 2 is complete, and it was recorded behind step (idx - 1) * q - 1)
+                if (watch && idx >= 2 && (int)e->stop_ring[(idx - 2) & 3] <= (idx - 1) * q - 1) quit[i] = true;
+            }
     }
     for (int i = 0; i < n; ++i) {
         bz_engine* e = engines[i];

@@ -427,6 +427,50 @@ def check_solver(solver, reuse_subtree=False, leaves_per_step=1, gumbel=None, fo
     return True
 
 
+@dataclass(frozen=True)
+class EarlyStop:
+    """Exact early stop (Huang, Coulom and Lin 2010; Baier and Winands 2012; LC0's "smart pruning" without its
+    slack): a search whose move is the first maximum of the root's visits stops at the first simulation index at which the
+    simulations left can no longer change that move.  The move is the full search's, always.  host_exit: the host also stops
+    issuing the tree steps of an engine once none of its slots walks any more (same results, fewer empty launches)."""
+    host_exit: bool = True
+
+
+def check_early_stop(early_stop, reuse_subtree=False, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
+                     solver=False, root_store=None, surprise=False, search_value=False, ownership=False, resign=None):
+    """None / False: off (None returned); True: EarlyStop(); or an EarlyStop -- validated, and refused with subtree reuse,
+    leaves_per_step > 1, Gumbel root search, the playout cap, forced playouts, the solver, a root store (root_store: the
+    checked value, a pair or None) and the training observers surprise, search_value, ownership and resign (ValueError, before
+    any device is touched)"""
+    if early_stop is None or early_stop is False:
+        return None
+    cfg = EarlyStop() if early_stop is True else early_stop
+    if not isinstance(cfg, EarlyStop):
+        raise ValueError(f"early_stop must be None, False, True or an EarlyStop (got {early_stop!r})")
+    if not isinstance(cfg.host_exit, (bool, np.bool_)):
+        raise ValueError(f"early_stop: host_exit must be a bool (got {cfg.host_exit!r})")
+    on = lambda x: x is not None and x is not False  # noqa: E731
+    if reuse_subtree:
+        raise ValueError("early_stop: early stop does not combine with reuse_subtree")
+    if leaves_per_step != 1:
+        raise ValueError("early_stop: early stop does not combine with leaves_per_step > 1")
+    if on(gumbel):
+        raise ValueError("early_stop: early stop does not combine with Gumbel root search (gumbel): sequential halving is its own schedule")
+    if on(playout_cap):
+        raise ValueError("early_stop: early stop does not combine with playout cap randomisation (playout_cap)")
+    if on(forced_playouts):
+        raise ValueError("early_stop: early stop does not combine with forced_playouts")
+    if on(solver):
+        raise ValueError("early_stop: early stop does not combine with the solver (solver)")
+    if on(root_store):
+        raise ValueError("early_stop: early stop does not combine with the root store (root_store): a shortened tree must not "
+                         "seed a later search")
+    for name, val in (("surprise", surprise), ("search_value", search_value), ("ownership", ownership), ("resign", resign)):
+        if on(val):
+            raise ValueError(f"early_stop: early stop does not combine with {name}: its targets come from complete searches")
+    return EarlyStop(bool(cfg.host_exit))
+
+
 def check_search_value(search_value):
     """search-value targets: a bool, anything else is refused (ValueError, before any device is touched)"""
     if not isinstance(search_value, (bool, np.bool_)):
@@ -446,7 +490,7 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False, resign=None):
+                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False, resign=None, early_stop=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -524,7 +568,18 @@ class SelfPlayEngine:
         full searches in a row resigns; a seeded share of the games is played out and only records where it would have
         resigned.  resign_rows() reads the records, resign_stats() the false-positive rate; set_resign() changes the rule
         between searches.  Searches, and the rows of games that do not resign, are what they are without it; it combines with
-        everything the engine accepts but ownership."""
+        everything the engine accepts but ownership.
+
+        early_stop: None / False = every search runs its whole budget (the default, unchanged); True or an
+        EarlyStop(host_exit) = a slot whose move is the first maximum of the visits (moves made >= temp_moves) stops searching
+        at the first simulation index at which the simulations left cannot change that move.  The move is the full search's;
+        root_stats() and pi are those of the shortened tree (pi = N / stop_at), stopped() reads stop_at, set_early_stop()
+        changes it between searches.  Meant for matches and players, not for training games.  Combines with fpu, eval_symmetry,
+        Dirichlet noise, temp_moves, every evaluator and eval_cache mode; with it on, root_store=None means no root store.
+        Refused with reuse_subtree, leaves_per_step > 1, gumbel, playout_cap, forced_playouts, solver, a root store, surprise,
+        search_value, ownership and resign."""
+        if early_stop is not None and early_stop is not False and root_store is None:
+            root_store = False  # (a shortened tree is not worth an entry and must not seed a later search)
         self.root_store = check_root_store(root_store, eval_cache)
         self.ownership = check_ownership(ownership)
         self.resign = check_resign(resign, self.ownership)
@@ -542,6 +597,8 @@ class SelfPlayEngine:
         self.fpu = check_fpu(fpu, reuse_subtree, self.K, gumbel)
         self._reuse = bool(reuse_subtree)
         self.solver = check_solver(solver, reuse_subtree, self.K, gumbel, forced_playouts, fpu)
+        self.early_stop = check_early_stop(early_stop, reuse_subtree, self.K, gumbel, playout_cap, forced_playouts, solver,
+                                           self.root_store, surprise, search_value, ownership, resign)
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -640,6 +697,8 @@ class SelfPlayEngine:
             self._call(L.bz_engine_set_ownership, self.ows.data_ptr() + self._opad, obytes)
         if self.resign is not None:
             self._set_resign(self.resign)
+        if self.early_stop is not None:
+            self._set_early_stop(self.early_stop)
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -738,9 +797,42 @@ class SelfPlayEngine:
     def set_solver(self, solver):
         """switch the solver on or off, between searches"""
         on = check_solver(solver, self._reuse, self.K, self.gumbel, self.forced_playouts, self.fpu)
+        if on and self.early_stop is not None:
+            raise ValueError("solver: proofs do not combine with early stop (early_stop)")
         self.drain()
         self._set_solver(on)
         self.solver = on
+
+    def _set_early_stop(self, es):
+        L = _lib.lib()
+        if es is None:
+            self._call(L.bz_engine_set_early_stop, 0, 0, None, 0)
+            return
+        if getattr(self, "ews", None) is None:  # the engine's stop_at buffer (caller-owned, like the workspace)
+            ebytes = L.bz_engine_early_stop_bytes(C.byref(self.cfg))
+            if ebytes < 0:
+                raise RuntimeError(_lib.last_error())
+            self.ews = torch.zeros(ebytes + 256, dtype=torch.uint8, device=self.device)
+            self._epad, self._ebytes = (-self.ews.data_ptr()) & 255, ebytes
+        self._call(L.bz_engine_set_early_stop, 1, int(es.host_exit), self.ews.data_ptr() + self._epad, self._ebytes)
+
+    def set_early_stop(self, early_stop):
+        """switch exact early stop on, off or to another host_exit, between searches: None / False, True or an
+        EarlyStop"""
+        es = check_early_stop(early_stop, self._reuse, self.K, self.gumbel, self.playout_cap, self.forced_playouts, self.solver,
+                              self.root_store, self.surprise, self.search_value, self.ownership, self.resign)
+        self.drain()
+        self._set_early_stop(es)
+        self.early_stop = es
+
+    def stopped(self):
+        """after a search with early stop on: stop_at, numpy uint32 [B] -- the simulations every slot's search
+        ran: sims when it ran its whole budget, 0 for a slot that sat the search out"""
+        if self.early_stop is None:
+            raise RuntimeError("stopped(): early stop is off (early_stop=)")
+        out = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        self._call(_lib.lib().bz_engine_stopped, out.data_ptr())
+        return out.cpu().numpy().view(np.uint32)
 
     def _set_resign(self, rs):
         L = _lib.lib()
@@ -759,6 +851,8 @@ class SelfPlayEngine:
         """switch resignation on, off or to another rule, between searches: None / False, True (the defaults)
         or a Resign.  While it stays on, streaks and records are kept; switching it off and on again clears them."""
         rs = check_resign(resign, self.ownership)
+        if rs is not None and self.early_stop is not None:
+            raise ValueError("resign: resignation does not combine with early stop (early_stop)")
         self.drain()
         self._set_resign(rs)
         self.resign = rs
@@ -803,6 +897,11 @@ class SelfPlayEngine:
                 {"n_decided": int(c[0]), "n_proven_stops": int(c[1])})
 
     def search(self):
+        if self.early_stop is not None and self.early_stop.host_exit and self.cfg.eval_kind != EVAL_EXTERNAL:
+            #  host exit lives in the interleaving loop: one engine, play_match's run-ahead
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().bz_engines_search((C.c_void_p * 1)(self.h), (C.c_void_p * 1)(self._stream()), 1, 16))
+            return
         self._call(_lib.lib().bz_engine_search)
 
     def search_external(self, eval_fn):
@@ -1325,6 +1424,8 @@ class PipelinedSelfPlay:
                  forced_playouts=None, surprise=False, search_value=False, eval_symmetry=None, fpu=None, ownership=False,
                  solver=False, resign=None, **engine_kwargs):
         assert 1 <= pipelines <= n_games
+        if "early_stop" in engine_kwargs:  #  a shortened search changes pi: not for training games
+            raise ValueError("PipelinedSelfPlay: early_stop is for matches and players, not for self-play pipelines")
         check_ownership(ownership)
         check_resign(resign, ownership)
         check_solver(solver, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel, forced_playouts, fpu)

@@ -14,7 +14,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .engine import check_eval_cache, check_fpu, check_gumbel, check_leaves_per_step, check_sims, check_solver
+from .engine import (check_early_stop, check_eval_cache, check_fpu, check_gumbel, check_leaves_per_step, check_sims,
+                     check_solver)
 
 
 @dataclass
@@ -27,7 +28,9 @@ class MatchPlayer:
     symmetry (True: seed 0) -- a match stays a pure function of its arguments.  fpu (True or an engine.Fpu): DESIGN.md 3.20,
     the side searches with first-play urgency reduction (not with gumbel or leaves_per_step > 1).  Each side has its own
     GumbelConfig.interior ("puct" or "gumbel").  solver=True: DESIGN.md 3.23, the side books proven wins, losses and
-    draws and plays the solver's move (not with gumbel, fpu or leaves_per_step > 1)."""
+    draws and plays the solver's move (not with gumbel, fpu or leaves_per_step > 1).  early_stop (True or an engine.EarlyStop):
+    DESIGN.md 3.25, the side's searches stop once the simulations left cannot change the move -- the games are the games without
+    it (not with gumbel, solver or leaves_per_step > 1)."""
     sims: int = 800
     net: object = None
     evaluator: str = None
@@ -38,6 +41,7 @@ class MatchPlayer:
     eval_symmetry: object = None
     fpu: object = None
     solver: bool = False
+    early_stop: object = None
 
     def checked(self, game, n_games, side):
         """-> (evaluator name, GumbelConfig or None); ValueError for anything a match cannot play, before any device is touched"""
@@ -47,6 +51,7 @@ class MatchPlayer:
         check_eval_cache(self.eval_cache)
         check_fpu(self.fpu, False, k, self.gumbel)
         check_solver(self.solver, False, k, self.gumbel, None, self.fpu)
+        check_early_stop(self.early_stop, False, k, self.gumbel, None, None, self.solver)
         is_mlp = type(self.net).__name__ == "DeviceMLP"
         ev = self.evaluator or (("mlp_f32" if is_mlp else "net_bf16") if self.net is not None else "uniform")
         if not isinstance(ev, str) or ev not in ("uniform", "hash", "net_f32", "net_bf16", "net_fp8", "mlp_f32", "mlp_bf16"):
@@ -214,13 +219,15 @@ def check_match(game, n_games, a, b, size, opening_plies):
     return ename, a.checked(g, int(n), "a"), b.checked(g, int(n), "b")
 
 
-def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cuda:0", run_ahead=16):
+def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cuda:0", run_ahead=16, on_ply=None):
     """n_games concurrent games between the MatchPlayers a and b -> MatchResult.  game: "ttt" | "reversi" (size 8, 6 or 4).
     Games 2k and 2k + 1 are a pair: the same `opening_plies` seeded random opening moves (by neither player), a plays X
     (moves first) in game 2k and O in game 2k + 1.  Past the opening every move is the mover's search: the first maximum
     of the visit counts (PUCT) or the Gumbel move.  Per ply: the roots of both engines, the two searches on two streams
     (interleaved step by step by bz_engines_search, at most `run_ahead` simulations ahead of the streams), their moves, one
-    k_match_ply launch, one 32-byte read.  Both engines hold all n_games slots (about half are searched per ply)."""
+    k_match_ply launch, one 32-byte read.  Both engines hold all n_games slots (about half are searched per ply).
+    on_ply(engines, searched): a measuring hook, called after every ply's searches and before its moves are applied, with the
+    two SelfPlayEngines and the indices of those that searched; it may read them (root_stats(), stopped(), counters())."""
     ename, (ev_a, gum_a), (ev_b, gum_b) = check_match(game, n_games, a, b, size, opening_plies)
     import torch
     from .engine import SelfPlayEngine, pipeline_streams
@@ -229,7 +236,8 @@ def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cud
     dev = torch.device(device)
     B = int(n_games)
     engs = [SelfPlayEngine(ename, B, p.sims, ev, p.net, p.c_puct, device=device, eval_cache=p.eval_cache,
-                           leaves_per_step=p.leaves_per_step, gumbel=gum, eval_symmetry=p.eval_symmetry, fpu=p.fpu, solver=bool(p.solver))
+                           leaves_per_step=p.leaves_per_step, gumbel=gum, eval_symmetry=p.eval_symmetry, fpu=p.fpu, solver=bool(p.solver),
+                           early_stop=p.early_stop)
             for p, ev, gum in ((a, ev_a, gum_a), (b, ev_b, gum_b))]
     m = Match(ename, B, device)
     streams = pipeline_streams(dev, 2)
@@ -250,6 +258,8 @@ def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cud
                 _lib.check(L.bz_engine_set_roots(engs[i].h, m.base + lay.own, m.base + lay.opp, tms[i], streams[i].cuda_stream))
             _lib.check(L.bz_engines_search((C.c_void_p * 2)(*[engs[i].h if i in go else None for i in range(2)]),
                                            (C.c_void_p * 2)(*[st.cuda_stream for st in streams]), 2, int(run_ahead)))
+            if on_ply is not None:
+                on_ply(engs, go)
             for i in go:
                 _lib.check(L.bz_engine_root_policy(engs[i].h, pis[i].data_ptr(), acts[i].data_ptr(), streams[i].cuda_stream))
                 cur.wait_stream(streams[i])

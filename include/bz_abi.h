@@ -608,6 +608,41 @@ int32_t bz_solver_node(const int8_t* vals, int32_t n);
 /* the move rule: N, vals [n] the root edges' visits and decided values, tau1 != 0: sampling with the 64-bit draw, else the
  * first maximum; returns the edge index; -1 for bad arguments.  Host only. */
 int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t n, int32_t tau1, uint64_t draw);
+/* Exact early stop ("early stop" of Huang, Coulom and Lin 2010 and Baier and Winands 2012, LC0's "smart
+ * pruning" without its slack), opt-in per engine, for the searches whose move is the first maximum of the root's visits.
+ * Rule (bz_early_stop_decided is the function the kernels run; all of it is integer): the root has n edges in ascending action
+ *   order with visits N_i, s = sum N_i simulations are done and left = sims - s are to go; L is the first maximum of N.  The
+ *   search is DECIDED when s >= 1 and every j != L has N_j + left < N_L, or N_j + left == N_L and j > L (a tie goes to the lower
+ *   action).  Visits never decrease and the remaining simulations add at most `left` to one edge, so a decided search plays the
+ *   move the full search plays.  left = 0 is always decided, a one-edge root at s = 1, and with n >= 2 nothing before s >= left:
+ *   at most half of a search is saved.
+ * Where: in the tree step of simulation index s (1 <= s < sims), behind its expansion and backup and in front of its walk.  A
+ *   decided slot selects nothing, is left without a leaf, records stop_at = s and is idle for the rest of the search, like a
+ *   slot at its playout-cap budget.  A slot whose move is sampled (moves made < temp_moves) never stops.
+ * For every observer a stopped search is a full search: its row is recorded, and bz_engine_root_policy, bz_engine_root_stats
+ *   and bz_engine_play see the tree as it stands (pi = N / stop_at).
+ * Host exit (host_exit != 0): bz_engines_search with run_ahead_sims > 0 ends an engine's step loop as soon as a completed
+ *   run-ahead mark shows that no slot of the engine walks any more -- no launch and no wait is added, the results are the same
+ *   bits, only empty launches are saved.  bz_engine_search and bz_engines_step run every step.
+ * Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step, Gumbel root search, the playout cap,
+ * forced playouts, the solver, the root store, surprise, search value, ownership and resignation (the setters refuse each
+ * other).  First-play urgency reduction, evaluation symmetry, Dirichlet noise, temp_moves, every evaluator (the external one
+ * through the step API) and every evaluation-cache mode work unchanged.  Searches go through the step kernels. */
+/* bytes of the caller-owned buffer: stop_at u32 [n_games] and one u32 word, each rounded up to 256 bytes.  Needs no GPU; -1
+ * (bz_last_error says why) for a bad config or a refused combination. */
+int64_t bz_engine_early_stop_bytes(const bz_engine_cfg* cfg);
+/* BZ_OK when an engine of this config accepts bz_engine_set_early_stop(e, 1, ...), else BZ_EINVAL.  Needs no GPU. */
+int32_t bz_engine_early_stop_check(const bz_engine_cfg* cfg);
+/* switch early stop on (on != 0) or off (on == 0: the plain kernels again), between searches.  buf: device memory of >=
+ * bz_engine_early_stop_bytes bytes, 256-byte aligned, owned by the caller and kept alive while the mode is on; zeroed on
+ * `stream` here, reset by every bz_engine_root_begin. */
+int32_t bz_engine_set_early_stop(bz_engine* e, int32_t on, int32_t host_exit, void* buf, int64_t bytes, void* stream);
+/* stop_at of the last search into device memory, uint32 [n_games]: the simulations the slot's search ran -- cfg.sims when it ran
+ * its whole budget, 0 for a slot that sat the search out. */
+int32_t bz_engine_stopped(bz_engine* e, uint32_t* out, void* stream);
+/* the rule: N [n] the root edges' visits (each < 2^24) in ascending action order, n in 1 .. 255, left the simulations to go;
+ * returns 1 (decided) or 0; -1 for bad arguments.  Host only. */
+int32_t bz_early_stop_decided(const uint32_t* N, int32_t n, uint32_t left);
 /* Policy surprise weighting (KataGo, Wu 2019, section 3.3), opt-in per engine.  Every row bz_engine_play
  * records gets kl = sum over the root's edges in ascending action order with pi_a > 0 of pi_a * (logf(pi_a) - logf(max(P_a,
  * FLT_MIN))), every operation one binary32 operation, then kl > 0 ? kl : 0 (a rounding negative or a NaN: 0).

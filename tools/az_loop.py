@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
 from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, Resign, check_forced_playouts,  # noqa: E402
-                                 check_fpu, check_playout_cap, check_resign, check_solver, concat_device_examples)
+                                 check_early_stop, check_fpu, check_playout_cap, check_resign, check_solver, concat_device_examples)
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
@@ -118,6 +118,9 @@ def main():
     ap.add_argument("--fpu-root-reduction", type=float, default=0.1, help="the reduction at the root under --fpu-reduction (KataGo's 0.1)")
     ap.add_argument("--solver", action="store_true", help="proven wins, losses and draws (DESIGN.md 3.23) in self-play, for both players "
                     "of the gate and for the arena's search player.  Not with --gumbel, --forced-k or --fpu-reduction")
+    ap.add_argument("--early-stop", action="store_true", help="exact early stop (DESIGN.md 3.25) for both players of the gate and for "
+                    "the arena's search player: a search stops once the simulations left cannot change its move, and plays the "
+                    "move the full search plays.  Never in self-play (a shortened search changes pi).  Not with --gumbel or --solver")
     ap.add_argument("--gate-games", type=int, default=0, help="games (even) of the match between the freshly trained net and the net "
                     "self-play uses, at --arena-sims and --opening-plies; 0 = no gate: every trained net goes to self-play")
     ap.add_argument("--gate-score", type=float, default=0.55, help="the candidate is promoted at a match score >= this (AlphaGo Zero's 55 %%)")
@@ -147,6 +150,8 @@ def main():
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
     ap.add_argument("--miopen-train", action="store_true", help="train the tower through stock autograd (MIOpen) instead of the HIP training kernels (csrc/bz_train.hip)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--save-net", default=None, help="write the state_dict of the net training ends with to this file (what the "
+                    "bench tools' --net takes)")
     args = ap.parse_args()
     if args.gumbel_interior and not args.gumbel:
         ap.error("--gumbel-interior takes effect only with --gumbel")
@@ -184,6 +189,7 @@ def main():
     solver = check_solver(args.solver, gumbel=gumbel, forced_playouts=forced, fpu=fpu)
     resign = check_resign(Resign(args.resign_threshold, args.resign_consecutive, args.resign_playout_frac)
                           if args.resign_threshold is not None else None, ownership=args.ownership)
+    early_stop = check_early_stop(args.early_stop, gumbel=gumbel, solver=solver)  # the gate's and the arena's players only
     lines = []
 
     def emit(d):
@@ -194,7 +200,8 @@ def main():
         t0 = time.time()
         try:
             res = play_arena("reversi", args.arena_games, args.arena_sims, opponent_depth=depth or args.depth, evaluator=evaluator,
-                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel, fpu=fpu, solver=solver)
+                             net=net, seed=args.seed, opening_plies=args.opening_plies, gumbel=gumbel, fpu=fpu, solver=solver,
+                             early_stop=early_stop)
         except RuntimeError:  # keep the weights that were in play for a post-mortem
             if args.out:
                 np.save(args.out + ".failed_params.npy", module.flat_params())
@@ -283,8 +290,9 @@ def main():
         gate = {}
         if args.gate_games:  # the candidate (A) against the net self-play uses (B)
             t2 = time.time()
-            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu, solver=solver),
-                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu, solver=solver), opening_plies=args.opening_plies,
+            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu, solver=solver,
+                                                                             early_stop=early_stop),
+                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu, solver=solver, early_stop=early_stop), opening_plies=args.opening_plies,
                              seed=args.seed * 1000 + it)
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
@@ -318,6 +326,8 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"args": vars(args), "lines": lines}, f, indent=1)
+    if args.save_net:
+        torch.save(module.state_dict(), args.save_net)
 
 
 if __name__ == "__main__":
