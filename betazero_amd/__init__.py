@@ -14,7 +14,7 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
            "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
            "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
-           "check_early_stop"]
+           "check_early_stop", "merge_positions", "merged_repeats"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -30,4 +30,7 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
     if name in ("EarlyStop", "check_early_stop"):  # exact early stop of a decided search
         from . import engine
         return getattr(engine, name)
+    if name in ("merge_positions", "merged_repeats"):  # position averaging of the training window
+        from . import merge
+        return getattr(merge, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

@@ -96,6 +96,10 @@ class TrainOwnAdam(C.Structure):      # bz_train_own_adam
                [(n, vp) for n in ("pw", "pb", "mw", "mb", "vw", "vb")]
 
 
+class MergeRows(C.Structure):         # bz_merge_rows: the columns of the rows going into / coming out of a merge
+    _fields_ = [(n, vp) for n in ("own", "opp", "pi", "z", "mover", "act", "game", "ply", "vt", "q", "kl")]
+
+
 _SIGS = {
     "bz_abi_version": (i32, []),
     "bz_last_error": (C.c_char_p, []),
@@ -206,6 +210,9 @@ _SIGS = {
     "bz_root_value": (i32, [vp, vp, i32, vp]),
     "bz_value_targets": (i32, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp]),
     "bz_value_targets_segment": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, vp]),
+    "bz_merge_group": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "bz_merge_workspace_bytes": (i64, [i64, i32]),
+    "bz_merge_positions": (i32, [C.POINTER(MergeRows), i64, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(MergeRows), vp, vp]),
     "bz_engine_ownership_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_set_ownership": (i32, [vp, vp, i64, vp]),
     "bz_engine_pack_ownership": (i32, [vp, vp, vp, i64, i32, vp]),

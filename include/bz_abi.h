@@ -723,6 +723,35 @@ int32_t bz_value_targets(const float* q, const int8_t* z, const int8_t* mover, c
                          float lam, float q_mix, float* vt, uint64_t* status_dev, void* stream);
 /* one segment, the function the kernel runs: q, z, mover, vt [T], T in 1 .. 1024.  Host only. */
 int32_t bz_value_targets_segment(const float* q, const int8_t* z, const int8_t* mover, int32_t T, float lam, float q_mix, float* vt);
+/* Position averaging (AlphaZero.jl's use_position_averaging): the rows of a window that share a position --
+ * exactly equal (own, opp) -- become one row with the mean pi, the mean value target and a count.  All sums are integer sums of
+ * fix_k(x) = (int64)(x * 2^k) (truncating; the product is exact in binary32): k = 32 for pi in [0, 1] and for the value input,
+ * q in [-1, 1]; k = 24 for kl in [0, 128].  The value input of a row is vt[i] when vt is given, else (float)z[i].  A group of n
+ * rows with sum S gives M = floor((2 S + n) / (2 n)) (integers: round half up, a true floor for negative S) and the result
+ * (float)((double)M * 2^-k).  n == 1: the row itself bit for bit, vt = its value input.  z = sign(the value sum).  A row holding
+ * a value that is NaN or outside its range adds to no sum and is counted; n stays the group's number of rows. */
+typedef struct bz_merge_rows {  /* the columns of n rows (input) or of the merged rows (output); q and kl may be NULL */
+    uint64_t* own; uint64_t* opp; float* pi; int8_t* z; int8_t* mover; uint8_t* act; int64_t* game; int32_t* ply;
+    float* vt;  /* input: NULL = the value input is (float)z; output: never NULL */
+    float* q; float* kl;
+} bz_merge_rows;
+/* one group, the function the kernels run: pi [n][na], z [n], vt / q / kl [n] or NULL; n in 1 .. 2^26, na 9 or 65.  *bad = the
+ * rows that were not summed.  Host only. */
+int32_t bz_merge_group(const float* pi, const float* vt, const int8_t* z, const float* q, const float* kl, int32_t n, int32_t na,
+                       float* pi_out, float* vt_out, int8_t* z_out, float* q_out, float* kl_out, int32_t* bad);
+/* bytes of bz_merge_positions' workspace: one row of na + 3 int64 sums per possible group, 256-byte aligned.  -1 for n outside
+ * 0 .. 2^26 or na not 9 / 65.  Needs no GPU. */
+int64_t bz_merge_workspace_bytes(int64_t n, int32_t na);
+/* Device only, asynchronous, nothing read back.  The caller has grouped the rows (two stable sorts make equal positions
+ * adjacent with the first occurrence in front): per sorted position i, order[i] = the row standing there, start[i] = the sorted
+ * position of the head of its run, dst[i] = the output row of its group (groups numbered by first occurrence in the input); per
+ * output row d < *n_groups (a device word), head[d] = the group's first row and count[d] = its rows.  Output row d gets the
+ * merged pi, vt, z (and q, kl when the input has them) and the head's own, opp, mover, act, game, ply.  *status_dev, a u64 word
+ * in device memory that the call zeroes first, counts the rows that were not summed (and the entries of order / dst outside
+ * 0 .. n-1, which are never followed).  n == 0: nothing is launched and no pointer is looked at. */
+int32_t bz_merge_positions(const bz_merge_rows* in, int64_t n, int32_t na, const int64_t* order, const int32_t* start,
+                           const int32_t* dst, const int64_t* head, const int32_t* count, const int64_t* n_groups, void* ws,
+                           int64_t ws_bytes, const bz_merge_rows* out, uint64_t* status_dev, void* stream);
 /* Ownership targets (KataGo, Wu 2019, section 5), opt-in per engine.  When a move of bz_engine_play ends a
  * game, the position that move produced is kept in absolute colours: fin_x = the stones of X (the side that moves with
  * to_move = +1), fin_o = O's, u64 [rounds][n_games] each, indexed like ex_len, in the engine's bit layout.  Valid iff

@@ -4,6 +4,8 @@
     self-play (PipelinedSelfPlay: two engines on two streams, bf16 MFMA net in the loop, Dirichlet root noise, temperature moves)
       -> example block -> 80 / 20 hold-out split of the new rows (the reference's split, SL/train.py:66-78)
       -> 8-fold D4 augmentation + exact dedupe of the training part on the device (augment_examples)
+      -> with --merge-positions: position averaging of the training window (merge_positions): the rows of one
+         position become one row with the mean pi and the mean value target
       -> policy cross-entropy + value MSE steps on the hand-written training kernels replayed as one HIP graph
          (GraphedTrainStep: stem, tower, heads, losses, every gradient and Adam as ten launches; --miopen-train /
          --eager-train / --fp32-train fall back to stock PyTorch autograd, run eagerly)
@@ -36,6 +38,7 @@ from betazero_amd.arena import play_arena  # noqa: E402
 from betazero_amd.augment import augment_examples  # noqa: E402
 from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig, PipelinedSelfPlay, PlayoutCap, Resign, check_forced_playouts,  # noqa: E402
                                  check_early_stop, check_fpu, check_playout_cap, check_resign, check_solver, concat_device_examples)
+from betazero_amd.merge import merge_positions, merged_repeats  # noqa: E402
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
 from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
@@ -145,6 +148,11 @@ def main():
                     "it would have (AlphaGo Zero's 10 %%): the false-positive rate is measured on them")
     ap.add_argument("--resign-fp-target", type=float, default=0.05, help="the false-positive rate the threshold is steered to stay "
                     "under (AlphaGo Zero's 5 %%)")
+    ap.add_argument("--merge-positions", action="store_true", help="position averaging (DESIGN.md 3.26; AlphaZero.jl): once per iteration "
+                    "the rows of the augmented training window that share a position become one row with the mean pi and the mean value "
+                    "target (the step then trains on float value targets); the held-out rows stay as they are.  Not with --ownership")
+    ap.add_argument("--merge-weight", choices=("constant", "log"), default="constant", help="under --merge-positions: how often a merged "
+                    "row of n rows stands in the list the batches are drawn from: once, or 1 + floor(log2 n) times (not with --surprise)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -162,6 +170,12 @@ def main():
         ap.error("--ownership needs the all-kernel training step")
     if args.resign_threshold is not None and args.ownership:
         ap.error("--resign-threshold does not combine with --ownership: a resigned game has no final board")
+    if args.merge_positions and args.ownership:
+        ap.error("--merge-positions does not combine with --ownership: the ownership targets are boards and have no mean")
+    if args.merge_weight != "constant" and not args.merge_positions:
+        ap.error("--merge-weight takes effect only with --merge-positions")
+    if args.merge_positions and args.merge_weight == "log" and args.surprise:
+        ap.error("--merge-weight log does not combine with --surprise: both repeat rows in the list the batches are drawn from")
     if not (0.0 <= args.resign_fp_target <= 1.0):
         ap.error("--resign-fp-target must be in [0, 1]")
     if not (0.0 <= args.own_weight < float("inf")):
@@ -170,13 +184,14 @@ def main():
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
     use_vt = args.value_lambda is not None or args.value_q_mix is not None
+    train_vt = use_vt or args.merge_positions   # merged rows carry float value targets
     v_lam, v_mix = 1.0 if args.value_lambda is None else args.value_lambda, 0.0 if args.value_q_mix is None else args.value_q_mix
     kernels = not (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256)
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
     own_head = OwnershipHead(args.channels) if args.ownership else None
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
-                                                                  value_targets=use_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
+                                                                  value_targets=train_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
                                                                   ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight)
     bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
@@ -253,6 +268,16 @@ def main():
         losses = []
         surprise = {}
         res = None
+        merge_info = {}
+        if args.merge_positions:  # once per iteration, over the window; the held-out rows stay unmerged
+            rows_before = len(data)
+            data, counts = merge_positions(data, return_counts=True)
+            steps = max(1, int(args.epochs * len(data) / args.batch))   # an epoch is a pass over the merged rows
+            if args.merge_weight == "log":
+                res = merged_repeats(counts, "log")
+            merge_info = {"merge": {"rows_before": rows_before, "rows_after": len(data), "largest_group": int(counts.max()),
+                                    "share_rows_in_groups": round(float(counts[counts > 1].sum()) / rows_before, 4),
+                                    "weight": args.merge_weight}}
         if args.surprise:  # once per iteration, over the window: row i stands count_i times in res
             res, counts = surprise_resample(data, args.surprise_uniform, seed=args.seed * 1000 + it, return_counts=True)
             surprise = {"surprise": {"mean_kl": round(float(data.kl.mean()), 5), "resampled_over_rows": round(len(res) / len(data), 4),
@@ -265,7 +290,7 @@ def main():
             if graphed is not None:
                 losses.append(graphed(data, idx))
             else:
-                losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train, value_targets=use_vt)))
+                losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train, value_targets=train_vt)))
         losses = torch.stack(losses).cpu().numpy()  # one transfer per iteration, after the last step
         if graphed is not None:
             graphed.check()                         # an out-of-range row index in any step of the iteration raises here
@@ -310,7 +335,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
-              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info, **resign_info,
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info, **resign_info, **merge_info,
               **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **({"solver": True} if solver else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               # the ownership loss L_own over the last (and the first) tenth of the steps
