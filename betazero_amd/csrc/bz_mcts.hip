@@ -25,6 +25,8 @@
 // The Gumbel interior rule below the root of a Gumbel search (k_gfull_step, csrc/bz_gumbel_interior.h) -- DESIGN.md 3.21.
 // Resignation in self-play (k_resign_note in front of the play kernel, k_resign_finish behind it, csrc/bz_resign.h) -- DESIGN.md 3.24.
 // Exact early stop of a search whose move is decided (k_stop_step / k_fpu_stop_step, csrc/bz_early_stop.h) -- DESIGN.md 3.25.
+// The replay seed: a carried slot's search starts from the played child's old subtree (k_replay_seed behind k_root_begin) and makes
+// its remaining walks in its own launches (k_pace_step, csrc/bz_pace.h) -- DESIGN.md 3.11.
 //
 // Float discipline: compiled with -ffp-contract=off; PUCT / softmax / backup use
 // the single-rounding operation order of the oracle (oracle/bz_oracle.c), so
@@ -44,6 +46,7 @@
 #include "bz_fpu.h"
 #include "bz_solver.h"
 #include "bz_early_stop.h"
+#include "bz_pace.h"
 #include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
 #include "bz_value.h"
@@ -108,7 +111,9 @@ struct __attribute__((aligned(64))) GameHot {
     // evaluation cache: this search's generation; a COPY leaf's source node (bit 31: it lives in the PREVIOUS search's arena)
     // and that node's first edge; the generation of the last search this slot took part in and how many nodes the
     // previous search's arena holds for it (0: nothing to carry over)
-    u32 tt_gen, copy_src, copy_e0, last_gen, prev_nodes, pad[1];
+    // replay seed: the simulations the slot's tree came with in this search (k_replay_seed; kPaceIdle: the slot
+    // has no search to run) -- written and read only when the search is paced
+    u32 tt_gen, copy_src, copy_e0, last_gen, prev_nodes, seeded;
 };
 constexpr u32 kSrcPrev = 1u << 31;
 static_assert(sizeof(GameHot) == 64, "layout");
@@ -299,13 +304,18 @@ enum : unsigned {
     // root's first kGW edges are the ones patched in registers, the others are loaded behind the group fence; the leader and the
     // "can still catch up" flag are two group reductions, skipped per game while early_stop_possible says the rule cannot fire.
     kModeStop = 1u << 7,
+    // kModePace (k_pace_step, DESIGN.md 3.11 "The replay seed"): a slot whose tree k_replay_seed filled with the first `seeded`
+    // simulations of its search walks only in the launches csrc/bz_pace.h gives its remaining ones, as simulation seeded + (walks
+    // made so far) instead of the launch index, and is left LEAF_NONE in the others; its root came expanded, so the root's net row
+    // is counted and nothing is written for it.  A slot with seeded = 0 walks in every launch: k_tree_step's search.
+    kModePace = 1u << 8,
 };
 // the mask's bits by name, and the combinations no code serves: the setters (bz_engine_set_*) refuse the same ones at run time
 template <unsigned M>
 struct Mode {
     static constexpr bool leaf = (M & kModeLeaf) != 0, gumbel = (M & kModeGumbel) != 0, cap = (M & kModeCap) != 0,
                           forced = (M & kModeForced) != 0, fpu = (M & kModeFpu) != 0, gfull = (M & kModeGfull) != 0,
-                          solve = (M & kModeSolve) != 0, stop = (M & kModeStop) != 0;
+                          solve = (M & kModeSolve) != 0, stop = (M & kModeStop) != 0, pace = (M & kModePace) != 0;
     static_assert(!gfull || gumbel, "search mode: the Gumbel interior rule needs Gumbel root search");
     static_assert(!gumbel || !(cap || forced || fpu || solve),
                   "search mode: Gumbel root search combines with none of playout cap, forced playouts, FPU reduction and the solver");
@@ -313,6 +323,7 @@ struct Mode {
     static_assert(!leaf || M == kModeLeaf, "search mode: leaf-parallel search combines with nothing");
     static_assert(!stop || !(leaf || gumbel || cap || forced || gfull || solve),
                   "search mode: early stop combines with FPU reduction and with nothing else");
+    static_assert(!pace || M == kModePace, "search mode: the paced step serves the plain search only");
 };
 // what the modes' kernels get beside EngineDev: each pointer is read only under its bit and stays null otherwise
 struct ModeArgs {
@@ -1380,7 +1391,7 @@ template <class T> __device__ __forceinline__ void pin(T& x) { asm volatile("" :
 template <class G, unsigned M>
 __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArgs& A, int do_expand, int do_select, u32 sim_idx) {
     constexpr bool kGumbel = Mode<M>::gumbel, kCap = Mode<M>::cap, kForced = Mode<M>::forced, kFpu = Mode<M>::fpu, kGfull = Mode<M>::gfull,
-                   kSolve = Mode<M>::solve, kStop = Mode<M>::stop;
+                   kSolve = Mode<M>::solve, kStop = Mode<M>::stop, kPace = Mode<M>::pace;
     static_assert(!Mode<M>::leaf, "search mode: the leaf-parallel step is k_leaf_step's own body");
     constexpr int kGW = G::GW;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1421,11 +1432,25 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
         const bool active = state == 0 && kind != LEAF_NONE;
         // a slot at its budget expands and backs up its last leaf below, selects nothing and is left LEAF_NONE: idle from then on
         bool walk = kCap ? (active && sim_idx < bud) : active;
+        [[maybe_unused]] u32 my_sim = sim_idx;  // kPace: the slot's own simulation number
+        [[maybe_unused]] bool seeded_root = false;
+        if constexpr (kPace) {  // a launch the slot skipped left it LEAF_NONE: whether it walks is the schedule's word, not the leaf's
+            const u32 sd = hot.seeded, r = sd == kPaceIdle ? 0u : (u32)E.sims - sd;
+            walk = state == 0 && pace_walks(sim_idx, r, (u32)E.sims);
+            my_sim = sd + pace_done(sim_idx, r, (u32)E.sims);
+            seeded_root = sd != 0u && leaf == 0u;
+        }
         st.mark(0);
         if (do_expand && (kind == LEAF_EVAL || kind == LEAF_TERMINAL || kind == LEAF_COPY)) {
             float v;
             u32 e0 = ne; int n = 0;
-            if (kind == LEAF_EVAL) {  // ---- round trip 2: the evaluator's row
+            if (kPace && kind == LEAF_EVAL && seeded_root) {  // the seed expanded this root: its row is counted, its tree stays
+                v = E.value[row];
+                if (sub == 0) {
+                    if (!(v >= -3.0e38f && v <= 3.0e38f)) atomicOr(&E.flags[FLAG_ERR], ERR_EVAL_NONFINITE);
+                    c.v[CNT_NET_LEAVES]++;
+                }
+            } else if (kind == LEAF_EVAL) {  // ---- round trip 2: the evaluator's row
                 LogitSrc ls; ls.kind = BZ_EVAL_EXTERNAL; ls.h = 0; ls.row = E.logits + (size_t)row * G::NA;
                 v = E.value[row];
                 if (sub == 0 && !(v >= -3.0e38f && v <= 3.0e38f)) atomicOr(&E.flags[FLAG_ERR], ERR_EVAL_NONFINITE);
@@ -1511,7 +1536,7 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
                 u32 leaf2; int k2, depth; float tv;
                 LeafPos lpos; lpos.own = 0; lpos.opp = 0; lpos.legal = 0; lpos.info = 0; lpos.src = 0; lpos.src_e0 = 0;
                 RootRef root; root.own = rown; root.opp = ropp; root.tm = rtm; root.n = root_n;
-                root.sumN = sim_idx + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
+                root.sumN = (kPace ? my_sim : sim_idx) + root_base; root.has_pre = pre_ok; root.pre = re0; root.tt_gen = hot.tt_gen; root.prev_nodes = hot.prev_nodes;
                 PathHbm<kGW> sink; sink.p = path; sink.mine.eidx = 0; sink.mine.w0 = 0; sink.mine.W = 0.0f; sink.mine.pad = 0;
                 const float fslot = (kForced && (!kCap || bud >= (u32)E.sims)) ? A.fo->k : 0.0f;
                 dev_select<G, M>(E, g, sub, root, nn, leaf2, k2, depth, tv, c, sink, lpos, st, A, fslot, kFpu ? rw : 0.0f);  // ---- one round trip per level
@@ -1556,6 +1581,12 @@ __device__ __forceinline__ void tree_step_body(const EngineDev& E, const ModeArg
 template <class G>
 __global__ void __launch_bounds__(256) k_tree_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
     tree_step_body<G, 0u>(E, ModeArgs{}, do_expand, do_select, sim_idx);
+}
+
+// The tree step of a paced search ("The replay seed"): k_tree_step, every slot walking in its own launches.
+template <class G>
+__global__ void __launch_bounds__(256) k_pace_step(EngineDev E, int do_expand, int do_select, u32 sim_idx) {
+    tree_step_body<G, kModePace>(E, ModeArgs{}, do_expand, do_select, sim_idx);
 }
 
 // The tree step of a Gumbel search: k_tree_step with the Gumbel root rule.  The root's statistics are read
@@ -2638,6 +2669,7 @@ struct StoreDev {
     Node* nodes; Edge* edges; float* node_v; u64* tt;  // [S][ncap], [S][ecap], [S][ncap], [S][tt_buckets * 16]
 };
 constexpr int kCntSeededEvals = 11, kCntSeededSearches = 12, kCntStoreSaves = 13;  // counters[] words, written like kCntCollisions
+constexpr int kCntReplaySeeds = 14, kCntReplaySims = 15;  // the replay seed's: searches it seeded, simulations they came with
 
 __device__ __forceinline__ u32 store_home(const StoreDev& St, u64 own, u64 opp) { return (u32)(hash_pos(own, opp) >> 20) & (u32)(St.n_idx - 1); }
 // the entry holding (own, opp) under `epoch`, or -1; *at: the index word the probe stopped at (an empty one on a miss)
@@ -2818,6 +2850,167 @@ __global__ void __launch_bounds__(256) k_store_seed(EngineDev E, StoreDev St, u3
     }
 }
 
+// ---- The replay seed.  A fresh search from the child the slot just played re-creates that child's old subtree
+// node for node -- deterministic PUCT on evaluations the carry-over hands back -- for the first N_e - 1 simulations, N_e the
+// visits of the edge into it.  Behind k_root_begin, block g (one lane group) copies that subtree from the previous arena into
+// the new tree instead: nodes and edge blocks compacted in their old creation order (the order the replay would create and
+// expand them in), N / W / P / node_v as they stand, child links rewritten; then it replays the evaluation cache's part --
+// tt_lookup_insert for every copied non-terminal node in creation order, the very calls the replay makes -- so that the table,
+// n_nodes, n_edges and the work counters are what N_e - 1 simulations would have left.  The slot then has seeded = N_e - 1.
+// Nothing is seeded -- the search runs as it always did -- when the new root is not found behind an edge of the old root (a
+// restarted slot, other roots), when the carry-over is refused or the previous arena holds a tree the root store put there, when
+// the previous search was not a plain one (do_seed = 0), or when a lookup of the replay would have missed (a full bucket): the
+// replay would have sent that leaf through the net, which a copy cannot; the table entries written so far are taken out again.
+// LDS, per node of the previous tree: {new id 13 | new first edge 19} (first: its edge count), its parent, and the old id by new id.
+template <class G>
+__global__ void __launch_bounds__(G::GW) k_replay_seed(EngineDev E, u32 gen, int do_seed, const u32* store_mark) {
+    constexpr int kGW = G::GW;
+    constexpr u32 kNone = 0xFFFFu;
+    extern __shared__ u32 s_map[];
+    uint16_t* s_par = reinterpret_cast<uint16_t*>(s_map + E.ncap);
+    uint16_t* s_ord = s_par + E.ncap;
+    const int g = blockIdx.x, sub = threadIdx.x;
+    GameHot* hot = E.hot + g;
+    const bool searching = E.g_state[g] == 0 && E.leaf_kind[g] == LEAF_EVAL;
+    const u32 pn = hot->prev_nodes;
+    u32 cand = ~0u;  // (visits of the edge into it << 13) | the previous tree's node that holds the new root's position
+    const Node* sn = E.nodes_alt + (size_t)g * E.ncap;
+    const Edge* se = E.edges_alt + (size_t)g * E.ecap;
+    if (do_seed && searching && pn > 1u && pn <= (u32)E.ncap && !(store_mark && store_mark[g] == tt_gen_before(gen))) {
+        const u64 rown = E.g_own[g], ropp = E.g_opp[g];
+        const Node oroot = sn[0];
+        const u32 n0 = ((oroot.info & kTerm) || oroot.edge0 + (oroot.info & 0xFFu) > (u32)E.ecap) ? 0u : (oroot.info & 0xFFu);
+        for (u32 i = sub; i < n0; i += kGW) {
+            const Edge e = se[oroot.edge0 + i];
+            u32 ch = e_child(e.w3), N = e_N(e.w0);
+            if (!ch || ch >= pn || e_decided(e.w0)) continue;
+            const Node* cn = sn + ch;
+            if (cn->legal == 0 && (cn->info & 0xFFu) == 1u && cn->edge0 < (u32)E.ecap) {  // the driver skips a forced pass: the root lies behind the pass edge
+                const Edge pe = se[cn->edge0];
+                ch = e_child(pe.w3); N = e_N(pe.w0);
+                if (!ch || ch >= pn || e_decided(pe.w0)) continue;
+                cn = sn + ch;
+            }
+            const u32 ci = cn->info;
+            if (cn->own == rown && cn->opp == ropp && !(ci & kTerm) && (ci & 0xFFu) != 0u && N >= 2u) cand = ch | (N << kChildBits);
+        }
+    }
+    cand = group_min_u32<kGW>(cand);
+    if (cand == ~0u) {  // (the same in every lane)
+        if (sub == 0) hot->seeded = searching ? 0u : kPaceIdle;
+        return;
+    }
+    const u32 r_old = cand & kChildMask, seeded = (cand >> kChildBits) - 1u;
+    // ---- every node's edge count and parent, lanes over the nodes behind r_old (a child is younger than its parent)
+    for (u32 i = r_old + sub; i < pn; i += kGW) s_par[i] = (uint16_t)kNone;
+    __syncthreads();
+    for (u32 i = r_old + sub; i < pn; i += kGW) {
+        const Node nd = sn[i];
+        const u32 n = ((nd.info & kTerm) || nd.edge0 + (nd.info & 0xFFu) > (u32)E.ecap) ? 0u : (nd.info & 0xFFu);
+        s_map[i] = n;
+        for (u32 j = 0; j < n; ++j) {
+            const u32 ch = e_child(se[nd.edge0 + j].w3);
+            if (ch > i && ch < pn) s_par[ch] = (uint16_t)i;
+        }
+    }
+    __syncthreads();
+    // ---- the subtree in creation order: new ids and first edges (every lane runs the same sweep on the same words)
+    u32 nT = 0, eT = 0;
+    for (u32 i = r_old; i < pn; ++i) {
+        const u32 p = s_par[i], n = s_map[i];
+        const bool in = i == r_old || (p != kNone && s_map[p] != ~0u);
+        if (in) {
+            s_map[i] = nT | (eT << kChildBits);
+            s_ord[nT] = (uint16_t)i;
+            ++nT; eT += n;
+        } else {
+            s_map[i] = ~0u;
+        }
+    }
+    __syncthreads();
+    if (eT > (u32)E.ecap) {  // (never, for a tree a search built: the subtree's edges are a subset of the old tree's)
+        if (sub == 0) hot->seeded = 0u;
+        return;
+    }
+    // ---- the copy, lanes over the nodes; what the replay's walks would have counted, from N and the child counts
+    Node* dn = E.nodes + (size_t)g * E.ncap;
+    Edge* de = E.edges + (size_t)g * E.ecap;
+    const float* sv = E.node_v_alt + (size_t)g * E.ncap;
+    float* dv = E.node_v + (size_t)g * E.ncap;
+    u32 c_vis = 0, c_scored = 0, c_exp = 0, c_written = 0, root_sum = 0;
+    for (u32 k = sub; k < nT; k += kGW) {
+        const u32 i = s_ord[k];
+        const Node nd = sn[i];
+        const u32 e0n = s_map[i] >> kChildBits;
+        const u32 n = ((nd.info & kTerm) || nd.edge0 + (nd.info & 0xFFu) > (u32)E.ecap) ? 0u : (nd.info & 0xFFu);  // (as counted above)
+        u32 sumN = 0;
+        for (u32 j = 0; j < n; ++j) {
+            Edge e = se[nd.edge0 + j];
+            const u32 ch = e_child(e.w3);
+            if (ch) {  // (first edge: only an expanded child's edge word has one)
+                const u32 mc = ch < pn ? s_map[ch] : 0u;
+                e.w3 = e_nch(e.w0) ? mc : (mc & kChildMask);
+            }
+            sumN += e_N(e.w0);
+            de[e0n + j] = e;
+        }
+        dv[k] = sv[i];
+        if (k != 0u) {
+            Node out;
+            out.own = nd.own; out.opp = nd.opp; out.legal = nd.legal; out.edge0 = n ? e0n : 0u; out.info = nd.info;
+            dn[k] = out;
+        } else {
+            root_sum = sumN;
+        }
+        c_vis += sumN; c_scored += n * sumN; c_exp += n ? 1u : 0u; c_written += n;
+    }
+    root_sum = group_sum_u32<kGW>(root_sum);
+    group_fence();  // the nodes written above are what the lookups below confirm this search's entries against
+    // ---- the evaluation cache's part of the replay: one lookup per created non-terminal node, in creation order
+    u32 hits = 0, hits_prev = 0;
+    bool exact = root_sum == seeded;
+    for (u32 k = 1; exact && k < nT; ++k) {
+        const Node nd = sn[s_ord[k]];  // (one address for the whole group)
+        if (nd.info & kTerm) continue;
+        u32 src = 0, src_e0 = 0;
+        if (tt_lookup_insert<kGW>(E, g, sub, nd.own, nd.opp, gen, pn, k, src, src_e0)) { ++hits; hits_prev += (src & kSrcPrev) ? 1u : 0u; }
+        else exact = false;
+    }
+    if (!exact) {  // not a pure copy phase: no seed, and no trace of it in the table
+        u64* tt = E.tt + (size_t)g * (size_t)E.tt_buckets * 16;
+        for (u32 k = sub; k < (u32)E.tt_buckets * 16u; k += kGW)
+            if (((u32)(tt[k] >> 32) >> kChildBits) == gen) tt[k] = 0ULL;
+        if (sub == 0) hot->seeded = 0u;
+        return;
+    }
+    c_vis = group_sum_u32<kGW>(c_vis); c_scored = group_sum_u32<kGW>(c_scored);
+    c_exp = group_sum_u32<kGW>(c_exp); c_written = group_sum_u32<kGW>(c_written);
+    if (sub == 0) {
+        const u32 rn = sn[r_old].info & 0xFFu;  // (the rest of node 0 is k_root_begin's: the position, the legal mask, the mover)
+        dn[0].edge0 = 0; dn[0].info = (dn[0].info & ~0xFFu) | rn;
+        hot->n_nodes = nT; hot->n_edges = eT; hot->root_n = rn; hot->seeded = seeded;
+        atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntReplaySeeds, 1ULL);
+        atomicAdd(reinterpret_cast<unsigned long long*>(E.counters) + kCntReplaySims, (unsigned long long)seeded);
+    }
+    // the work counters, into the slot's wave's row of the per-wave slots (lane k: counter k)
+    u32 add = 0;
+    switch (sub) {
+    case CNT_SIMS: add = seeded; break;
+    case CNT_PATH_NODES: add = seeded + c_vis; break;
+    case CNT_CHILD_SCORED: add = c_scored; break;
+    case CNT_EDGES_BACKED: add = c_vis; break;
+    case CNT_EXPANDED: add = c_exp; break;
+    case CNT_CHILD_WRITTEN: add = c_written; break;
+    case CNT_ENV_STEPS: add = nT - 1u; break;
+    case CNT_CACHE_HITS: add = hits; break;
+    case CNT_CACHE_HITS_PREV: add = hits_prev; break;
+    default: break;
+    }
+    if (add)
+        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(E.cnt_slots) + (size_t)(g % E.n_cnt_slots) * CNT_N + sub,
+                               (unsigned long long)add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2858,6 +3051,13 @@ struct bz_engine {
     // and two match players share one bz_net
     int sym_on;
     uint64_t sym_seed;
+    // the replay seed (bz_engine_set_replay_seed): the switch (0 off, 1 on, 2 = the default: on where the engine
+    // has more than kPaceAutoSlots slots); whether the search under way is
+    // paced (engines_run / bz_engine_search set it behind bz_engine_root_begin, which clears it: the step API is never paced);
+    // whether the last search run to its end was a whole paced one -- the only trees the seed copies from -- and the same of the
+    // search before the one bz_engine_root_begin has just begun (it moves the one word into the other: a search begun through the
+    // step API leaves nothing to seed from)
+    int replay_seed, paced, seed_from_prev, seed_src;
 };
 
 namespace {
@@ -2994,6 +3194,7 @@ BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t b
     if (!e) { set_error("out of host memory"); return BZ_ENOMEM; }
     e->cfg = *cfg; e->net = nullptr; e->mlp = nullptr; e->bytes = o.total; e->pack_parity = 1; e->n_ahead = 0; e->search_seq = 0; e->eval_epoch = 0;
     e->sym_on = 0; e->sym_seed = 0;
+    e->replay_seed = 2; e->paced = 0; e->seed_from_prev = 0; e->seed_src = 0;
     e->gumbel = GumbelDev{};  // off
     e->gin = GumbelInDev{};
     e->cap = CapDev{};
@@ -3105,6 +3306,28 @@ BZ_EXPORT int32_t bz_engine_set_eval_symmetry(bz_engine* e, int32_t on, uint64_t
     return BZ_OK;
 }
 
+/* The replay seed: mode 1 -> a plain search with the carry-over starts every slot from the played child's old
+ * subtree and paces its remaining walks over the move's launches; 0 -> every search is stepped as before; 2 (the default) -> 1 for
+ * an engine of more than 1024 slots, where levelling the launches pays, else 0.  No result and no counter depends on the setting.
+ * Takes effect with the next search. */
+BZ_EXPORT int32_t bz_engine_set_replay_seed(bz_engine* e, int32_t mode) {
+    BZ_REQUIRE(e && mode >= 0 && mode <= 2, "bz_engine_set_replay_seed: null engine, or mode not 0 (off), 1 (on) or 2 (by the engine's size)");
+    e->replay_seed = mode;
+    return BZ_OK;
+}
+
+/* the pacing rule of a replay-seeded slot (csrc/bz_pace.h, the code k_pace_step runs) over the launches 0 .. sims - 1 of a move, for
+ * a slot with r <= sims walks left: walk[L] = 1 iff the slot walks in launch L, done[L] = the walks it made before launch L */
+BZ_EXPORT int32_t bz_pace_walk(int32_t sims, int32_t r, uint8_t* walk, uint32_t* done) {
+    BZ_REQUIRE(walk && done && sims >= 1 && sims <= BZ_ENGINE_MAX_SIMS && r >= 0 && r <= sims,
+               "bz_pace_walk: null pointer, sims outside 1 .. 8189 or r outside 0 .. sims");
+    for (int32_t L = 0; L < sims; ++L) {
+        walk[L] = pace_walks((u32)L, (u32)r, (u32)sims) ? 1 : 0;
+        done[L] = pace_done((u32)L, (u32)r, (u32)sims);
+    }
+    return BZ_OK;
+}
+
 /* test hook: the number of searches begun so far, as the evaluation cache counts them (its generation stamp cycles through
  * 1 .. 2^19 - 2).  Lets a test start an engine just below the wrap instead of running half a million searches. */
 BZ_EXPORT int32_t bz_engine_debug_set_search_seq(bz_engine* e, uint32_t seq) {
@@ -3176,6 +3399,8 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     }
     e->pack_parity = 1;
     e->fpu_done = 0;
+    e->paced = 0;  // (paced_search, behind this call, says otherwise)
+    e->seed_src = e->seed_from_prev; e->seed_from_prev = 0;
     if (e->solve.root)  //  no root is decided, both counts 0
         BZ_HIP(hipMemsetAsync(e->solve.root, 0, (size_t)e->solve_bytes, (hipStream_t)stream));
     if (e->stop.stop_at) {  //  every slot with a root: its whole budget; the others: 0; no step has walked
@@ -3197,12 +3422,13 @@ static const u32* cap_budgets(const bz_engine* e) { return e->cap.fast > 0 ? sta
 
 static int32_t tree_step(bz_engine* e, int do_expand, int do_select, uint32_t sim_idx, void* stream) {
     ProfScope ps(do_select ? BZ_PROF_SELECT : BZ_PROF_EXPAND_BACKUP, stream);
-    const unsigned m = engine_mode(e);
+    const unsigned m = engine_mode(e) | (e->paced ? kModePace : 0u);  // (paced_search: only the plain mode is ever paced)
     //  the FPU kernels take sim_idx = simulations backed up after this step, on an expand-only step too
     if ((m & kModeFpu) && !do_select) sim_idx = (uint32_t)e->fpu_done;
 #define BZ_STEP(KERNEL, ...) BZ_DISPATCH_G(e, KERNEL, stream, __VA_ARGS__, do_expand, do_select, sim_idx); break
     switch (m) {
     case 0u: BZ_STEP(k_tree_step, e->dev);
+    case kModePace: BZ_STEP(k_pace_step, e->dev);  // 
     case kModeLeaf: BZ_STEP(k_leaf_step, e->dev);  // 
     case kModeGumbel: BZ_STEP(k_gumbel_step, e->dev, e->gumbel);  // 
     case kModeGumbel | kModeGfull: BZ_STEP(k_gfull_step, e->dev, e->gumbel, e->gin);  // 
@@ -3297,6 +3523,34 @@ static bool search_is_fused(const bz_engine* e) {
     return (ek == BZ_EVAL_UNIFORM || ek == BZ_EVAL_HASH) && !e->dev.reuse && !root_prep(e) && engine_mode(e) == 0u;
 }
 
+// ("The replay seed") behind bz_engine_root_begin of a search this file drives from its first step to its last:
+// where the carry-over is on and the search is otherwise plain, the search is paced -- k_replay_seed gives every slot its seeded
+// count (0 where nothing can be seeded: always, when the previous search was not such a search itself) and the steps are
+// k_pace_step's.  Everything else runs as it always did.
+// Levelling pays where a launch's time follows its rows.  The tower's throughput shape holds 4 positions per workgroup on 256 CUs:
+// a pipeline of up to 1024 slots finishes ANY of its launches in one round of workgroups, a levelled launch costs it what a dense
+// one does, and all the pacing does is trade the ~100 cheap latency-shape launches at the head of a move for full-price ones
+// (measured: 2 x 1024 slots -2.2 %, 2 x 512 slots -8.6 % games per second, 2 x 2048 +1.8 %).
+constexpr int kPaceAutoSlots = 1024;
+static int32_t paced_search(bz_engine* e, void* stream) {
+    const int from_prev = e->seed_src;
+    const bool plain = engine_mode(e) == 0u && !(e->dev.dir_eps > 0.0f) && !e->dev.reuse && !e->sym_on && e->dev.ecache == 2 &&
+                       net_eval(e->cfg.eval_kind) && e->cfg.game != BZ_GAME_TTT && e->dev.compact;
+    if (!plain || e->replay_seed == 0 || (e->replay_seed == 2 && e->dev.B <= kPaceAutoSlots)) return BZ_OK;
+    const size_t lds = (size_t)e->dev.ncap * 8;  // (ncap <= 8191: below the 64 KiB a block gets without asking)
+    const u32* mark = e->store.S > 0 ? e->store.mark : nullptr;
+#define BZ_SEED(G) hipLaunchKernelGGL(k_replay_seed<G>, dim3(e->dev.B), dim3(G::GW), lds, (hipStream_t)stream, e->dev, e->search_seq, from_prev, mark)
+    switch (e->cfg.game) {
+    case BZ_GAME_REVERSI6: BZ_SEED(Reversi6); break;
+    case BZ_GAME_REVERSI4: BZ_SEED(Reversi4); break;
+    default: BZ_SEED(Reversi); break;
+    }
+#undef BZ_SEED
+    BZ_LAUNCH_CHECK("k_replay_seed");
+    e->paced = 1;
+    return BZ_OK;
+}
+
 //  behind the last tree step of a stepwise search: the finished trees of early roots go to the root store
 static int32_t store_save(bz_engine* e, void* stream) {
     if (e->store.S == 0) return BZ_OK;
@@ -3336,6 +3590,7 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
     BZ_REQUIRE(ek != BZ_EVAL_EXTERNAL, "bz_engine_search: BZ_EVAL_EXTERNAL callers drive the step API");
     int32_t rc;
     if ((rc = bz_engine_root_begin(e, stream)) != BZ_OK) return rc;
+    if ((rc = paced_search(e, stream)) != BZ_OK) return rc;
     if ((rc = bz_engine_evaluate(e, stream)) != BZ_OK) return rc;
     if (noise) {  // expand the roots on their own, then draw the noise, then start selecting
         if ((rc = tree_step(e, 1, 0, 0, stream)) != BZ_OK) return rc;
@@ -3347,6 +3602,7 @@ BZ_EXPORT int32_t bz_engine_search(bz_engine* e, void* stream) {
         if ((rc = bz_engine_evaluate(e, stream)) != BZ_OK) return rc;
     }
     if ((rc = tree_step(e, 1, 0, 0, stream)) != BZ_OK) return rc;
+    e->seed_from_prev = e->paced;
     return store_save(e, stream);
 }
 
@@ -4224,6 +4480,7 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
         steps = ns > steps ? ns : steps;
         Kmax = e->dev.K > Kmax ? e->dev.K : Kmax;
         if ((rc = bz_engine_root_begin(e, streams[i])) != BZ_OK) return rc;
+        if ((rc = paced_search(e, streams[i])) != BZ_OK) return rc;
         if ((rc = bz_engine_evaluate(e, streams[i])) != BZ_OK) return rc;
         if (root_prep(e)) {
             if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
@@ -4276,6 +4533,7 @@ static int32_t engines_run(bz_engine* const* engines, void* const* streams, int 
         bz_engine* e = engines[i];
         if (!e || search_is_fused(e)) continue;
         if ((rc = tree_step(e, 1, 0, 0, streams[i])) != BZ_OK) return rc;
+        e->seed_from_prev = e->paced;
         if ((rc = store_save(e, streams[i])) != BZ_OK) return rc;
         if (play && (rc = bz_engine_play(e, restart, streams[i])) != BZ_OK) return rc;
     }

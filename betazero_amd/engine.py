@@ -195,6 +195,15 @@ def check_root_store(root_store, eval_cache=True):
 MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
 
 
+def check_replay_seed(replay_seed):
+    """None (by the engine's size), True or False; anything else is refused (ValueError, before any device is touched)"""
+    if replay_seed is None:
+        return None
+    if not isinstance(replay_seed, (bool, np.bool_)):
+        raise ValueError(f"replay_seed must be None, True or False (got {replay_seed!r})")
+    return bool(replay_seed)
+
+
 @dataclass(frozen=True)
 class GumbelConfig:
     """Gumbel root search (Danihelka et al., ICLR 2022).  The defaults are those of mctx's
@@ -490,7 +499,8 @@ class SelfPlayEngine:
                  seed=0, rounds=1, game_id_base=0, game_id_stride=None, device="cuda:0", stagger=0,
                  dirichlet_alpha=0.0, dirichlet_eps=0.0, reuse_subtree=False, ttt_lanes=0, eval_cache=True,
                  leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None, surprise=False, search_value=False,
-                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False, resign=None, early_stop=None):
+                 eval_symmetry=None, fpu=None, ownership=False, root_store=None, solver=False, resign=None, early_stop=None,
+                 replay_seed=None):
         """eval_cache (BZ_ENGINE_EVAL_CACHE, bz_abi.h): with a net evaluator, a leaf whose position was evaluated earlier in
         the same search shares that evaluation instead of running the net again; True / "carry" (the default) also takes
         evaluations from the slot's PREVIOUS search (BZ_ENGINE_EVAL_CACHE_CARRY: after a move, the played child's old subtree
@@ -577,7 +587,15 @@ class SelfPlayEngine:
         changes it between searches.  Meant for matches and players, not for training games.  Combines with fpu, eval_symmetry,
         Dirichlet noise, temp_moves, every evaluator and eval_cache mode; with it on, root_store=None means no root store.
         Refused with reuse_subtree, leaves_per_step > 1, gumbel, playout_cap, forced_playouts, solver, a root store, surprise,
-        search_value, ownership and resign."""
+        search_value, ownership and resign.
+
+        replay_seed: True = where the carry-over cache is on and the search is otherwise plain (no other search
+        option, no noise, no reuse_subtree, no eval_symmetry), a slot's search starts from a copy of the played child's old
+        subtree -- what its first N_e - 1 simulations would rebuild -- and spreads its remaining walks evenly over the move's tree
+        steps; False = every search is stepped simulation by simulation; None (the default) = True for an engine of more than
+        1024 games, where level launches pay, else False.  No result and no counter depends on it; everywhere else it is
+        ignored.  set_replay_seed() changes it between searches."""
+        self.replay_seed = check_replay_seed(replay_seed)
         if early_stop is not None and early_stop is not False and root_store is None:
             root_store = False  # (a shortened tree is not worth an entry and must not seed a later search)
         self.root_store = check_root_store(root_store, eval_cache)
@@ -635,6 +653,8 @@ class SelfPlayEngine:
                 _lib.check(L.bz_engine_set_mlp(self.h, net.h))
             else:
                 _lib.check(L.bz_engine_set_net(self.h, net.h))
+        if self.replay_seed is not None:
+            _lib.check(L.bz_engine_set_replay_seed(self.h, int(self.replay_seed)))
         if self.gumbel is not None:  # the engine's Gumbel buffer (caller-owned, like the workspace)
             gc = self.gumbel
             gbytes = L.bz_engine_gumbel_bytes(C.byref(self.cfg), gc.max_considered)
@@ -995,6 +1015,19 @@ class SelfPlayEngine:
         # what it was before leaves_per_step existed
         names = _lib.COUNTER_NAMES if self.K > 1 else _lib.COUNTER_NAMES[:_lib.COUNTER_NAMES.index("n_collisions")]
         return dict(zip(names, (int(v) for v in c[:len(names)])))
+
+    def set_replay_seed(self, on=None):
+        """the replay seed on (True), off (False) or by the engine's size (None) from the next search on; results
+        and counters do not depend on it"""
+        self.replay_seed = check_replay_seed(on)
+        _lib.check(_lib.lib().bz_engine_set_replay_seed(self.h, 2 if self.replay_seed is None else int(self.replay_seed)))
+
+    def replay_seed_counters(self):
+        """the replay seed's counters: n_replay_seeds -- searches of a slot that began from the played child's old
+        subtree --, n_replay_sims -- the simulations those subtrees stood for, each one a tree step the slot then sat out"""
+        self._call(_lib.lib().bz_engine_sum_counters)
+        c = self._view(self.lay.counters, torch.int64, (24,)).cpu().numpy()
+        return {"n_replay_seeds": int(c[14]), "n_replay_sims": int(c[15])}
 
     def root_store_counters(self):
         """the root store's counters: n_seeded_evals -- evaluations taken from a seeded tree (part of
@@ -1521,6 +1554,13 @@ class PipelinedSelfPlay:
         """the last search's budgets of all pipelines, in slot order (SelfPlayEngine.budgets)"""
         self.sync()
         return np.concatenate([e.budgets() for e in self.engines])
+
+    def replay_seed_counters(self):
+        tot = {}
+        for c in self._each(lambda e: e.replay_seed_counters()):
+            for k, v in c.items():
+                tot[k] = tot.get(k, 0) + v
+        return tot
 
     def root_store_counters(self):
         tot = {}

@@ -643,6 +643,18 @@ int32_t bz_engine_stopped(bz_engine* e, uint32_t* out, void* stream);
 /* the rule: N [n] the root edges' visits (each < 2^24) in ascending action order, n in 1 .. 255, left the simulations to go;
  * returns 1 (decided) or 0; -1 for bad arguments.  Host only. */
 int32_t bz_early_stop_decided(const uint32_t* N, int32_t n, uint32_t left);
+
+/* ---- The replay seed.  After a move the new root is a child of the old one, and a fresh search from it
+ * re-creates that child's old subtree node for node for its first N_e - 1 simulations (N_e = the played edge's visits).  Where the
+ * carry-over is on and the search is otherwise plain (no other search mode, no noise, no subtree reuse, no evaluation symmetry;
+ * bz_engine_search / bz_engines_search / bz_engines_step), every such slot starts from a copy of that subtree instead and makes its
+ * remaining r = sims - (N_e - 1) walks in the launches bz_pace_walk names, so that the move's launches carry even row counts.
+ * No result and no counter changes.  bz_engine_set_replay_seed: mode 0 = off, 1 = on, 2 (the default) = on for an engine of more
+ * than 1024 slots -- below that a launch's time does not follow its rows and level launches cost more than they save.
+ * bz_pace_walk: walk[L] = 1 iff a slot with r walks left walks in launch L of 0 .. sims - 1, done[L] = its walks before launch L:
+ * floor((L + 1) r / sims) > floor(L r / sims), and floor(L r / sims). */
+int32_t bz_engine_set_replay_seed(bz_engine* e, int32_t mode);
+int32_t bz_pace_walk(int32_t sims, int32_t r, uint8_t* walk, uint32_t* done);
 /* Policy surprise weighting (KataGo, Wu 2019, section 3.3), opt-in per engine.  Every row bz_engine_play
  * records gets kl = sum over the root's edges in ascending action order with pi_a > 0 of pi_a * (logf(pi_a) - logf(max(P_a,
  * FLT_MIN))), every operation one binary32 operation, then kl > 0 ? kl : 0 (a rounding negative or a NaN: 0).

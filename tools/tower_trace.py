@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tower and tree-step duration by simulation index within a move, from a rocprofv3 --kernel-trace result database
 (rocpd SQLite) of a self-play bench run.  Per stream (queue), a k_root_begin dispatch starts a move; the n-th tower
-dispatch after it is the root evaluation (n = 0) or simulation n - 1, and so is the n-th k_tree_step.  The head of a
+dispatch after it is the root evaluation (n = 0) or simulation n - 1, and so is the n-th k_tree_step (k_pace_step).  The head of a
 move is where the evaluation cache serves nearly every leaf, so the tower launches there carry few rows.
 An empty (self-gated) tower launch is listed apart from the one that did the work: of the launches of one evaluation the
 longest is the worker.
@@ -19,7 +19,7 @@ key = next((k for k in ("stream_id", "queue_id", "queue", "stream", "tid") if k 
 rows = c.execute(f"select name, start, duration, {key or '0'} from kernels order by start").fetchall()
 print(f"# {len(rows)} dispatches; pipelines told apart by column {key!r}", file=out)
 
-TOWER = ("k_tower_bf16", "k_sym_bf16", "k_tower_fp8", "k_sym_fp8")
+TOWER = ("k_tower_bf16", "k_edge_bf16", "k_sym_bf16", "k_tower_fp8", "k_sym_fp8")
 state = {}  # stream -> [tower evaluations seen this move, tree steps seen this move, evaluation open?]
 tower, gate, tree, names = [], [], [], {}
 for name, start, dur, q in rows:
@@ -35,7 +35,7 @@ for name, start, dur, q in rows:
         else:                             # a second launch of the same evaluation: the shorter one only looked at the count
             gate.append((st[2][0], min(st[2][1], dur)))
             st[2][1] = max(st[2][1], dur)
-    elif "k_tree_step" in name:
+    elif "k_tree_step" in name or "k_pace_step" in name:  # (the paced step of a replay-seeded search)
         if st[2] is not None:
             tower.append(tuple(st[2]))
             st[2] = None
@@ -62,4 +62,4 @@ def table(title, seq):
 
 table("tower (index 0 = the root evaluation, n = simulation n - 1)", tower)
 table("empty tower launch of a gated pair", gate)
-table("k_tree_step", tree)
+table("k_tree_step / k_pace_step", tree)
