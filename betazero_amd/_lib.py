@@ -197,6 +197,8 @@ _SIGS = {
     "bz_engine_set_early_stop": (i32, [vp, i32, i32, vp, i64, vp]),
     "bz_engine_stopped": (i32, [vp, vp, vp]),
     "bz_early_stop_decided": (i32, [vp, i32, u32]),
+    "bz_option_conflict": (i32, [i32, i32]),
+    "bz_option_name": (C.c_char_p, [i32]),
     "bz_engine_set_replay_seed": (i32, [vp, i32]),
     "bz_pace_walk": (i32, [i32, i32, vp, vp]),
     "bz_engine_surprise_bytes": (i64, [C.POINTER(EngineCfg)]),

@@ -53,11 +53,11 @@ def play_arena(game, n_games, sims, opponent_depth=4, evaluator="uniform", net=N
     games are the games without it."""
     from .engine import check_early_stop, check_fpu, check_gumbel, check_leaves_per_step, check_solver
     from .symmetry import check_eval_symmetry
-    check_leaves_per_step(leaves_per_step)
-    solver = check_solver(solver, False, leaves_per_step, gumbel, None, fpu)
-    early_stop = check_early_stop(early_stop, False, leaves_per_step, gumbel, None, None, solver)
-    fpu = check_fpu(fpu, False, leaves_per_step, gumbel)
+    leaves_per_step = check_leaves_per_step(leaves_per_step)
     gumbel = check_gumbel(gumbel, leaves_per_step=leaves_per_step)
+    fpu = check_fpu(fpu, leaves_per_step=leaves_per_step, gumbel=gumbel)
+    solver = check_solver(solver, leaves_per_step=leaves_per_step, gumbel=gumbel, fpu=fpu)
+    early_stop = check_early_stop(early_stop, leaves_per_step=leaves_per_step, gumbel=gumbel, solver=solver)
     eval_symmetry = check_eval_symmetry(eval_symmetry, 0, "ttt" if game == "ttt" else "reversi", evaluator)
     if game != "ttt" and not 0 <= int(opponent_depth) <= 8:
         raise ValueError(f"play_arena: opponent_depth must be in 0..8 (got {opponent_depth}): the minimax kernel keeps an "

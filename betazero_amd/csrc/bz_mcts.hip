@@ -46,6 +46,7 @@
 #include "bz_fpu.h"
 #include "bz_solver.h"
 #include "bz_early_stop.h"
+#include "bz_options.h"
 #include "bz_pace.h"
 #include "bz_gumbel_interior.h"
 #include "bz_surprise.h"
@@ -263,66 +264,16 @@ constexpr uint8_t kStateResigned = 2;
 // kernel argument of the stop kernels only.
 struct StopDev { u32* stop_at; u32* walked; };
 
-// ---- The search mode: which rules the walk (dev_select), the tree step around it (tree_step_body) and the move (play_body, which
-// says what each bit does to the move) run under.  One bit per rule, one compile-time mask M per kernel; the host derives the same
-// mask from the engine (engine_mode) and switches over it.  With no bit set the code is k_tree_step's / k_play's exactly.
-enum : unsigned {
-    // kModeLeaf (k_leaf_step): K > 1 walks per game per step.  In the walk, a non-terminal child without edges was
-    // created by an earlier walk of this step and ends the walk as LEAF_COLLIDE; the evaluation cache is not consulted.
-    kModeLeaf = 1u << 0,
-    // kModeGumbel (k_gumbel_step): the root's edge is chosen by gumbel_root_pick instead of PUCT (every deeper
-    // level is PUCT), and v_root is stored with the root's expansion.
-    kModeGumbel = 1u << 1,
-    // kModeCap (k_cap_step): the walk runs only while sim_idx is below the slot's budget.
-    kModeCap = 1u << 2,
-    // kModeForced (k_forced_step / k_forced_cap_step): at the root an edge with 0 < N < fsqrt(fk P sumN) scores +inf
-    // (fk = 0: this slot does not force -- under kModeCap the full searches only force); every deeper level is PUCT.
-    kModeForced = 1u << 3,
-    // kModeFpu (k_fpu_*_step): at every level an edge with N == 0 takes q = the node's own value minus a reduction
-    // that grows with the prior mass of the node's visited edges, instead of 0.  The mass needs all of the node's edges before any
-    // is scored: its <= kCH chunks are loaded together into registers (still ONE dependent load per level), summed as integers
-    // across the group, then scored from the registers.  The root's running value sum Wr is loaded with the per-game words,
-    // advanced by what this step's backup adds to the path's root edge and stored beside it.  sim_idx is the number of simulations
-    // backed up once this step's backup is done (an expand-only step gets it from the host too): the backup of simulation 0 starts
-    // Wr from 0, so no search needs a reset.
-    kModeFpu = 1u << 4,
-    // kModeGfull (k_gfull_step; with kModeGumbel): every level below the root takes the edge whose visit share lags
-    // the node's improved policy softmax(logf(P~) + sigma(completed Q)) the most, in place of PUCT.  Like kModeFpu the node's <= kCH
-    // edge chunks are loaded together into registers, and the node's own value v_X (this game's row of the interior buffer) is
-    // loaded beside its position: still ONE dependent load per level.  Per-edge terms are computed one edge per lane; max / min are
-    // group reductions; the three sums run in ascending edge order (group_seq_sum), so the bits are those of gi_pick_serial.  Every
-    // expanded node's value is stored in the interior buffer with its expansion, on the EVAL and on the COPY path.
-    kModeGfull = 1u << 5,
-    // kModeSolve (k_solve_step / k_solve_cap_step; the plain PUCT branch of the walk only): a decided edge (terminal
-    // or proven) with c = -1 scores +inf, with c = +1 -inf, with c = 0 takes q = 0; when every edge scores -inf the walk takes edge
-    // 0; a walk that takes a decided edge ends there with the edge's value, as at a terminal edge.  The proof pass runs behind the
-    // backup of a terminal or proven leaf; the backup of an evaluated or copied leaf stays the pure-store path it is.
-    kModeSolve = 1u << 6,
-    // kModeStop (k_stop_step / k_fpu_stop_step): behind the backup of the step of simulation s, a slot whose move is
-    // decided (early_stop_decided over the root's visits, s done, sims - s to go) and not sampled (moves made >= temp_moves)
-    // records stop_at = s, selects nothing and is left LEAF_NONE: idle from then on, like a slot at its playout-cap budget.  The
-    // root's first kGW edges are the ones patched in registers, the others are loaded behind the group fence; the leader and the
-    // "can still catch up" flag are two group reductions, skipped per game while early_stop_possible says the rule cannot fire.
-    kModeStop = 1u << 7,
-    // kModePace (k_pace_step, DESIGN.md 3.11 "The replay seed"): a slot whose tree k_replay_seed filled with the first `seeded`
-    // simulations of its search walks only in the launches csrc/bz_pace.h gives its remaining ones, as simulation seeded + (walks
-    // made so far) instead of the launch index, and is left LEAF_NONE in the others; its root came expanded, so the root's net row
-    // is counted and nothing is written for it.  A slot with seeded = 0 walks in every launch: k_tree_step's search.
-    kModePace = 1u << 8,
-};
-// the mask's bits by name, and the combinations no code serves: the setters (bz_engine_set_*) refuse the same ones at run time
+// ---- The search mode (kMode*, csrc/bz_options.h): one compile-time mask M per kernel
+// the mask's bits by name, and the combinations no code serves: mode_served asks the table the setters (bz_engine_set_*) refuse
+// from at run time
 template <unsigned M>
 struct Mode {
     static constexpr bool leaf = (M & kModeLeaf) != 0, gumbel = (M & kModeGumbel) != 0, cap = (M & kModeCap) != 0,
                           forced = (M & kModeForced) != 0, fpu = (M & kModeFpu) != 0, gfull = (M & kModeGfull) != 0,
                           solve = (M & kModeSolve) != 0, stop = (M & kModeStop) != 0, pace = (M & kModePace) != 0;
     static_assert(!gfull || gumbel, "search mode: the Gumbel interior rule needs Gumbel root search");
-    static_assert(!gumbel || !(cap || forced || fpu || solve),
-                  "search mode: Gumbel root search combines with none of playout cap, forced playouts, FPU reduction and the solver");
-    static_assert(!solve || !(forced || fpu), "search mode: the solver combines with neither forced playouts nor FPU reduction");
-    static_assert(!leaf || M == kModeLeaf, "search mode: leaf-parallel search combines with nothing");
-    static_assert(!stop || !(leaf || gumbel || cap || forced || gfull || solve),
-                  "search mode: early stop combines with FPU reduction and with nothing else");
+    static_assert(mode_served(M), "search mode: two of its options are a refused pair (kConflicts, csrc/bz_options.h)");
     static_assert(!pace || M == kModePace, "search mode: the paced step serves the plain search only");
 };
 // what the modes' kernels get beside EngineDev: each pointer is read only under its bit and stays null otherwise
@@ -3173,19 +3124,68 @@ inline dim3 grid_lane(int B, int) { return grid_of(B); }
 #define BZ_DISPATCH(e, KERNEL, stream, ...) BZ_DISPATCH_IMPL(e, KERNEL, grid_lane, stream, __VA_ARGS__)
 #define BZ_DISPATCH_G(e, KERNEL, stream, ...) BZ_DISPATCH_IMPL(e, KERNEL, grid_groups, stream, __VA_ARGS__)
 
+namespace {
 const char* kBadCfg = "bad config (note: sims <= 8189, or <= 2045 with BZ_ENGINE_REUSE_SUBTREE -- the packed edge record, bz_abi.h)";
 const char* kBadFlags = "bad config: cfg.flags has bits set above bit 12 (the leaves-per-step field BZ_ENGINE_LEAVES_MASK ends there)";
+// the preface of every entry point that takes a config: false, and the message, for reserved flag bits or a bad config
+bool cfg_guard(const char* fn, const bz_engine_cfg* cfg) {
+    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("%s: %s", fn, kBadFlags); return false; }
+    if (!cfg_ok(cfg)) { set_error("%s: %s", fn, kBadCfg); return false; }
+    return true;
+}
+// the preface of every setter that takes a caller-owned buffer: BZ_OK, or the message and BZ_EINVAL for a null or misaligned
+// buffer, small_rc for one below `need` bytes
+int32_t option_buffer(const char* fn, const void* buf, int64_t bytes, int64_t need, int32_t small_rc = BZ_ENOMEM) {
+    if (!buf || (reinterpret_cast<uintptr_t>(buf) & 255)) { set_error("%s: the buffer must be non-null and 256-byte aligned", fn); return BZ_EINVAL; }
+    if (bytes < need) { set_error("%s: buffer too small (%lld < %lld)", fn, (long long)bytes, (long long)need); return small_rc; }
+    return BZ_OK;
+}
+// Whether a search option (BZ_OPT_*) is on: THE place that reads the config's option fields and the setters' state.
+bool option_on(const bz_engine_cfg& c, int opt) {
+    switch (opt) {
+    case BZ_OPT_REUSE_SUBTREE: return (c.flags & BZ_ENGINE_REUSE_SUBTREE) != 0;
+    case BZ_OPT_LEAVES: return leaves_per_step(c) > 1;
+    case BZ_OPT_DIRICHLET: return c.dirichlet_eps > 0.0f;
+    default: return false;  // (switched on by a setter: no config carries it)
+    }
+}
+bool option_on(const bz_engine* e, int opt) {
+    switch (opt) {
+    case BZ_OPT_GUMBEL: return e->gumbel.m > 0;
+    case BZ_OPT_GUMBEL_INTERIOR: return e->gin.node_v != nullptr;
+    case BZ_OPT_PLAYOUT_CAP: return e->cap.fast > 0;
+    case BZ_OPT_FORCED_PLAYOUTS: return e->forced.k > 0.0f;
+    case BZ_OPT_FPU: return e->fpu.root_w != nullptr;
+    case BZ_OPT_SOLVER: return e->solve.root != nullptr;
+    case BZ_OPT_EARLY_STOP: return e->stop.stop_at != nullptr;
+    case BZ_OPT_ROOT_STORE: return e->store.S > 0;
+    case BZ_OPT_SURPRISE: return e->surp.prior != nullptr;
+    case BZ_OPT_SEARCH_VALUE: return e->value.ex_q != nullptr;
+    case BZ_OPT_OWNERSHIP: return e->own.fin_x != nullptr;
+    case BZ_OPT_RESIGN: return e->resign.streak != nullptr;
+    default: return option_on(e->cfg, opt);
+    }
+}
+// the first option that is on in the engine (in a config: that the config carries) and does not run with `opt`: true and the message
+bool option_refusal(const char* fn, int opt, const bz_engine* e) {
+    return refuse_first_conflict(fn, opt, [e](int o) { return option_on(e, o); });
+}
+bool option_refusal(const char* fn, int opt, const bz_engine_cfg& c) {
+    return refuse_first_conflict(fn, opt, [&c](int o) { return option_on(c, o); });
+}
+}  // namespace
+
+BZ_EXPORT int32_t bz_option_conflict(int32_t a, int32_t b) { return option_id_ok(a) && option_id_ok(b) ? (option_conflict(a, b) ? 1 : 0) : -1; }
+BZ_EXPORT const char* bz_option_name(int32_t a) { return option_id_ok(a) ? kOptions[a].phrase : nullptr; }
 
 BZ_EXPORT int64_t bz_engine_workspace_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_workspace_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_workspace_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_workspace_bytes", cfg)) return -1;
     return carve(*cfg).total;
 }
 
 BZ_EXPORT int32_t bz_engine_create(const bz_engine_cfg* cfg, void* ws, int64_t bytes, bz_engine** out) {
     BZ_REQUIRE(ws && out, "bz_engine_create: null pointer");
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_create: %s", kBadFlags); return BZ_EINVAL; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_create: %s", kBadCfg); return BZ_EINVAL; }
+    if (!cfg_guard("bz_engine_create", cfg)) return BZ_EINVAL;
     if (bz_device_count() <= 0) { set_error("bz_engine_create: no HIP device (the engine has no CPU path)"); return BZ_ENOGPU; }
     Offsets o = carve(*cfg);
     if (bytes < o.total) { set_error("bz_engine_create: workspace too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
@@ -3410,12 +3410,12 @@ BZ_EXPORT int32_t bz_engine_root_begin(bz_engine* e, void* stream) {
     return BZ_OK;
 }
 
-// The engine's search mode (Mode): THE place that reads the setters' state.  The setters refuse every combination Mode refuses,
-// so what comes out is one of the masks tree_step() and bz_engine_play() switch over.
+// The engine's search mode (Mode): the bits of the options that are on (option_on).  The setters refuse every combination Mode
+// refuses, so what comes out is one of the masks tree_step() and bz_engine_play() switch over.
 static unsigned engine_mode(const bz_engine* e) {
-    return (e->dev.K > 1 ? kModeLeaf : 0u) | (e->gumbel.m > 0 ? kModeGumbel : 0u) | (e->cap.fast > 0 ? kModeCap : 0u) |
-           (e->forced.k > 0.0f ? kModeForced : 0u) | (e->fpu.root_w ? kModeFpu : 0u) | (e->gin.node_v ? kModeGfull : 0u) |
-           (e->solve.root ? kModeSolve : 0u) | (e->stop.stop_at ? kModeStop : 0u);
+    unsigned m = 0u;
+    for (int o = 0; o < BZ_OPT_COUNT; ++o) m |= option_on(e, o) ? kOptions[o].mode : 0u;
+    return m;
 }
 // every slot's budget for the observers of a search: null without playout cap randomisation (every search is a full one)
 static const u32* cap_budgets(const bz_engine* e) { return e->cap.fast > 0 ? static_cast<const u32*>(e->cap.budget) : nullptr; }
@@ -3653,23 +3653,15 @@ GumbelOffsets gumbel_carve(const bz_engine_cfg& c, int m) {
     o.total = k.off;
     return o;
 }
-// the combinations Gumbel root search refuses (nullptr: none)
-const char* gumbel_refusal(const bz_engine_cfg& c) {
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "Gumbel root search does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "Gumbel root search does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
-    if (c.dirichlet_eps > 0.0f) return "Gumbel root search does not combine with Dirichlet noise (dirichlet_eps > 0)";
-    return nullptr;
-}
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_gumbel_bytes(const bz_engine_cfg* cfg, int32_t max_considered) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_gumbel_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_gumbel_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_gumbel_bytes", cfg)) return -1;
     if (max_considered < 1 || max_considered > BZ_GUMBEL_MAX_CONSIDERED) {
         set_error("bz_engine_gumbel_bytes: max_considered must be in 1..64 (got %d)", (int)max_considered);
         return -1;
     }
-    if (const char* why = gumbel_refusal(*cfg)) { set_error("bz_engine_gumbel_bytes: %s", why); return -1; }
+    if (option_refusal("bz_engine_gumbel_bytes", BZ_OPT_GUMBEL, *cfg)) return -1;
     return gumbel_carve(*cfg, max_considered).total;
 }
 
@@ -3685,15 +3677,9 @@ BZ_EXPORT int32_t bz_engine_set_gumbel(bz_engine* e, int32_t max_considered, flo
     const bool finite = __builtin_isfinite(gumbel_scale) && __builtin_isfinite(maxvisit_init) && __builtin_isfinite(value_scale);
     BZ_REQUIRE(finite && gumbel_scale >= 0.0f && maxvisit_init >= 0.0f && value_scale >= 0.0f,
                "bz_engine_set_gumbel: gumbel_scale, maxvisit_init and value_scale must be finite and >= 0");
-    if (const char* why = gumbel_refusal(e->cfg)) { set_error("bz_engine_set_gumbel: %s", why); return BZ_EINVAL; }
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_gumbel: Gumbel root search does not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_gumbel: Gumbel root search does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
-    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_gumbel: Gumbel root search does not combine with forced playouts (bz_engine_set_forced_playouts)");
-    BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_gumbel: Gumbel root search does not combine with first-play urgency reduction (bz_engine_set_fpu)");
-    BZ_REQUIRE(!e->solve.root, "bz_engine_set_gumbel: Gumbel root search does not combine with the solver (bz_engine_set_solver)");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel: the buffer must be non-null and 256-byte aligned");
+    if (option_refusal("bz_engine_set_gumbel", BZ_OPT_GUMBEL, e)) return BZ_EINVAL;
     const GumbelOffsets o = gumbel_carve(e->cfg, max_considered);
-    if (buf_bytes < o.total) { set_error("bz_engine_set_gumbel: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_gumbel", buf, buf_bytes, o.total)) return rc;
     // T [m][sims]: setup, not the hot path -- built on the host and uploaded once
     const int sims = e->cfg.sims;
     uint16_t* T = new (std::nothrow) uint16_t[(size_t)max_considered * sims];
@@ -3715,9 +3701,8 @@ inline int64_t gumbel_interior_bytes(const bz_engine_cfg& c) { Carver k; k.take(
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_gumbel_interior_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_gumbel_interior_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_gumbel_interior_bytes: %s", kBadCfg); return -1; }
-    if (const char* why = gumbel_refusal(*cfg)) { set_error("bz_engine_gumbel_interior_bytes: %s", why); return -1; }
+    if (!cfg_guard("bz_engine_gumbel_interior_bytes", cfg)) return -1;
+    if (option_refusal("bz_engine_gumbel_interior_bytes", BZ_OPT_GUMBEL, *cfg)) return -1;
     return gumbel_interior_bytes(*cfg);
 }
 
@@ -3729,12 +3714,7 @@ BZ_EXPORT int32_t bz_engine_set_gumbel_interior(bz_engine* e, int32_t on, void* 
         return BZ_OK;
     }
     BZ_REQUIRE(e->gumbel.m > 0, "bz_engine_set_gumbel_interior: the Gumbel interior rule needs Gumbel root search (bz_engine_set_gumbel first)");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_gumbel_interior: the buffer must be non-null and 256-byte aligned");
-    const int64_t need = gumbel_interior_bytes(e->cfg);
-    if (buf_bytes < need) {
-        set_error("bz_engine_set_gumbel_interior: buffer too small (%lld < %lld)", (long long)buf_bytes, (long long)need);
-        return BZ_EINVAL;
-    }
+    if (int32_t rc = option_buffer("bz_engine_set_gumbel_interior", buf, buf_bytes, gumbel_interior_bytes(e->cfg), BZ_EINVAL)) return rc;
     e->gin.node_v = static_cast<float*>(buf);
     return BZ_OK;
 }
@@ -3752,19 +3732,12 @@ BZ_EXPORT int32_t bz_gumbel_interior_pick(const uint32_t* N, const float* W, con
 
 /* ---- playout cap randomisation */
 namespace {
-// the combinations playout cap randomisation refuses (nullptr: none)
-const char* cap_refusal(const bz_engine_cfg& c) {
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "playout cap randomisation does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "playout cap randomisation does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
-    return nullptr;
-}
 inline int64_t cap_bytes(const bz_engine_cfg& c) { Carver k; k.take((int64_t)c.n_games * 4); return k.off; }
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_playout_cap_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_playout_cap_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_playout_cap_bytes: %s", kBadCfg); return -1; }
-    if (const char* why = cap_refusal(*cfg)) { set_error("bz_engine_playout_cap_bytes: %s", why); return -1; }
+    if (!cfg_guard("bz_engine_playout_cap_bytes", cfg)) return -1;
+    if (option_refusal("bz_engine_playout_cap_bytes", BZ_OPT_PLAYOUT_CAP, *cfg)) return -1;
     return cap_bytes(*cfg);
 }
 
@@ -3776,12 +3749,8 @@ BZ_EXPORT int32_t bz_engine_set_playout_cap(bz_engine* e, int32_t fast_sims, uin
     }
     BZ_REQUIRE(fast_sims >= 1 && fast_sims < e->cfg.sims, "bz_engine_set_playout_cap: fast_sims must be 0 (off) or in 1 .. sims - 1");
     BZ_REQUIRE(full_q <= 65536u, "bz_engine_set_playout_cap: full_q must be in 0 .. 65536 (the probability of a full search in units of 2^-16)");
-    if (const char* why = cap_refusal(e->cfg)) { set_error("bz_engine_set_playout_cap: %s", why); return BZ_EINVAL; }
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_playout_cap: playout cap randomisation does not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_playout_cap: playout cap randomisation does not combine with Gumbel root search (bz_engine_set_gumbel)");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_playout_cap: the buffer must be non-null and 256-byte aligned");
-    const int64_t need = cap_bytes(e->cfg);
-    if (bytes < need) { set_error("bz_engine_set_playout_cap: buffer too small (%lld < %lld)", (long long)bytes, (long long)need); return BZ_ENOMEM; }
+    if (option_refusal("bz_engine_set_playout_cap", BZ_OPT_PLAYOUT_CAP, e)) return BZ_EINVAL;
+    if (int32_t rc = option_buffer("bz_engine_set_playout_cap", buf, bytes, cap_bytes(e->cfg))) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)e->cfg.n_games * 4, (hipStream_t)stream));  // no search yet: no budgets
     e->cap.fast = fast_sims; e->cap.full_q = full_q; e->cap.budget = static_cast<u32*>(buf);
     return BZ_OK;
@@ -3797,19 +3766,14 @@ BZ_EXPORT int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t mo
 
 /* ---- forced playouts and policy target pruning */
 namespace {
-// what forced playouts refuse (nullptr: nothing)
-const char* forced_refusal(const bz_engine_cfg& c, float k) {
-    if (!(k >= 0.0f && k <= 3.0e38f)) return "forced playouts: k must be finite and >= 0 (0 = off)";
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "forced playouts do not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "forced playouts do not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
-    return nullptr;
-}
+// the k forced playouts refuse (nullptr: none)
+const char* forced_refusal(float k) { return k >= 0.0f && k <= 3.0e38f ? nullptr : "forced playouts: k must be finite and >= 0 (0 = off)"; }
 }  // namespace
 
 BZ_EXPORT int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_forced_playouts_check: %s", kBadFlags); return BZ_EINVAL; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_forced_playouts_check: %s", kBadCfg); return BZ_EINVAL; }
-    if (const char* why = forced_refusal(*cfg, k)) { set_error("bz_engine_forced_playouts_check: %s", why); return BZ_EINVAL; }
+    if (!cfg_guard("bz_engine_forced_playouts_check", cfg)) return BZ_EINVAL;
+    if (const char* why = forced_refusal(k)) { set_error("bz_engine_forced_playouts_check: %s", why); return BZ_EINVAL; }
+    if (option_refusal("bz_engine_forced_playouts_check", BZ_OPT_FORCED_PLAYOUTS, *cfg)) return BZ_EINVAL;
     return BZ_OK;
 }
 
@@ -3820,10 +3784,8 @@ BZ_EXPORT int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t p
         e->forced = ForcedDev{};
         return BZ_OK;
     }
-    if (const char* why = forced_refusal(e->cfg, k)) { set_error("bz_engine_set_forced_playouts: %s", why); return BZ_EINVAL; }
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_forced_playouts: forced playouts do not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_forced_playouts: forced playouts do not combine with Gumbel root search (bz_engine_set_gumbel)");
-    BZ_REQUIRE(!(k > 0.0f && e->solve.root), "bz_engine_set_forced_playouts: forced playouts do not combine with the solver (bz_engine_set_solver)");
+    if (const char* why = forced_refusal(k)) { set_error("bz_engine_set_forced_playouts: %s", why); return BZ_EINVAL; }
+    if (option_refusal("bz_engine_set_forced_playouts", BZ_OPT_FORCED_PLAYOUTS, e)) return BZ_EINVAL;
     e->forced.k = k; e->forced.prune = prune ? 1 : 0;
     return BZ_OK;
 }
@@ -3843,28 +3805,20 @@ BZ_EXPORT int32_t bz_forced_prune(const uint32_t* N, const float* W, const float
 /* ---- first-play urgency reduction */
 namespace {
 inline bool fpu_red_ok(float r) { return r >= 0.0f && r <= 3.0e38f; }  // (a NaN fails)
-// what first-play urgency reduction refuses (nullptr: nothing)
-const char* fpu_refusal(const bz_engine_cfg& c) {
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "first-play urgency reduction does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "first-play urgency reduction does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
-    return nullptr;
-}
 inline int64_t fpu_bytes(const bz_engine_cfg& c) { Carver k; k.take((int64_t)c.n_games * 4); return k.off; }
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_fpu_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_fpu_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_fpu_bytes: %s", kBadCfg); return -1; }
-    if (const char* why = fpu_refusal(*cfg)) { set_error("bz_engine_fpu_bytes: %s", why); return -1; }
+    if (!cfg_guard("bz_engine_fpu_bytes", cfg)) return -1;
+    if (option_refusal("bz_engine_fpu_bytes", BZ_OPT_FPU, *cfg)) return -1;
     return fpu_bytes(*cfg);
 }
 
 BZ_EXPORT int32_t bz_engine_fpu_check(const bz_engine_cfg* cfg, float reduction, float root_reduction) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_fpu_check: %s", kBadFlags); return BZ_EINVAL; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_fpu_check: %s", kBadCfg); return BZ_EINVAL; }
-    if (const char* why = fpu_refusal(*cfg)) { set_error("bz_engine_fpu_check: %s", why); return BZ_EINVAL; }
+    if (!cfg_guard("bz_engine_fpu_check", cfg)) return BZ_EINVAL;
     BZ_REQUIRE(fpu_red_ok(reduction) && fpu_red_ok(root_reduction),
                "bz_engine_fpu_check: first-play urgency reduction: reduction and root_reduction must be finite and >= 0");
+    if (option_refusal("bz_engine_fpu_check", BZ_OPT_FPU, *cfg)) return BZ_EINVAL;
     return BZ_OK;
 }
 
@@ -3874,14 +3828,10 @@ BZ_EXPORT int32_t bz_engine_set_fpu(bz_engine* e, int32_t on, float reduction, f
         e->fpu = FpuDev{};
         return BZ_OK;
     }
-    if (const char* why = fpu_refusal(e->cfg)) { set_error("bz_engine_set_fpu: %s", why); return BZ_EINVAL; }
     BZ_REQUIRE(fpu_red_ok(reduction) && fpu_red_ok(root_reduction),
                "bz_engine_set_fpu: first-play urgency reduction: reduction and root_reduction must be finite and >= 0");
-    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_fpu: first-play urgency reduction does not combine with Gumbel root search (bz_engine_set_gumbel)");
-    BZ_REQUIRE(!e->solve.root, "bz_engine_set_fpu: first-play urgency reduction does not combine with the solver (bz_engine_set_solver)");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_fpu: the buffer must be non-null and 256-byte aligned");
-    const int64_t need = fpu_bytes(e->cfg);
-    if (bytes < need) { set_error("bz_engine_set_fpu: buffer too small (%lld < %lld)", (long long)bytes, (long long)need); return BZ_ENOMEM; }
+    if (option_refusal("bz_engine_set_fpu", BZ_OPT_FPU, e)) return BZ_EINVAL;
+    if (int32_t rc = option_buffer("bz_engine_set_fpu", buf, bytes, fpu_bytes(e->cfg))) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)e->cfg.n_games * 4, (hipStream_t)stream));
     e->fpu.reduction = reduction; e->fpu.root_reduction = root_reduction; e->fpu.root_w = static_cast<float*>(buf);
     return BZ_OK;
@@ -3902,12 +3852,6 @@ BZ_EXPORT float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float
 
 /* ---- proven wins, losses and draws */
 namespace {
-// what the solver refuses in a config (nullptr: nothing)
-const char* solver_refusal(const bz_engine_cfg& c) {
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "the solver does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "the solver does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*): concurrent walks race on proofs";
-    return nullptr;
-}
 struct SolveOffsets { int64_t root, counts, total; };
 inline SolveOffsets solver_carve(const bz_engine_cfg& c) {
     Carver k; SolveOffsets o;
@@ -3917,16 +3861,14 @@ inline SolveOffsets solver_carve(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_solver_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_solver_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_solver_bytes: %s", kBadCfg); return -1; }
-    if (const char* why = solver_refusal(*cfg)) { set_error("bz_engine_solver_bytes: %s", why); return -1; }
+    if (!cfg_guard("bz_engine_solver_bytes", cfg)) return -1;
+    if (option_refusal("bz_engine_solver_bytes", BZ_OPT_SOLVER, *cfg)) return -1;
     return solver_carve(*cfg).total;
 }
 
 BZ_EXPORT int32_t bz_engine_solver_check(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_solver_check: %s", kBadFlags); return BZ_EINVAL; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_solver_check: %s", kBadCfg); return BZ_EINVAL; }
-    if (const char* why = solver_refusal(*cfg)) { set_error("bz_engine_solver_check: %s", why); return BZ_EINVAL; }
+    if (!cfg_guard("bz_engine_solver_check", cfg)) return BZ_EINVAL;
+    if (option_refusal("bz_engine_solver_check", BZ_OPT_SOLVER, *cfg)) return BZ_EINVAL;
     return BZ_OK;
 }
 
@@ -3936,14 +3878,9 @@ BZ_EXPORT int32_t bz_engine_set_solver(bz_engine* e, int32_t on, void* buf, int6
         e->solve = SolveDev{}; e->solve_bytes = 0;
         return BZ_OK;
     }
-    if (const char* why = solver_refusal(e->cfg)) { set_error("bz_engine_set_solver: %s", why); return BZ_EINVAL; }
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_solver: the solver does not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_solver: the solver does not combine with Gumbel root search (bz_engine_set_gumbel)");
-    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_solver: the solver does not combine with forced playouts (bz_engine_set_forced_playouts): both score +inf");
-    BZ_REQUIRE(!e->fpu.root_w, "bz_engine_set_solver: the solver does not combine with first-play urgency reduction (bz_engine_set_fpu)");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_solver: the buffer must be non-null and 256-byte aligned");
+    if (option_refusal("bz_engine_set_solver", BZ_OPT_SOLVER, e)) return BZ_EINVAL;
     const SolveOffsets o = solver_carve(e->cfg);
-    if (bytes < o.total) { set_error("bz_engine_set_solver: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_solver", buf, bytes, o.total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));
     char* b = static_cast<char*>(buf);
     e->solve.root = reinterpret_cast<int32_t*>(b + o.root); e->solve.counts = reinterpret_cast<u32*>(b + o.counts);
@@ -3975,12 +3912,6 @@ BZ_EXPORT int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t 
 
 /* ---- exact early stop */
 namespace {
-// what early stop refuses in a config (nullptr: nothing)
-const char* early_stop_refusal(const bz_engine_cfg& c) {
-    if (c.flags & BZ_ENGINE_REUSE_SUBTREE) return "early stop does not combine with subtree reuse (BZ_ENGINE_REUSE_SUBTREE)";
-    if (leaves_per_step(c) > 1) return "early stop does not combine with leaves_per_step > 1 (BZ_ENGINE_LEAVES_*)";
-    return nullptr;
-}
 struct StopOffsets { int64_t stop_at, walked, total; };
 inline StopOffsets early_stop_carve(const bz_engine_cfg& c) {
     Carver k; StopOffsets o;
@@ -3990,16 +3921,14 @@ inline StopOffsets early_stop_carve(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_early_stop_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_early_stop_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_early_stop_bytes: %s", kBadCfg); return -1; }
-    if (const char* why = early_stop_refusal(*cfg)) { set_error("bz_engine_early_stop_bytes: %s", why); return -1; }
+    if (!cfg_guard("bz_engine_early_stop_bytes", cfg)) return -1;
+    if (option_refusal("bz_engine_early_stop_bytes", BZ_OPT_EARLY_STOP, *cfg)) return -1;
     return early_stop_carve(*cfg).total;
 }
 
 BZ_EXPORT int32_t bz_engine_early_stop_check(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_early_stop_check: %s", kBadFlags); return BZ_EINVAL; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_early_stop_check: %s", kBadCfg); return BZ_EINVAL; }
-    if (const char* why = early_stop_refusal(*cfg)) { set_error("bz_engine_early_stop_check: %s", why); return BZ_EINVAL; }
+    if (!cfg_guard("bz_engine_early_stop_check", cfg)) return BZ_EINVAL;
+    if (option_refusal("bz_engine_early_stop_check", BZ_OPT_EARLY_STOP, *cfg)) return BZ_EINVAL;
     return BZ_OK;
 }
 
@@ -4009,19 +3938,9 @@ BZ_EXPORT int32_t bz_engine_set_early_stop(bz_engine* e, int32_t on, int32_t hos
         e->stop = StopDev{}; e->stop_host_exit = 0;
         return BZ_OK;
     }
-    if (const char* why = early_stop_refusal(e->cfg)) { set_error("bz_engine_set_early_stop: %s", why); return BZ_EINVAL; }
-    BZ_REQUIRE(e->gumbel.m == 0, "bz_engine_set_early_stop: early stop does not combine with Gumbel root search (bz_engine_set_gumbel): sequential halving is its own schedule");
-    BZ_REQUIRE(e->cap.fast == 0, "bz_engine_set_early_stop: early stop does not combine with playout cap randomisation (bz_engine_set_playout_cap)");
-    BZ_REQUIRE(!(e->forced.k > 0.0f), "bz_engine_set_early_stop: early stop does not combine with forced playouts (bz_engine_set_forced_playouts)");
-    BZ_REQUIRE(!e->solve.root, "bz_engine_set_early_stop: early stop does not combine with the solver (bz_engine_set_solver)");
-    BZ_REQUIRE(e->store.S == 0, "bz_engine_set_early_stop: early stop does not combine with the root store (bz_engine_set_root_store): a shortened tree must not seed a later search");
-    BZ_REQUIRE(!e->surp.prior, "bz_engine_set_early_stop: early stop does not combine with policy surprise weighting (bz_engine_set_surprise): its targets come from complete searches");
-    BZ_REQUIRE(!e->value.ex_q, "bz_engine_set_early_stop: early stop does not combine with search-value targets (bz_engine_set_search_value): its targets come from complete searches");
-    BZ_REQUIRE(!e->own.fin_x, "bz_engine_set_early_stop: early stop does not combine with ownership targets (bz_engine_set_ownership): its targets come from complete searches");
-    BZ_REQUIRE(!e->resign.streak, "bz_engine_set_early_stop: early stop does not combine with resignation (bz_engine_set_resign): its records come from complete searches");
-    BZ_REQUIRE(buf && (reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_early_stop: the buffer must be non-null and 256-byte aligned");
+    if (option_refusal("bz_engine_set_early_stop", BZ_OPT_EARLY_STOP, e)) return BZ_EINVAL;
     const StopOffsets o = early_stop_carve(e->cfg);
-    if (bytes < o.total) { set_error("bz_engine_set_early_stop: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_early_stop", buf, bytes, o.total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no search yet: every slot 0
     e->stop.stop_at = at<u32>(buf, o.stop_at); e->stop.walked = at<u32>(buf, o.walked);
     e->stop_host_exit = host_exit ? 1 : 0;
@@ -4058,8 +3977,7 @@ SurpOffsets surp_carve(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_surprise_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_surprise_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_surprise_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_surprise_bytes", cfg)) return -1;
     return surp_carve(*cfg).total;
 }
 
@@ -4069,10 +3987,9 @@ BZ_EXPORT int32_t bz_engine_set_surprise(bz_engine* e, void* buf, int64_t bytes,
         e->surp = SurpDev{};
         return BZ_OK;
     }
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_surprise: the buffer must be 256-byte aligned");
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_surprise: policy surprise weighting does not combine with early stop (bz_engine_set_early_stop)");
+    if (option_refusal("bz_engine_set_surprise", BZ_OPT_SURPRISE, e)) return BZ_EINVAL;
     const SurpOffsets o = surp_carve(e->cfg);
-    if (bytes < o.total) { set_error("bz_engine_set_surprise: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_surprise", buf, bytes, o.total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no prior saved, no row pending, every kl 0
     e->surp.prior = at<float>(buf, o.prior); e->surp.pend = at<u64>(buf, o.pend); e->surp.ex_kl = at<float>(buf, o.ex_kl);
     return BZ_OK;
@@ -4099,8 +4016,7 @@ int64_t value_bytes(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_search_value_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_search_value_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_search_value_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_search_value_bytes", cfg)) return -1;
     return value_bytes(*cfg);
 }
 
@@ -4110,10 +4026,9 @@ BZ_EXPORT int32_t bz_engine_set_search_value(bz_engine* e, void* buf, int64_t by
         e->value = ValueDev{};
         return BZ_OK;
     }
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_search_value: the buffer must be 256-byte aligned");
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_search_value: search-value targets do not combine with early stop (bz_engine_set_early_stop)");
+    if (option_refusal("bz_engine_set_search_value", BZ_OPT_SEARCH_VALUE, e)) return BZ_EINVAL;
     const int64_t total = value_bytes(e->cfg);
-    if (bytes < total) { set_error("bz_engine_set_search_value: buffer too small (%lld < %lld)", (long long)bytes, (long long)total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_search_value", buf, bytes, total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)total, (hipStream_t)stream));  // every q 0
     e->value.ex_q = static_cast<float*>(buf);
     return BZ_OK;
@@ -4147,8 +4062,7 @@ OwnOffsets own_carve(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_ownership_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_ownership_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_ownership_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_ownership_bytes", cfg)) return -1;
     return own_carve(*cfg).total;
 }
 
@@ -4158,11 +4072,9 @@ BZ_EXPORT int32_t bz_engine_set_ownership(bz_engine* e, void* buf, int64_t bytes
         e->own = OwnDev{};
         return BZ_OK;
     }
-    BZ_REQUIRE(!e->resign.streak, "bz_engine_set_ownership: ownership targets do not combine with resignation (bz_engine_set_resign): a resigned game has no final board");
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_ownership: the buffer must be 256-byte aligned");
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_ownership: ownership targets do not combine with early stop (bz_engine_set_early_stop)");
+    if (option_refusal("bz_engine_set_ownership", BZ_OPT_OWNERSHIP, e)) return BZ_EINVAL;
     const OwnOffsets o = own_carve(e->cfg);
-    if (bytes < o.total) { set_error("bz_engine_set_ownership: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_ownership", buf, bytes, o.total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));  // no final board; (act 0 is never read before k_root_policy wrote it)
     e->own.fin_x = at<u64>(buf, o.fin_x); e->own.fin_o = at<u64>(buf, o.fin_o);
     e->own.pi = at<float>(buf, o.pi); e->own.act = at<int32_t>(buf, o.act);
@@ -4196,8 +4108,7 @@ ResignOffsets resign_carve(const bz_engine_cfg& c) {
 }  // namespace
 
 BZ_EXPORT int64_t bz_engine_resign_bytes(const bz_engine_cfg* cfg) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_resign_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_resign_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_resign_bytes", cfg)) return -1;
     return resign_carve(*cfg).total;
 }
 
@@ -4214,10 +4125,9 @@ BZ_EXPORT int32_t bz_engine_set_resign(bz_engine* e, float threshold, int32_t co
         e->resign = ResignDev{}; e->resign_bytes = 0;
         return BZ_OK;
     }
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_resign: resignation does not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE(!e->own.fin_x, "bz_engine_set_resign: resignation does not combine with ownership targets (bz_engine_set_ownership): a resigned game has no final board");
+    if (option_refusal("bz_engine_set_resign", BZ_OPT_RESIGN, e)) return BZ_EINVAL;
     const ResignOffsets o = resign_carve(e->cfg);
-    if (bytes < o.total) { set_error("bz_engine_set_resign: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_EINVAL; }
+    if (int32_t rc = option_buffer("bz_engine_set_resign", buf, bytes, o.total, BZ_EINVAL)) return rc;
     // the buffer the engine already records in: only the rule changes, streaks and records stay
     if (at<uint8_t>(buf, o.streak) != e->resign.streak) BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.total, (hipStream_t)stream));
     ResignDev& r = e->resign;
@@ -4277,8 +4187,7 @@ inline bool store_args_ok(int32_t S, int32_t D) { return S >= 1 && S <= 65536 &&
 /* The root store: bytes of the buffer for `entries` stored searches; 0 for a config whose engine does not run
  * the carry-over cache (the store is off there) */
 BZ_EXPORT int64_t bz_engine_root_store_bytes(const bz_engine_cfg* cfg, int32_t entries, int32_t plies) {
-    if (cfg && (cfg->flags & ~kFlagBits)) { set_error("bz_engine_root_store_bytes: %s", kBadFlags); return -1; }
-    if (!cfg_ok(cfg)) { set_error("bz_engine_root_store_bytes: %s", kBadCfg); return -1; }
+    if (!cfg_guard("bz_engine_root_store_bytes", cfg)) return -1;
     if (!store_args_ok(entries, plies)) { set_error("bz_engine_root_store_bytes: 1 <= entries <= 65536, 1 <= plies <= 64"); return -1; }
     if (carve(*cfg).ecache != 2) return 0;
     return store_carve(*cfg, entries).total;
@@ -4291,10 +4200,9 @@ BZ_EXPORT int32_t bz_engine_set_root_store(bz_engine* e, void* buf, int64_t byte
         return BZ_OK;
     }
     BZ_REQUIRE(store_args_ok(entries, plies), "bz_engine_set_root_store: 1 <= entries <= 65536, 1 <= plies <= 64");
-    BZ_REQUIRE(!e->stop.stop_at, "bz_engine_set_root_store: the root store does not combine with early stop (bz_engine_set_early_stop)");
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "bz_engine_set_root_store: the buffer must be 256-byte aligned");
+    if (option_refusal("bz_engine_set_root_store", BZ_OPT_ROOT_STORE, e)) return BZ_EINVAL;
     const StoreOffsets o = store_carve(e->cfg, entries);
-    if (bytes < o.total) { set_error("bz_engine_set_root_store: buffer too small (%lld < %lld)", (long long)bytes, (long long)o.total); return BZ_ENOMEM; }
+    if (int32_t rc = option_buffer("bz_engine_set_root_store", buf, bytes, o.total)) return rc;
     BZ_HIP(hipMemsetAsync(buf, 0, (size_t)o.nodes, (hipStream_t)stream));  // an empty store, no slot seeded
     StoreDev& s = e->store;
     s.S = entries; s.D = plies; s.n_idx = o.n_idx;

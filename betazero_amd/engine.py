@@ -194,6 +194,49 @@ def check_root_store(root_store, eval_cache=True):
 
 MAX_CONSIDERED = 64  # BZ_GUMBEL_MAX_CONSIDERED (include/bz_abi.h)
 
+# ---- The search options and THE table of the pairs that do not run together ("The search mode"), under
+# SelfPlayEngine's keyword names: the rows of BZ_OPT_* / kOptions and the pairs of kConflicts (csrc/bz_options.h), in their
+# order -- kept here as well because these messages name keywords, not setters, and because the checks run before the library
+# or a device is touched (argument parsers call them).  tests/test_option_conflicts_cpu.py holds the two tables equal.
+SEARCH_OPTIONS = {  # keyword: the phrase the messages use
+    "reuse_subtree": "subtree reuse", "leaves_per_step": "leaves_per_step > 1", "dirichlet_eps": "Dirichlet noise",
+    "gumbel": "Gumbel root search", "gumbel_interior": "the Gumbel interior rule",  # (GumbelConfig.interior == "gumbel")
+    "playout_cap": "playout cap randomisation", "forced_playouts": "forced playouts", "fpu": "first-play urgency reduction",
+    "solver": "the solver", "early_stop": "early stop", "root_store": "the root store", "surprise": "policy surprise weighting",
+    "search_value": "search-value targets", "ownership": "ownership targets", "resign": "resignation"}
+SEARCH_OPTION_CONFLICTS = (  # (keyword, keyword, reason or None): each pair once, in either order
+    *(("reuse_subtree", o, None) for o in ("gumbel", "playout_cap", "forced_playouts", "fpu", "solver", "early_stop")),
+    *(("leaves_per_step", o, None) for o in ("gumbel", "playout_cap", "forced_playouts", "fpu")),
+    ("leaves_per_step", "solver", "concurrent walks race on proofs"), ("leaves_per_step", "early_stop", None),
+    ("dirichlet_eps", "gumbel", None),
+    *(("gumbel", o, None) for o in ("playout_cap", "forced_playouts", "fpu", "solver")),
+    ("gumbel", "early_stop", "sequential halving is its own schedule"),
+    ("solver", "forced_playouts", "both score +inf"), ("solver", "fpu", None), ("solver", "early_stop", None),
+    ("early_stop", "playout_cap", None), ("early_stop", "forced_playouts", None),
+    ("early_stop", "root_store", "a shortened tree must not seed a later search"),
+    *(("early_stop", o, "its targets come from complete searches") for o in ("surprise", "search_value", "ownership")),
+    ("early_stop", "resign", "its records come from complete searches"),
+    ("ownership", "resign", "a resigned game has no final board"))
+
+
+def _option_on(name, value):
+    if name == "leaves_per_step":
+        return value != 1
+    if name == "dirichlet_eps":
+        return value > 0
+    return bool(value) if name == "reuse_subtree" else value is not None and value is not False
+
+
+def refuse_option_conflict(name, others):
+    """ValueError for the first pair of SEARCH_OPTION_CONFLICTS that option `name` makes with an option that is on in `others`,
+    {keyword: value} (an option it does not name is off); before any device is touched"""
+    for a, b, reason in SEARCH_OPTION_CONFLICTS:
+        other = b if a == name else a if b == name else None
+        if other in others and _option_on(other, others[other]):
+            p = SEARCH_OPTIONS[name]
+            raise ValueError(f"{name}: {p} {'do' if p.endswith('s') else 'does'} not combine with {SEARCH_OPTIONS[other]} ({other})" +
+                             (f": {reason}" if reason else ""))
+
 
 def check_replay_seed(replay_seed):
     """None (by the engine's size), True or False; anything else is refused (ValueError, before any device is touched)"""
@@ -222,8 +265,8 @@ GUMBEL_INTERIORS = ("puct", "gumbel")
 
 
 def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0.0):
-    """None / False: off (None returned); True: GumbelConfig(); or a GumbelConfig -- validated, and refused with subtree
-    reuse, leaves_per_step > 1 and Dirichlet noise (ValueError, before any device is touched)"""
+    """None / False: off (None returned); True: GumbelConfig(); or a GumbelConfig -- validated, and refused against the other
+    options named (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if gumbel is None or gumbel is False:
         return None
     cfg = GumbelConfig() if gumbel is True else gumbel
@@ -238,12 +281,7 @@ def check_gumbel(gumbel, reuse_subtree=False, leaves_per_step=1, dirichlet_eps=0
             raise ValueError(f"gumbel: {name} must be a finite number >= 0 (got {x!r})")
     if not isinstance(cfg.interior, str) or cfg.interior not in GUMBEL_INTERIORS:
         raise ValueError(f"gumbel: interior must be 'puct' or 'gumbel' (got {cfg.interior!r})")
-    if reuse_subtree:
-        raise ValueError("gumbel: Gumbel root search does not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("gumbel: Gumbel root search does not combine with leaves_per_step > 1")
-    if dirichlet_eps > 0:
-        raise ValueError("gumbel: Gumbel root search does not combine with Dirichlet noise (dirichlet_eps > 0)")
+    refuse_option_conflict("gumbel", dict(reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, dirichlet_eps=dirichlet_eps))
     return GumbelConfig(int(m), float(cfg.scale), float(cfg.maxvisit_init), float(cfg.value_scale), str(cfg.interior))
 
 
@@ -262,8 +300,8 @@ class PlayoutCap:
 
 
 def check_playout_cap(playout_cap, sims=None, reuse_subtree=False, leaves_per_step=1, gumbel=None):
-    """None / False: off (None returned); or a PlayoutCap -- validated, and refused with subtree reuse, leaves_per_step > 1
-    and Gumbel root search (ValueError, before any device is touched)"""
+    """None / False: off (None returned); or a PlayoutCap -- validated, and refused against the other options named
+    (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if playout_cap is None or playout_cap is False:
         return None
     cap = playout_cap
@@ -276,12 +314,7 @@ def check_playout_cap(playout_cap, sims=None, reuse_subtree=False, leaves_per_st
     p = cap.full_prob
     if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= p <= 1.0:  # (NaN fails)
         raise ValueError(f"playout_cap: full_prob must be a number in [0, 1] (got {p!r})")
-    if reuse_subtree:
-        raise ValueError("playout_cap: playout cap randomisation does not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("playout_cap: playout cap randomisation does not combine with leaves_per_step > 1")
-    if gumbel is not None and gumbel is not False:
-        raise ValueError("playout_cap: playout cap randomisation does not combine with Gumbel root search (gumbel)")
+    refuse_option_conflict("playout_cap", dict(reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, gumbel=gumbel))
     return PlayoutCap(int(n), float(p))
 
 
@@ -303,8 +336,8 @@ class Resign:
 
 
 def check_resign(resign, ownership=False):
-    """None / False: off (None returned); True: Resign(); or a Resign -- validated in float32, and refused with ownership
-    targets: a resigned game has no final board (ValueError, before any device is touched)"""
+    """None / False: off (None returned); True: Resign(); or a Resign -- validated in float32, and refused against the other
+    option named (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if resign is None or resign is False:
         return None
     cfg = Resign() if resign is True else resign
@@ -322,8 +355,7 @@ def check_resign(resign, ownership=False):
     f = cfg.playout_frac
     if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, float, np.integer, np.floating)) or not 0.0 <= f <= 1.0:  # (NaN fails)
         raise ValueError(f"resign: playout_frac must be a number in [0, 1] (got {f!r})")
-    if ownership is not None and ownership is not False:
-        raise ValueError("resign: resignation does not combine with ownership targets (ownership): a resigned game has no final board")
+    refuse_option_conflict("resign", dict(ownership=ownership))
     return Resign(t32, int(n), float(f))
 
 
@@ -356,8 +388,8 @@ class ForcedPlayouts:
 
 
 def check_forced_playouts(forced_playouts, reuse_subtree=False, leaves_per_step=1, gumbel=None):
-    """None / False: off (None returned); True: ForcedPlayouts(); or a ForcedPlayouts -- validated, and refused with subtree
-    reuse, leaves_per_step > 1 and Gumbel root search (ValueError, before any device is touched)"""
+    """None / False: off (None returned); True: ForcedPlayouts(); or a ForcedPlayouts -- validated, and refused against the other
+    options named (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if forced_playouts is None or forced_playouts is False:
         return None
     fp = ForcedPlayouts() if forced_playouts is True else forced_playouts
@@ -370,12 +402,7 @@ def check_forced_playouts(forced_playouts, reuse_subtree=False, leaves_per_step=
         raise ValueError(f"forced_playouts: k must be a finite number > 0 in float32 (got {k!r})")  # (NaN fails)
     if not isinstance(fp.prune, (bool, np.bool_)):
         raise ValueError(f"forced_playouts: prune must be a bool (got {fp.prune!r})")
-    if reuse_subtree:
-        raise ValueError("forced_playouts: forced playouts do not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("forced_playouts: forced playouts do not combine with leaves_per_step > 1")
-    if gumbel is not None and gumbel is not False:
-        raise ValueError("forced_playouts: forced playouts do not combine with Gumbel root search (gumbel)")
+    refuse_option_conflict("forced_playouts", dict(reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, gumbel=gumbel))
     return ForcedPlayouts(float(k), bool(fp.prune))
 
 
@@ -389,8 +416,8 @@ class Fpu:
 
 
 def check_fpu(fpu, reuse_subtree=False, leaves_per_step=1, gumbel=None):
-    """None / False: off (None returned); True: Fpu(); or an Fpu -- validated, and refused with subtree reuse,
-    leaves_per_step > 1 and Gumbel root search (ValueError, before any device is touched)"""
+    """None / False: off (None returned); True: Fpu(); or an Fpu -- validated, and refused against the other options named
+    (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if fpu is None or fpu is False:
         return None
     cfg = Fpu() if fpu is True else fpu
@@ -405,34 +432,21 @@ def check_fpu(fpu, reuse_subtree=False, leaves_per_step=1, gumbel=None):
         if not 0.0 <= x32 < np.inf:  # (NaN fails)
             raise ValueError(f"fpu: {name} must be a finite number >= 0 in float32 (got {x!r})")
         out.append(x32)
-    if reuse_subtree:
-        raise ValueError("fpu: first-play urgency reduction does not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("fpu: first-play urgency reduction does not combine with leaves_per_step > 1")
-    if gumbel is not None and gumbel is not False:
-        raise ValueError("fpu: first-play urgency reduction does not combine with Gumbel root search (gumbel)")
+    refuse_option_conflict("fpu", dict(reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, gumbel=gumbel))
     return Fpu(*out)
 
 
 def check_solver(solver, reuse_subtree=False, leaves_per_step=1, gumbel=None, forced_playouts=None, fpu=None):
-    """proven wins, losses and draws: a bool; True is refused with subtree reuse, leaves_per_step > 1, Gumbel
-    root search, forced playouts and first-play urgency reduction (ValueError, before any device is touched)"""
+    """proven wins, losses and draws: a bool; True is refused against the other options named
+    (SEARCH_OPTION_CONFLICTS; ValueError, before any device is touched)"""
     if solver is None:
         return False
     if not isinstance(solver, (bool, np.bool_)):
         raise ValueError(f"solver must be a bool (got {solver!r})")
     if not solver:
         return False
-    if reuse_subtree:
-        raise ValueError("solver: proofs do not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("solver: proofs do not combine with leaves_per_step > 1 (concurrent walks race on proofs)")
-    if gumbel is not None and gumbel is not False:
-        raise ValueError("solver: proofs do not combine with Gumbel root search (gumbel)")
-    if forced_playouts is not None and forced_playouts is not False:
-        raise ValueError("solver: proofs do not combine with forced_playouts (both score +inf)")
-    if fpu is not None and fpu is not False:
-        raise ValueError("solver: proofs do not combine with first-play urgency reduction (fpu)")
+    refuse_option_conflict("solver", dict(reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, gumbel=gumbel,
+                                          forced_playouts=forced_playouts, fpu=fpu))
     return True
 
 
@@ -447,10 +461,8 @@ class EarlyStop:
 
 def check_early_stop(early_stop, reuse_subtree=False, leaves_per_step=1, gumbel=None, playout_cap=None, forced_playouts=None,
                      solver=False, root_store=None, surprise=False, search_value=False, ownership=False, resign=None):
-    """None / False: off (None returned); True: EarlyStop(); or an EarlyStop -- validated, and refused with subtree reuse,
-    leaves_per_step > 1, Gumbel root search, the playout cap, forced playouts, the solver, a root store (root_store: the
-    checked value, a pair or None) and the training observers surprise, search_value, ownership and resign (ValueError, before
-    any device is touched)"""
+    """None / False: off (None returned); True: EarlyStop(); or an EarlyStop -- validated, and refused against the other options
+    named (SEARCH_OPTION_CONFLICTS; root_store: the checked value, a pair or None; ValueError, before any device is touched)"""
     if early_stop is None or early_stop is False:
         return None
     cfg = EarlyStop() if early_stop is True else early_stop
@@ -458,25 +470,10 @@ def check_early_stop(early_stop, reuse_subtree=False, leaves_per_step=1, gumbel=
         raise ValueError(f"early_stop must be None, False, True or an EarlyStop (got {early_stop!r})")
     if not isinstance(cfg.host_exit, (bool, np.bool_)):
         raise ValueError(f"early_stop: host_exit must be a bool (got {cfg.host_exit!r})")
-    on = lambda x: x is not None and x is not False  # noqa: E731
-    if reuse_subtree:
-        raise ValueError("early_stop: early stop does not combine with reuse_subtree")
-    if leaves_per_step != 1:
-        raise ValueError("early_stop: early stop does not combine with leaves_per_step > 1")
-    if on(gumbel):
-        raise ValueError("early_stop: early stop does not combine with Gumbel root search (gumbel): sequential halving is its own schedule")
-    if on(playout_cap):
-        raise ValueError("early_stop: early stop does not combine with playout cap randomisation (playout_cap)")
-    if on(forced_playouts):
-        raise ValueError("early_stop: early stop does not combine with forced_playouts")
-    if on(solver):
-        raise ValueError("early_stop: early stop does not combine with the solver (solver)")
-    if on(root_store):
-        raise ValueError("early_stop: early stop does not combine with the root store (root_store): a shortened tree must not "
-                         "seed a later search")
-    for name, val in (("surprise", surprise), ("search_value", search_value), ("ownership", ownership), ("resign", resign)):
-        if on(val):
-            raise ValueError(f"early_stop: early stop does not combine with {name}: its targets come from complete searches")
+    refuse_option_conflict("early_stop", dict(
+        reuse_subtree=reuse_subtree, leaves_per_step=leaves_per_step, gumbel=gumbel, playout_cap=playout_cap,
+        forced_playouts=forced_playouts, solver=solver, root_store=root_store, surprise=surprise, search_value=search_value,
+        ownership=ownership, resign=resign))
     return EarlyStop(bool(cfg.host_exit))
 
 
@@ -519,46 +516,40 @@ class SelfPlayEngine:
         the example rows' pi is the improved policy.  Gumbel noise is drawn while moves made < temp_moves (and scale > 0).
         GumbelConfig(interior="gumbel") replaces PUCT below the root by the paper's interior rule (DESIGN.md 3.21);
         set_gumbel_interior() changes it between searches.
-        Refused with reuse_subtree, leaves_per_step > 1 and dirichlet_eps > 0.
 
         playout_cap: None / False = every search has `sims` simulations (the default, unchanged); a
         PlayoutCap(fast_sims, full_prob) = every move draws a full search (sims, records its example row) or a fast one
         (fast_sims, records nothing; Dirichlet noise is drawn on full searches only).  budgets() reads the last search's
-        draws.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel.
+        draws.
 
         forced_playouts: None / False = off (the default, unchanged); True or a ForcedPlayouts(k, prune) =
         forced playouts at the root and, with prune, the pruned policy target in the example rows and in root_policy().  The
-        move choice and root_stats() keep the raw visits.  Under playout_cap only the full searches force.  Refused with
-        reuse_subtree, leaves_per_step > 1 and gumbel.
+        move choice and root_stats() keep the raw visits.  Under playout_cap only the full searches force.
 
         surprise: False = off (the default, unchanged); True = policy surprise weighting: every recorded
         row also gets kl = KL(pi || the root's raw prior), which examples() / device_examples() then carry as `kl` and
         betazero_amd.surprise.surprise_resample turns into repeat counts.  Searches, moves and rows are what they are
-        without it; it combines with everything the engine accepts.  surprise_rows() is the unpacked per-row view.
+        without it.  surprise_rows() is the unpacked per-row view.
 
         search_value: False = off (the default, unchanged); True = every recorded row also gets q = the root's
         sum W / sum N of its search (the mover's expected outcome, from the raw visit statistics), which examples() /
         device_examples() then carry as `q` and betazero_amd.value_targets.value_targets turns into value targets.  Searches,
-        moves and rows are what they are without it; it combines with everything the engine accepts.  search_value_rows() is
-        the unpacked per-row view.
+        moves and rows are what they are without it.  search_value_rows() is the unpacked per-row view.
 
         eval_symmetry: None / False = off (the default, unchanged); True or an EvalSymmetry(seed) = every
         leaf is evaluated under a board symmetry chosen by a hash of (its position, the seed) -- True takes the engine's
         `seed` -- inside the fused net kernels; priors and values come back in the position's own orientation.  The
-        evaluator stays a function of the position, so it combines with everything the engine accepts and the cache stays
+        evaluator stays a function of the position, so it combines with every search option and the cache stays
         exact; set_eval_symmetry() changes it between searches.  Refused on tic-tac-toe and with the synthetic, external
         and MLP evaluators.
 
         fpu: None / False = an unvisited child is scored with q = 0 (the default, unchanged); True or an
         Fpu(reduction, root_reduction) = first-play urgency reduction at every level of every walk.  root_stats(), pi, the
-        move choice and the rows follow the usual rules on the tree this search builds.  Combines with Dirichlet noise,
-        playout_cap, forced_playouts, surprise, search_value, eval_symmetry, every evaluator and eval_cache mode; set_fpu()
-        changes it between searches.  Refused with reuse_subtree, leaves_per_step > 1 and gumbel.
+        move choice and the rows follow the usual rules on the tree this search builds.  set_fpu() changes it between searches.
 
         ownership: False = off (the default, unchanged); True = the final board of every finished game is kept
         (ownership_rows()), and examples() / device_examples() carry every row's ownership target `fown`, `fopp`: that board in
-        the row's side-to-move frame.  Searches, moves and rows are what they are without it; it combines with everything the
-        engine accepts.
+        the row's side-to-move frame.  Searches, moves and rows are what they are without it.
 
         root_store: None = the default for the cache mode -- ROOT_STORE_DEFAULT = (entries, plies) with
         eval_cache True / "carry", off otherwise; False = off; (entries, plies) = a store of that size.  Finished searches of
@@ -569,38 +560,39 @@ class SelfPlayEngine:
         solver: False = off (the default, unchanged); True = the search books proven wins, losses and draws:
         an edge whose child is decided is marked, the mark travels up the path with the backup, the select rule never
         walks through a decided edge, and play() / root_policy() play the lowest winning move and avoid lost ones.  pi stays
-        N / sum N.  proven() reads the proof state; set_solver() changes it between searches.  Combines with Dirichlet
-        noise, playout_cap, surprise, search_value, ownership, eval_symmetry, every evaluator, eval_cache mode and the root
-        store.  Refused with reuse_subtree, leaves_per_step > 1, gumbel, forced_playouts and fpu.
+        N / sum N.  proven() reads the proof state; set_solver() changes it between searches.
 
         resign: None / False = every game is played to the end (the default, unchanged); True or a
         Resign(threshold, consecutive, playout_frac) = a side whose root value stayed below the threshold for `consecutive`
         full searches in a row resigns; a seeded share of the games is played out and only records where it would have
         resigned.  resign_rows() reads the records, resign_stats() the false-positive rate; set_resign() changes the rule
-        between searches.  Searches, and the rows of games that do not resign, are what they are without it; it combines with
-        everything the engine accepts but ownership.
+        between searches.  Searches, and the rows of games that do not resign, are what they are without it.
 
         early_stop: None / False = every search runs its whole budget (the default, unchanged); True or an
         EarlyStop(host_exit) = a slot whose move is the first maximum of the visits (moves made >= temp_moves) stops searching
         at the first simulation index at which the simulations left cannot change that move.  The move is the full search's;
         root_stats() and pi are those of the shortened tree (pi = N / stop_at), stopped() reads stop_at, set_early_stop()
-        changes it between searches.  Meant for matches and players, not for training games.  Combines with fpu, eval_symmetry,
-        Dirichlet noise, temp_moves, every evaluator and eval_cache mode; with it on, root_store=None means no root store.
-        Refused with reuse_subtree, leaves_per_step > 1, gumbel, playout_cap, forced_playouts, solver, a root store, surprise,
-        search_value, ownership and resign.
+        changes it between searches.  Meant for matches and players, not for training games.  With it on, root_store=None
+        means no root store.
 
         replay_seed: True = where the carry-over cache is on and the search is otherwise plain (no other search
         option, no noise, no reuse_subtree, no eval_symmetry), a slot's search starts from a copy of the played child's old
         subtree -- what its first N_e - 1 simulations would rebuild -- and spreads its remaining walks evenly over the move's tree
         steps; False = every search is stepped simulation by simulation; None (the default) = True for an engine of more than
         1024 games, where level launches pay, else False.  No result and no counter depends on it; everywhere else it is
-        ignored.  set_replay_seed() changes it between searches."""
+        ignored.  set_replay_seed() changes it between searches.
+
+        Which of these options run together: every pair but those of SEARCH_OPTION_CONFLICTS (the matrix of DESIGN.md 5, "The
+        search mode"), in __init__ and in every set_*(); a refused pair is a ValueError that names both keywords, before any
+        device is touched.  Every evaluator and eval_cache mode serves every option."""
         self.replay_seed = check_replay_seed(replay_seed)
         if early_stop is not None and early_stop is not False and root_store is None:
             root_store = False  # (a shortened tree is not worth an entry and must not seed a later search)
+        # every option is validated, then refused against what is on so far (_switch): the later of a refused pair names it
+        self._reuse, self._dirichlet_eps, self.K = bool(reuse_subtree), dirichlet_eps, check_leaves_per_step(leaves_per_step)
         self.root_store = check_root_store(root_store, eval_cache)
         self.ownership = check_ownership(ownership)
-        self.resign = check_resign(resign, self.ownership)
+        self.resign = self._switch("resign", check_resign(resign))
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, seed, game, evaluator)
         if not isinstance(surprise, (bool, np.bool_)):
             raise ValueError(f"surprise must be a bool (got {surprise!r})")
@@ -608,15 +600,12 @@ class SelfPlayEngine:
         self.search_value = check_search_value(search_value)
         check_sims(sims, reuse_subtree)
         check_eval_cache(eval_cache)
-        self.K = check_leaves_per_step(leaves_per_step)
-        self.gumbel = check_gumbel(gumbel, reuse_subtree, self.K, dirichlet_eps)
-        self.playout_cap = check_playout_cap(playout_cap, sims, reuse_subtree, self.K, gumbel)
-        self.forced_playouts = check_forced_playouts(forced_playouts, reuse_subtree, self.K, gumbel)
-        self.fpu = check_fpu(fpu, reuse_subtree, self.K, gumbel)
-        self._reuse = bool(reuse_subtree)
-        self.solver = check_solver(solver, reuse_subtree, self.K, gumbel, forced_playouts, fpu)
-        self.early_stop = check_early_stop(early_stop, reuse_subtree, self.K, gumbel, playout_cap, forced_playouts, solver,
-                                           self.root_store, surprise, search_value, ownership, resign)
+        self.gumbel = self._switch("gumbel", check_gumbel(gumbel))
+        self.playout_cap = self._switch("playout_cap", check_playout_cap(playout_cap, sims))
+        self.forced_playouts = self._switch("forced_playouts", check_forced_playouts(forced_playouts))
+        self.fpu = self._switch("fpu", check_fpu(fpu))
+        self.solver = self._switch("solver", check_solver(solver))
+        self.early_stop = self._switch("early_stop", check_early_stop(early_stop))
         if evaluator.startswith("mlp_") and _GAMES[game] != GAME_TTT:
             raise ValueError(f"evaluator {evaluator!r}: the MLP evaluators serve tic-tac-toe only")
         _lib.require_gpu()
@@ -624,6 +613,7 @@ class SelfPlayEngine:
         self.game = _GAMES[game]
         self.device = torch.device(device)
         self._streams = {}  # every stream this engine's kernels were launched on (drained before the workspace dies)
+        self._buffers = {}  # the caller-owned option buffers (_option_buffer), kept like the workspace until __del__ has drained
         t_max = 9 if self.game == GAME_TTT else 64
         self.cfg = EngineCfg(self.game, n_games, sims, _EVALS[evaluator], c_puct, temp_moves, openings, rounds, t_max,
                              stagger, seed, game_id_base, n_games if game_id_stride is None else game_id_stride,
@@ -655,70 +645,69 @@ class SelfPlayEngine:
                 _lib.check(L.bz_engine_set_net(self.h, net.h))
         if self.replay_seed is not None:
             _lib.check(L.bz_engine_set_replay_seed(self.h, int(self.replay_seed)))
-        if self.gumbel is not None:  # the engine's Gumbel buffer (caller-owned, like the workspace)
+        if self.gumbel is not None:
             gc = self.gumbel
-            gbytes = L.bz_engine_gumbel_bytes(C.byref(self.cfg), gc.max_considered)
-            if gbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.gws = torch.zeros(gbytes + 256, dtype=torch.uint8, device=self.device)
-            gpad = (-self.gws.data_ptr()) & 255
             self._call(L.bz_engine_set_gumbel, gc.max_considered, gc.scale, gc.maxvisit_init, gc.value_scale,
-                       self.gws.data_ptr() + gpad, gbytes)
+                       *self._option_buffer("gumbel", L.bz_engine_gumbel_bytes, gc.max_considered))
             if gc.interior == "gumbel":
                 self._set_gumbel_interior(True)
-        if self.playout_cap is not None:  # the engine's budget buffer (caller-owned, like the workspace)
-            pc = self.playout_cap
-            cbytes = L.bz_engine_playout_cap_bytes(C.byref(self.cfg))
-            if cbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.cws = torch.zeros(cbytes + 256, dtype=torch.uint8, device=self.device)
-            self._cpad = (-self.cws.data_ptr()) & 255
-            self._call(L.bz_engine_set_playout_cap, pc.fast_sims, pc.full_q, self.cws.data_ptr() + self._cpad, cbytes)
+        if self.playout_cap is not None:
+            self._call(L.bz_engine_set_playout_cap, self.playout_cap.fast_sims, self.playout_cap.full_q,
+                       *self._option_buffer("playout_cap", L.bz_engine_playout_cap_bytes))
         if self.forced_playouts is not None:
             self._call(L.bz_engine_set_forced_playouts, self.forced_playouts.k, int(self.forced_playouts.prune))
         if self.fpu is not None:
             self._set_fpu(self.fpu)
         if self.solver:
             self._set_solver(True)
-        if self.surprise:  # the engine's surprise buffer (caller-owned, like the workspace)
-            sbytes = L.bz_engine_surprise_bytes(C.byref(self.cfg))
-            if sbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.sws = torch.zeros(sbytes + 256, dtype=torch.uint8, device=self.device)
-            self._spad = (-self.sws.data_ptr()) & 255
-            self._sbytes = sbytes
-            self._call(L.bz_engine_set_surprise, self.sws.data_ptr() + self._spad, sbytes)
+        if self.surprise:
+            self._call(L.bz_engine_set_surprise, *self._option_buffer("surprise", L.bz_engine_surprise_bytes))
         if self.eval_symmetry is not None:
             _lib.check(L.bz_engine_set_eval_symmetry(self.h, 1, self.eval_symmetry.seed))
-        if self.search_value:  # the engine's ex_q buffer (caller-owned, like the workspace)
-            vbytes = L.bz_engine_search_value_bytes(C.byref(self.cfg))
-            if vbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.vws = torch.zeros(vbytes + 256, dtype=torch.uint8, device=self.device)
-            self._vpad = (-self.vws.data_ptr()) & 255
-            self._call(L.bz_engine_set_search_value, self.vws.data_ptr() + self._vpad, vbytes)
-        if self.root_store is not None:  # the engine's root store (caller-owned, like the workspace)
-            S, D = self.root_store
-            rbytes = L.bz_engine_root_store_bytes(C.byref(self.cfg), S, D)
-            if rbytes < 0:
-                raise RuntimeError(_lib.last_error())
+        if self.search_value:
+            self._call(L.bz_engine_set_search_value, *self._option_buffer("search_value", L.bz_engine_search_value_bytes))
+        if self.root_store is not None:
+            # (empty, not zeros: the setter clears the index, and nothing reads an entry the index does not name)
+            ptr, rbytes = self._option_buffer("root_store", L.bz_engine_root_store_bytes, *self.root_store, zero=False)
             if rbytes == 0:  # no carry-over cache in this engine (synthetic evaluator, reuse_subtree, leaves_per_step > 1)
                 self.root_store = None
-            else:  # (empty, not zeros: the setter clears the index, and nothing reads an entry the index does not name)
-                self.rws = torch.empty(rbytes + 256, dtype=torch.uint8, device=self.device)
-                rpad = (-self.rws.data_ptr()) & 255
-                self._call(L.bz_engine_set_root_store, self.rws.data_ptr() + rpad, rbytes, S, D)
-        if self.ownership:  # the engine's final-board buffer (caller-owned, like the workspace)
-            obytes = L.bz_engine_ownership_bytes(C.byref(self.cfg))
-            if obytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.ows = torch.zeros(obytes + 256, dtype=torch.uint8, device=self.device)
-            self._opad = (-self.ows.data_ptr()) & 255
-            self._call(L.bz_engine_set_ownership, self.ows.data_ptr() + self._opad, obytes)
+            else:
+                self._call(L.bz_engine_set_root_store, ptr, rbytes, *self.root_store)
+        if self.ownership:
+            self._call(L.bz_engine_set_ownership, *self._option_buffer("ownership", L.bz_engine_ownership_bytes))
         if self.resign is not None:
             self._set_resign(self.resign)
         if self.early_stop is not None:
             self._set_early_stop(self.early_stop)
+
+    # ---- the search options
+    def _options(self):
+        """the value every search option (SEARCH_OPTIONS) has now, by keyword; one that __init__ has not reached yet is off"""
+        on = {k: vars(self).get(k) for k in SEARCH_OPTIONS}
+        on.update(reuse_subtree=self._reuse, leaves_per_step=self.K, dirichlet_eps=self._dirichlet_eps,
+                  gumbel_interior=on["gumbel"] is not None and on["gumbel"].interior == "gumbel")
+        return on
+
+    def _switch(self, name, value):
+        """`value`, the checked new value of option `name`, unless it is on and makes a refused pair with what is on"""
+        if _option_on(name, value):
+            refuse_option_conflict(name, self._options())
+        return value
+
+    def _option_buffer(self, key, bytes_fn, *args, zero=True):
+        """(pointer, bytes) of the caller-owned device buffer of option `key`, 256-byte aligned: allocated at its first use --
+        bytes_fn(cfg, *args) of the library says how large -- and used again when the option is switched off and on;
+        (0, 0) where the library says the engine has no such buffer"""
+        if key not in self._buffers:
+            n = bytes_fn(C.byref(self.cfg), *args)
+            if n < 0:
+                raise RuntimeError(_lib.last_error())
+            if n == 0:
+                return 0, 0
+            t = (torch.zeros if zero else torch.empty)(n + 256, dtype=torch.uint8, device=self.device)
+            pad = (-t.data_ptr()) & 255
+            self._buffers[key] = t[pad:pad + n]
+        return self._buffers[key].data_ptr(), self._buffers[key].numel()
 
     # ---- views into the workspace
     def _view(self, off, dtype, shape):
@@ -761,13 +750,7 @@ class SelfPlayEngine:
         if not on:
             self._call(L.bz_engine_set_gumbel_interior, 0, None, 0)
             return
-        if getattr(self, "giws", None) is None:  # the engine's v_X buffer (caller-owned, next to the Gumbel one)
-            ibytes = L.bz_engine_gumbel_interior_bytes(C.byref(self.cfg))
-            if ibytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.giws = torch.zeros(ibytes + 256, dtype=torch.uint8, device=self.device)
-            self._gipad, self._gibytes = (-self.giws.data_ptr()) & 255, ibytes
-        self._call(L.bz_engine_set_gumbel_interior, 1, self.giws.data_ptr() + self._gipad, self._gibytes)
+        self._call(L.bz_engine_set_gumbel_interior, 1, *self._option_buffer("gumbel_interior", L.bz_engine_gumbel_interior_bytes))
 
     def set_gumbel_interior(self, interior):
         """switch the select rule below the root of a Gumbel search between "puct" and "gumbel" (DESIGN.md 3.21), between
@@ -776,6 +759,7 @@ class SelfPlayEngine:
             raise ValueError("gumbel: the interior rule needs Gumbel root search (gumbel=)")
         from dataclasses import replace
         gc = check_gumbel(replace(self.gumbel, interior=interior))
+        self._switch("gumbel_interior", gc.interior == "gumbel")
         self.drain()
         self._set_gumbel_interior(gc.interior == "gumbel")
         self.gumbel = gc
@@ -785,18 +769,12 @@ class SelfPlayEngine:
         if fp is None:
             self._call(L.bz_engine_set_fpu, 0, 0.0, 0.0, None, 0)
             return
-        if getattr(self, "fws", None) is None:  # the engine's Wr buffer (caller-owned, like the workspace)
-            fbytes = L.bz_engine_fpu_bytes(C.byref(self.cfg))
-            if fbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.fws = torch.zeros(fbytes + 256, dtype=torch.uint8, device=self.device)
-            self._fpad, self._fbytes = (-self.fws.data_ptr()) & 255, fbytes
-        self._call(L.bz_engine_set_fpu, 1, fp.reduction, fp.root_reduction, self.fws.data_ptr() + self._fpad, self._fbytes)
+        self._call(L.bz_engine_set_fpu, 1, fp.reduction, fp.root_reduction, *self._option_buffer("fpu", L.bz_engine_fpu_bytes))
 
     def set_fpu(self, fpu):
         """switch first-play urgency reduction on, off or to other reductions, between searches: None /
         False, True (the defaults) or an Fpu"""
-        fp = check_fpu(fpu, self._reuse, self.K, self.gumbel)
+        fp = self._switch("fpu", check_fpu(fpu))
         self.drain()
         self._set_fpu(fp)
         self.fpu = fp
@@ -806,19 +784,11 @@ class SelfPlayEngine:
         if not on:
             self._call(L.bz_engine_set_solver, 0, None, 0)
             return
-        if getattr(self, "pws", None) is None:  # the engine's proof buffer (caller-owned, like the workspace)
-            pbytes = L.bz_engine_solver_bytes(C.byref(self.cfg))
-            if pbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.pws = torch.zeros(pbytes + 256, dtype=torch.uint8, device=self.device)
-            self._ppad, self._pbytes = (-self.pws.data_ptr()) & 255, pbytes
-        self._call(L.bz_engine_set_solver, 1, self.pws.data_ptr() + self._ppad, self._pbytes)
+        self._call(L.bz_engine_set_solver, 1, *self._option_buffer("solver", L.bz_engine_solver_bytes))
 
     def set_solver(self, solver):
         """switch the solver on or off, between searches"""
-        on = check_solver(solver, self._reuse, self.K, self.gumbel, self.forced_playouts, self.fpu)
-        if on and self.early_stop is not None:
-            raise ValueError("solver: proofs do not combine with early stop (early_stop)")
+        on = self._switch("solver", check_solver(solver))
         self.drain()
         self._set_solver(on)
         self.solver = on
@@ -828,19 +798,12 @@ class SelfPlayEngine:
         if es is None:
             self._call(L.bz_engine_set_early_stop, 0, 0, None, 0)
             return
-        if getattr(self, "ews", None) is None:  # the engine's stop_at buffer (caller-owned, like the workspace)
-            ebytes = L.bz_engine_early_stop_bytes(C.byref(self.cfg))
-            if ebytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.ews = torch.zeros(ebytes + 256, dtype=torch.uint8, device=self.device)
-            self._epad, self._ebytes = (-self.ews.data_ptr()) & 255, ebytes
-        self._call(L.bz_engine_set_early_stop, 1, int(es.host_exit), self.ews.data_ptr() + self._epad, self._ebytes)
+        self._call(L.bz_engine_set_early_stop, 1, int(es.host_exit), *self._option_buffer("early_stop", L.bz_engine_early_stop_bytes))
 
     def set_early_stop(self, early_stop):
         """switch exact early stop on, off or to another host_exit, between searches: None / False, True or an
         EarlyStop"""
-        es = check_early_stop(early_stop, self._reuse, self.K, self.gumbel, self.playout_cap, self.forced_playouts, self.solver,
-                              self.root_store, self.surprise, self.search_value, self.ownership, self.resign)
+        es = self._switch("early_stop", check_early_stop(early_stop))
         self.drain()
         self._set_early_stop(es)
         self.early_stop = es
@@ -859,20 +822,13 @@ class SelfPlayEngine:
         if rs is None:
             self._call(L.bz_engine_set_resign, 0.0, 0, 0, None, 0)
             return
-        if getattr(self, "zws", None) is None:  # the engine's resignation buffer (caller-owned, like the workspace)
-            zbytes = L.bz_engine_resign_bytes(C.byref(self.cfg))
-            if zbytes < 0:
-                raise RuntimeError(_lib.last_error())
-            self.zws = torch.zeros(zbytes + 256, dtype=torch.uint8, device=self.device)
-            self._zpad, self._zbytes = (-self.zws.data_ptr()) & 255, zbytes
-        self._call(L.bz_engine_set_resign, rs.threshold, rs.consecutive, rs.playout_q, self.zws.data_ptr() + self._zpad, self._zbytes)
+        # (the same buffer every time: while resignation stays on the setter keeps its streaks and records)
+        self._call(L.bz_engine_set_resign, rs.threshold, rs.consecutive, rs.playout_q, *self._option_buffer("resign", L.bz_engine_resign_bytes))
 
     def set_resign(self, resign):
         """switch resignation on, off or to another rule, between searches: None / False, True (the defaults)
         or a Resign.  While it stays on, streaks and records are kept; switching it off and on again clears them."""
-        rs = check_resign(resign, self.ownership)
-        if rs is not None and self.early_stop is not None:
-            raise ValueError("resign: resignation does not combine with early stop (early_stop)")
+        rs = self._switch("resign", check_resign(resign))
         self.drain()
         self._set_resign(rs)
         self.resign = rs
@@ -1005,7 +961,7 @@ class SelfPlayEngine:
             raise RuntimeError("budgets(): the engine was built without playout_cap")
         self.drain()
         torch.cuda.current_stream(self.device).synchronize()
-        return self.cws[self._cpad:self._cpad + 4 * self.B].view(torch.int32).cpu().numpy().view(np.uint32)
+        return self._buffers["playout_cap"][:4 * self.B].view(torch.int32).cpu().numpy().view(np.uint32)
 
     def counters(self):
         """the work counters by name (_lib.COUNTER_NAMES); "n_collisions" only for leaves_per_step > 1"""
@@ -1076,8 +1032,9 @@ class SelfPlayEngine:
         if not self.surprise:
             raise RuntimeError("surprise_rows(): the engine was built without surprise=True")
         n = self.rounds * self.B * self.t_max * 4
-        o = self._spad + self._sbytes - ((n + 255) & ~255)  # ex_kl is the buffer's last array
-        return self.sws[o:o + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
+        buf = self._buffers["surprise"]
+        o = buf.numel() - ((n + 255) & ~255)  # ex_kl is the buffer's last array
+        return buf[o:o + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
 
     def pack_surprise(self, out=None, cap_rows=None, append=False):
         """the finished games' kl in the row order of the packed block the preceding pack_examples() (same cap_rows, same
@@ -1101,7 +1058,7 @@ class SelfPlayEngine:
         if not self.search_value:
             raise RuntimeError("search_value_rows(): the engine was built without search_value=True")
         n = self.rounds * self.B * self.t_max * 4
-        return self.vws[self._vpad:self._vpad + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
+        return self._buffers["search_value"][:n].view(torch.float32).view(self.rounds, self.B, self.t_max)
 
     def pack_search_value(self, out=None, cap_rows=None, append=False):
         """the finished games' q in the row order of the packed block the preceding pack_examples() (same cap_rows, same
@@ -1127,8 +1084,7 @@ class SelfPlayEngine:
             raise RuntimeError("ownership_rows(): the engine was built without ownership=True")
         n = self.rounds * self.B * 8
         step = (n + 255) & ~255  # fin_x and fin_o are the buffer's first two arrays
-        return tuple(self.ows[self._opad + k * step:self._opad + k * step + n].view(torch.int64).view(self.rounds, self.B)
-                     for k in (0, 1))
+        return tuple(self._buffers["ownership"][k * step:k * step + n].view(torch.int64).view(self.rounds, self.B) for k in (0, 1))
 
     def pack_ownership(self, out=None, cap_rows=None, append=False):
         """the finished games' rows' ownership targets in the row order of the packed block the preceding pack_examples() (same
@@ -1440,6 +1396,17 @@ def pipeline_stream_info(device="cuda:0", n=2):
     return _PIPE_INFO.get((str(torch.device(device)), n))
 
 
+def _check_search_options(sims, reuse_subtree, leaves_per_step, dirichlet_eps, gumbel, playout_cap, forced_playouts, fpu, solver):
+    """the search options self_play and its pipelines pass on to their engines, each validated before it is another's "other
+    option" (ValueError, before any device is touched)"""
+    cfg = dict(reuse_subtree=reuse_subtree, leaves_per_step=check_leaves_per_step(leaves_per_step))
+    gumbel = check_gumbel(gumbel, dirichlet_eps=dirichlet_eps, **cfg)
+    check_playout_cap(playout_cap, sims, gumbel=gumbel, **cfg)
+    forced_playouts = check_forced_playouts(forced_playouts, gumbel=gumbel, **cfg)
+    fpu = check_fpu(fpu, gumbel=gumbel, **cfg)
+    check_solver(solver, gumbel=gumbel, forced_playouts=forced_playouts, fpu=fpu, **cfg)
+
+
 class PipelinedSelfPlay:
     """The batched self-play of `n_games` concurrent games on one GPU as `pipelines` independent SelfPlayEngines of
     n_games / pipelines slots, each on its own HIP stream, sharing one net: the tree step of one pipeline overlaps the
@@ -1460,16 +1427,12 @@ class PipelinedSelfPlay:
         if "early_stop" in engine_kwargs:  #  a shortened search changes pi: not for training games
             raise ValueError("PipelinedSelfPlay: early_stop is for matches and players, not for self-play pipelines")
         check_ownership(ownership)
-        check_resign(resign, ownership)
-        check_solver(solver, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel, forced_playouts, fpu)
+        check_resign(resign, ownership=ownership)
         # every pipeline gets the same seed, so the same position has the same orientation in all of them
         eval_symmetry = check_eval_symmetry(eval_symmetry, engine_kwargs.get("seed", 0), game, evaluator)
         check_search_value(search_value)
-        check_leaves_per_step(leaves_per_step)
-        check_gumbel(gumbel, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0))
-        check_playout_cap(playout_cap, sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
-        check_forced_playouts(forced_playouts, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
-        check_fpu(fpu, engine_kwargs.get("reuse_subtree", False), leaves_per_step, gumbel)
+        _check_search_options(sims, engine_kwargs.get("reuse_subtree", False), leaves_per_step, engine_kwargs.get("dirichlet_eps", 0.0),
+                              gumbel, playout_cap, forced_playouts, fpu, solver)
         check_eval_cache(engine_kwargs.get("eval_cache", True))
         check_root_store(engine_kwargs.get("root_store"), engine_kwargs.get("eval_cache", True))
         # simulations the host thread may queue ahead of the GPU (0 = unbounded: it then spins on the runtime's full queue,
@@ -1671,7 +1634,7 @@ class PipelinedSelfPlay:
 
     def set_resign(self, resign):
         """SelfPlayEngine.set_resign on every pipeline, between searches"""
-        rs = check_resign(resign, self.ownership)
+        rs = check_resign(resign, ownership=self.ownership)
         self.sync()
         self._each(lambda e: e.set_resign(rs))
 
@@ -1717,14 +1680,9 @@ def self_play(game, n_games, sims, net=None, seed=0, evaluator=None, temp_moves=
     carry `fown`, `fopp`.  resign: SelfPlayEngine -- decided games end early; a resigned game's rows are the
     first rows of the game it would have been."""
     check_ownership(ownership)
-    check_resign(resign, ownership)
+    check_resign(resign, ownership=ownership)
     check_search_value(search_value)
-    check_leaves_per_step(leaves_per_step)
-    check_gumbel(gumbel, reuse_subtree, leaves_per_step, dirichlet_eps)
-    check_playout_cap(playout_cap, sims, reuse_subtree, leaves_per_step, gumbel)
-    check_forced_playouts(forced_playouts, reuse_subtree, leaves_per_step, gumbel)
-    check_fpu(fpu, reuse_subtree, leaves_per_step, gumbel)
-    check_solver(solver, reuse_subtree, leaves_per_step, gumbel, forced_playouts, fpu)
+    _check_search_options(sims, reuse_subtree, leaves_per_step, dirichlet_eps, gumbel, playout_cap, forced_playouts, fpu, solver)
     if evaluator is None:
         from .mlp import DeviceMLP
         evaluator = ("mlp_bf16" if isinstance(net, DeviceMLP) else "net_bf16") if net is not None else "uniform"

@@ -49,9 +49,9 @@ class MatchPlayer:
         k = check_leaves_per_step(self.leaves_per_step)
         gumbel = check_gumbel(self.gumbel, leaves_per_step=k)
         check_eval_cache(self.eval_cache)
-        check_fpu(self.fpu, False, k, self.gumbel)
-        check_solver(self.solver, False, k, self.gumbel, None, self.fpu)
-        check_early_stop(self.early_stop, False, k, self.gumbel, None, None, self.solver)
+        fpu = check_fpu(self.fpu, leaves_per_step=k, gumbel=gumbel)
+        solver = check_solver(self.solver, leaves_per_step=k, gumbel=gumbel, fpu=fpu)
+        check_early_stop(self.early_stop, leaves_per_step=k, gumbel=gumbel, solver=solver)
         is_mlp = type(self.net).__name__ == "DeviceMLP"
         ev = self.evaluator or (("mlp_f32" if is_mlp else "net_bf16") if self.net is not None else "uniform")
         if not isinstance(ev, str) or ev not in ("uniform", "hash", "net_f32", "net_bf16", "net_fp8", "mlp_f32", "mlp_bf16"):

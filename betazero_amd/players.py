@@ -166,10 +166,10 @@ class MCTSPlayer(Player):
         check_sims(sims)  # a ValueError naming the limit here, not a RuntimeError at the first get_move
         self.leaves_per_step = check_leaves_per_step(leaves_per_step)  # K walks per tree step
         self.gumbel = check_gumbel(gumbel, leaves_per_step=self.leaves_per_step)
-        self.fpu = check_fpu(fpu, False, self.leaves_per_step, gumbel)
-        self.solver = check_solver(solver, False, self.leaves_per_step, gumbel, None, fpu)
+        self.fpu = check_fpu(fpu, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel)
+        self.solver = check_solver(solver, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel, fpu=self.fpu)
         self.last_proven = None  # solver mode: the root's proven value of the last search (-1, 0, +1) or None
-        self.early_stop = check_early_stop(early_stop, False, self.leaves_per_step, gumbel, None, None, solver)
+        self.early_stop = check_early_stop(early_stop, leaves_per_step=self.leaves_per_step, gumbel=self.gumbel, solver=self.solver)
         self.last_sims = None  # early stop: the simulations the last search ran (<= sims)
         self.symbol, self.sims, self.net, self.c_puct, self.device = symbol, sims, net, c_puct, device
         # evaluator: "uniform" | "hash" | "net_bf16" | "net_f32" | "net_fp8", or a callable (own, opp, kind) -> (logits, value)

@@ -444,12 +444,51 @@ int32_t bz_engine_root_stats(bz_engine* e, void* stream);
 /* M5: pi, move choice, example row, env step, pass rule, terminal handling.
  * restart != 0: a finished slot starts its next game (next round) at once. */
 int32_t bz_engine_play(bz_engine* e, int32_t restart, void* stream);
+/* ---- The search options and the pairs that do not run together ("The search mode").  Fifteen switches change what a
+ * search does or records; three travel in the config (subtree reuse, leaves per step, Dirichlet noise), the others have a
+ * setter.  THE list of refused pairs, each in either order (csrc/bz_options.h is its code):
+ *   subtree reuse, and leaves_per_step > 1, with each of Gumbel root search, the playout cap, forced playouts, first-play urgency
+ *     reduction, the solver (concurrent walks race on proofs) and early stop;
+ *   Dirichlet noise with Gumbel root search;
+ *   Gumbel root search with the playout cap, forced playouts, first-play urgency reduction, the solver and early stop (sequential
+ *     halving is its own schedule);
+ *   the solver with forced playouts (both score +inf), first-play urgency reduction and early stop;
+ *   early stop with the playout cap, forced playouts, the root store (a shortened tree must not seed a later search) and the
+ *     observers surprise, search value, ownership and resignation (their targets and records come from complete searches);
+ *   ownership with resignation (a resigned game has no final board).
+ * Every other pair runs together.  A setter that would complete a refused pair returns BZ_EINVAL, a *_bytes function -1 and a
+ * *_check function BZ_EINVAL for a config that carries one half of it, and bz_last_error names the function, both options and how
+ * the other one is switched on.  (The Gumbel interior rule needs Gumbel root search and otherwise combines with what that
+ * combines with: a requirement, not a pair.) */
+enum {
+    BZ_OPT_REUSE_SUBTREE = 0,   /* cfg.flags & BZ_ENGINE_REUSE_SUBTREE */
+    BZ_OPT_LEAVES = 1,          /* cfg.flags: BZ_ENGINE_LEAVES_* says more than one leaf per step */
+    BZ_OPT_DIRICHLET = 2,       /* cfg.dirichlet_eps > 0 */
+    BZ_OPT_GUMBEL = 3,          /* bz_engine_set_gumbel */
+    BZ_OPT_GUMBEL_INTERIOR = 4, /* bz_engine_set_gumbel_interior */
+    BZ_OPT_PLAYOUT_CAP = 5,     /* bz_engine_set_playout_cap */
+    BZ_OPT_FORCED_PLAYOUTS = 6, /* bz_engine_set_forced_playouts */
+    BZ_OPT_FPU = 7,             /* bz_engine_set_fpu */
+    BZ_OPT_SOLVER = 8,          /* bz_engine_set_solver */
+    BZ_OPT_EARLY_STOP = 9,      /* bz_engine_set_early_stop */
+    BZ_OPT_ROOT_STORE = 10,     /* bz_engine_set_root_store */
+    BZ_OPT_SURPRISE = 11,       /* bz_engine_set_surprise */
+    BZ_OPT_SEARCH_VALUE = 12,   /* bz_engine_set_search_value */
+    BZ_OPT_OWNERSHIP = 13,      /* bz_engine_set_ownership */
+    BZ_OPT_RESIGN = 14,         /* bz_engine_set_resign */
+    BZ_OPT_COUNT = 15
+};
+/* 1 when options a and b (BZ_OPT_*) are a refused pair, 0 when they run together (a == b included); -1 for an id outside
+ * 0 .. BZ_OPT_COUNT - 1.  Host only. */
+int32_t bz_option_conflict(int32_t a, int32_t b);
+/* the phrase the refusals use for option a (static storage), or null for an id outside 0 .. BZ_OPT_COUNT - 1.  Host only. */
+const char* bz_option_name(int32_t a);
 /* Gumbel root search (Danihelka et al., ICLR 2022), opt-in per engine.  The root's edge of every walk is
  * chosen by Gumbel-top-k sampling plus sequential halving over the max_considered best root actions; every deeper level of
  * the walk stays PUCT.  The move is the considered action that survives the halving, and the example row's pi is the improved
  * policy softmax(log P + sigma(completed Q)).  Gumbel noise is drawn while moves made < cfg.temp_moves and gumbel_scale > 0
- * (tau = 1 visit sampling is not used in this mode).  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one
- * leaf per step, Dirichlet noise.  The evaluation cache works unchanged.  Searches go through the step kernels. */
+ * (tau = 1 visit sampling is not used in this mode).  Refused combinations: the list at BZ_OPT_*.  The evaluation cache works
+ * unchanged.  Searches go through the step kernels. */
 #define BZ_GUMBEL_MAX_CONSIDERED 64
 /* bytes of the caller-owned Gumbel buffer for cfg and max_considered (1..64): the considered-visit table u16
  * [max_considered][sims], every root edge's base value f32 [n_games][MAXCH] and the root's value f32 [n_games], each array
@@ -492,9 +531,8 @@ int32_t bz_gumbel_interior_pick(const uint32_t* N, const float* W, const float* 
  * caller still issues cfg.sims steps.  bz_engine_play records an example row for a full search only; a fast search plays its
  * move by the same rule and writes nothing, so a finished game may have ex_len = 0 (unfinished stays -1) -- the packed block
  * counts such a game in n_games.  Dirichlet noise is drawn on full searches only.  The budgets are drawn by
- * bz_engine_root_begin, so step-API callers need no new call.  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more
- * than one leaf per step, Gumbel root search.  Every evaluator and evaluation-cache mode works unchanged.  Searches go through
- * the step kernels. */
+ * bz_engine_root_begin, so step-API callers need no new call.  Refused combinations: the list at BZ_OPT_*.  Every evaluator and
+ * evaluation-cache mode works unchanged.  Searches go through the step kernels. */
 /* bytes of the caller-owned buffer: the budgets u32 [n_games] of the current search (0 = the slot took no part), rounded up
  * to 256 bytes.  Needs no GPU; -1 (bz_last_error says why) for a bad config or a refused combination. */
 int64_t bz_engine_playout_cap_bytes(const bz_engine_cfg* cfg);
@@ -512,15 +550,14 @@ int32_t bz_playout_cap_budget(uint64_t seed, uint64_t gid, uint32_t moves_made, 
  * lowest forced action.  Policy target pruning (prune != 0): the pi of the example row and of bz_engine_root_policy is N' / sum N'
  * with the N' of bz_forced_prune below; the move is chosen from the raw N as before, and bz_engine_root_stats
  * reports the raw N.  prune == 0: forcing alone, pi = N / sum N.  Under playout cap randomisation only the full searches force
- * (and only they record).  Refused (BZ_EINVAL with a message): subtree reuse, more than one leaf per step, Gumbel root search,
- * a negative or non-finite k.  Dirichlet noise, the playout cap, every evaluator and every evaluation-cache mode work
- * unchanged.  Searches go through the step kernels. */
+ * (and only they record).  Refused combinations: the list at BZ_OPT_*.  Also refused (BZ_EINVAL with a message): a negative or
+ * non-finite k.  Every evaluator and every evaluation-cache mode work unchanged.  Searches go through the step kernels. */
 /* switch forced playouts on (k > 0; KataGo's default is 2.0) or off (k == 0), between searches.  Nothing is uploaded: `stream`
  * is accepted for symmetry with the other setters. */
 int32_t bz_engine_set_forced_playouts(bz_engine* e, float k, int32_t prune, void* stream);
 /* BZ_OK when an engine of this config accepts bz_engine_set_forced_playouts(e, k, ...), else BZ_EINVAL (bz_last_error says
- * why: a bad config, a refused combination, a bad k).  Needs no GPU.  (Gumbel root search is not part of the config: the two
- * setters refuse each other.) */
+ * why: a bad config, a refused combination, a bad k).  Needs no GPU.  (It sees the config-carried options only: the setters
+ * refuse each other.) */
 int32_t bz_engine_forced_playouts_check(const bz_engine_cfg* cfg, float k);
 /* Policy target pruning of one root, the function the kernels run.  N, W, P [n]: the root edges' visits, value sums and priors
  * in edge order (ascending action), n in 1 .. 255, N[i] <= 16383, k finite and > 0.  N_out [n]: with c* the first maximum of N
@@ -543,11 +580,10 @@ int32_t bz_forced_prune(const uint32_t* N, const float* W, const float* P, int32
  *        u, s = q + u, the ascending order and the strict first maximum are unchanged.  No clamp: f may be below -1.
  * The Dirichlet noise is in the root's P when the mass is taken.  Both reductions may be 0 (an unvisited child is then worth
  * exactly its parent), which is still not "off".  bz_engine_root_stats, pi = N / sum N, the move choice and the example rows are
- * what they are without it.  Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step (virtual losses
- * sit in W_in), Gumbel root search (the two setters refuse each other), a negative or non-finite reduction.  Dirichlet noise,
- * the playout cap (fast searches use the rule too), forced playouts (the +inf of a forced edge still wins), surprise, search
- * value, evaluation symmetry, every evaluator (the external one through the step API included) and every evaluation-cache mode
- * work unchanged.  Searches go through the step kernels. */
+ * what they are without it.  Refused combinations: the list at BZ_OPT_*.  Also refused (BZ_EINVAL / -1 with a message): a negative
+ * or non-finite reduction.  Under the playout cap fast searches use the rule too; the +inf of a forced edge still wins.  Every
+ * evaluator (the external one through the step API included) and every evaluation-cache mode work unchanged.  Searches go through
+ * the step kernels. */
 /* bytes of the caller-owned buffer: Wr f32 [n_games], rounded up to 256 bytes.  Needs no GPU; -1 (bz_last_error says why) for a
  * bad config or a refused combination. */
 int64_t bz_engine_fpu_bytes(const bz_engine_cfg* cfg);
@@ -585,10 +621,8 @@ float bz_fpu_value(const uint32_t* N, const float* P, int32_t n, float q_node, f
  * Move (bz_engine_play, bz_engine_root_policy; bz_solver_pick is the function): the lowest root edge decided c = -1 at every
  *   temperature; otherwise the rule of DESIGN.md 3.7 over the edges not decided c = +1 (sampling: the draw modulo THEIR visit
  *   sum); when every edge is decided +1 or the remaining visit sum is 0, over all edges.  The recorded pi stays N / sum N.
- * Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step, Gumbel root search, forced playouts,
- * first-play urgency reduction (the setters refuse each other).  Dirichlet noise, the playout cap, surprise, search value,
- * ownership, evaluation symmetry, every evaluator (the external one through the step API), every evaluation-cache mode and
- * the root store work unchanged.  Searches go through the step kernels. */
+ * Refused combinations: the list at BZ_OPT_*.  Every evaluator (the external one through the step API) and every evaluation-cache
+ * mode work unchanged.  Searches go through the step kernels. */
 /* bytes of the caller-owned buffer: the roots' values i32 [n_games] and two u32 counts, each rounded up to 256 bytes.  Needs no
  * GPU; -1 (bz_last_error says why) for a bad config or a refused combination. */
 int64_t bz_engine_solver_bytes(const bz_engine_cfg* cfg);
@@ -624,10 +658,8 @@ int32_t bz_solver_pick(const uint32_t* N, const int8_t* vals, int32_t n, int32_t
  * Host exit (host_exit != 0): bz_engines_search with run_ahead_sims > 0 ends an engine's step loop as soon as a completed
  *   run-ahead mark shows that no slot of the engine walks any more -- no launch and no wait is added, the results are the same
  *   bits, only empty launches are saved.  bz_engine_search and bz_engines_step run every step.
- * Refused (BZ_EINVAL / -1 with a message): subtree reuse, more than one leaf per step, Gumbel root search, the playout cap,
- * forced playouts, the solver, the root store, surprise, search value, ownership and resignation (the setters refuse each
- * other).  First-play urgency reduction, evaluation symmetry, Dirichlet noise, temp_moves, every evaluator (the external one
- * through the step API) and every evaluation-cache mode work unchanged.  Searches go through the step kernels. */
+ * Refused combinations: the list at BZ_OPT_*.  temp_moves, every evaluator (the external one through the step API) and every
+ * evaluation-cache mode work unchanged.  Searches go through the step kernels. */
 /* bytes of the caller-owned buffer: stop_at u32 [n_games] and one u32 word, each rounded up to 256 bytes.  Needs no GPU; -1
  * (bz_last_error says why) for a bad config or a refused combination. */
 int64_t bz_engine_early_stop_bytes(const bz_engine_cfg* cfg);

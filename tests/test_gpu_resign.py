@@ -177,7 +177,7 @@ def _streaks(eng):
     """the engine's streak array u8 [rounds, B, 2] (side +1, side -1): the first array of the resignation buffer"""
     torch.cuda.synchronize()
     n = eng.rounds * eng.B * 2
-    return eng.zws[eng._zpad:eng._zpad + n].cpu().numpy().reshape(eng.rounds, eng.B, 2)
+    return eng._buffers["resign"][:n].cpu().numpy().reshape(eng.rounds, eng.B, 2)
 
 
 @pytest.mark.parametrize("reuse", [False, True])
@@ -398,7 +398,7 @@ def test_switching_it_off_restores_the_engine_without_it_and_off_is_off():
         blocks.append((_raw(e), e.counters()))
     assert np.array_equal(blocks[0][0], blocks[2][0]) and np.array_equal(blocks[1][0], blocks[2][0])
     assert blocks[0][1] == blocks[1][1] == blocks[2][1]
-    assert not hasattr(b, "zws") and not hasattr(c, "zws")  # no buffer, no launch
+    assert "resign" not in b._buffers and "resign" not in c._buffers  # no buffer, no launch
 
 
 def test_the_setter_refuses_a_small_buffer_and_ownership_in_either_order():
