@@ -271,6 +271,13 @@ _SIGS = {
     "bz_train_optim_partials": (i32, []),
     "bz_train_optim_hyper": (i32, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]),
     "bz_train_optim_step": (i32, [C.POINTER(TrainTensors), C.POINTER(TrainOptim), i32, i32, i32, vp]),
+    "bz_qat_weight_row": (i32, [vp, i32, vp, vp]),
+    "bz_qat_act": (C.c_float, [C.c_float]),
+    "bz_qat_act_batch": (i32, [vp, vp, i64, vp]),
+    "bz_train_qat_scales": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "bz_train_qat_pack_weights": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "bz_train_qat_tower_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "bz_train_qat_stem_fwd": (i32, [vp, i32, vp, vp, i32, vp, vp]),
     "bz_profile_enable": (i32, [i32]),
     "bz_profile_reserve": (i32, [i32, i64]),
     "bz_profile_read": (i32, [i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]),

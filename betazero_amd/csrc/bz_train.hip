@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "bz_common.h"
+#include "bz_qat.h"
 #include "bz_tower.h"
 
 using namespace bz;
@@ -116,7 +117,10 @@ __device__ __forceinline__ void epilogue_train(f32x16 (&acc)[G::MW][G::NU], char
 // The same for the 16x16x32 path (Tw<128, 4, true>; lane map of bz_tower.h's epilogue16): lane (c, g) register 4 (2a + b) + i
 // of unit u holds channel 32 wt + 16 a + 4 g + i of board cell (row u, column c & 7) of position 2 b + (c >> 3).  ReLU bits:
 // word 2a + b, bits 4u .. 4u + 3 -- again 128 bits per lane and layer.
-template <class G, bool BWD>
+// QAT (forward only): the ReLU'd fp32 value goes through the fp8 net's activation rule (bz_qat.h: one rounding
+// to e4m3(16 v) / 16, saturating at 28) before the bf16 store, which is then exact; the ReLU bits are still bf16_pos of what is
+// stored, so a positive value that rounds to 0 passes no gradient (the straight-through estimator's mask).
+template <class G, bool BWD, bool QAT = false>
 __device__ __forceinline__ void epilogue_train16(f32x16 (&acc)[G::MW][G::NU], char* out, bool second, const Bias<G>& bias, int wt,
                                                  int lane, unsigned (&bits)[4], bool use_bits) {
     static_assert(G::MW == 1 && G::NU == 8 && G::M16, "the 16x16x32 path serves the row-tile shape of the 128-channel net");
@@ -148,6 +152,7 @@ __device__ __forceinline__ void epilogue_train16(f32x16 (&acc)[G::MW][G::NU], ch
                         for (int i = 0; i < 4; ++i) v[i] = (nib >> i) & 1u ? v[i] : 0.0f;
                     } else {
                         v = __builtin_elementwise_maximum(v, (f32x4)(0.0f));
+                        if constexpr (QAT) v = qat_act_dev4(v);
                     }
                     f32x2 vlo = {v[0], v[1]}, vhi = {v[2], v[3]};
                     s16x2 lo = __builtin_bit_cast(s16x2, __builtin_convertvector(vlo, bf16x2));
@@ -175,7 +180,7 @@ template <class G> constexpr bool kCopyInEpilogue = G::ROWT;
 // (Rejected, code removed: a layer's result stored to HBM from its own epilogue, straight from the registers that go to LDS --
 // no copy pass at all, but 8 bytes per lane and store, 32-byte runs per cell: 10 % slower, profiles/r04_exp_epilogue_stores.txt;
 // and the copy pass dealt to the next K-loop's sub-steps: 5 % slower, profiles/r04_exp_kloop_copy.txt.)
-template <class G, bool BWD> struct EpTrain {
+template <class G, bool BWD, bool QAT = false> struct EpTrain {
     unsigned* bits;   // the lane's 128 ReLU bits of this layer (FWD: written, BWD: read)
     bool use_bits;
     const char* copy_buf;   // the workgroup's LDS tile to copy out first (this layer's input) ...
@@ -185,7 +190,8 @@ template <class G, bool BWD> struct EpTrain {
                                                int r, int h) const {
         if (kCopyInEpilogue<G> && copy_dst) store_tile<G>(copy_buf, copy_dst, 0, tid);
         unsigned (&b)[4] = *reinterpret_cast<unsigned (*)[4]>(bits);
-        if constexpr (G::M16) epilogue_train16<G, BWD>(acc, out, second, bias, wt0, 32 * h + r, b, use_bits);
+        static_assert(!QAT || (G::M16 && !BWD), "fp8 quantisation-aware training: the 128-channel forward only");
+        if constexpr (G::M16) epilogue_train16<G, BWD, QAT>(acc, out, second, bias, wt0, 32 * h + r, b, use_bits);
         else epilogue_train<G, BWD>(acc, out, second, bias, wt0, r, h, b, use_bits);
     }
 };
@@ -219,43 +225,13 @@ __device__ __forceinline__ void weights_prologue(WSets<G>& WS, const uint4*& ap,
 }
 
 // forward with saved activations: act[0] (HBM) -> act[1 .. L] (HBM) + ReLU bits
-template <class G>
-__global__ void __launch_bounds__(256, 1) k_train_fwd(TrainArgs T) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pos0 = blockIdx.x * G::P, r = lane & 31, h = lane >> 5;
-    if (pos0 >= T.n) return;
-    [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0};
-    char* bufX = smem;
-    char* bufM = smem + G::BUF;
-    zero_halo<G>(smem, tid);
-    const uint4* ap = T.wf + (size_t)G::wt0(w) * (G::M16 ? 2 * 64 : 64);
-    typename WSetsOf<G>::type WS;
-    weights_prologue<G>(WS, ap, lane);
-    load_tile<G>(bufX, T.in, pos0, tid);
-    __syncthreads();
-    const size_t slot = (size_t)T.n * 64 * G::C;                       // elements of one activation tensor
-    __bf16* const mine = T.out + (size_t)pos0 * 64 * G::C;             // the workgroup's positions in the first output tensor
-    const size_t mslot = (size_t)(T.n / G::P) * 256;                    // mask words of one layer
-    uint4* mk = T.masks + (size_t)blockIdx.x * 256 + tid;
-#pragma unroll 1
-    for (int blk = 0; blk < T.n_layers / 2; ++blk) {
-        unsigned bits[4];
-        // (act[2 blk] = X, the previous block's result, leaves in this layer's epilogue; act[0] came from HBM)
-        conv_layer<0, G>(bufX, bufM, false, T.bias + (size_t)(2 * blk) * G::C, WS, ap, w, r, h, tacc,
-                         EpTrain<G, false>{bits, true, bufX, blk > 0 ? mine + (size_t)(2 * blk - 1) * slot : nullptr, tid});
-        if constexpr (!kCopyInEpilogue<G>)
-            if (__bf16* cd = blk > 0 ? mine + (size_t)(2 * blk - 1) * slot : nullptr) store_tile<G>(bufX, cd, 0, tid);
-        mk[(size_t)(2 * blk) * mslot] = make_uint4(bits[0], bits[1], bits[2], bits[3]);
-        conv_layer<G::NCH % G::DEPTH, G>(bufM, bufX, true, T.bias + (size_t)(2 * blk + 1) * G::C, WS, ap, w, r, h, tacc,
-                                         EpTrain<G, false>{bits, true, bufM, mine + (size_t)(2 * blk) * slot, tid});
-        if constexpr (!kCopyInEpilogue<G>)
-            if (__bf16* cd = mine + (size_t)(2 * blk) * slot) store_tile<G>(bufM, cd, 0, tid);
-        mk[(size_t)(2 * blk + 1) * mslot] = make_uint4(bits[0], bits[1], bits[2], bits[3]);
-    }
-    store_tile<G>(bufX, mine + (size_t)(T.n_layers - 1) * slot, 0, tid);
-}
+// k_train_fwd<G> and k_qat_fwd
+#define BZ_TRAIN_QAT 0
+#include "bz_train_fwd_body.h"
+#undef BZ_TRAIN_QAT
+#define BZ_TRAIN_QAT 1
+#include "bz_train_fwd_body.h"
+#undef BZ_TRAIN_QAT
 
 // backward-data: g[L] (HBM) -> g[L-1 .. 0] (HBM).  g[l] = d(loss)/d(pre-activation of act[l]) for l >= 1, g[0] =
 // d(loss)/d(act[0]) (the stem's ReLU belongs to the caller).  Weight stream: layers L-1, L-2, .., 0, each with mirrored
@@ -355,6 +331,71 @@ __global__ void __launch_bounds__(256) k_pack_weights16(const float* __restrict_
     }
     wf_fwd[idx] = __builtin_bit_cast(uint4, f);
     wf_bwd[((((((long long)(L - 1 - l) * 9 + t) * KQ + kq) * MT + wt) * 2 + a) * 64) + lane] = __builtin_bit_cast(uint4, b);
+}
+
+// ---- fp8 quantisation-aware training (bz_qat.h): the weights the forward AND backward-data see are the fp8
+// net's, w_q = e4m3(bf16(w) s) / s with the engine's per-output-channel power-of-two scale s
+// k_qat_scales: one wave per row -- the L C output channels of the tower (C 9 contiguous floats each, torch's [L][co][ci][3][3]),
+// then the 3 head conv1x1 rows (pol.weight [2][C], val.weight [C]).  A maximum has no order: a lane's running maximum, then a
+// butterfly; no atomics.  The head rows leave fake-quantised in `head_q` [3][C], the shadow the head kernels read.
+__global__ void __launch_bounds__(256) k_qat_scales(const float* __restrict__ W, const float* __restrict__ pol_w, const float* __restrict__ val_w,
+                                                    int L, int C, float* __restrict__ scales, float* __restrict__ head_q) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), rows = L * C + 3;
+    if (row >= rows) return;
+    const int hr = row - L * C;   // >= 0: a head row
+    const float* src = hr < 0 ? W + (size_t)row * C * 9 : (hr < 2 ? pol_w + hr * C : val_w);
+    const int n = hr < 0 ? C * 9 : C;
+    float m = 0.0f;
+    for (int i = lane; i < n; i += 64) m = qat_absmax(m, qat_bf16(src[i]));
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = qat_absmax(m, __shfl_xor(m, o));
+    const float s = qat_pow2_scale(m);
+    if (lane == 0) scales[row] = s;
+    if (hr >= 0)
+        for (int i = lane; i < C; i += 64) head_q[hr * C + i] = qat_weight(qat_bf16(src[i]), s);
+}
+
+// k_qat_pack: k_pack_weights16's two fragment streams with every entry w_q in place of bf16(w) (exact in bf16); the mirrored
+// backward stream is quantised with the scale of its OUTPUT channel (the backward's k index), like the forward's
+__global__ void __launch_bounds__(256) k_qat_pack(const float* __restrict__ W, const float* __restrict__ scales, uint4* __restrict__ wf_fwd,
+                                                  uint4* __restrict__ wf_bwd, int L, int C) {
+    const int KQ = C / 32, MT = C / 32;
+    const long long total = (long long)L * 9 * KQ * MT * 2 * 64;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int lane = (int)(idx & 63), c = lane & 15, g = lane >> 4;
+    long long rest = idx >> 6;
+    const int a = (int)(rest & 1); rest >>= 1;
+    const int wt = (int)(rest % MT); rest /= MT;
+    const int kq = (int)(rest % KQ); rest /= KQ;
+    const int t = (int)(rest % 9);
+    const int l = (int)(rest / 9);
+    const float* Wl = W + (size_t)l * C * C * 9;
+    const float* sl = scales + (size_t)l * C;
+    const int m = 32 * wt + 16 * a + c;
+    const float sm = sl[m];
+    bf16x8 f, b;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int k = 32 * kq + 8 * g + j;
+        f[j] = (__bf16)qat_weight(qat_bf16(Wl[((size_t)m * C + k) * 9 + t]), sm);
+        b[j] = (__bf16)qat_weight(qat_bf16(Wl[((size_t)k * C + m) * 9 + (8 - t)]), sl[k]);
+    }
+    wf_fwd[idx] = __builtin_bit_cast(uint4, f);
+    wf_bwd[((((((long long)(L - 1 - l) * 9 + t) * KQ + kq) * MT + wt) * 2 + a) * 64) + lane] = __builtin_bit_cast(uint4, b);
+}
+
+// the epilogues' device form of the activation rule over an array (4 values per thread), for the test that pins it to bz_qat_act
+__global__ void __launch_bounds__(256) k_qat_act_batch(const float* __restrict__ in, float* __restrict__ out, long long n) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? in[i + j] : 0.0f;
+    v = qat_act_dev4(__builtin_elementwise_maximum(v, (f32x4)(0.0f)));
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i + j < n) out[i + j] = v[j];
 }
 
 // ---- backward-weights
@@ -659,5 +700,65 @@ BZ_EXPORT int32_t bz_train_wgrad(const void* acts, const void* gs, int32_t C, in
         hipLaunchKernelGGL(k_train_wgrad<128>, dim3(grid), dim3(Wg<128>::NT), Wg<128>::LDS, s, T);
     }
     BZ_LAUNCH_CHECK("k_train_wgrad");
+    return BZ_OK;
+}
+
+// ---- fp8 quantisation-aware training: offered where the fp8 tower exists, C == 128
+BZ_EXPORT int32_t bz_qat_weight_row(const float* w, int32_t n, float* w_q, float* scale) {
+    BZ_REQUIRE(w && w_q && n >= 1, "bz_qat_weight_row: bad arguments");
+    float m = 0.0f;
+    for (int32_t i = 0; i < n; ++i) m = qat_absmax(m, qat_bf16(w[i]));
+    const float s = qat_pow2_scale(m);
+    for (int32_t i = 0; i < n; ++i) w_q[i] = qat_weight(qat_bf16(w[i]), s);
+    if (scale) *scale = s;
+    return BZ_OK;
+}
+BZ_EXPORT float bz_qat_act(float v) { return qat_act(v); }
+BZ_EXPORT int32_t bz_qat_act_batch(const float* in, float* out, int64_t n, void* stream) {
+    BZ_REQUIRE(in && out && n >= 1 && n <= (int64_t(1) << 33), "bz_qat_act_batch: bad arguments");
+    if (bz_device_count() <= 0) { set_error("bz_qat_act_batch: no HIP device"); return BZ_ENOGPU; }
+    hipLaunchKernelGGL(k_qat_act_batch, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, in, out, (long long)n);
+    BZ_LAUNCH_CHECK("k_qat_act_batch");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_train_qat_scales(const float* W, const float* pol_w, const float* val_w, int32_t C, int32_t n_layers, float* scales,
+                                      float* head_q, void* stream) {
+    BZ_REQUIRE(C == 128, "bz_train_qat_scales: fp8 quantisation-aware training is built for C == 128 (the fp8 tower's channel count)");
+    BZ_REQUIRE(W && pol_w && val_w && scales && head_q && train_shape_ok(C, n_layers, 1), "bz_train_qat_scales: bad arguments (n_layers even)");
+    if (bz_device_count() <= 0) { set_error("bz_train_qat_scales: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    const int rows = n_layers * C + 3;
+    hipLaunchKernelGGL(k_qat_scales, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, pol_w, val_w, n_layers, C, scales, head_q);
+    BZ_LAUNCH_CHECK("k_qat_scales");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_train_qat_pack_weights(const float* W, const float* scales, int32_t C, int32_t n_layers, void* wf_fwd, void* wf_bwd,
+                                            void* stream) {
+    BZ_REQUIRE(C == 128, "bz_train_qat_pack_weights: fp8 quantisation-aware training is built for C == 128 (the fp8 tower's channel count)");
+    BZ_REQUIRE(W && scales && wf_fwd && wf_bwd && train_shape_ok(C, n_layers, 1), "bz_train_qat_pack_weights: bad arguments (n_layers even)");
+    if (bz_device_count() <= 0) { set_error("bz_train_qat_pack_weights: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    const long long total = (long long)n_layers * 9 * (C / 32) * (C / 32) * 2 * 64;
+    hipLaunchKernelGGL(k_qat_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, scales,
+                       static_cast<uint4*>(wf_fwd), static_cast<uint4*>(wf_bwd), n_layers, C);
+    BZ_LAUNCH_CHECK("k_qat_pack");
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_train_qat_tower_fwd(const void* act0, const void* wf_fwd, const float* bias, int32_t C, int32_t n_layers, int32_t n,
+                                         void* acts_out, void* masks, void* stream) {
+    BZ_REQUIRE(C == 128, "bz_train_qat_tower_fwd: fp8 quantisation-aware training is built for C == 128 (the fp8 tower's channel count)");
+    BZ_REQUIRE(act0 && wf_fwd && bias && acts_out && masks && train_shape_ok(C, n_layers, n), "bz_train_qat_tower_fwd: bad arguments (n_layers even)");
+    typedef Tw<128, 4, true> G;
+    BZ_REQUIRE(n % G::P == 0, "bz_train_qat_tower_fwd: the batch must be a multiple of the 4 positions per workgroup");
+    if (bz_device_count() <= 0) { set_error("bz_train_qat_tower_fwd: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    TrainArgs T;
+    T.n = n; T.n_layers = n_layers; T.wf = static_cast<const uint4*>(wf_fwd); T.bias = bias; T.in = static_cast<const __bf16*>(act0);
+    T.out = static_cast<__bf16*>(acts_out); T.masks = static_cast<uint4*>(masks);
+    static unsigned done = 0;   // per device
+    if (hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_qat_fwd), G::LDS, &done); e != hipSuccess)
+        return hip_fail(e, "hipFuncSetAttribute(k_qat_fwd)");
+    hipLaunchKernelGGL(k_qat_fwd, dim3(n / G::P), dim3(256), G::LDS, (hipStream_t)stream, T);
+    BZ_LAUNCH_CHECK("k_qat_fwd");
     return BZ_OK;
 }

@@ -15,6 +15,7 @@
 // FC 128 -> 65 | value: conv1x1 C -> 1, ReLU, FC 64 -> VH, ReLU, FC VH -> 1, tanh.  Loss = mean CE(pi, softmax) + mean
 // (v - z)^2 (betazero_amd/train.py).
 #include "bz_common.h"
+#include "bz_qat.h"
 
 using namespace bz;
 
@@ -86,9 +87,11 @@ __device__ __forceinline__ bool batch_row_bad(const bz_train_batch& B, int p) {
 // stem forward: act0[pos][cell][c] = relu(b[c] + sum_k nbhd_k * w[c][k]), k = 9 plane + tap (torch's [C][2][3][3]).
 // A workgroup takes 4 positions; a thread owns 8 channels (its 8 x 18 weights in registers) and walks the rows
 // (position, cell), so that the lanes of a row write one contiguous 16-byte piece each.
-template <int C>
-__global__ __launch_bounds__(256) void k_train_stem(const bz_train_batch* __restrict__ batch, int n, const float* __restrict__ w,
-                                                    const float* __restrict__ b, __bf16* __restrict__ act0) {
+// (QAT, DESIGN.md 12.3: the output goes through the fp8 net's activation rule, e4m3(16 relu(.)) / 16 from the fp32 sum, before
+// the bf16 store, which is then exact -- k_qat_stem)
+template <int C, bool QAT>
+__device__ __forceinline__ void train_stem_body(const bz_train_batch* __restrict__ batch, int n, const float* __restrict__ w,
+                                                const float* __restrict__ b, __bf16* __restrict__ act0) {
     constexpr int CG = C / 8, RPP = 256 / CG;
     __shared__ unsigned nb[256];
     const int tid = threadIdx.x, pos0 = blockIdx.x * 4;
@@ -122,10 +125,29 @@ __global__ __launch_bounds__(256) void k_train_stem(const bz_train_batch* __rest
             for (int j = 0; j < 8; ++j) acc[j] = fmaf(f, wr[j][k], acc[j]);
         }
         u32x4 o;
+        if constexpr (QAT) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = pack2(relu(acc[2 * j]), relu(acc[2 * j + 1]));
+            for (int j = 0; j < 2; ++j) {
+                const qat_f32x4 v = {relu(acc[4 * j]), relu(acc[4 * j + 1]), relu(acc[4 * j + 2]), relu(acc[4 * j + 3])};
+                const qat_f32x4 a = qat_act_dev4(v);
+                o[2 * j] = pack2(a[0], a[1]);
+                o[2 * j + 1] = pack2(a[2], a[3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = pack2(relu(acc[2 * j]), relu(acc[2 * j + 1]));
+        }
         *reinterpret_cast<u32x4*>(act0 + ((size_t)p * 64 + (row & 63)) * C + 8 * cg) = o;
     }
+}
+template <int C>
+__global__ __launch_bounds__(256) void k_train_stem(const bz_train_batch* __restrict__ batch, int n, const float* __restrict__ w,
+                                                    const float* __restrict__ b, __bf16* __restrict__ act0) {
+    train_stem_body<C, false>(batch, n, w, b, act0);
+}
+__global__ __launch_bounds__(256) void k_qat_stem(const bz_train_batch* __restrict__ batch, int n, const float* __restrict__ w,
+                                                  const float* __restrict__ b, __bf16* __restrict__ act0) {
+    train_stem_body<128, true>(batch, n, w, b, act0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -798,6 +820,17 @@ BZ_EXPORT int32_t bz_train_stem_fwd(const bz_train_batch* batch_dev, int32_t n, 
     if (C == 64) hipLaunchKernelGGL(k_train_stem<64>, grid, dim3(256), 0, (hipStream_t)stream, batch_dev, n, stem_w, stem_b, static_cast<__bf16*>(act0));
     else hipLaunchKernelGGL(k_train_stem<128>, grid, dim3(256), 0, (hipStream_t)stream, batch_dev, n, stem_w, stem_b, static_cast<__bf16*>(act0));
     BZ_LAUNCH_CHECK("k_train_stem");
+    return BZ_OK;
+}
+
+/* bz_train_stem_fwd with the fp8 net's activation rule on its output (k_qat_stem) */
+BZ_EXPORT int32_t bz_train_qat_stem_fwd(const bz_train_batch* batch_dev, int32_t n, const float* stem_w, const float* stem_b, int32_t C,
+                                        void* act0, void* stream) {
+    BZ_REQUIRE(C == 128, "bz_train_qat_stem_fwd: fp8 quantisation-aware training is built for C == 128 (the fp8 tower's channel count)");
+    BZ_REQUIRE(batch_dev && stem_w && stem_b && act0 && ends_shape_ok(C, n), "bz_train_qat_stem_fwd: bad arguments (n a multiple of 4)");
+    if (bz_device_count() <= 0) { set_error("bz_train_qat_stem_fwd: no HIP device (the training kernels have no CPU path)"); return BZ_ENOGPU; }
+    hipLaunchKernelGGL(k_qat_stem, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, batch_dev, n, stem_w, stem_b, static_cast<__bf16*>(act0));
+    BZ_LAUNCH_CHECK("k_qat_stem");
     return BZ_OK;
 }
 

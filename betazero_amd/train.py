@@ -40,15 +40,19 @@ def ownership_targets(fown, fopp):
     return (((fown[:, None] >> sh) & 1) - ((fopp[:, None] >> sh) & 1)).to(torch.float32)
 
 
-def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False, ownership=None, own_weight=1.0):
+def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False, ownership=None, own_weight=1.0,
+               fp8_qat=False):
     """one Adam step on the rows `idx` of ex (Reversi 8x8 net).  ex: DeviceExamples (stays on the GPU; idx a device
     index tensor or None = all rows) or host Examples (uploaded first).  Returns (loss, policy CE, value MSE) as
     detached device scalars.  value_targets: the value MSE is against ex.vt (fp32) instead of z.
     ownership: an OwnershipHead on the trunk's output, trained on ex.fown / ex.fopp -- the loss gains
     own_weight * L_own, L_own = the mean over positions and all 64 cells of (o - t)^2, and a fourth value, L_own, is returned.
-    The optimizer must then hold the head's parameters too."""
-    from .train_kernels import check_own_weight
+    The optimizer must then hold the head's parameters too.
+    fp8_qat: the forward is quant.qat_forward -- the fp8 net's arithmetic in fp32 torch, straight-through
+    gradients -- instead of the module's under autocast (128 channels only)."""
+    from .train_kernels import check_fp8_qat, check_own_weight
     own_weight = check_own_weight(own_weight)
+    check_fp8_qat(fp8_qat, module)
     if isinstance(ex, Examples):
         ex = DeviceExamples.from_host(ex, device)
     if value_targets and ex.vt is None:
@@ -64,13 +68,19 @@ def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, 
     else:
         idx = torch.as_tensor(idx, device=dev)
         own, opp, pi, z = ex.own[idx], ex.opp[idx], ex.pi[idx], (ex.vt if value_targets else ex.z)[idx]
-    x = planes_from_bits(own, opp)
-    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-        if ownership is None:
-            logits, v = module(x)
-        else:
-            logits, v, trunk = module(x, trunk=True)
-            o = ownership.to(dev)(trunk)
+    if fp8_qat:
+        from .quant import qat_forward
+        logits, v, saved = qat_forward(module, own, opp, acts=True)
+        if ownership is not None:
+            o = ownership.to(dev)(saved[-1])
+    else:
+        x = planes_from_bits(own, opp)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            if ownership is None:
+                logits, v = module(x)
+            else:
+                logits, v, trunk = module(x, trunk=True)
+                o = ownership.to(dev)(trunk)
     logits, v = logits.float(), v.float()
     ce = -(pi * F.log_softmax(logits, dim=1)).sum(1).mean()
     mse = F.mse_loss(v, z.to(torch.float32))
@@ -104,14 +114,14 @@ def select_rows(ex, idx):
 
 
 @torch.no_grad()
-def validate(device_net, ex, idx=None, symmetry=None):
+def validate(device_net, ex, idx=None, symmetry=None, fp8=False):
     """The validation line of the reference's training loop (SL/train.py:121-146: loss and accuracy on the held-out rows
     after every epoch) for (s, pi, z) examples, on the net the SEARCH uses -- the engine's bf16 MFMA forward
     (DeviceNet.forward), i.e. on the weights as they will play: mean policy cross-entropy against pi, value MSE against z,
     and top-1 agreement (argmax of the logits == argmax of pi; the reference's accuracy is `predicted == actions.argmax`,
     :139-142).  Everything stays on the GPU; returns a dict of Python floats (one synchronisation).
     symmetry: passed to DeviceNet.forward with the examples' board size -- e.g. "mean" validates the
-    symmetrised net; None (the default) is the plain forward."""
+    symmetrised net; None (the default) is the plain forward.  fp8: the engine's fp8 forward instead (what net_fp8 searches use)."""
     own, opp, pi, z = (ex.own, ex.opp, ex.pi, ex.z) if idx is None else (ex.own[idx], ex.opp[idx], ex.pi[idx], ex.z[idx])
     n = int(own.shape[0])
     if n == 0:
@@ -121,9 +131,9 @@ def validate(device_net, ex, idx=None, symmetry=None):
     for a in range(0, n, device_net.max_batch):
         b = min(n, a + device_net.max_batch)
         if symmetry is None:
-            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous())
+            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous(), fp8=fp8)
         else:
-            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous(), symmetry=symmetry, size=ex.size)
+            logits, v = device_net.forward(own[a:b].contiguous(), opp[a:b].contiguous(), symmetry=symmetry, size=ex.size, fp8=fp8)
         ce += -(pi[a:b] * F.log_softmax(logits, dim=1)).sum()
         se += ((v - z[a:b].to(torch.float32)) ** 2).sum()
         hit += (logits.argmax(1) == pi[a:b].argmax(1)).sum()
@@ -145,7 +155,14 @@ class GraphedTrainStep:
 
     def __init__(self, module, lr=1e-4, batch=1024, na=65, device="cuda:0", autocast=True, tower_kernels=None, lr_warmup_steps=0,
                  step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False, weight_decay=0.0, clip_norm=0.0,
-                 ema_decay=None, decay_biases=False, ownership=None, own_weight=1.0):
+                 ema_decay=None, decay_biases=False, ownership=None, own_weight=1.0, fp8_qat=False):
+        # fp8_qat: quantisation-aware training for the fp8 net, inside the all-kernel step (StepPlan(fp8_qat=True):
+        # the four k_qat_* kernels in place of stem / pack / tower forward, one launch more in the same graph).  128 channels
+        # only, and any other form of the step refuses it.
+        from .train_kernels import check_fp8_qat
+        self.fp8_qat = check_fp8_qat(fp8_qat, module)
+        if self.fp8_qat and (step_kernels is False or not getattr(module, "fused_tower", False) or not autocast or na != 65):
+            raise ValueError("fp8_qat=True needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels)")
         # ownership: an OwnershipHead trained next to the net on the examples' fown / fopp, inside the all-kernel
         # step (StepPlan(ownership=...): k_train_heads_own and one more launch, k_train_own_finish, in the same graph); the loss
         # is CE + MSE + own_weight * L_own and __call__ returns L_own as a fourth value.  Any other form of the step refuses it.
@@ -185,12 +202,14 @@ class GraphedTrainStep:
                 if ownership is not None:
                     ownership.to(device)
                 self.step_plan = self.plan = StepPlan(self.module, batch, device, value_targets=self.value_targets, ownership=ownership,
-                                                      own_weight=self.own_weight)
+                                                      own_weight=self.own_weight, fp8_qat=self.fp8_qat)
                 self.idx = torch.zeros(batch, dtype=torch.int64, device=self.dev)   # the batch's rows: the kernels gather them themselves
             else:
                 self.plan = TowerPlan(module.C, 2 * module.NB, batch, device)
         if ownership is not None and self.step_plan is None:
             raise ValueError("ownership= needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels, fused_adam)")
+        if self.fp8_qat and self.step_plan is None:
+            raise ValueError("fp8_qat=True needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels)")
         # lr_warmup_steps > 0: the learning rate ramps linearly from lr / warmup to lr over the first steps.  Adam's first
         # updates move every weight by ~lr whatever the gradient's size; at the loop demo's lr = 2e-3 that kills the
         # single-channel value head's ReLU (and in 2 of 4 seeds every head ReLU, i.e. the whole net) within the first

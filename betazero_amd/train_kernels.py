@@ -136,6 +136,15 @@ def check_own_weight(own_weight):
     return float(w)
 
 
+def check_fp8_qat(fp8_qat, module):
+    """fp8 quantisation-aware training exists where the fp8 tower does: 128 channels; anything else is refused
+    (ValueError, before any device is touched)"""
+    if fp8_qat and getattr(module, "C", None) != 128:
+        raise ValueError(f"fp8_qat: the fp8 tower is built for 128 channels (got {getattr(module, 'C', None)}); "
+                         "quantisation-aware training is offered for that net only")
+    return bool(fp8_qat)
+
+
 class StepPlan(TowerPlan):
     """forward + losses + backward (+ Adam) of one training step of `module` (PolicyValueNet(fused_tower=True), on the
     device) at a fixed batch size, entirely on the HIP kernels:
@@ -161,8 +170,13 @@ class StepPlan(TowerPlan):
                 "val_w": module.val.weight, "val_b": module.val.bias, "v1_w": module.v1.weight, "v1_b": module.v1.bias,
                 "v2_w": module.v2.weight, "v2_b": module.v2.bias}
 
-    def __init__(self, module, batch, device="cuda:0", value_targets=False, ownership=None, own_weight=1.0):
-        """value_targets: the head kernel reads a float value target per row (set_batch(..., vt=...)) in place
+    def __init__(self, module, batch, device="cuda:0", value_targets=False, ownership=None, own_weight=1.0, fp8_qat=False):
+        """fp8_qat: quantisation-aware training for the fp8 net -- the step's forward is bz_net_forward_fp8's
+        arithmetic (k_qat_stem, k_qat_scales, k_qat_pack, k_qat_fwd in place of the stem, the weight packing and the tower
+        forward: one launch more), the backward the straight-through estimator: the gradients with respect to the quantised
+        weights land in the fp32 masters' .grad.  128 channels only (the fp8 tower's); composes with every option below.
+
+        value_targets: the head kernel reads a float value target per row (set_batch(..., vt=...)) in place
         of z, through k_train_heads_vt; everything else of the step is the same.
 
         ownership: an OwnershipHead(C) -- the head kernel becomes k_train_heads_own (or its _vt form), which
@@ -178,6 +192,7 @@ class StepPlan(TowerPlan):
             raise ValueError("StepPlan needs PolicyValueNet(..., fused_tower=True)")
         if module.VH > 64:
             raise ValueError("the head kernels hold the value head's hidden layer in one wavefront: value_hidden <= 64")
+        check_fp8_qat(fp8_qat, module)
         super().__init__(module.C, 2 * module.NB, batch, device)
         L, dev = _lib.lib(), self.device
         self.module, self.VH = module, module.VH
@@ -194,6 +209,12 @@ class StepPlan(TowerPlan):
         self.hv, self.dl, self.dv1 = f32(batch, 192), f32(batch, 65), f32(batch, 64)
         self.losses = f32(4)   # loss, CE, MSE and the error word: batch positions whose row index was out of range, summed over steps
         self._head = _lib.TrainHeadParams(**{k: named[k].data_ptr() for k, _ in _lib.TrainHeadParams._fields_})
+        # fp8_qat: the per-output-channel scales (tower, then the 3 head rows) and the fake-quantised shadow of the head conv1x1
+        # rows, which the head kernels read in place of the masters (their gradients still go to the masters' .grad)
+        self.fp8_qat = bool(fp8_qat)
+        if self.fp8_qat:
+            self.qat_scales, self.qat_head = f32(self.L * self.C + 3), f32(3, self.C)
+            self._head.pol_w, self._head.val_w = self.qat_head.data_ptr(), self.qat_head[2].data_ptr()
         self._grads = _lib.TrainTensors(**{k: named[k].grad.data_ptr() for k in self.NAMES})
         self._partials = _lib.TrainPartials(tower=self.partial.data_ptr(), tower_b=self.db_partial.data_ptr(), stem=self.stem_partial.data_ptr(),
                                             heads=self.heads_partial.data_ptr(), heads_w=self.heads_w_partial.data_ptr(), splits=self.splits)
@@ -391,7 +412,8 @@ class StepPlan(TowerPlan):
     # ---- the launches
     def launch(self, adam=False):
         """the 9 (adam: 10, or 11 with the extended optimiser) launches of one step on the current stream (no host work besides:
-        this is what a HIP graph captures); with the ownership head one more, k_train_own_finish, at the end"""
+        this is what a HIP graph captures); with the ownership head one more, k_train_own_finish, at the end; with fp8_qat one
+        more, k_qat_scales, in front of the weight packing"""
         L, p, n, Cc, Ly = _lib.lib(), self.params, self.n, self.C, self.L
         if self._batch_refs is None:
             raise RuntimeError("StepPlan: set_batch() first")
@@ -402,10 +424,19 @@ class StepPlan(TowerPlan):
         with torch.cuda.device(self.device):
             st, bd = self._stream(), self.batch_desc.data_ptr()
             chk = _lib.check
-            chk(L.bz_train_stem_fwd(bd, n, p["stem_w"].data_ptr(), p["stem_b"].data_ptr(), Cc, self.acts[0].data_ptr(), st))
-            chk(L.bz_train_pack_weights(p["tower_w"].data_ptr(), Cc, Ly, self.wf_fwd.data_ptr(), self.wf_bwd.data_ptr(), st))
-            chk(L.bz_train_tower_fwd(self.acts[0].data_ptr(), self.wf_fwd.data_ptr(), p["tower_b"].data_ptr(), Cc, Ly, n, self.acts[1].data_ptr(),
-                                     self.masks.data_ptr(), st))
+            if self.fp8_qat:
+                chk(L.bz_train_qat_stem_fwd(bd, n, p["stem_w"].data_ptr(), p["stem_b"].data_ptr(), Cc, self.acts[0].data_ptr(), st))
+                chk(L.bz_train_qat_scales(p["tower_w"].data_ptr(), p["pol_w"].data_ptr(), p["val_w"].data_ptr(), Cc, Ly,
+                                          self.qat_scales.data_ptr(), self.qat_head.data_ptr(), st))
+                chk(L.bz_train_qat_pack_weights(p["tower_w"].data_ptr(), self.qat_scales.data_ptr(), Cc, Ly, self.wf_fwd.data_ptr(),
+                                                self.wf_bwd.data_ptr(), st))
+                chk(L.bz_train_qat_tower_fwd(self.acts[0].data_ptr(), self.wf_fwd.data_ptr(), p["tower_b"].data_ptr(), Cc, Ly, n,
+                                             self.acts[1].data_ptr(), self.masks.data_ptr(), st))
+            else:
+                chk(L.bz_train_stem_fwd(bd, n, p["stem_w"].data_ptr(), p["stem_b"].data_ptr(), Cc, self.acts[0].data_ptr(), st))
+                chk(L.bz_train_pack_weights(p["tower_w"].data_ptr(), Cc, Ly, self.wf_fwd.data_ptr(), self.wf_bwd.data_ptr(), st))
+                chk(L.bz_train_tower_fwd(self.acts[0].data_ptr(), self.wf_fwd.data_ptr(), p["tower_b"].data_ptr(), Cc, Ly, n,
+                                         self.acts[1].data_ptr(), self.masks.data_ptr(), st))
             if self._own is not None and self._own_ref is None:
                 raise RuntimeError("StepPlan: set_batch(..., fown=..., fopp=...) first")
             if self.value_targets and self._vt_ref is None:

@@ -1201,6 +1201,39 @@ int32_t bz_train_optim_hyper(float lr, float steps_done, float warmup_steps, flo
 int32_t bz_train_optim_step(const bz_train_tensors* G, const bz_train_optim* opt, int32_t C, int32_t n_layers, int32_t VH, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* fp8 quantisation-aware training: the step's forward is the */
+/* fp8 net's (bz_net_forward_fp8), run on the bf16 MFMA training tower with   */
+/* exact operands; the backward is the straight-through estimator.  The rule  */
+/* (csrc/bz_qat.h; betazero_amd/quant.py):                                    */
+/*   weights     : w_b = bf16_RNE(w); m = max |w_b| over the output channel   */
+/*                 (a NaN is skipped); s = 2^floor(log2(448 / m)), 1 for m = 0;*/
+/*                 w_q = e4m3_RNE_sat(w_b s) / s (a NaN weight stays a NaN)     */
+/*   activations : a = e4m3_RNE_sat(16 maximum(v, +0)) / 16 from the fp32 value */
+/*                 (one rounding; a NaN passes, +inf becomes 28)               */
+/* Offered where the fp8 tower exists: C == 128, anything else is BZ_EINVAL.  */
+/* ------------------------------------------------------------------------ */
+/* host: one output channel (n = C 9 for a tower channel, C for a head row); scale may be NULL */
+int32_t bz_qat_weight_row(const float* w, int32_t n, float* w_q, float* scale);
+/* host: the stored activation of the fp32 value v */
+float bz_qat_act(float v);
+/* device: the kernels' form of bz_qat_act (the fp8 conversion instructions) over n floats in device memory */
+int32_t bz_qat_act_batch(const float* in, float* out, int64_t n, void* stream);
+/* k_qat_scales: scales [n_layers C + 3] = the tower's per-output-channel scales, then those of the 3 head conv1x1 rows (pol.weight
+ * [2][C], val.weight [C]); head_q [3][C] = those rows fake-quantised (what bz_train_head_params.pol_w / val_w point at in a QAT
+ * step: the gradients still go to the masters) */
+int32_t bz_train_qat_scales(const float* W, const float* pol_w, const float* val_w, int32_t C, int32_t n_layers, float* scales,
+                            float* head_q, void* stream);
+/* k_qat_pack: bz_train_pack_weights' two streams with w_q in every entry (backward-data sees the quantised weights too) */
+int32_t bz_train_qat_pack_weights(const float* W, const float* scales, int32_t C, int32_t n_layers, void* wf_fwd, void* wf_bwd,
+                                  void* stream);
+/* k_qat_fwd / k_qat_stem: bz_train_tower_fwd / bz_train_stem_fwd with the activation rule on every stored activation; the ReLU
+ * masks are those of the STORED values (a positive value that rounds to 0 passes no gradient; saturation at 28 is not masked) */
+int32_t bz_train_qat_tower_fwd(const void* act0, const void* wf_fwd, const float* bias, int32_t C, int32_t n_layers, int32_t n,
+                               void* acts_out, void* masks, void* stream);
+int32_t bz_train_qat_stem_fwd(const bz_train_batch* batch_dev, int32_t n, const float* stem_w, const float* stem_b, int32_t C, void* act0,
+                              void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* In-library kernel timers: HIP events recorded on the launch stream around  */
 /* each launch of the named kernel (off by default; bench.py turns them on).  */
 /* ------------------------------------------------------------------------ */

@@ -13,6 +13,9 @@
       -> validation on the held-out rows with the engine's own bf16 MFMA forward (validate: policy CE, value MSE, top-1
          agreement -- the reference's per-epoch validation line, SL/train.py:121-146)
       -> weights pushed back into the engine's net (refresh_device_net)
+      -> with --fp8: all of the above with the fp8 net in the loop (net_fp8 self-play, gate and arena; 128 channels) and the
+         training step quantisation-aware (fp8_qat: the fp8 net's forward, straight-through gradients -- DESIGN.md 12.3);
+         --fp8-no-qat keeps the plain bf16 step as the ablation.  The validation line is then the fp8 forward's too
       -> batched arena against the reference's depth-limited minimax player (play_arena)
       -> with --gate-games N: a head-to-head match (play_match) of the freshly trained net against the net
          self-play currently uses; the candidate is promoted to self-play only at score >= --gate-score (AlphaGo Zero's
@@ -153,6 +156,11 @@ def main():
                     "target (the step then trains on float value targets); the held-out rows stay as they are.  Not with --ownership")
     ap.add_argument("--merge-weight", choices=("constant", "log"), default="constant", help="under --merge-positions: how often a merged "
                     "row of n rows stands in the list the batches are drawn from: once, or 1 + floor(log2 n) times (not with --surprise)")
+    ap.add_argument("--fp8", action="store_true", help="the fp8 net in the loop (DESIGN.md 12.3): self-play, the gate match and the "
+                    "arena run on net_fp8, and the training step is quantisation-aware (GraphedTrainStep(fp8_qat=True): the fp8 net's "
+                    "forward, straight-through gradients).  Needs --channels 128 and the all-kernel training step")
+    ap.add_argument("--fp8-no-qat", action="store_true", help="under --fp8: keep the plain bf16 training step (the ablation: fp8 "
+                    "self-play on post-training-quantised weights)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -180,6 +188,14 @@ def main():
         ap.error("--resign-fp-target must be in [0, 1]")
     if not (0.0 <= args.own_weight < float("inf")):
         ap.error("--own-weight must be finite and >= 0")
+    if args.fp8_no_qat and not args.fp8:
+        ap.error("--fp8-no-qat takes effect only with --fp8")
+    if args.fp8 and args.channels != 128:
+        ap.error("--fp8 needs --channels 128: the fp8 tower is built for 128 channels")
+    if args.fp8 and not args.fp8_no_qat and (args.miopen_train or args.eager_train or args.fp32_train):
+        ap.error("--fp8 trains with the all-kernel step (quantisation-aware); --fp8-no-qat keeps any other step")
+    net_eval = "net_fp8" if args.fp8 else "net_bf16"   # the evaluator of self-play, the gate and the arena
+    fp8_qat = args.fp8 and not args.fp8_no_qat
 
     torch.manual_seed(args.seed)
     gen = torch.Generator(device="cuda:0").manual_seed(args.seed)
@@ -192,7 +208,8 @@ def main():
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
                                                                   value_targets=train_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
-                                                                  ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight)
+                                                                  ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight,
+                                                                  fp8_qat=fp8_qat)
     bmax = max(args.games, args.arena_games, args.gate_games)
     dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
@@ -228,12 +245,12 @@ def main():
 
     emit({"what": "arena, MCTS with the uniform evaluator (no net)", "sims": args.arena_sims, "opponent_depth": args.depth,
           **arena("uniform", None)})
-    emit({"what": "arena, untrained net", "iter": 0, **arena("net_bf16", dnet)})
+    emit({"what": "arena, untrained net", "iter": 0, "evaluator": net_eval, **arena(net_eval, dnet)})
 
     window, val_window = [], []
     for it in range(1, args.iters + 1):
         t0 = time.time()
-        sp = PipelinedSelfPlay("reversi", args.games, args.sims, "net_bf16", dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
+        sp = PipelinedSelfPlay("reversi", args.games, args.sims, net_eval, dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
                                surprise=args.surprise, search_value=use_vt, fpu=fpu, solver=solver, ownership=args.ownership, resign=resign,
                                eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, **({} if args.gumbel else dict(dirichlet_alpha=0.3, dirichlet_eps=0.25)))
@@ -263,7 +280,7 @@ def main():
         window = (window + [aug])[-args.window:]
         val_window = (val_window + [select_rows(ex, va_idx)])[-args.window:]
         data, val = concat_device_examples(window), concat_device_examples(val_window)
-        val_before = validate(dnet, val)   # the net that just played, on rows it has not been trained on
+        val_before = validate(dnet, val, fp8=args.fp8)   # the net that just played, on rows it has not been trained on
         steps = max(1, int(args.epochs * len(data) / args.batch))
         losses = []
         surprise = {}
@@ -309,15 +326,15 @@ def main():
         if args.lr_decay != 1.0:
             graphed.set_lr(graphed.lr * args.lr_decay)
         t_train = time.time() - t1
-        val_after = validate(cand, val)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
-        val_mean = {"after_mean_of_8": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in validate(cand, val, symmetry="mean").items()
+        val_after = validate(cand, val, fp8=args.fp8)    # the refreshed engine net (bf16 MFMA forward) on the same held-out rows
+        val_mean = {"after_mean_of_8": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in validate(cand, val, symmetry="mean", fp8=args.fp8).items()
                                         if k != "rows"}} if args.eval_symmetry else {}
         gate = {}
         if args.gate_games:  # the candidate (A) against the net self-play uses (B)
             t2 = time.time()
-            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, gumbel=gumbel, fpu=fpu, solver=solver,
-                                                                             early_stop=early_stop),
-                             MatchPlayer(sims=args.arena_sims, net=dnet, gumbel=gumbel, fpu=fpu, solver=solver, early_stop=early_stop), opening_plies=args.opening_plies,
+            res = play_match("reversi", args.gate_games, MatchPlayer(sims=args.arena_sims, net=cand, evaluator=net_eval, gumbel=gumbel, fpu=fpu,
+                                                                             solver=solver, early_stop=early_stop),
+                             MatchPlayer(sims=args.arena_sims, net=dnet, evaluator=net_eval, gumbel=gumbel, fpu=fpu, solver=solver, early_stop=early_stop), opening_plies=args.opening_plies,
                              seed=args.seed * 1000 + it)
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
@@ -344,9 +361,10 @@ def main():
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
-              "arena": arena("net_bf16", cand), **gate})
+              **({"fp8": True, "fp8_qat": fp8_qat} if args.fp8 else {}),
+              "arena": arena(net_eval, cand), **gate})
     for d in (int(x) for x in args.final_depths.split(",") if x):
-        emit({"what": "final arena", "opponent_depth": d, "sims": args.arena_sims, "trained": arena("net_bf16", dnet, d),
+        emit({"what": "final arena", "opponent_depth": d, "sims": args.arena_sims, "trained": arena(net_eval, dnet, d),
               "uniform_evaluator": arena("uniform", None, d)})
     if args.out:
         with open(args.out, "w") as f:
