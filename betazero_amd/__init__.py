@@ -14,7 +14,7 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
            "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
            "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
-           "check_early_stop", "merge_positions", "merged_repeats"]
+           "check_early_stop", "merge_positions", "merged_repeats", "save_checkpoint", "load_checkpoint"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -33,4 +33,7 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
     if name in ("merge_positions", "merged_repeats"):  # position averaging of the training window
         from . import merge
         return getattr(merge, name)
+    if name in ("save_checkpoint", "load_checkpoint"):  # one file that carries a training run across processes
+        from . import checkpoint
+        return getattr(checkpoint, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

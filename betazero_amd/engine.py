@@ -51,6 +51,7 @@ class Examples:
     # cell i is worth bit_i(fown) - bit_i(fopp); None = not recorded
     fown: np.ndarray = None
     fopp: np.ndarray = None
+    count: np.ndarray = None  # position averaging: the rows merged into this one, int32 [n]; None = not merged
 
     def __len__(self):
         return self.own.shape[0]
@@ -84,6 +85,7 @@ class DeviceExamples:
     vt: torch.Tensor = None  # value target: f32 [n], or None = train on z
     fown: torch.Tensor = None  # ownership target: int64 [n] holding the uint64 bit patterns, or None = not recorded
     fopp: torch.Tensor = None
+    count: torch.Tensor = None  # position averaging: int32 [n] rows merged into this one, or None = not merged
 
     def __len__(self):
         return int(self.own.shape[0])
@@ -96,7 +98,8 @@ class DeviceExamples:
                         kl=None if self.kl is None else n(self.kl), q=None if self.q is None else n(self.q),
                         vt=None if self.vt is None else n(self.vt),
                         fown=None if self.fown is None else n(self.fown).view(np.uint64),
-                        fopp=None if self.fopp is None else n(self.fopp).view(np.uint64))
+                        fopp=None if self.fopp is None else n(self.fopp).view(np.uint64),
+                        count=None if self.count is None else n(self.count))
 
     @staticmethod
     def from_host(ex, device="cuda:0"):
@@ -108,7 +111,8 @@ class DeviceExamples:
                               q=None if ex.q is None else t(np.asarray(ex.q, np.float32)),
                               vt=None if ex.vt is None else t(np.asarray(ex.vt, np.float32)),
                               fown=None if ex.fown is None else t(np.asarray(ex.fown, np.uint64).view(np.int64)),
-                              fopp=None if ex.fopp is None else t(np.asarray(ex.fopp, np.uint64).view(np.int64)))
+                              fopp=None if ex.fopp is None else t(np.asarray(ex.fopp, np.uint64).view(np.int64)),
+                              count=None if ex.count is None else t(np.asarray(ex.count, np.int32)))
 
     def states(self):
         """canonical boards [n, size, size] int8 on the device: +1 = side to move, -1 = opponent"""

@@ -42,20 +42,26 @@ def save_examples_csv(ex, filename):
 
 
 _NPZ_FIELDS = ("own", "opp", "pi", "z", "mover", "act", "game", "ply")
+# the columns a row may or may not carry (Examples' optional fields): each under its own key when the rows have it, absent otherwise
+_NPZ_OPTIONAL = ("kl", "q", "vt", "fown", "fopp", "count")
 
 
 def save_examples_npz(ex, filename):
-    """Examples (host) or DeviceExamples -> one compressed .npz: the arrays as they are, plus the board size"""
+    """Examples (host) or DeviceExamples -> one compressed .npz: the arrays as they are, plus the board size.  The optional
+    columns (kl, q, vt, fown, fopp and the merge count) are written, bit for bit, when the rows carry them"""
     if hasattr(ex, "cpu") and not isinstance(ex.own, np.ndarray):
         ex = ex.cpu()
-    np.savez_compressed(filename, size=np.int64(ex.size), **{k: np.asarray(getattr(ex, k)) for k in _NPZ_FIELDS})
+    cols = {k: np.asarray(getattr(ex, k)) for k in _NPZ_FIELDS}
+    cols.update({k: np.asarray(getattr(ex, k)) for k in _NPZ_OPTIONAL if getattr(ex, k, None) is not None})
+    np.savez_compressed(filename, size=np.int64(ex.size), **cols)
 
 
 def load_examples_npz(filename):
-    """-> Examples, bit for bit what save_examples_npz was given (no pickle involved)"""
+    """-> Examples, bit for bit what save_examples_npz was given (no pickle involved); a file without an optional column (any
+    file written before they were carried) gives rows without it"""
     from .engine import Examples
-    d = np.load(filename, allow_pickle=False)
-    return Examples(**{k: d[k] for k in _NPZ_FIELDS}, size=int(d["size"]))
+    with np.load(filename, allow_pickle=False) as d:
+        return Examples(**{k: d[k] for k in _NPZ_FIELDS}, size=int(d["size"]), **{k: d[k] for k in _NPZ_OPTIONAL if k in d.files})
 
 
 def load_csv(filename):

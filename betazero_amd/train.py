@@ -244,6 +244,7 @@ class GraphedTrainStep:
         self.pi = torch.full((batch, na), 1.0 / na, dtype=torch.float32, device=self.dev)
         self.z = torch.zeros(batch, dtype=torch.float32 if self.value_targets else torch.int8, device=self.dev)
         self.graph, self.out = None, None
+        self._restore = None   # a state_dict loaded before the graph exists (load_state_dict)
 
     def _lr_at(self, k):
         return self.lr * min(1.0, (k + 1) / self.warmup) if self.warmup > 0 else self.lr
@@ -288,6 +289,9 @@ class GraphedTrainStep:
                 for k, v in st.items():
                     if torch.is_tensor(v):
                         v.zero_()
+        if self._restore is not None:   # a state loaded before the first call: the warm-up above ran over it
+            self._apply_state(self._restore)
+            self._restore = None
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = self._step()
@@ -343,6 +347,72 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: ema_module() needs ema_decay")
         return self.step_plan.ema_module()
 
+    # ---- the step's state, to carry a run across processes
+    def state_dict(self):
+        """StepPlan.state_dict() of the all-kernel step -- enough to continue bit for bit -- plus the host-side fields this
+        class keeps (the replay counter behind _lr_at, lr, warm-up).  The forms of the step that go through torch's optimiser
+        (no fused Adam) save the module's parameters and torch's optimiser state_dict instead, under "module." keys and
+        "optimizer"; nothing is claimed about their bits.  CPU tensors and plain numbers only; synchronises."""
+        host = dict(steps_done=self.steps_done, lr=self.lr, warmup=self.warmup, fused_adam=self.fused_adam)
+        if self.fused_adam:
+            return {**self.step_plan.state_dict(), **host}
+        cpu = lambda x: x.detach().cpu().clone() if torch.is_tensor(x) else x  # noqa: E731
+        opt = self.optimizer.state_dict()
+        opt = {"state": {i: {k: cpu(v) for k, v in st.items()} for i, st in opt["state"].items()},
+               "param_groups": [{k: (list(v) if isinstance(v, tuple) else cpu(v)) for k, v in g.items()} for g in opt["param_groups"]]}
+        return {**{f"module.{k}": cpu(p) for k, p in self.module.named_parameters()}, "optimizer": opt,
+                "C": getattr(self.module, "C", None), "blocks": getattr(self.module, "NB", None), "VH": getattr(self.module, "VH", None),
+                "batch": self.batch, **host}
+
+    def load_state_dict(self, sd):
+        """continue from a state_dict(): copied into the existing tensors (StepPlan.load_state_dict), so a step that has captured
+        its graph keeps that graph and the next replay continues from the loaded state; before the first call the state is
+        put in place again behind the capture's warm-up steps, which would otherwise zero the moments.  A state that does not
+        fit raises ValueError naming the first difference before anything is written."""
+        if bool(sd.get("fused_adam")) != self.fused_adam:
+            raise ValueError(f"load_state_dict: fused_adam differs: the state was saved with fused_adam = {sd.get('fused_adam')!r}, "
+                             f"this step has {self.fused_adam!r}")
+        for k in ("steps_done", "lr", "warmup"):
+            if not isinstance(sd.get(k), (int, float)) or isinstance(sd.get(k), bool):
+                raise ValueError(f"load_state_dict: the state's {k} is not a number")
+        if self.fused_adam:
+            self.step_plan._check_state(sd)
+        else:
+            for k, p in self.module.named_parameters():
+                s = sd.get(f"module.{k}")
+                if not torch.is_tensor(s) or s.shape != p.shape or s.dtype != p.dtype:
+                    raise ValueError(f"load_state_dict: tensor module.{k} differs from this step's module")
+            if not isinstance(sd.get("optimizer"), dict):
+                raise ValueError("load_state_dict: the state has no torch optimiser state")
+        self._apply_state(sd)
+        self._restore = sd if (self.capture and self.graph is None) else None   # _capture() puts it back behind its warm-up
+
+    def _apply_state(self, sd):
+        """the writing half of load_state_dict (the state has been checked)"""
+        if self.fused_adam:
+            self.step_plan.load_state_dict(sd)
+        else:
+            with torch.no_grad():
+                for k, p in self.module.named_parameters():
+                    p.copy_(sd[f"module.{k}"])
+            self._load_torch_optimizer(sd["optimizer"])
+        self.steps_done, self.lr, self.warmup = int(sd["steps_done"]), float(sd["lr"]), int(sd["warmup"])
+
+    def _load_torch_optimizer(self, opt):
+        """torch's optimiser state: in place where the tensors exist (a captured graph holds their addresses), through
+        torch's own load_state_dict otherwise; the rate stays the device scalar lr_t"""
+        groups = [{**g, "lr": self.lr_t, "betas": tuple(g["betas"])} for g in opt["param_groups"]]
+        ps = [p for g in self.optimizer.param_groups for p in g["params"]]
+        if self.graph is not None and all(p in self.optimizer.state for p in ps):
+            with torch.no_grad():
+                for i, p in enumerate(ps):
+                    for k, v in opt["state"][i].items():
+                        self.optimizer.state[p][k].copy_(v)
+        else:
+            self.optimizer.load_state_dict({"state": opt["state"], "param_groups": groups})
+            for g in self.optimizer.param_groups:
+                g["lr"] = self.lr_t
+
     def check(self):
         """raise IndexError if a step since the last check was handed a row index outside the data set (the all-kernel step
         clamps instead of faulting and counts the event in its error word; the autograd forms raise inside index_select).
@@ -364,4 +434,6 @@ def refresh_device_net(device_net, module):
                                  "the engine's net was NOT updated")
     m = copy.deepcopy(module).cpu()
     m.round_to_bf16_()
-    device_net.update(m.flat_params())
+    flat = m.flat_params()
+    device_net.update(flat)
+    return flat

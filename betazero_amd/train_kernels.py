@@ -409,6 +409,70 @@ class StepPlan(TowerPlan):
         """steps done so far (reads the device counter: synchronises)"""
         return int(self.hyper[1].item()) if self.hyper is not None else 0
 
+    # ---- the step's state, to carry a run across processes (DESIGN.md 12.4)
+    def _describe(self):
+        """what a saved state must agree on with the step it is loaded into, in the order a mismatch is reported"""
+        return {"C": self.C, "blocks": self.L // 2, "VH": self.VH, "extended": self._optim is not None, "has_ema": self.ema is not None,
+                "has_ownership": self._own is not None, "fp8_qat": self.fp8_qat}
+
+    def _state_tensors(self):
+        """{key: device tensor} of everything a step reads and writes from one replay to the next"""
+        if self.adam_m is None:
+            raise RuntimeError("StepPlan: enable_adam() first (the state is the optimiser's as much as the net's)")
+        t = {f"param.{k}": self.params[k].detach() for k in self.NAMES}
+        t.update({f"adam_m.{k}": self.adam_m[k] for k in self.NAMES})
+        t.update({f"adam_v.{k}": self.adam_v[k] for k in self.NAMES})
+        t["hyper"] = self.hyper
+        if self.stats is not None:
+            t["stats"] = self.stats
+        if self.ema is not None:
+            t.update({f"ema.{k}": self.ema[k] for k in self.NAMES})
+        if self._own is not None:
+            for k in ("w", "b"):
+                t[f"own.{k}"], t[f"own_m.{k}"], t[f"own_v.{k}"] = self.own_params[k].detach(), self.own_m[k], self.own_v[k]
+        return t
+
+    def state_dict(self):
+        """a flat dict of CPU tensors and plain numbers, enough to continue bit for bit: the fp32 parameters ("param." + NAMES),
+        adam_m / adam_v, the whole hyper block as stored (the device step counter included), stats, ema and the ownership head's
+        w, b and moments where they exist, the host-side lr and warm-up -- and C, blocks, VH, batch and which optional parts
+        exist, for load_state_dict's check.  Synchronises."""
+        sd = {k: t.cpu().clone() for k, t in self._state_tensors().items()}
+        sd.update(self._describe())
+        sd.update(batch=self.n, value_targets=self.value_targets, lr=self.lr, warmup=self.warmup)
+        if self._optim is not None:
+            sd.update(weight_decay=self.weight_decay, clip_norm=self.clip_norm, ema_decay=self.ema_decay)
+        return sd
+
+    def _check_state(self, sd):
+        """ValueError naming the first difference between `sd` and this step; nothing is written"""
+        for k, mine in self._describe().items():
+            if k not in sd:
+                raise ValueError(f"load_state_dict: the state has no {k!r}: not a StepPlan state")
+            if sd[k] != mine:
+                raise ValueError(f"load_state_dict: {k} differs: the state was saved with {k} = {sd[k]!r}, this step has {mine!r}")
+        for k, t in self._state_tensors().items():
+            s = sd.get(k)
+            if not torch.is_tensor(s) or s.shape != t.shape or s.dtype != t.dtype:
+                got = f"{s.dtype} {tuple(s.shape)}" if torch.is_tensor(s) else repr(type(s).__name__)
+                raise ValueError(f"load_state_dict: tensor {k} differs: the state has {got}, this step {t.dtype} {tuple(t.shape)}")
+        for k in ("lr", "warmup"):
+            if not isinstance(sd.get(k), (int, float)) or isinstance(sd.get(k), bool):
+                raise ValueError(f"load_state_dict: the state's {k} is not a number")
+
+    def load_state_dict(self, sd):
+        """copy a state_dict() into the step's own tensors, in place and on the current stream: the addresses a captured graph
+        holds stay valid, so the next launch (or replay) continues from the loaded state.  C / blocks / VH, plain against
+        extended optimiser, an EMA or an ownership head on one side only, or fp8_qat differing raise ValueError naming the first
+        difference BEFORE anything is written.  (batch and value_targets shape no state and may differ.)"""
+        self._check_state(sd)
+        with torch.cuda.device(self.device), torch.no_grad():
+            for k, t in self._state_tensors().items():
+                t.copy_(sd[k])
+        self.lr, self.warmup = float(sd["lr"]), int(sd["warmup"])
+        if self._optim is not None and "weight_decay" in sd:
+            self.weight_decay, self.clip_norm, self.ema_decay = float(sd["weight_decay"]), float(sd["clip_norm"]), float(sd["ema_decay"])
+
     # ---- the launches
     def launch(self, adam=False):
         """the 9 (adam: 10, or 11 with the extended optimiser) launches of one step on the current stream (no host work besides:

@@ -66,7 +66,11 @@ def next_resign_threshold(threshold, stats, fp_target):
     return min(max(threshold, RESIGN_T_MIN), RESIGN_T_MAX)
 
 
-def main():
+# the arguments a resumed run may change: everything else shapes the state or the run's course and must be the checkpoint's
+RESUME_FREE = ("iters", "checkpoint", "checkpoint_every", "no_checkpoint_window", "resume", "init_net", "out", "save_net")
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=64, choices=(64, 128, 256))
     ap.add_argument("--blocks", type=int, default=4)
@@ -168,7 +172,67 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--save-net", default=None, help="write the state_dict of the net training ends with to this file (what the "
                     "bench tools' --net takes)")
+    ap.add_argument("--checkpoint", default=None, metavar="PATH", help="write the run's whole state to this file (DESIGN.md 12.4; "
+                    "betazero_amd.checkpoint: one file, replaced atomically) after every --checkpoint-every'th completed iteration and "
+                    "after the last one")
+    ap.add_argument("--checkpoint-every", type=int, default=1, help="iterations between two checkpoints")
+    ap.add_argument("--no-checkpoint-window", action="store_true", help="leave the training window out of the checkpoint (a much "
+                    "smaller file); a run resumed from it starts with an empty window and is NOT the uninterrupted run bit for bit")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="continue the run of this checkpoint up to --iters: with the "
+                    "all-kernel training step the resumed run is the uninterrupted run bit for bit.  Every argument but --iters, "
+                    "--out, --save-net and the checkpoint flags must be the checkpoint's")
+    ap.add_argument("--init-net", default=None, metavar="FILE", help="start a new run from this saved state_dict (what --save-net "
+                    "writes) instead of random weights")
+    return ap
+
+
+def window_rows(ex):
+    """DeviceExamples -> {column: CPU tensor} (+ the board size), every column the rows carry: what a checkpoint keeps of a
+    window slot"""
+    cols = {k: getattr(ex, k).cpu() for k in ("own", "opp", "pi", "z", "mover", "act", "game", "ply", "kl", "q", "vt", "fown", "fopp")
+            if getattr(ex, k) is not None}
+    return {"size": int(ex.size), **cols}
+
+
+def to_host(x):
+    """tensors anywhere inside dicts / lists / tuples -> CPU tensors, tuples -> lists: what a checkpoint holds"""
+    if torch.is_tensor(x):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return {k: to_host(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [to_host(v) for v in x]
+    return x
+
+
+def rows_to_device(rows, device="cuda:0"):
+    from betazero_amd.engine import DeviceExamples
+    return DeviceExamples(**{k: (v if k == "size" else v.to(device)) for k, v in rows.items()})
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
+    ckpt = None
+    if args.checkpoint_every < 1:
+        ap.error("--checkpoint-every must be >= 1")
+    if args.resume and args.init_net:
+        ap.error("--init-net starts a new run; --resume continues one")
+    if args.resume:  # read and checked on the host: a checkpoint that does not fit is refused before any device is touched
+        from betazero_amd.checkpoint import load_checkpoint
+        try:
+            ckpt = load_checkpoint(args.resume)
+        except (OSError, ValueError) as e:
+            ap.error(f"--resume: {e}")
+        saved = ckpt.get("args")
+        if not isinstance(saved, dict) or "iter" not in ckpt:
+            ap.error(f"--resume: {args.resume} is not a checkpoint of this tool")
+        for k, v in vars(args).items():
+            if k not in RESUME_FREE and (k not in saved or saved[k] != v):
+                ap.error(f"--resume: --{k.replace('_', '-')} differs from the checkpoint's: it was written with "
+                         f"{saved.get(k, 'no such argument')!r}, this run has {v!r}")
+        if ckpt["iter"] > args.iters:
+            ap.error(f"--resume: the checkpoint has completed iteration {ckpt['iter']}, --iters is {args.iters}")
     if args.gumbel_interior and not args.gumbel:
         ap.error("--gumbel-interior takes effect only with --gumbel")
     extended = bool(args.weight_decay or args.clip_norm or args.ema_decay is not None)
@@ -204,6 +268,8 @@ def main():
     v_lam, v_mix = 1.0 if args.value_lambda is None else args.value_lambda, 0.0 if args.value_q_mix is None else args.value_q_mix
     kernels = not (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256)
     module = PolicyValueNet(args.channels, args.blocks, 64, fused_tower=kernels)
+    if args.init_net:
+        module.load_state_dict(torch.load(args.init_net, map_location="cpu", weights_only=True))
     own_head = OwnershipHead(args.channels) if args.ownership else None
     opt = make_optimizer(module, lr=args.lr) if args.eager_train else None
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
@@ -211,7 +277,22 @@ def main():
                                                                   ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight,
                                                                   fp8_qat=fp8_qat)
     bmax = max(args.games, args.arena_games, args.gate_games)
-    dnet = DeviceNet.from_module(module.round_to_bf16_(), bmax)
+    if ckpt is not None:  # the trained state: the step's (parameters, optimiser, EMA, ownership head), or torch's where it trained
+        with torch.no_grad():
+            for k, p in module.state_dict().items():
+                p.copy_(ckpt["module"][k])
+            if own_head is not None:
+                for k, p in own_head.state_dict().items():
+                    p.copy_(ckpt["own_head"][k])
+        if graphed is not None:
+            graphed.load_state_dict(ckpt["step"])
+        else:  # (torch's optimiser keeps its state where the parameters are when it is loaded)
+            module.to("cuda:0")
+            opt.load_state_dict(ckpt["optimizer"])
+        gen.set_state(ckpt["generator"])
+    # the net self-play uses, as the flat bf16-representable vector it was last given (a DeviceNet cannot be read back)
+    dnet_flat = ckpt["dnet"].numpy() if ckpt is not None else module.round_to_bf16_().flat_params()
+    dnet = DeviceNet(args.channels, args.blocks, 64, dnet_flat, bmax)
     # with the gate on, the freshly trained weights live in a net of their own until they have won their match
     cand = DeviceNet.from_module(module, bmax) if args.gate_games else dnet
     gumbel = GumbelConfig(interior="gumbel" if args.gumbel_interior else "puct") if args.gumbel else None
@@ -222,7 +303,9 @@ def main():
     resign = check_resign(Resign(args.resign_threshold, args.resign_consecutive, args.resign_playout_frac)
                           if args.resign_threshold is not None else None, ownership=args.ownership)
     early_stop = check_early_stop(args.early_stop, gumbel=gumbel, solver=solver)  # the gate's and the arena's players only
-    lines = []
+    lines = list(ckpt["lines"]) if ckpt is not None else []
+    if ckpt is not None and resign is not None:
+        resign = check_resign(Resign(ckpt["resign_threshold"], resign.consecutive, resign.playout_frac))
 
     def emit(d):
         lines.append(d)
@@ -243,12 +326,32 @@ def main():
         s["seconds"] = round(time.time() - t0, 1)
         return s
 
-    emit({"what": "arena, MCTS with the uniform evaluator (no net)", "sims": args.arena_sims, "opponent_depth": args.depth,
-          **arena("uniform", None)})
-    emit({"what": "arena, untrained net", "iter": 0, "evaluator": net_eval, **arena(net_eval, dnet)})
+    if ckpt is None:  # (a resumed run has these two lines in the checkpoint's)
+        emit({"what": "arena, MCTS with the uniform evaluator (no net)", "sims": args.arena_sims, "opponent_depth": args.depth,
+              **arena("uniform", None)})
+        emit({"what": "arena, untrained net", "iter": 0, "evaluator": net_eval, **arena(net_eval, dnet)})
 
     window, val_window = [], []
-    for it in range(1, args.iters + 1):
+    # what a checkpoint keeps of the window: every slot's rows BEFORE augmentation (an eighth of the augmented rows), on the host
+    keep_rows = bool(args.checkpoint) and not args.no_checkpoint_window
+    raw_window = []
+    if ckpt is not None and ckpt.get("window") is not None:   # augmentation and dedupe are deterministic: the same window again
+        raw_window = list(ckpt["window"]) if keep_rows else []
+        window = [augment_examples(rows_to_device(w["train"]), dedupe=True) for w in ckpt["window"]]
+        val_window = [rows_to_device(w["val"]) for w in ckpt["window"]]
+
+    def write_checkpoint(it):
+        from betazero_amd.checkpoint import save_checkpoint
+        save_checkpoint(args.checkpoint, to_host({
+            "iter": it, "args": vars(args), "lines": lines, "module": dict(module.state_dict()),
+            "own_head": dict(own_head.state_dict()) if own_head is not None else None,
+            "step": graphed.state_dict() if graphed is not None else None,
+            "optimizer": opt.state_dict() if opt is not None else None,
+            "dnet": torch.from_numpy(np.ascontiguousarray(dnet_flat, dtype=np.float32)), "generator": gen.get_state(),
+            "resign_threshold": resign.threshold if resign is not None else None,
+            "window": raw_window if keep_rows else None}))
+
+    for it in range((ckpt["iter"] if ckpt is not None else 0) + 1, args.iters + 1):
         t0 = time.time()
         sp = PipelinedSelfPlay("reversi", args.games, args.sims, net_eval, dnet, pipelines=args.pipelines, temp_moves=args.temp_moves,
                                openings=1, seed=args.seed * 1000 + it, gumbel=gumbel, playout_cap=cap, forced_playouts=forced,
@@ -275,10 +378,13 @@ def main():
         t1 = time.time()
         # hold-out split of this iteration's rows BEFORE augmentation (a row's symmetric copies must not sit on both sides)
         tr_idx, va_idx = holdout_split(len(ex), args.val_split, gen, ex.own.device)
-        aug = augment_examples(select_rows(ex, tr_idx), dedupe=True)
+        tr_rows, va_rows = select_rows(ex, tr_idx), select_rows(ex, va_idx)
+        aug = augment_examples(tr_rows, dedupe=True)
         del sp
         window = (window + [aug])[-args.window:]
-        val_window = (val_window + [select_rows(ex, va_idx)])[-args.window:]
+        val_window = (val_window + [va_rows])[-args.window:]
+        if keep_rows:
+            raw_window = (raw_window + [{"train": window_rows(tr_rows), "val": window_rows(va_rows)}])[-args.window:]
         data, val = concat_device_examples(window), concat_device_examples(val_window)
         val_before = validate(dnet, val, fp8=args.fp8)   # the net that just played, on rows it has not been trained on
         steps = max(1, int(args.epochs * len(data) / args.batch))
@@ -308,7 +414,12 @@ def main():
                 losses.append(graphed(data, idx))
             else:
                 losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train, value_targets=train_vt)))
-        losses = torch.stack(losses).cpu().numpy()  # one transfer per iteration, after the last step
+        # the weights' fingerprint: the sum of the trained parameters' bit patterns (as int32) in 64 bits, computed on the device
+        # and brought over with the losses -- as two more floats' bits, so that it stays one transfer
+        whash = torch.stack([p.detach().reshape(-1).view(torch.int32).sum(dtype=torch.int64) for p in module.parameters()]).sum()
+        losses = torch.stack(losses)
+        packed = torch.cat([losses.reshape(-1), whash.reshape(1).view(torch.float32)]).cpu().numpy()  # one transfer per iteration
+        losses, whash = packed[:-2].reshape(tuple(losses.shape)), int(packed[-2:].view(np.int64)[0])
         if graphed is not None:
             graphed.check()                         # an out-of-range row index in any step of the iteration raises here
         optim = {}
@@ -322,7 +433,9 @@ def main():
             raise RuntimeError(f"training diverged in iteration {it}: first non-finite loss at step "
                                f"{int(np.argmax(~np.isfinite(losses).all(1)))} of {steps}")
         trained = graphed.ema_module() if args.ema_decay is not None else module   # the net that is validated, gated and played
-        refresh_device_net(cand, trained)
+        cand_flat = refresh_device_net(cand, trained)
+        if not args.gate_games:
+            dnet_flat = cand_flat
         if args.lr_decay != 1.0:
             graphed.set_lr(graphed.lr * args.lr_decay)
         t_train = time.time() - t1
@@ -339,12 +452,13 @@ def main():
             g = res.summary()
             g.update(promoted=bool(g["score"] >= args.gate_score), threshold=args.gate_score, seconds=round(time.time() - t2, 1))
             if g["promoted"]:
-                refresh_device_net(dnet, trained)
+                dnet_flat = refresh_device_net(dnet, trained)
             gate = {"gate": g}
         head, tail = np.mean(losses[: max(1, steps // 10)], axis=0), np.mean(losses[-max(1, steps // 10):], axis=0)
         emit({"what": "iteration", "iter": it, "games": args.games, "plies": plies, "examples": int(len(ex)),
               "augmented_rows": int(len(aug)), "train_rows": int(len(data)), "steps": steps,
               "loss_first_tenth": [round(float(x), 4) for x in head], "loss_last_tenth": [round(float(x), 4) for x in tail],
+              "weights_hash": f"{whash & 0xFFFFFFFFFFFFFFFF:016x}",
               "validation": {"rows": val_after["rows"], "split": args.val_split,
                              "before": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in val_before.items() if k != "rows"},
                              "after": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in val_after.items() if k != "rows"},
@@ -363,6 +477,8 @@ def main():
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
               **({"fp8": True, "fp8_qat": fp8_qat} if args.fp8 else {}),
               "arena": arena(net_eval, cand), **gate})
+        if args.checkpoint and (it % args.checkpoint_every == 0 or it == args.iters):
+            write_checkpoint(it)
     for d in (int(x) for x in args.final_depths.split(",") if x):
         emit({"what": "final arena", "opponent_depth": d, "sims": args.arena_sims, "trained": arena(net_eval, dnet, d),
               "uniform_evaluator": arena("uniform", None, d)})
