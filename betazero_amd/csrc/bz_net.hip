@@ -138,7 +138,7 @@ enum { kShapeLatency = 0, kShapeMiddle = 1, kShapeThroughput = 2, kShapes = 4 };
 
 struct TowerArgs {
     const u64 *own, *opp;            // [n] bitboards, side-to-move canonical
-    const u32* n_dev;                // optional device-side count (<= n): workgroups beyond it exit at once
+    const u32* n_dev;                // optional device-side count, clamped to n by the towers: workgroups beyond it exit at once
     int n, n_layers, VH;
     int lo, hi;                      // the launch runs only when lo <= count <= hi (adaptive shape; 0, INT_MAX otherwise)
     u32* tally;                      // optional: +1 per launch that ran (one lane of workgroup 0)

@@ -24,8 +24,14 @@ k_tower_bf16(TowerArgs T) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pos0 = blockIdx.x * P;
-    if (T.n_dev) T.n = (int)*T.n_dev;
-    if (pos0 >= T.n || T.n < T.lo || T.n > T.hi) return;  // block-uniform, before any barrier
+    // the [lo, hi] window sees the count as it stands (an adaptive pair's latency launch carries T.n = kAdaptT1: a larger
+    // count is the other launch's); the rows are then clamped to the launch's own T.n, so that no count reaches past the
+    // caller's buffers.  The window is one unsigned compare, which needs 0 <= lo <= hi (the host sets them so): a count
+    // >= 2^31 reads as negative, wraps past the span and runs nothing.  (Why this order and this form: DESIGN.md 5.)
+    const int cnt = T.n_dev ? (int)*T.n_dev : T.n;
+    if ((unsigned)cnt - (unsigned)T.lo > (unsigned)T.hi - (unsigned)T.lo) return;  // not lo <= cnt <= hi; block-uniform, before any barrier
+    T.n = cnt < T.n ? cnt : T.n;
+    if (pos0 >= T.n) return;
     if (T.tally && blockIdx.x == 0 && tid == 0) atomicAdd(T.tally, 1u);
     [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0}, tk0 = 0, tk1 = 0, tr0 = 0, tr1 = 0;
     BZ_STAMP(tk0);

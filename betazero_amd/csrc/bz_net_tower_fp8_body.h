@@ -16,7 +16,7 @@ __global__ void __launch_bounds__(256, 2) k_tower_fp8(TowerArgs T) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pos0 = blockIdx.x * 4;
-    if (T.n_dev) T.n = (int)*T.n_dev;
+    if (T.n_dev) { const int cnt = (int)*T.n_dev; T.n = cnt < T.n ? cnt : T.n; }  // clamped to the launch's rows (a count >= 2^31: negative, nothing runs)
     if (pos0 >= T.n) return;
     [[maybe_unused]] unsigned long long tacc[4] = {0, 0, 0, 0}, tk0 = 0, tk1 = 0, tr0 = 0, tr1 = 0;
     BZ_STAMP(tk0);

@@ -195,7 +195,8 @@ class DeviceNet:
     def forward_counted(self, own, opp, count, logits, value, bf16=True, fp8=False, symmetry=None, size=8, seed=0):
         """The engine's call: the forward over the first count[0] rows (a uint32-as-int32 CUDA tensor, read on the device
         when the kernel runs) of own / opp [max_n] into the caller's logits [max_n, 65] / value [max_n]; the rows from
-        count[0] on are not written.  symmetry: None, an int 0..7 or "hash", as in forward().  At 128 channels, bf16 and
+        count[0] on are not written.  A count above max_n is clamped to max_n on the device (2^31 and above: out of
+        contract, nothing runs).  symmetry: None, an int 0..7 or "hash", as in forward().  At 128 channels, bf16 and
         max_n > 256 the tower's workgroup shape follows the count (set_adaptive_shape)."""
         from .symmetry import SYM_MEAN, check_forward_symmetry
         sym = check_forward_symmetry(symmetry, size, seed)

@@ -199,8 +199,11 @@ int32_t bz_net_forward_fp8(bz_net* net, const uint64_t* own, const uint64_t* opp
                            float* logits, float* value, void* stream);
 
 /* ---- device-side row counts and the adaptive tower shape (an addition to ABI 7) ----
- * _counted: the forward over the first *n_dev rows (device u32, <= max_n <= max_batch) of buffers of max_n rows -- the
- * call the engine makes with its packed-leaf count.  Rows >= *n_dev are never written; a count of 0 touches no memory.
+ * _counted: the forward over the first *n_dev rows (device u32) of buffers of max_n <= max_batch rows -- the call the
+ * engine makes with its packed-leaf count.  Rows >= *n_dev are never written; a count of 0 touches no memory.  A count
+ * above max_n is clamped to max_n on the device (rows, shape and tally are those of max_n rows): no count reaches past
+ * the buffers.  Counts of 2^31 and above are outside the contract: they read as negative and run nothing.  Every row is
+ * bit for bit what the host-count forward gives (tests/test_gpu_net_counted.py).
  * At C == 128, bf16 and max_n > 256 the tower's workgroup shape follows the count: the latency shape (one position per
  * workgroup) up to the threshold, the throughput shape above it; both are launched and the one the count rules out exits
  * at once.  Every row is bit for bit what either shape gives (they agree by construction of the accumulation order).
