@@ -14,7 +14,8 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
            "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
            "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
-           "check_early_stop", "merge_positions", "merged_repeats", "save_checkpoint", "load_checkpoint"]
+           "check_early_stop", "merge_positions", "merged_repeats", "save_checkpoint", "load_checkpoint",
+           "Reanalyser", "reanalyse", "reanalyse_rows"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -36,4 +37,8 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
     if name in ("save_checkpoint", "load_checkpoint"):  # one file that carries a training run across processes
         from . import checkpoint
         return getattr(checkpoint, name)
+    if name in ("Reanalyser", "reanalyse", "reanalyse_rows"):  # re-search stored rows with the current net
+        import importlib
+        mod = importlib.import_module(".reanalyse", __name__)   # (`reanalyse` is the MODULE; its one-shot function is betazero_amd.reanalyse.reanalyse)
+        return mod if name == "reanalyse" else getattr(mod, name)
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

@@ -229,6 +229,8 @@ _SIGS = {
     "bz_engine_root_store_bytes": (i64, [C.POINTER(EngineCfg), i32, i32]),
     "bz_engine_set_root_store": (i32, [vp, vp, i64, i32, i32, vp]),
     "bz_engine_root_policy": (i32, [vp, vp, vp, vp]),
+    "bz_engine_reanalyse_load": (i32, [vp, vp, vp, vp, i64, vp, i64, i32, i32, vp]),
+    "bz_engine_reanalyse_store": (i32, [vp, vp, vp, vp, i64, vp, i64, i32, vp]),
     "bz_engine_status": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     "bz_mcts_select": (i32, [vp, u32, vp]),
     "bz_mcts_expand_backup": (i32, [vp, vp]),

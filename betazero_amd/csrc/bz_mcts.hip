@@ -99,7 +99,8 @@ constexpr int kCntWords = 24;  // u64 words of the counters block: CNT_N work co
 enum { FLAG_ERR = 0, FLAG_FINISHED = 1, FLAG_ACTIVE = 2, FLAG_NEVAL = 4, FLAG_N = 8 };
 // ERR_EVAL_NONFINITE: the evaluator handed back a NaN / infinity (a diverged net, an external evaluator's bug): the
 // softmax of such a row is NaN, every PUCT comparison with it is false and the search would quietly walk garbage
-enum { ERR_EDGE_OVERFLOW = 1, ERR_TERMINAL_ROOT = 2, ERR_EXAMPLE_OVERFLOW = 4, ERR_DEPTH = 8, ERR_EVAL_NONFINITE = 16 };
+enum { ERR_EDGE_OVERFLOW = 1, ERR_TERMINAL_ROOT = 2, ERR_EXAMPLE_OVERFLOW = 4, ERR_DEPTH = 8, ERR_EVAL_NONFINITE = 16,
+       ERR_REANALYSE_ROW = 32 };  //  a reanalysed row index outside the caller's columns
 
 struct __attribute__((aligned(16))) PathEnt { u32 eidx; u32 w0; float W; u32 pad; };
 
@@ -2317,6 +2318,93 @@ __global__ void __launch_bounds__(256) k_root_policy(EngineDev E, GumbelDev Gm, 
     act_out[g] = e_action(ed[pick].w0);
 }
 
+// ---- reanalysis: stored rows in, fresh targets out, around one search of the roots they name
+// slot g < count searches row r = rows ? rows[first + g] : first + g of the caller's columns (64-bit indices)
+__device__ __forceinline__ int64_t dev_reanalyse_row(const int64_t* rows, int64_t first, int g) {
+    const int64_t i = first + (int64_t)g;
+    return rows ? rows[i] : i;
+}
+// k_set_roots from example columns: slot g < count becomes a fresh root at row r's boards and mover, every other slot idle.
+// A row outside 0 .. n_rows - 1 leaves its slot idle and raises ERR_REANALYSE_ROW; nothing is read at it.  clear != 0: the
+// sticky error word and the eval counters start over (k_set_roots' last line), else they stay, so that the chunks of one run
+// report together.  Block 0 alone clears and raises, in that order across its barrier: no other block touches the word.
+template <class G>
+__global__ void __launch_bounds__(256) k_reanalyse_load(EngineDev E, const u64* own, const u64* opp, const int8_t* mover,
+                                                        int64_t n_rows, const int64_t* rows, int64_t first, int count, int clear) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0 && clear) { E.flags[FLAG_ERR] = 0; E.flags[FLAG_FINISHED] = 0; E.flags[FLAG_NEVAL] = 0; E.flags[FLAG_NEVAL + 1] = 0; }
+        __syncthreads();
+        bool bad = false;
+        for (int s = threadIdx.x; s < count; s += 256) {
+            const int64_t r = dev_reanalyse_row(rows, first, s);
+            bad = bad || r < 0 || r >= n_rows;
+        }
+        if (bad) atomicOr(&E.flags[FLAG_ERR], ERR_REANALYSE_ROW);
+    }
+    if (g >= E.B) return;
+    const int64_t r = g < count ? dev_reanalyse_row(rows, first, g) : -1;
+    const bool use = r >= 0 && r < n_rows;
+    const int8_t tm = use ? mover[r] : (int8_t)0;
+    E.g_own[g] = use ? own[r] : 0ULL; E.g_opp[g] = use ? opp[r] : 0ULL; E.g_to_move[g] = tm;
+    E.g_state[g] = tm == 0 ? 1 : 0;
+    if (E.reuse) E.g_reuse[g] = 0;
+    E.hot[g].root_base = 0;
+    E.g_moves[g] = 0; E.g_nex[g] = 0; E.g_round[g] = 0; E.g_passes[g] = 0;
+}
+
+// behind the search: row r of slot g < count gets the pi bz_engine_root_policy reports for the slot (k_root_policy's and
+// k_forced_root_policy's device functions), q[r] = root_value of the raw visit statistics and kl[r] = surprise_kl of that pi
+// against the root edges' priors (no noise is ever drawn here: they are the raw priors); q / kl null: not written.  Idle slots,
+// terminal roots (flagged by the search) and unexpanded ones write nothing.  One lane per slot, 64 slots per block: a slot's pi
+// is built in the block's shared memory -- the Gumbel softmax reads back what it wrote, and two slots may name one row -- and
+// then leaves as whole rows.  Slots that name the same row write the same bits.
+template <class G>
+__global__ void __launch_bounds__(64) k_reanalyse_store(EngineDev E, GumbelDev Gm, ForcedDev F, int forced, int solve, float* pi_out,
+                                                        float* q_out, float* kl_out, int64_t n_rows, const int64_t* rows,
+                                                        int64_t first, int count) {
+    __shared__ float s_pi[64 * G::NA];
+    __shared__ int64_t s_row[64];
+    const int lane = threadIdx.x, g = blockIdx.x * 64 + lane;
+    int64_t r = -1;
+    if (g < E.B && g < count && E.g_state[g] == 0) r = dev_reanalyse_row(rows, first, g);
+    if (r >= n_rows) r = -1;
+    if (r >= 0) {
+        const u64 lg = G::legal(E.g_own[g], E.g_opp[g]);
+        int tv;
+        if (G::terminal(E.g_own[g], E.g_opp[g], (int)E.g_to_move[g], lg, &tv)) r = -1;  // (its node 0 is an earlier search's)
+    }
+    if (r >= 0) {
+        const Node root = E.nodes[(size_t)g * E.ncap];
+        const Edge* ed = E.edges + (size_t)g * E.ecap + root.edge0;
+        const int n = (int)(root.info & 0xFFu);
+        if (n == 0) {
+            r = -1;
+        } else {
+            float* pi = s_pi + lane * G::NA;
+            if (Gm.m > 0 && !forced) {
+                dev_gumbel_choice<G>(Gm, g, ed, n, pi);
+            } else {
+                u32 sumN = 0;
+                for (int i = 0; i < n; ++i) sumN += e_N(ed[i].w0);
+                if (forced) dev_forced_choice<G>(E, F, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+                else if (solve) dev_solver_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+                else dev_puct_choice<G>(E, g, ed, n, sumN, E.g_moves[g], E.g_round[g], pi);
+            }
+            if (q_out) q_out[r] = root_value(n, [ed](int i) { return e_N(ed[i].w0); }, [ed](int i) { return ed[i].W; });
+            if (kl_out) kl_out[r] = surprise_kl(n, [pi, ed](int i) { return pi[e_action(ed[i].w0)]; }, [ed](int i) { return ed[i].P; });
+        }
+    }
+    s_row[lane] = r;
+    __syncthreads();
+    for (int s = 0; s < 64; ++s) {
+        const int64_t rs = s_row[s];
+        if (rs < 0) continue;
+        float* dst = pi_out + (size_t)rs * G::NA;
+        for (int a = lane; a < G::NA; a += 64) dst[a] = s_pi[s * G::NA + a];
+    }
+}
+
 // Gumbel preparation of every active game's freshly expanded root, in the style of k_root_noise:
 // base_i = g_i + logf(P~_i), g_i = scale * -log(-log u) while moves made < temp_moves (and scale > 0), else 0
 template <class G>
@@ -4235,6 +4323,37 @@ BZ_EXPORT int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action
         return BZ_OK;
     }
     BZ_DISPATCH(e, k_root_policy, stream, e->dev, e->gumbel, (m & kModeSolve) ? 1 : 0, pi, action);
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_reanalyse_load(bz_engine* e, const uint64_t* own, const uint64_t* opp, const int8_t* mover, int64_t n_rows,
+                                           const int64_t* rows, int64_t first, int32_t count, int32_t clear, void* stream) {
+    BZ_REQUIRE(e && own && opp && mover, "bz_engine_reanalyse_load: null pointer");
+    BZ_REQUIRE(count >= 0 && count <= e->dev.B, "bz_engine_reanalyse_load: count outside 0 .. n_games");
+    BZ_REQUIRE(first >= 0 && n_rows >= 0, "bz_engine_reanalyse_load: negative first or n_rows");
+    BZ_DISPATCH(e, k_reanalyse_load, stream, e->dev, own, opp, mover, n_rows, rows, first, (int)count, (int)(clear != 0));
+    return BZ_OK;
+}
+
+BZ_EXPORT int32_t bz_engine_reanalyse_store(bz_engine* e, float* pi, float* q, float* kl, int64_t n_rows, const int64_t* rows,
+                                            int64_t first, int32_t count, void* stream) {
+    BZ_REQUIRE(e && pi, "bz_engine_reanalyse_store: null pointer");
+    BZ_REQUIRE(count >= 0 && count <= e->dev.B, "bz_engine_reanalyse_store: count outside 0 .. n_games");
+    BZ_REQUIRE(first >= 0 && n_rows >= 0, "bz_engine_reanalyse_store: negative first or n_rows");
+    if (count == 0) return BZ_OK;
+    const unsigned m = engine_mode(e);
+    const dim3 grid((count + 63) / 64);  // (one lane per slot, 64 slots per block)
+#define BZ_RSTORE(G) \
+    hipLaunchKernelGGL(k_reanalyse_store<G>, grid, dim3(64), 0, (hipStream_t)stream, e->dev, e->gumbel, e->forced, \
+                       (m & kModeForced) ? 1 : 0, (m & kModeSolve) ? 1 : 0, pi, q, kl, n_rows, rows, first, (int)count)
+    switch (e->cfg.game) {
+    case BZ_GAME_TTT: BZ_RSTORE(TicTacToe); break;
+    case BZ_GAME_REVERSI6: BZ_RSTORE(Reversi6); break;
+    case BZ_GAME_REVERSI4: BZ_RSTORE(Reversi4); break;
+    default: BZ_RSTORE(Reversi); break;
+    }
+#undef BZ_RSTORE
+    BZ_LAUNCH_CHECK("k_reanalyse_store");
     return BZ_OK;
 }
 

@@ -724,6 +724,11 @@ class SelfPlayEngine:
         self._streams[st.cuda_stream] = st
         return st.cuda_stream
 
+    def track_stream(self, stream):
+        """a torch stream on which the caller launches this engine's kernels through the ABI itself (play_match, Reanalyser): kept, and
+        drained with the others before the workspace dies"""
+        self._streams[stream.cuda_stream] = stream
+
     def _call(self, fn, *args):
         with torch.cuda.device(self.device):
             _lib.check(fn(self.h, *args, self._stream()))
@@ -932,7 +937,8 @@ class SelfPlayEngine:
         if e.value:
             names = [n for bit, n in ((1, "edge arena overflow"), (2, "terminal root"), (4, "example buffer overflow"),
                                       (8, "walk deeper than the path buffer"),
-                                      (16, "the evaluator returned a non-finite logit or value")) if e.value & bit]
+                                      (16, "the evaluator returned a non-finite logit or value"),
+                                      (32, "reanalyse row index out of range")) if e.value & bit]
             raise RuntimeError(f"bz_engine error flags 0x{e.value:x}: " + ", ".join(names))
         return a.value, f.value
 

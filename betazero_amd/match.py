@@ -242,7 +242,7 @@ def play_match(game, n_games, a, b, size=8, opening_plies=0, seed=0, device="cud
     m = Match(ename, B, device)
     streams = pipeline_streams(dev, 2)
     for e, st in zip(engs, streams):
-        e._streams[st.cuda_stream] = st
+        e.track_stream(st)
     lay = m.lay
     tms = (m.base + lay.to_move_a, m.base + lay.to_move_b)
     acts = [torch.full((B,), -1, dtype=torch.int32, device=dev) for _ in engs]

@@ -880,10 +880,31 @@ int32_t bz_engine_set_root_store(bz_engine* e, void* buf, int64_t bytes, int32_t
  * [n_games][NA] and action i32 [n_games].  PUCT: pi = N / sum N and the DESIGN.md 3.7 rule (tau = 1 sampling included);
  * Gumbel: the improved policy and the Gumbel move.  Idle or finished slots get pi = 0 and action -1. */
 int32_t bz_engine_root_policy(bz_engine* e, float* pi, int32_t* action, void* stream);
+/* Reanalysis: stored example rows in, fresh targets out, around one search (bz_engine_search /
+ * bz_engines_search) of the positions they hold.  own / opp / mover: the caller's example columns, device arrays [n_rows]
+ * (side-to-move canonical bitboards, the mover's absolute colour +1 / -1); rows: device i64 indices into them or NULL = the
+ * identity (rows holds at least first + count of them); slot g < count serves row r = rows ? rows[first + g] : first + g, every
+ * index in 64-bit arithmetic.
+ * bz_engine_reanalyse_load is bz_engine_set_roots from those columns: slot g < count becomes a fresh root at row r (boards,
+ * to_move = mover[r], moves / round / passes / rows 0, nothing kept from an earlier search), slots count .. n_games - 1 are
+ * idle.  A row outside 0 .. n_rows - 1 leaves its slot idle and raises BZ_ENGINE_ERR_REANALYSE_ROW; nothing is read or
+ * written at it.  clear != 0 resets the sticky error word and the eval counters as bz_engine_set_roots does; clear == 0 keeps
+ * them, so that one bz_engine_status behind the last chunk reports every chunk.
+ * bz_engine_reanalyse_store, behind the search: pi[r * NA ..] = the pi bz_engine_root_policy reports for the slot (N / sum N,
+ * the Gumbel improved policy, the pruned pi of forced playouts, the solver's), and where the pointers are not NULL q[r] =
+ * bz_root_value of the root's raw statistics and kl[r] = bz_surprise_kl of that pi against the root edges' priors (raw: the
+ * caller searches without noise).  Idle slots, terminal roots (BZ_ENGINE_ERR_TERMINAL_ROOT) and unexpanded roots write nothing.
+ * Slots that name the same row write the same bits.  BZ_EINVAL for a null engine, a null own / opp / mover / pi, count
+ * outside 0 .. n_games, a negative first or n_rows. */
+int32_t bz_engine_reanalyse_load(bz_engine* e, const uint64_t* own, const uint64_t* opp, const int8_t* mover, int64_t n_rows,
+                                 const int64_t* rows, int64_t first, int32_t count, int32_t clear, void* stream);
+int32_t bz_engine_reanalyse_store(bz_engine* e, float* pi, float* q, float* kl, int64_t n_rows, const int64_t* rows,
+                                  int64_t first, int32_t count, void* stream);
 /* synchronises the stream; number of active slots / finished games so far.  error_flags (sticky until the next
  * reset_games / set_roots): 1 = a game's edge arena overflowed, 2 = a root position was already terminal, 4 = more example
  * rows than t_max, 8 = a walk deeper than the path buffer, 16 = the evaluator returned a non-finite logit or value (the
- * search results of that move are meaningless) */
+ * search results of that move are meaningless), 32 = a reanalysed row index outside the caller's columns */
+#define BZ_ENGINE_ERR_REANALYSE_ROW 32
 #define BZ_ENGINE_ERR_EDGE_OVERFLOW 1
 #define BZ_ENGINE_ERR_TERMINAL_ROOT 2
 #define BZ_ENGINE_ERR_EXAMPLE_OVERFLOW 4

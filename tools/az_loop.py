@@ -4,6 +4,9 @@
     self-play (PipelinedSelfPlay: two engines on two streams, bf16 MFMA net in the loop, Dirichlet root noise, temperature moves)
       -> example block -> 80 / 20 hold-out split of the new rows (the reference's split, SL/train.py:66-78)
       -> 8-fold D4 augmentation + exact dedupe of the training part on the device (augment_examples)
+      -> with --reanalyse-frac F: reanalysis of the older window slots (Reanalyser): a seeded share F of every
+         older slot's un-augmented training rows is searched again with the net self-play just used and gets that search's pi
+         (and kl); the slot is augmented again
       -> with --merge-positions: position averaging of the training window (merge_positions): the rows of one
          position become one row with the mean pi and the mean value target
       -> policy cross-entropy + value MSE steps on the hand-written training kernels replayed as one HIP graph
@@ -43,6 +46,7 @@ from betazero_amd.engine import (EvalSymmetry, ForcedPlayouts, Fpu, GumbelConfig
                                  check_early_stop, check_fpu, check_playout_cap, check_resign, check_solver, concat_device_examples)
 from betazero_amd.merge import merge_positions, merged_repeats  # noqa: E402
 from betazero_amd.match import MatchPlayer, play_match  # noqa: E402
+from betazero_amd.reanalyse import Reanalyser, reanalyse_rows  # noqa: E402
 from betazero_amd.net import DeviceNet, OwnershipHead, PolicyValueNet  # noqa: E402
 from betazero_amd.surprise import surprise_resample  # noqa: E402
 from betazero_amd.value_targets import value_targets  # noqa: E402
@@ -165,6 +169,12 @@ def build_parser():
                     "forward, straight-through gradients).  Needs --channels 128 and the all-kernel training step")
     ap.add_argument("--fp8-no-qat", action="store_true", help="under --fp8: keep the plain bf16 training step (the ablation: fp8 "
                     "self-play on post-training-quantised weights)")
+    ap.add_argument("--reanalyse-frac", type=float, default=0.0, help="reanalysis (DESIGN.md 3.27; MuZero Reanalyse): every iteration, after "
+                    "self-play and before training, this share of the training rows of every window slot older than the current one is "
+                    "searched again with the net self-play just used and self-play's search options (no noise, no playout cap, no "
+                    "resignation), and gets that search's pi (and kl under --surprise); the value targets stay, the held-out rows are "
+                    "never touched; 0 = off")
+    ap.add_argument("--reanalyse-sims", type=int, default=None, help="simulations of a reanalysis search (default: --sims)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
     ap.add_argument("--eager-train", action="store_true", help="launch every kernel of a training step by itself instead of replaying the captured HIP graph")
@@ -233,6 +243,12 @@ def main():
                          f"{saved.get(k, 'no such argument')!r}, this run has {v!r}")
         if ckpt["iter"] > args.iters:
             ap.error(f"--resume: the checkpoint has completed iteration {ckpt['iter']}, --iters is {args.iters}")
+    if not (0.0 <= args.reanalyse_frac <= 1.0):
+        ap.error("--reanalyse-frac must be in [0, 1]")
+    if args.reanalyse_sims is not None and not args.reanalyse_frac > 0:
+        ap.error("--reanalyse-sims takes effect only with --reanalyse-frac")
+    if args.reanalyse_sims is not None and args.reanalyse_sims < 1:
+        ap.error("--reanalyse-sims must be >= 1")
     if args.gumbel_interior and not args.gumbel:
         ap.error("--gumbel-interior takes effect only with --gumbel")
     extended = bool(args.weight_decay or args.clip_norm or args.ema_decay is not None)
@@ -335,8 +351,14 @@ def main():
     # what a checkpoint keeps of the window: every slot's rows BEFORE augmentation (an eighth of the augmented rows), on the host
     keep_rows = bool(args.checkpoint) and not args.no_checkpoint_window
     raw_window = []
+    # reanalysis: every slot's un-augmented training rows stay on the device, next to the slot they augment to
+    reanalysing = args.reanalyse_frac > 0
+    raw_dev = []
+    rean = None
     if ckpt is not None and ckpt.get("window") is not None:   # augmentation and dedupe are deterministic: the same window again
         raw_window = list(ckpt["window"]) if keep_rows else []
+        if reanalysing:
+            raw_dev = [rows_to_device(w["train"]) for w in ckpt["window"]]
         window = [augment_examples(rows_to_device(w["train"]), dedupe=True) for w in ckpt["window"]]
         val_window = [rows_to_device(w["val"]) for w in ckpt["window"]]
 
@@ -375,6 +397,33 @@ def main():
             resign = check_resign(Resign(nxt, resign.consecutive, resign.playout_frac))
         torch.cuda.synchronize()
         t_play = time.time() - t0
+        rean_info = {}
+        if reanalysing:  # the older slots that stay in the window, with the net that just played (dnet) and self-play's search
+            t_re = time.time()
+            if rean is None:
+                rean = Reanalyser("reversi", args.reanalyse_sims or args.sims, net_eval, dnet, batch=max(1, min(1024, args.games // args.pipelines)),
+                                  pipelines=args.pipelines, gumbel=gumbel, fpu=fpu, forced_playouts=forced, solver=solver,
+                                  eval_symmetry=EvalSymmetry(args.seed + it) if args.eval_symmetry else None, seed=args.seed)
+            elif args.eval_symmetry:
+                for e in rean.engines:
+                    e.set_eval_symmetry(EvalSymmetry(args.seed + it))
+            keep = min(len(window), args.window - 1)   # the slots this iteration's rows do not push out
+            n_re, n_moved = 0, torch.zeros((), dtype=torch.int64, device=ex.own.device)
+            for j in range(len(window) - keep, len(window)):
+                raw = raw_dev[j]
+                idx = reanalyse_rows(len(raw), args.reanalyse_frac, args.seed, (it, len(window) - j)).to(raw.own.device)
+                if len(idx) == 0:
+                    continue
+                top = raw.pi[idx].argmax(1)
+                rean.run(raw, idx, update_q=False)   # the slot's value targets were computed over whole games and stay
+                n_moved += (raw.pi[idx].argmax(1) != top).sum()
+                n_re += len(idx)
+                window[j] = augment_examples(raw, dedupe=True)
+                if keep_rows:
+                    raw_window[j] = {"train": window_rows(raw), "val": raw_window[j]["val"]}
+            torch.cuda.synchronize()
+            rean_info = {"reanalysed_rows": n_re, "reanalyse_s": round(time.time() - t_re, 1),
+                         "reanalyse_argmax_changed": round(int(n_moved) / n_re, 4) if n_re else 0.0}
         t1 = time.time()
         # hold-out split of this iteration's rows BEFORE augmentation (a row's symmetric copies must not sit on both sides)
         tr_idx, va_idx = holdout_split(len(ex), args.val_split, gen, ex.own.device)
@@ -382,6 +431,8 @@ def main():
         aug = augment_examples(tr_rows, dedupe=True)
         del sp
         window = (window + [aug])[-args.window:]
+        if reanalysing:
+            raw_dev = (raw_dev + [tr_rows])[-args.window:]
         val_window = (val_window + [va_rows])[-args.window:]
         if keep_rows:
             raw_window = (raw_window + [{"train": window_rows(tr_rows), "val": window_rows(va_rows)}])[-args.window:]
@@ -466,7 +517,7 @@ def main():
               "self_play_x_wins": int((winners > 0).sum()), "self_play_o_wins": int((winners < 0).sum()),
               "self_play_s": round(t_play, 1), "games_per_s": round(args.games / t_play, 1),
               "rows_per_game": round(len(ex) / args.games, 2), "train_s": round(t_train, 1),
-              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info, **resign_info, **merge_info,
+              **({"forced_k": forced.k, "prune": forced.prune} if forced else {}), **surprise, **vt_info, **resign_info, **merge_info, **rean_info,
               **({"fpu": [fpu.reduction, fpu.root_reduction]} if fpu else {}), **({"solver": True} if solver else {}), **optim,
               **({"gumbel_interior": gumbel.interior} if gumbel else {}),
               # the ownership loss L_own over the last (and the first) tenth of the steps
