@@ -9,7 +9,7 @@ back as host Examples."""
 import torch
 
 from . import _lib
-from .engine import DeviceExamples, Examples
+from .examples import DeviceExamples, Examples, columns
 
 
 def _first_by_key(key8, own8, opp8, pi8):
@@ -53,8 +53,8 @@ def _first_occurrences(key8, own8, opp8, pi8):
 
 def augment_examples(ex, dedupe=True, device="cuda:0"):
     """Examples / DeviceExamples (n rows) -> the same type (<= 8n rows, row 8*i+t = transform t of row i before dedupe).
-    z, mover and game carry over; `act` is permuted with the board; `ply` is kept; `kl` (policy surprise, when present) is the
-    source row's: the eight copies share it, and the dedupe keeps the first occurrence's; `q` and `vt` likewise.
+    z, mover, game and ply and -- when present -- kl, q, vt and count are the source row's: the eight copies share them, and the
+    dedupe keeps the first occurrence's; `act` is permuted with the board.
     `fown` / `fopp` (the ownership target) are boards: they go through the same kernel, so every copy's target is
     transformed by the symmetry of its position; the dedupe key does not see them and keeps the first occurrence's."""
     _lib.require_gpu()
@@ -77,7 +77,6 @@ def augment_examples(ex, dedupe=True, device="cuda:0"):
     has_own = ex.fown is not None and ex.fopp is not None
     if (ex.fown is None) != (ex.fopp is None):
         raise ValueError("augment_examples: the examples must carry both fown and fopp (ownership target), or neither")
-    fown8 = fopp8 = None
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
         L = _lib.lib()
@@ -92,10 +91,10 @@ def augment_examples(ex, dedupe=True, device="cuda:0"):
         _lib.check(L.bz_augment_d4_batch(own.data_ptr(), opp.data_ptr(), act1.data_ptr(), n, size, na,
                                          scr_a.data_ptr(), scr_b.data_ptr(), act8.data_ptr(), None, st))
     keep = _first_occurrences(key8, own8, opp8, pi8) if dedupe else torch.arange(8 * n, device=dev)
+    # the columns that went through the kernel; every other column the rows carry is the source row's
+    moved = dict(own=own8[keep], opp=opp8[keep], pi=pi8[keep], act=act8[keep].argmax(1).to(torch.uint8))
+    if has_own:
+        moved.update(fown=fown8[keep], fopp=fopp8[keep])
     src = keep // 8
-    out = DeviceExamples(own=own8[keep], opp=opp8[keep], pi=pi8[keep], z=ex.z[src], mover=ex.mover[src],
-                         act=act8[keep].argmax(1).to(torch.uint8), game=ex.game[src], ply=ex.ply[src], size=size,
-                         kl=None if ex.kl is None else ex.kl[src], q=None if ex.q is None else ex.q[src],
-                         vt=None if ex.vt is None else ex.vt[src], fown=None if fown8 is None else fown8[keep],
-                         fopp=None if fopp8 is None else fopp8[keep])
+    out = DeviceExamples(size=size, **{k: moved[k] if k in moved else t[src] for k, t in columns(ex).items()})
     return out.cpu() if host_in else out

@@ -2565,15 +2565,22 @@ __global__ void __launch_bounds__(256) k_surp_kl(EngineDev E, SurpDev S) {
     const float* pr = S.prior + (size_t)g * G::MAXCH;
     S.ex_kl[row] = surprise_kl(n, [pi, ed](int i) { return pi[e_action(ed[i].w0)]; }, [pr](int i) { return pr[i]; });
 }
-// ex_kl in the packed block's row order: the pack_off k_pack_scan left (it counts the rows earlier engines appended)
-__global__ void __launch_bounds__(256) k_pack_kl(EngineDev E, SurpDev S, float* out, int64_t cap) {
+// THE walk of the kernels that put a per-row array into the packed block's row order, over the pack_off k_pack_scan left (it
+// counts the rows earlier engines appended): one wave per game i of [rounds, B], the game's rows 64 at a time; row(i, src, dst)
+// with src the row's index in the engine's [rounds, B, t_max] arrays and dst < cap its row in the block
+template <class Row>
+__device__ __forceinline__ void dev_pack_walk(const EngineDev& E, int64_t cap, Row row) {
     const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= E.rounds * E.B) return;
     const int off = E.pack_off[i];
     if (off < 0) return;
     const int len = E.ex_len[i];
     const size_t src = (size_t)i * E.t_max;
-    for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = S.ex_kl[src + t];
+    for (int t = lane; t < len && t < E.t_max && (int64_t)off + t < cap; t += 64) row(i, src + t, (size_t)off + t);
+}
+// a float per row -- ex_kl, ex_q -- in the packed block's row order
+__global__ void __launch_bounds__(256) k_pack_f32(EngineDev E, const float* src, float* out, int64_t cap) {
+    dev_pack_walk(E, cap, [=](int, size_t s, size_t d) { out[d] = src[s]; });
 }
 
 // ---- search-value targets: in front of the play kernel, while the searched tree is in place -- the row the
@@ -2587,16 +2594,6 @@ __global__ void __launch_bounds__(256) k_root_q(EngineDev E, ValueDev V, const u
     const Node r = E.nodes[(size_t)g * E.ncap];
     const Edge* ed = E.edges + (size_t)g * E.ecap + r.edge0;
     V.ex_q[(size_t)(p - 1ULL)] = root_value((int)(r.info & 0xFFu), [ed](int i) { return e_N(ed[i].w0); }, [ed](int i) { return ed[i].W; });
-}
-// ex_q in the packed block's row order (k_pack_kl's walk over the pack_off k_pack_scan left)
-__global__ void __launch_bounds__(256) k_pack_q(EngineDev E, ValueDev V, float* out, int64_t cap) {
-    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= E.rounds * E.B) return;
-    const int off = E.pack_off[i];
-    if (off < 0) return;
-    const int len = E.ex_len[i];
-    const size_t src = (size_t)i * E.t_max;
-    for (int t = lane; t < len && (int64_t)off + t < cap; t += 64) out[(size_t)off + t] = V.ex_q[src + t];
 }
 
 // ---- ownership targets: in front of the play kernel, behind k_root_policy / k_forced_root_policy, which left
@@ -2673,21 +2670,14 @@ __global__ void __launch_bounds__(256) k_resign_finish(EngineDev E, int restart)
     E.g_state[g] = 1;
 }
 
-// the rows' target boards in the packed block's row order (k_pack_q's walk over the pack_off k_pack_scan left): every row of
-// a game gets its game's final board in the row's own side-to-move frame
+// the rows' target boards in the packed block's row order (dev_pack_walk): every row of a game gets its game's final board in
+// the row's own side-to-move frame
 __global__ void __launch_bounds__(256) k_pack_own(EngineDev E, OwnDev O, u64* fown, u64* fopp, int64_t cap) {
-    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= E.rounds * E.B) return;
-    const int off = E.pack_off[i];
-    if (off < 0) return;
-    const int len = E.ex_len[i];
-    const size_t src = (size_t)i * E.t_max;
-    const u64 fx = O.fin_x[i], fo = O.fin_o[i];
-    for (int t = lane; t < len && t < E.t_max && (int64_t)off + t < cap; t += 64) {
+    dev_pack_walk(E, cap, [=](int i, size_t s, size_t d) {
         u64 a, b;
-        ownership_row(fx, fo, (int)E.ex_mover[src + t], &a, &b);
-        fown[(size_t)off + t] = a; fopp[(size_t)off + t] = b;
-    }
+        ownership_row(O.fin_x[i], O.fin_o[i], (int)E.ex_mover[s], &a, &b);
+        fown[d] = a; fopp[d] = b;
+    });
 }
 
 // ---- the root store (S = 0: off), set by bz_engine_set_root_store in the caller's buffer: finished searches of
@@ -4089,8 +4079,8 @@ BZ_EXPORT int32_t bz_engine_pack_surprise(bz_engine* e, float* out, int64_t cap_
     BZ_REQUIRE(cap_rows >= 1 && cap_rows <= (int64_t(1) << 31) - 1 && append_rows >= 0 && append_rows <= cap_rows,
                "bz_engine_pack_surprise: bad capacity or append_rows");
     const int n = e->dev.rounds * e->dev.B;
-    hipLaunchKernelGGL(k_pack_kl, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp, out, cap_rows);
-    BZ_LAUNCH_CHECK("k_pack_kl");
+    hipLaunchKernelGGL(k_pack_f32, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->surp.ex_kl, out, cap_rows);
+    BZ_LAUNCH_CHECK("k_pack_f32");
     return BZ_OK;
 }
 
@@ -4128,8 +4118,8 @@ BZ_EXPORT int32_t bz_engine_pack_search_value(bz_engine* e, float* out, int64_t 
     BZ_REQUIRE(cap_rows >= 1 && cap_rows <= (int64_t(1) << 31) - 1 && append_rows >= 0 && append_rows <= cap_rows,
                "bz_engine_pack_search_value: bad capacity or append_rows");
     const int n = e->dev.rounds * e->dev.B;
-    hipLaunchKernelGGL(k_pack_q, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->value, out, cap_rows);
-    BZ_LAUNCH_CHECK("k_pack_q");
+    hipLaunchKernelGGL(k_pack_f32, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->dev, e->value.ex_q, out, cap_rows);
+    BZ_LAUNCH_CHECK("k_pack_f32");
     return BZ_OK;
 }
 

@@ -9,13 +9,14 @@ import torch
 
 from . import _lib
 from .symmetry import EvalSymmetry, check_eval_symmetry  # noqa: F401  (EvalSymmetry: re-exported next to the other options)
-from ._lib import (EVAL_EXTERNAL, EVAL_HASH, EVAL_NET_BF16, EVAL_NET_F32, EVAL_NET_FP8, EVAL_UNIFORM, GAME_REVERSI,
+from ._lib import (EVAL_EXTERNAL, EVAL_HASH, EVAL_NET_BF16, EVAL_NET_F32, EVAL_NET_FP8, EVAL_UNIFORM, GAME_REVERSI,  # noqa: F401
                    GAME_REVERSI4, GAME_REVERSI6, GAME_TTT, EngineCfg, EngineLayout)
+# the row types and the block code live in betazero_amd.examples; their names stay importable from here
+from .examples import (_EX_FIELDS, _GAMES, _PK_FIELDS, _SIZES, COLUMN, EX_MAGIC, PACKED_MAGIC, DeviceExamples, Examples,  # noqa: F401
+                       _packed_views, _u64, alloc_packed_block, build_example_block, build_packed_block, concat_device_examples,
+                       concat_examples, example_block_views, packed_block_header, packed_layout, unpack_example_block,
+                       unpack_example_block_device, unpack_packed_block, unpack_packed_block_device)
 
-_GAMES = {"ttt": GAME_TTT, "tic_tac_toe": GAME_TTT, "reversi": GAME_REVERSI, "reversi8": GAME_REVERSI,
-          "reversi6": GAME_REVERSI6, "reversi4": GAME_REVERSI4, GAME_TTT: GAME_TTT, GAME_REVERSI: GAME_REVERSI,
-          GAME_REVERSI6: GAME_REVERSI6, GAME_REVERSI4: GAME_REVERSI4}
-_SIZES = {GAME_TTT: 3, GAME_REVERSI: 8, GAME_REVERSI6: 6, GAME_REVERSI4: 4}
 _EVALS = {"uniform": EVAL_UNIFORM, "hash": EVAL_HASH, "net_f32": EVAL_NET_F32, "net_bf16": EVAL_NET_BF16,
           "external": EVAL_EXTERNAL, "net_fp8": EVAL_NET_FP8,
           # the reference's tic-tac-toe MLP (betazero_amd.mlp.DeviceMLP as `net`): policy logits, value 0
@@ -23,124 +24,6 @@ _EVALS = {"uniform": EVAL_UNIFORM, "hash": EVAL_HASH, "net_f32": EVAL_NET_F32, "
 
 
 _EVAL_NAMES = {v: k for k, v in _EVALS.items()}
-
-
-def _u64(t):
-    """int64 tensor holding uint64 bit patterns -> numpy uint64"""
-    return t.cpu().numpy().view(np.uint64)
-
-
-@dataclass
-class Examples:
-    """(s, pi, z) rows.  own/opp: side-to-move canonical bitboards (the bitboard
-    form of generate_training_games.py:17-18); pi [n, NA]; z in {-1,0,+1} for the
-    mover; game = global game id; ply = row index inside its game."""
-    own: np.ndarray
-    opp: np.ndarray
-    pi: np.ndarray
-    z: np.ndarray
-    mover: np.ndarray
-    act: np.ndarray
-    game: np.ndarray
-    ply: np.ndarray
-    size: int
-    kl: np.ndarray = None  # policy surprise (DESIGN.md 3.17): KL(pi || raw prior) per row, f32 [n]; None = not recorded
-    q: np.ndarray = None   # search value (DESIGN.md 3.18): the root's sum W / sum N for the mover, f32 [n]; None = not recorded
-    vt: np.ndarray = None  # value target (DESIGN.md 3.18, betazero_amd.value_targets), f32 [n]; None = train on z
-    # ownership target (DESIGN.md 3.22): the final board of the row's game in the row's side-to-move frame, uint64 [n] each --
-    # cell i is worth bit_i(fown) - bit_i(fopp); None = not recorded
-    fown: np.ndarray = None
-    fopp: np.ndarray = None
-    count: np.ndarray = None  # position averaging (DESIGN.md 3.26): the rows merged into this one, int32 [n]; None = not merged
-
-    def __len__(self):
-        return self.own.shape[0]
-
-    def states(self):
-        """canonical boards [n, size, size] int8: +1 = side to move, -1 = opponent"""
-        s = self.size
-        stride = 3 if s == 3 else 8
-        sh = np.array([[stride * r + c for c in range(s)] for r in range(s)], dtype=np.uint64)
-        a = ((self.own[:, None, None] >> sh) & np.uint64(1)).astype(np.int8)
-        b = ((self.opp[:, None, None] >> sh) & np.uint64(1)).astype(np.int8)
-        return a - b
-
-
-@dataclass
-class DeviceExamples:
-    """The same rows as Examples, as torch tensors living on the GPU: what the device-resident pipeline
-    gather -> augment -> train passes along (SL/train.py:24-52 then :85-136 in the reference's pipeline).
-    own/opp: int64 tensors holding the uint64 bit patterns."""
-    own: torch.Tensor
-    opp: torch.Tensor
-    pi: torch.Tensor
-    z: torch.Tensor
-    mover: torch.Tensor
-    act: torch.Tensor
-    game: torch.Tensor
-    ply: torch.Tensor
-    size: int
-    kl: torch.Tensor = None  # policy surprise (DESIGN.md 3.17): f32 [n], or None = not recorded
-    q: torch.Tensor = None   # search value (DESIGN.md 3.18): f32 [n], or None = not recorded
-    vt: torch.Tensor = None  # value target (DESIGN.md 3.18): f32 [n], or None = train on z
-    fown: torch.Tensor = None  # ownership target (DESIGN.md 3.22): int64 [n] holding the uint64 bit patterns, or None = not recorded
-    fopp: torch.Tensor = None
-    count: torch.Tensor = None  # position averaging (DESIGN.md 3.26): int32 [n] rows merged into this one, or None = not merged
-
-    def __len__(self):
-        return int(self.own.shape[0])
-
-    def cpu(self):
-        """-> Examples (numpy, host)"""
-        n = lambda t: t.cpu().numpy()  # noqa: E731
-        return Examples(own=n(self.own).view(np.uint64), opp=n(self.opp).view(np.uint64), pi=n(self.pi), z=n(self.z),
-                        mover=n(self.mover), act=n(self.act), game=n(self.game), ply=n(self.ply).astype(np.int32), size=self.size,
-                        kl=None if self.kl is None else n(self.kl), q=None if self.q is None else n(self.q),
-                        vt=None if self.vt is None else n(self.vt),
-                        fown=None if self.fown is None else n(self.fown).view(np.uint64),
-                        fopp=None if self.fopp is None else n(self.fopp).view(np.uint64),
-                        count=None if self.count is None else n(self.count))
-
-    @staticmethod
-    def from_host(ex, device="cuda:0"):
-        t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(device)  # noqa: E731
-        return DeviceExamples(own=t(ex.own.view(np.int64)), opp=t(ex.opp.view(np.int64)), pi=t(ex.pi.astype(np.float32)),
-                              z=t(ex.z.astype(np.int8)), mover=t(ex.mover.astype(np.int8)), act=t(ex.act.astype(np.uint8)),
-                              game=t(np.asarray(ex.game, np.int64)), ply=t(np.asarray(ex.ply, np.int32)), size=ex.size,
-                              kl=None if ex.kl is None else t(np.asarray(ex.kl, np.float32)),
-                              q=None if ex.q is None else t(np.asarray(ex.q, np.float32)),
-                              vt=None if ex.vt is None else t(np.asarray(ex.vt, np.float32)),
-                              fown=None if ex.fown is None else t(np.asarray(ex.fown, np.uint64).view(np.int64)),
-                              fopp=None if ex.fopp is None else t(np.asarray(ex.fopp, np.uint64).view(np.int64)),
-                              count=None if ex.count is None else t(np.asarray(ex.count, np.int32)))
-
-    def states(self):
-        """canonical boards [n, size, size] int8 on the device: +1 = side to move, -1 = opponent"""
-        s = self.size
-        stride = 3 if s == 3 else 8
-        sh = torch.tensor([[stride * r + c for c in range(s)] for r in range(s)], dtype=torch.int64, device=self.own.device)
-        a = ((self.own[:, None, None] >> sh) & 1).to(torch.int8)
-        b = ((self.opp[:, None, None] >> sh) & 1).to(torch.int8)
-        return a - b
-
-
-_OPTIONAL_FIELDS = (("kl", "policy surprise"), ("q", "search value"), ("vt", "value target"), ("fown", "ownership target"),
-                    ("fopp", "ownership target"))
-
-
-def _all_or_none(parts, field, what):
-    """True when every part carries `field`, False when none does; a mixture has no meaningful concatenation"""
-    have = [getattr(p, field) is not None for p in parts]
-    if any(have) and not all(have):
-        raise ValueError(f"concatenating examples: every part must carry {field} ({what}), or none")
-    return all(have) and len(have) > 0
-
-
-def concat_device_examples(parts):
-    cat = lambda f: torch.cat([getattr(p, f) for p in parts])  # noqa: E731
-    return DeviceExamples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                          parts[0].size, *(cat(f) if _all_or_none(parts, f, what) else None for f, what in _OPTIONAL_FIELDS))
-
 
 MAX_SIMS, MAX_SIMS_REUSE = 8189, 2045  # BZ_ENGINE_MAX_SIMS / BZ_ENGINE_MAX_SIMS_REUSE (include/bz_abi.h)
 
@@ -493,6 +376,23 @@ def check_ownership(ownership):
     if not isinstance(ownership, (bool, np.bool_)):
         raise ValueError(f"ownership must be a bool (got {ownership!r})")
     return bool(ownership)
+
+
+# ---- THE table of the columns an engine records beside its example block, per engine option: (columns, device dtype, pack entry
+# point).  SelfPlayEngine._pack_extra / _pack_with_extras and _attach_extras are written against it ("Adding a
+# per-row column").
+ENGINE_EXTRAS = {"surprise": (("kl",), torch.float32, "bz_engine_pack_surprise"),
+                 "search_value": (("q",), torch.float32, "bz_engine_pack_search_value"),
+                 "ownership": (("fown", "fopp"), torch.int64, "bz_engine_pack_ownership")}
+
+
+def _attach_extras(ex, extras):
+    """_pack_with_extras' {column: [cap_rows] device tensor} cut to ex's rows and set on ex (host Examples: copied out, in the
+    column's host dtype); -> ex"""
+    for k, t in extras.items():
+        t = t[:len(ex)]
+        setattr(ex, k, t if isinstance(ex, DeviceExamples) else t.cpu().numpy().view(COLUMN[k].host))
+    return ex
 
 
 class SelfPlayEngine:
@@ -1047,20 +947,8 @@ class SelfPlayEngine:
         return buf[o:o + n].view(torch.float32).view(self.rounds, self.B, self.t_max)
 
     def pack_surprise(self, out=None, cap_rows=None, append=False):
-        """the finished games' kl in the row order of the packed block the preceding pack_examples() (same cap_rows, same
-        stream) filled: float32 [cap_rows] on the device, rows [0, n_rows) valid"""
-        cap = int(cap_rows or self.rounds * self.B * self.t_max)
-        if out is None:
-            assert not append
-            out = torch.zeros(cap, dtype=torch.float32, device=self.device)
-        self._call(_lib.lib().bz_engine_pack_surprise, out.data_ptr(), cap, int(append))
-        return out
-
-    def _packed_kl(self, n_rows):
-        """kl of the finished games' rows in (round, slot, ply) order -- the order of examples() and device_examples()"""
-        cap = self.rounds * self.B * self.t_max
-        self.pack_examples(cap_rows=cap)
-        return self.pack_surprise(cap_rows=cap)[:n_rows]
+        """_pack_extra("surprise"): the finished games' kl, float32 [cap_rows] on the device"""
+        return self._pack_extra("surprise", out if out is None else (out,), cap_rows, append)[0]
 
     def search_value_rows(self):
         """search-value targets: the engine's ex_q, a float32 [rounds, B, t_max] view of the search-value
@@ -1071,20 +959,8 @@ class SelfPlayEngine:
         return self._buffers["search_value"][:n].view(torch.float32).view(self.rounds, self.B, self.t_max)
 
     def pack_search_value(self, out=None, cap_rows=None, append=False):
-        """the finished games' q in the row order of the packed block the preceding pack_examples() (same cap_rows, same
-        stream) filled: float32 [cap_rows] on the device, rows [0, n_rows) valid"""
-        cap = int(cap_rows or self.rounds * self.B * self.t_max)
-        if out is None:
-            assert not append
-            out = torch.zeros(cap, dtype=torch.float32, device=self.device)
-        self._call(_lib.lib().bz_engine_pack_search_value, out.data_ptr(), cap, int(append))
-        return out
-
-    def _packed_q(self, n_rows):
-        """q of the finished games' rows in (round, slot, ply) order -- the order of examples() and device_examples()"""
-        cap = self.rounds * self.B * self.t_max
-        self.pack_examples(cap_rows=cap)
-        return self.pack_search_value(cap_rows=cap)[:n_rows]
+        """_pack_extra("search_value"): the finished games' q, float32 [cap_rows] on the device"""
+        return self._pack_extra("search_value", out if out is None else (out,), cap_rows, append)[0]
 
     def ownership_rows(self):
         """ownership targets: the finished games' final boards in absolute colours, (fin_x, fin_o), int64
@@ -1097,33 +973,42 @@ class SelfPlayEngine:
         return tuple(self._buffers["ownership"][k * step:k * step + n].view(torch.int64).view(self.rounds, self.B) for k in (0, 1))
 
     def pack_ownership(self, out=None, cap_rows=None, append=False):
-        """the finished games' rows' ownership targets in the row order of the packed block the preceding pack_examples() (same
-        cap_rows, same stream) filled: (fown, fopp), int64 [cap_rows] on the device, rows [0, n_rows) valid"""
+        """_pack_extra("ownership"): the finished games' rows' ownership targets, (fown, fopp), int64 [cap_rows] on the device"""
+        return self._pack_extra("ownership", out, cap_rows, append)
+
+    def _pack_extra(self, option, out=None, cap_rows=None, append=False):
+        """the finished games' columns of `option` (ENGINE_EXTRAS) in the row order of the packed block the preceding
+        pack_examples() (same cap_rows, same stream) filled: one [cap_rows] device tensor per column, rows [0, n_rows) valid"""
+        cols, dtype, entry = ENGINE_EXTRAS[option]
         cap = int(cap_rows or self.rounds * self.B * self.t_max)
         if out is None:
             assert not append
-            out = (torch.zeros(cap, dtype=torch.int64, device=self.device), torch.zeros(cap, dtype=torch.int64, device=self.device))
-        self._call(_lib.lib().bz_engine_pack_ownership, out[0].data_ptr(), out[1].data_ptr(), cap, int(append))
+            out = tuple(torch.zeros(cap, dtype=dtype, device=self.device) for _ in cols)
+        self._call(getattr(_lib.lib(), entry), *(t.data_ptr() for t in out), cap, int(append))
         return out
 
-    def _packed_own(self, n_rows):
-        """the ownership targets of the finished games' rows in (round, slot, ply) order -- the order of examples() and
-        device_examples()"""
-        cap = self.rounds * self.B * self.t_max
-        self.pack_examples(cap_rows=cap)
-        fown, fopp = self.pack_ownership(cap_rows=cap)
-        return fown[:n_rows], fopp[:n_rows]
+    def _pack_with_extras(self, out=None, cap_rows=None, append=False, extras=None):
+        """pack_examples() and, right behind it, while the row offsets it left are current, the columns of the options that are on:
+        (block, {column: [cap_rows] device tensor in the block's row order}).  `extras`: the dict to fill (append=True: behind
+        the rows of the engines before this one)"""
+        cap = int(cap_rows or self.rounds * self.B * self.t_max)
+        out = self.pack_examples(out, cap, append)
+        on = {o: cols for o, (cols, _, _) in ENGINE_EXTRAS.items() if getattr(self, o)}
+        if extras is None:
+            assert not append
+            extras = {k: torch.zeros(cap, dtype=ENGINE_EXTRAS[o][1], device=self.device) for o, cols in on.items() for k in cols}
+        for o, cols in on.items():
+            self._pack_extra(o, tuple(extras[k] for k in cols), cap, append)
+        return out, extras
+
+    def _extras(self):
+        """the columns of the options that are on, in (round, slot, ply) order -- the order of examples() and device_examples() --
+        behind ONE pack_examples(); an engine without such an option packs nothing"""
+        return self._pack_with_extras()[1] if any(getattr(self, o) for o in ENGINE_EXTRAS) else {}
 
     def examples(self):
         """finished games' rows, compacted on the device; only the valid rows cross PCIe"""
-        ex = unpack_example_block(self.example_block())
-        if self.surprise:
-            ex.kl = self._packed_kl(len(ex)).cpu().numpy()
-        if self.search_value:
-            ex.q = self._packed_q(len(ex)).cpu().numpy()
-        if self.ownership:
-            ex.fown, ex.fopp = (_u64(t) for t in self._packed_own(len(ex)))
-        return ex
+        return _attach_extras(unpack_example_block(self.example_block()), self._extras())
 
     def block_geometry(self):
         """host-side description of this engine's example block (what its 256-byte header says), so that a block of the
@@ -1136,14 +1021,7 @@ class SelfPlayEngine:
 
     def device_examples(self):
         """finished games' rows as DeviceExamples: nothing leaves the GPU"""
-        ex = unpack_example_block_device(self.example_block(), self.block_geometry())
-        if self.surprise:
-            ex.kl = self._packed_kl(len(ex))
-        if self.search_value:
-            ex.q = self._packed_q(len(ex))
-        if self.ownership:
-            ex.fown, ex.fopp = self._packed_own(len(ex))
-        return ex
+        return _attach_extras(unpack_example_block_device(self.example_block(), self.block_geometry()), self._extras())
 
     def winners(self):
         t = self.example_tensors()
@@ -1184,185 +1062,6 @@ class SelfPlayEngine:
             _lib.lib().bz_engine_destroy(self.h)
         except Exception:
             pass
-
-
-EX_MAGIC = 0x425A455841000002
-_EX_FIELDS = (("own", torch.int64, 8), ("opp", torch.int64, 8), ("pi", torch.float32, 4), ("z", torch.int8, 1),
-              ("mover", torch.int8, 1), ("act", torch.uint8, 1), ("len", torch.int32, 4), ("winner", torch.int8, 1))
-
-
-def example_block_views(block):
-    """uint8 example block (device or host tensor) -> (dict of [R,B,T,...] tensor views, meta dict).
-    The block describes itself through its trailing 256-byte header (include/bz_abi.h)."""
-    meta = block[-256:].cpu().numpy().view(np.uint64)
-    if int(meta[0]) != EX_MAGIC:
-        raise ValueError("not a betazero_amd example block (bad magic)")
-    base, stride, B, R, T, na, game = (int(v) for v in meta[1:8])
-    offs = [int(v) for v in meta[8:16]]
-    shapes = {"own": (R, B, T), "opp": (R, B, T), "pi": (R, B, T, na), "z": (R, B, T), "mover": (R, B, T),
-              "act": (R, B, T), "len": (R, B), "winner": (R, B)}
-    out = {}
-    for (name, dt, esz), off in zip(_EX_FIELDS, offs):
-        n = int(np.prod(shapes[name])) * esz
-        out[name] = block[off:off + n].view(dt).view(*shapes[name])
-    return out, {"game_id_base": base, "game_id_stride": stride, "B": B, "rounds": R, "t_max": T, "na": na,
-                 "game": game, "size": _SIZES[game]}
-
-
-def build_example_block(arrays, game_id_base, game_id_stride, game, device="cpu"):
-    """host-side constructor of an example block with the engine's exact layout (256-byte aligned
-    arrays + header): `arrays` = dict of [R,B,T,...] tensors as example_tensors() returns them.
-    Used to re-load saved examples and by the CPU rehearsal of the multi-GPU path."""
-    R, B, T = arrays["own"].shape
-    na = arrays["pi"].shape[-1]
-    offs, off = [], 0
-    for name, dt, esz in _EX_FIELDS:
-        offs.append(off)
-        off += (arrays[name].numel() * esz + 255) & ~255
-    block = torch.zeros(off + 256, dtype=torch.uint8, device=device)
-    for (name, dt, esz), o in zip(_EX_FIELDS, offs):
-        a = arrays[name].to(device=device, dtype=dt).contiguous()
-        block[o:o + a.numel() * esz] = a.view(torch.uint8).reshape(-1)
-    meta = np.zeros(32, np.uint64)
-    meta[0:8] = [EX_MAGIC, game_id_base, game_id_stride, B, R, T, na, _GAMES[game]]
-    meta[8:16] = offs
-    block[off:off + 256] = torch.from_numpy(meta.view(np.uint8).copy()).to(device)
-    return block
-
-
-def unpack_example_block(block):
-    """example block -> compact Examples of the finished games; the row selection runs where the
-    block lives (on the GPU for a device block), so only valid rows are copied to the host"""
-    t, m = example_block_views(block)
-    T = m["t_max"]
-    valid = torch.arange(T, device=block.device)[None, None, :] < t["len"][:, :, None]
-    r, b, k = valid.nonzero(as_tuple=True)
-    pick = lambda a: a[r, b, k].cpu().numpy()  # noqa: E731
-    gid = m["game_id_base"] + r.cpu().numpy().astype(np.int64) * m["game_id_stride"] + b.cpu().numpy()
-    return Examples(own=pick(t["own"]).view(np.uint64), opp=pick(t["opp"]).view(np.uint64), pi=pick(t["pi"]),
-                    z=pick(t["z"]), mover=pick(t["mover"]), act=pick(t["act"]), game=gid,
-                    ply=k.cpu().numpy().astype(np.int32), size=m["size"])
-
-
-def unpack_example_block_device(block, geom):
-    """device example block -> DeviceExamples of the finished games, entirely on the device: the array views come from
-    `geom` (SelfPlayEngine.block_geometry() of an engine with the same configuration -- every rank's engines are built
-    alike), the game-id base / stride are read from the block's own header AS DEVICE SCALARS, the row selection is a
-    device-side nonzero().  No example data is copied to the host: the only host visits are the 112-byte header check and
-    the size read-back of nonzero()."""
-    R, B, T, na = geom["rounds"], geom["B"], geom["t_max"], geom["na"]
-    assert block.numel() == geom["ex_bytes"], "example block of another geometry"
-    # the block's own header must say what `geom` says (a peer built with another configuration can have the same byte
-    # size): magic and words 3..15 (B, rounds, t_max, NA, game, the 8 array offsets) compared on the device
-    want = torch.tensor([EX_MAGIC, B, R, T, na, geom["game"]] + list(geom["offs"]), dtype=torch.int64)
-    got = block[-256:].view(torch.int64)
-    if not torch.equal(torch.cat([got[0:1], got[3:16]]).cpu(), want):
-        raise ValueError("example block does not have the local engine's geometry (header words differ)")
-    shapes = {"own": (R, B, T), "opp": (R, B, T), "pi": (R, B, T, na), "z": (R, B, T), "mover": (R, B, T),
-              "act": (R, B, T), "len": (R, B), "winner": (R, B)}
-    t = {}
-    for (name, dt, esz), off in zip(_EX_FIELDS, geom["offs"]):
-        n = int(np.prod(shapes[name])) * esz
-        t[name] = block[off:off + n].view(dt).view(*shapes[name])
-    meta = block[-256:].view(torch.int64)  # header words: [1] = game-id base, [2] = stride (device scalars)
-    valid = torch.arange(T, device=block.device)[None, None, :] < t["len"][:, :, None]
-    r, b, k = valid.nonzero(as_tuple=True)
-    pick = lambda a: a[r, b, k]  # noqa: E731
-    return DeviceExamples(own=pick(t["own"]), opp=pick(t["opp"]), pi=pick(t["pi"]), z=pick(t["z"]), mover=pick(t["mover"]),
-                          act=pick(t["act"]), game=meta[1] + r * meta[2] + b, ply=k.to(torch.int32), size=geom["size"])
-
-
-def concat_examples(parts):
-    cat = lambda f: np.concatenate([getattr(p, f) for p in parts])  # noqa: E731
-    return Examples(cat("own"), cat("opp"), cat("pi"), cat("z"), cat("mover"), cat("act"), cat("game"), cat("ply"),
-                    parts[0].size, *(cat(f) if _all_or_none(parts, f, what) else None for f, what in _OPTIONAL_FIELDS))
-
-
-# ---------------------------------------------------------------- packed example blocks (include/bz_abi.h)
-PACKED_MAGIC = 0x425A50414B000001
-_PK_FIELDS = (("own", torch.int64), ("opp", torch.int64), ("pi", torch.float32), ("game", torch.int64),
-              ("z", torch.int8), ("mover", torch.int8), ("act", torch.uint8), ("ply", torch.uint8))
-
-
-def packed_layout(na, cap_rows):
-    """(byte offsets of the 8 arrays, total bytes) of a packed example block: 256-byte header, then own, opp, pi,
-    game id, z, mover, act, ply -- each at a multiple of 256 bytes (== bz_examples_packed_bytes)"""
-    offs, off = [], 256
-    for esz in (8, 8, 4 * na, 8, 1, 1, 1, 1):
-        offs.append(off)
-        off += (cap_rows * esz + 255) & ~255
-    return offs, off
-
-
-def alloc_packed_block(na, cap_rows, device="cuda:0"):
-    """an (uninitialised) packed example block: 1-D uint8 tensor, 256-byte aligned"""
-    _, total = packed_layout(na, cap_rows)
-    t = torch.empty(total + 256, dtype=torch.uint8, device=device)
-    pad = (-t.data_ptr()) & 255
-    return t[pad:pad + total]
-
-
-def packed_block_header(block, strict=True):
-    """the block's header as a dict (ONE 256-byte copy to the host when the block lives on a GPU).  strict: raise when
-    the block overflowed (rows of finished games did not fit) -- unpacking such a block would silently lose games;
-    strict=False only reports `dropped_rows` (bench.py's post-mortem of its own capacity estimate)."""
-    h = block[:256].cpu().numpy().view(np.uint64)
-    if int(h[0]) != PACKED_MAGIC:
-        raise ValueError("not a betazero_amd packed example block (bad magic)")
-    d = {"n_rows": int(h[1]), "n_games": int(h[2]), "cap_rows": int(h[3]), "na": int(h[4]), "game": int(h[5]),
-         "dropped_rows": int(h[6]), "bytes": int(h[7]), "offs": [int(v) for v in h[8:16]]}
-    if d["dropped_rows"] and strict:
-        raise RuntimeError("packed example block overflow: " +
-                           ("an engine of another geometry was appended" if d["dropped_rows"] == 2**64 - 1 else
-                            f"{d['dropped_rows']} rows of finished games did not fit into cap_rows = {d['cap_rows']}"))
-    return d
-
-
-def _packed_views(block, h):
-    n, na = h["n_rows"], h["na"]
-    out = {}
-    for (name, dt), off in zip(_PK_FIELDS, h["offs"]):
-        per = na if name == "pi" else 1
-        esz = torch.empty((), dtype=dt).element_size()
-        v = block[off:off + n * per * esz].view(dt)
-        out[name] = v.view(n, na) if name == "pi" else v
-    return out
-
-
-def unpack_packed_block_device(block):
-    """packed example block on a GPU -> DeviceExamples (views of its first n_rows rows; one header read-back)"""
-    h = packed_block_header(block)
-    v = _packed_views(block, h)
-    return DeviceExamples(own=v["own"], opp=v["opp"], pi=v["pi"], z=v["z"], mover=v["mover"], act=v["act"], game=v["game"],
-                          ply=v["ply"].to(torch.int32), size=_SIZES[h["game"]])
-
-
-def unpack_packed_block(block):
-    """packed example block (device or host) -> host Examples; only the valid rows are copied"""
-    h = packed_block_header(block)
-    v = {k: t.cpu().numpy() for k, t in _packed_views(block, h).items()}
-    return Examples(own=v["own"].view(np.uint64), opp=v["opp"].view(np.uint64), pi=v["pi"], z=v["z"], mover=v["mover"],
-                    act=v["act"], game=v["game"], ply=v["ply"].astype(np.int32), size=_SIZES[h["game"]])
-
-
-def build_packed_block(ex, cap_rows, game, device="cpu"):
-    """host-side constructor of a packed block from Examples (saved examples, and the CPU rehearsal of the multi-GPU
-    path): the same bytes bz_engine_pack_examples writes for these rows"""
-    n, na = len(ex), int(ex.pi.shape[1])
-    assert n <= cap_rows
-    offs, total = packed_layout(na, cap_rows)
-    block = torch.zeros(total, dtype=torch.uint8)
-    hdr = np.zeros(32, np.uint64)
-    hdr[0:8] = [PACKED_MAGIC, n, len(np.unique(ex.game)), cap_rows, na, _GAMES[game], 0, total]
-    hdr[8:16] = offs
-    block[:256] = torch.from_numpy(hdr.view(np.uint8).copy())
-    src = {"own": ex.own.view(np.int64), "opp": ex.opp.view(np.int64), "pi": ex.pi.astype(np.float32),
-           "game": np.asarray(ex.game, np.int64), "z": ex.z.astype(np.int8), "mover": ex.mover.astype(np.int8),
-           "act": ex.act.astype(np.uint8), "ply": np.asarray(ex.ply).astype(np.uint8)}
-    for (name, dt), off in zip(_PK_FIELDS, offs):
-        a = torch.from_numpy(np.ascontiguousarray(src[name])).view(torch.uint8).reshape(-1)
-        block[off:off + a.numel()] = a
-    return block.to(device)
 
 
 # ---------------------------------------------------------------- pipelined self-play
@@ -1571,67 +1270,49 @@ class PipelinedSelfPlay:
         return out
 
     def _pack_with_extras(self, out=None, cap_rows=None):
-        """pack_examples() plus the per-row arrays the engines record next to the block: (block, kl or None, q or None, (fown,
-        fopp) or None), kl and q float32 [cap_rows] device tensors in the block's row order, the ownership targets (DESIGN.md
-        3.22) int64 [cap_rows].  Each engine's arrays are packed right behind its rows, while the row offsets its pack left are
-        current."""
+        """pack_examples() plus the per-row columns the engines record next to the block (ENGINE_EXTRAS): (block, {column:
+        [cap_rows] device tensor in the block's row order}).  Each engine's arrays are packed right behind its rows, while the
+        row offsets its pack left are current."""
         cap = int(cap_rows or self.packed_capacity())
         if out is None:
             out = alloc_packed_block(self.na, cap, self.device)
-        kl = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.surprise else None
-        q = torch.zeros(cap, dtype=torch.float32, device=self.device) if self.search_value else None
-        own = tuple(torch.zeros(cap, dtype=torch.int64, device=self.device) for _ in range(2)) if self.ownership else None
+        extras = None
         self.join()
         for i, e in enumerate(self.engines):
-            e.pack_examples(out, cap, append=i > 0)
-            if kl is not None:
-                e.pack_surprise(kl, cap, append=i > 0)
-            if q is not None:
-                e.pack_search_value(q, cap, append=i > 0)
-            if own is not None:
-                e.pack_ownership(own, cap, append=i > 0)
-        return out, kl, q, own
+            out, extras = e._pack_with_extras(out, cap, append=i > 0, extras=extras)
+        return out, extras
 
     def pack_examples_with_ownership(self, out=None, cap_rows=None):
         """pack_examples() plus the rows' ownership targets (ownership=True): (block, fown, fopp), int64 [cap_rows] device
         tensors in the block's row order"""
         if not self.ownership:
             raise RuntimeError("pack_examples_with_ownership(): built without ownership=True")
-        blk, _, _, own = self._pack_with_extras(out, cap_rows)
-        return blk, own[0], own[1]
+        blk, x = self._pack_with_extras(out, cap_rows)
+        return blk, x["fown"], x["fopp"]
 
     def pack_examples_with_surprise(self, out=None, cap_rows=None):
         """pack_examples() plus the rows' kl (surprise=True): (block, float32 [cap_rows] device tensor in the block's row
         order)"""
         if not self.surprise:
             raise RuntimeError("pack_examples_with_surprise(): built without surprise=True")
-        return self._pack_with_extras(out, cap_rows)[:2]
+        blk, x = self._pack_with_extras(out, cap_rows)
+        return blk, x["kl"]
 
     def pack_examples_with_search_value(self, out=None, cap_rows=None):
         """pack_examples() plus the rows' q (search_value=True): (block, float32 [cap_rows] device tensor in the block's row
         order)"""
         if not self.search_value:
             raise RuntimeError("pack_examples_with_search_value(): built without search_value=True")
-        blk, _, q, _ = self._pack_with_extras(out, cap_rows)
-        return blk, q
+        blk, x = self._pack_with_extras(out, cap_rows)
+        return blk, x["q"]
 
     def device_examples(self):
-        blk, kl, q, own = self._pack_with_extras()
-        ex = unpack_packed_block_device(blk)
-        ex.kl = None if kl is None else kl[:len(ex)]
-        ex.q = None if q is None else q[:len(ex)]
-        if own is not None:
-            ex.fown, ex.fopp = own[0][:len(ex)], own[1][:len(ex)]
-        return ex
+        blk, extras = self._pack_with_extras()
+        return _attach_extras(unpack_packed_block_device(blk), extras)
 
     def examples(self):
-        blk, kl, q, own = self._pack_with_extras()
-        ex = unpack_packed_block(blk)
-        ex.kl = None if kl is None else kl[:len(ex)].cpu().numpy()
-        ex.q = None if q is None else q[:len(ex)].cpu().numpy()
-        if own is not None:
-            ex.fown, ex.fopp = _u64(own[0][:len(ex)]), _u64(own[1][:len(ex)])
-        return ex
+        blk, extras = self._pack_with_extras()
+        return _attach_extras(unpack_packed_block(blk), extras)
 
     def ownership_rows(self):
         """the final boards of all pipelines, slots in pipeline order: (fin_x, fin_o), int64 [rounds, B] device tensors

@@ -41,27 +41,21 @@ def save_examples_csv(ex, filename):
                      str(int(ex.z[i])) + "\n" for i in range(len(ex)))
 
 
-_NPZ_FIELDS = ("own", "opp", "pi", "z", "mover", "act", "game", "ply")
-# the columns a row may or may not carry (Examples' optional fields): each under its own key when the rows have it, absent otherwise
-_NPZ_OPTIONAL = ("kl", "q", "vt", "fown", "fopp", "count")
-
-
 def save_examples_npz(ex, filename):
-    """Examples (host) or DeviceExamples -> one compressed .npz: the arrays as they are, plus the board size.  The optional
-    columns (kl, q, vt, fown, fopp and the merge count) are written, bit for bit, when the rows carry them"""
+    """Examples (host) or DeviceExamples -> one compressed .npz: the arrays as they are, plus the board size.  Every column
+    the rows carry (betazero_amd.examples.COLUMNS) is written, bit for bit, under its own key; an optional column they lack is absent"""
+    from .examples import columns
     if hasattr(ex, "cpu") and not isinstance(ex.own, np.ndarray):
         ex = ex.cpu()
-    cols = {k: np.asarray(getattr(ex, k)) for k in _NPZ_FIELDS}
-    cols.update({k: np.asarray(getattr(ex, k)) for k in _NPZ_OPTIONAL if getattr(ex, k, None) is not None})
-    np.savez_compressed(filename, size=np.int64(ex.size), **cols)
+    np.savez_compressed(filename, size=np.int64(ex.size), **{k: np.asarray(a) for k, a in columns(ex).items()})
 
 
 def load_examples_npz(filename):
     """-> Examples, bit for bit what save_examples_npz was given (no pickle involved); a file without an optional column (any
     file written before they were carried) gives rows without it"""
-    from .engine import Examples
+    from .examples import COLUMNS, Examples
     with np.load(filename, allow_pickle=False) as d:
-        return Examples(**{k: d[k] for k in _NPZ_FIELDS}, size=int(d["size"]), **{k: d[k] for k in _NPZ_OPTIONAL if k in d.files})
+        return Examples(size=int(d["size"]), **{c.name: d[c.name] for c in COLUMNS if not c.optional or c.name in d.files})
 
 
 def load_csv(filename):

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import DeviceExamples, Examples
+from .examples import COLUMN, DeviceExamples, Examples, columns
 
 MAX_ROWS = 1 << 26  # bz_merge_positions' limit (include/bz_abi.h): no sum leaves int64
 POLICIES = ("constant", "log")
@@ -58,9 +58,11 @@ def _grouping(own, opp):
     return order.contiguous(), start.to(torch.int32), dst.to(torch.int32), head, count, n_groups
 
 
-def _rows(own, opp, pi, z, mover, act, game, ply, vt, q, kl):
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    return _lib.MergeRows(p(own), p(opp), p(pi), p(z), p(mover), p(act), p(game), p(ply), p(vt), p(q), p(kl))
+_MERGED = tuple(name for name, _ in _lib.MergeRows._fields_)  # the columns bz_merge_positions reads and writes, in the struct's order
+
+
+def _rows(cols):
+    return _lib.MergeRows(*(cols[k].data_ptr() if k in cols else None for k in _MERGED))
 
 
 def merge_positions(ex, return_counts=False):
@@ -88,14 +90,9 @@ def merge_positions(ex, return_counts=False):
     dev = ex.own.device
     if dev.type != "cuda":
         raise ValueError("merge_positions: the examples must live on the GPU (DeviceExamples)")
-    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
-    own, opp, pi = ex.own.contiguous(), ex.opp.contiguous(), f32(ex.pi)
-    z, mover, act = ex.z.to(torch.int8).contiguous(), ex.mover.to(torch.int8).contiguous(), ex.act.to(torch.uint8).contiguous()
-    game, ply = ex.game.to(torch.int64).contiguous(), ex.ply.to(torch.int32).contiguous()
-    vt, q, kl = f32(ex.vt), f32(ex.q), f32(ex.kl)
-    new = lambda t, *shape: None if t is None else torch.empty((n, *shape), dtype=t.dtype, device=dev)  # noqa: E731
-    o = dict(own=new(own), opp=new(opp), pi=new(pi, na), z=new(z), mover=new(mover), act=new(act), game=new(game), ply=new(ply),
-             vt=new(pi), q=new(q), kl=new(kl))
+    cin = {k: t.to(COLUMN[k].device).contiguous() for k, t in columns(ex).items() if k in _MERGED}
+    o = {k: torch.empty_like(t) for k, t in cin.items()}
+    o.setdefault("vt", torch.empty(n, dtype=torch.float32, device=dev))  # always set: a row's value input is vt or (float)z
     L = _lib.lib()
     wbytes = L.bz_merge_workspace_bytes(n, na)
     if wbytes < 0:
@@ -104,8 +101,8 @@ def merge_positions(ex, return_counts=False):
     ws = ws[(-ws.data_ptr()) & 255:][:wbytes]
     status = torch.empty(1, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        order, start, dst, head, count, n_groups = _grouping(own, opp)
-        rin, rout = _rows(own, opp, pi, z, mover, act, game, ply, vt, q, kl), _rows(**o)
+        order, start, dst, head, count, n_groups = _grouping(cin["own"], cin["opp"])
+        rin, rout = _rows(cin), _rows(o)
         _lib.check(L.bz_merge_positions(C.byref(rin), n, na, order.data_ptr(), start.data_ptr(), dst.data_ptr(), head.data_ptr(),
                                         count.data_ptr(), n_groups.data_ptr(), ws.data_ptr(), wbytes, C.byref(rout),
                                         status.data_ptr(), torch.cuda.current_stream().cuda_stream))

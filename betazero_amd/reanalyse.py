@@ -8,7 +8,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _GAMES, _SIZES, DeviceExamples, Examples, SelfPlayEngine, pipeline_streams
+from .engine import SelfPlayEngine, pipeline_streams
+from .examples import _GAMES, _SIZES, COLUMN, DeviceExamples, Examples, columns
 
 _GAME_OF_SIZE = {3: "ttt", 8: "reversi", 6: "reversi6", 4: "reversi4"}
 
@@ -107,10 +108,10 @@ class Reanalyser:
         if ex.own.device != self.device:
             raise ValueError(f"reanalyse: the examples live on {ex.own.device}, the engines on {self.device}")
         q = ex.q if update_q else None
-        cols = {"own": (ex.own, torch.int64), "opp": (ex.opp, torch.int64), "mover": (ex.mover, torch.int8), "pi": (ex.pi, torch.float32)}
-        cols.update({k: (t, torch.float32) for k, t in (("kl", ex.kl), ("q", q)) if t is not None})
-        for k, (t, dt) in cols.items():
-            if t.dtype != dt or not t.is_contiguous() or t.shape[0] != n:
+        touched = ("own", "opp", "mover", "pi", "kl") + (("q",) if update_q else ())  # what the kernels read or write, when carried
+        for k, t in columns(ex).items():
+            dt = COLUMN[k].device
+            if k in touched and (t.dtype != dt or not t.is_contiguous() or t.shape[0] != n):
                 raise ValueError(f"reanalyse: column {k} must be a contiguous {dt} tensor of {n} rows")
         if tuple(ex.pi.shape) != (n, self.na):
             raise ValueError(f"reanalyse: pi must be [{n}, {self.na}] (got {tuple(ex.pi.shape)})")

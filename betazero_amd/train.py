@@ -9,7 +9,7 @@ values come back as device scalars (call .item() when you want to look at them, 
 import torch
 import torch.nn.functional as F
 
-from .engine import DeviceExamples, Examples
+from .examples import DeviceExamples, Examples, take
 
 _SHIFTS = {}
 
@@ -106,11 +106,8 @@ def holdout_split(n_rows, val_fraction=0.2, generator=None, device="cuda:0"):
 
 
 def select_rows(ex, idx):
-    """DeviceExamples holding the rows `idx` (a device index tensor) of ex"""
-    return DeviceExamples(own=ex.own[idx], opp=ex.opp[idx], pi=ex.pi[idx], z=ex.z[idx], mover=ex.mover[idx], act=ex.act[idx],
-                          game=ex.game[idx], ply=ex.ply[idx], size=ex.size, kl=None if ex.kl is None else ex.kl[idx],
-                          q=None if ex.q is None else ex.q[idx], vt=None if ex.vt is None else ex.vt[idx],
-                          fown=None if ex.fown is None else ex.fown[idx], fopp=None if ex.fopp is None else ex.fopp[idx])
+    """DeviceExamples holding the rows `idx` (a device index tensor) of ex: every column ex carries"""
+    return take(ex, idx)
 
 
 @torch.no_grad()

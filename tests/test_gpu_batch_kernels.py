@@ -344,3 +344,40 @@ def test_augment_zero_rows_in_zero_rows_out():
             dout = augment_examples(DeviceExamples.from_host(ex, DEV), dedupe=dedupe)
             assert isinstance(dout, DeviceExamples) and len(dout) == 0 and tuple(dout.pi.shape) == (0, na)
             assert dout.own.device.type == "cuda" and dout.own.dtype == torch.int64
+
+
+def test_augment_carries_every_column_that_rides_with_the_source_row():
+    """3 tic-tac-toe rows with every optional column: the eight copies of row i have its z / mover / game / ply / kl / q / vt /
+    count (dedupe=False: row 8 i + t; dedupe=True: whichever copies are kept -- kl, distinct per row, names the source); the
+    ownership target goes through the kernel with its position (here fown = own, fopp = opp: equal after every transform)"""
+    from betazero_amd.augment import augment_examples
+    from betazero_amd.engine import DeviceExamples, Examples
+    from betazero_amd.examples import COLUMNS
+    own = np.array([0b000010001, 0b100000000, 0b000000000], np.uint64)   # the first row is symmetric under the main diagonal
+    opp = np.array([0b000000000, 0b000010010, 0b000010000], np.uint64)
+    pi = np.zeros((3, 9), np.float32)
+    pi[0, [2, 6]], pi[1, [0, 2, 3]], pi[2, :4] = 0.5, (0.5, 0.25, 0.25), 0.25
+    ex = Examples(own, opp, pi, np.array([1, -1, 0], np.int8), np.array([1, -1, -1], np.int8), np.array([2, 0, 3], np.uint8),
+                  np.array([7, 7, 2**40], np.int64), np.array([2, 3, 1], np.int32), 3, kl=np.array([0.5, 0.25, 0.125], np.float32),
+                  q=np.array([-0.5, 0.75, 0.1], np.float32), vt=np.array([1.0, -0.25, 0.3], np.float32), fown=own.copy(), fopp=opp.copy(),
+                  count=np.array([1, 5, 2**20], np.int32))
+    assert all(getattr(ex, c.name) is not None for c in COLUMNS)
+    rides = ("z", "mover", "game", "ply", "kl", "q", "vt", "count")
+    for rows in (ex, DeviceExamples.from_host(ex, DEV)):
+        full = augment_examples(rows, dedupe=False)
+        kept = augment_examples(rows, dedupe=True)
+        assert type(full) is type(rows) and type(kept) is type(rows)
+        if rows is not ex:
+            full, kept = full.cpu(), kept.cpu()
+        assert len(full) == 24 and 3 < len(kept) < 24   # the symmetric row loses copies, no row loses all
+        for f in rides:
+            a, b = getattr(full, f), getattr(ex, f)
+            assert a.dtype == b.dtype and np.array_equal(a, np.repeat(b, 8)), f
+        src = np.array([{0.5: 0, 0.25: 1, 0.125: 2}[float(v)] for v in kept.kl])
+        assert sorted(set(src.tolist())) == [0, 1, 2] and (np.diff(src) >= 0).all()
+        for f in rides:
+            a, b = getattr(kept, f), getattr(ex, f)
+            assert a.dtype == b.dtype and np.array_equal(a, b[src]), f
+        for out in (full, kept):
+            assert out.fown.dtype == np.uint64 and np.array_equal(out.fown, out.own) and np.array_equal(out.fopp, out.opp)
+            assert all(getattr(out, c.name) is not None for c in COLUMNS)

@@ -1,4 +1,4 @@
-"""The example pack kernels on the GPU -- k_pack_scan, k_pack_rows, k_pack_kl, k_pack_q (csrc/bz_mcts.hip) -- against pack_twin
+"""The example pack kernels on the GPU -- k_pack_scan, k_pack_rows, k_pack_f32 (csrc/bz_mcts.hip) -- against pack_twin
 of tests/test_pack_cpu.py, byte for byte over the WHOLE block: the header, every row, every byte the kernels must leave alone,
 the pack_off they leave in the engine and the kl / q vectors.  Most blocks are synthetic: an engine that never plays, whose
 example buffers (writable views) are filled from a seeded generator, at every games-per-block count around the scan's
@@ -414,3 +414,76 @@ def test_games_without_rows_in_a_chain_of_three_engines():
     for i, e in enumerate(sp.engines):
         p = blk.pack(Played(e, sum(sp.sizes[:i]), 48), len(want), append=i > 0)
     assert (p.n_rows, p.n_games, p.dropped) == (len(want), 48, 0)
+
+
+# ---------------------------------------------------------------- the engine's per-row extras, all three together
+def _extras_want(engines):
+    """kl, q, fown, fopp of the finished games' rows in (engine, round, slot, ply) order, from the engines' raw buffers:
+    surprise_rows(), search_value_rows() and the ownership-row twin on ownership_rows() and the rows' mover"""
+    from test_ownership_cpu import ownership_row
+    want = {"kl": [np.zeros(0, np.float32)], "q": [np.zeros(0, np.float32)], "fown": [np.zeros(0, np.uint64)], "fopp": [np.zeros(0, np.uint64)]}
+    for e in engines:
+        t = e.example_tensors()
+        lens, mover = t["len"].cpu().numpy(), t["mover"].cpu().numpy()
+        kl, q = e.surprise_rows().cpu().numpy(), e.search_value_rows().cpu().numpy()
+        fx, fo = (x.cpu().numpy().view(np.uint64) for x in e.ownership_rows())
+        for r in range(lens.shape[0]):
+            for b in range(lens.shape[1]):
+                n = max(0, lens[r, b])
+                a, o = ownership_row(np.full(n, fx[r, b]), np.full(n, fo[r, b]), mover[r, b, :n])
+                for k, v in (("kl", kl[r, b, :n]), ("q", q[r, b, :n]), ("fown", a), ("fopp", o)):
+                    want[k].append(v)
+    return {k: np.concatenate(v) for k, v in want.items()}
+
+
+def _check_extras(src, engines, packed):
+    """examples() and device_examples() of `src` carry the engines' kl / q / fown / fopp, host and device alike; `packed`:
+    {column: [cap_rows] device tensor} of the public pack calls, the same vectors"""
+    want = _extras_want(engines)
+    raw = concat_examples([unpack_example_block(e.example_block()) for e in engines])
+    n = len(raw)
+    assert n > 0 and all(len(v) == n for v in want.values()) and len(set(want["kl"].view(np.uint32).tolist())) > 1
+    dev = src.device_examples()
+    assert all(torch.is_tensor(getattr(dev, k)) and getattr(dev, k).is_cuda for k in want)
+    for ex in (src.examples(), dev.cpu()):
+        _same_examples(ex, raw)
+        for k, w in want.items():
+            a = getattr(ex, k)
+            assert a.dtype == w.dtype and a.shape == w.shape and np.array_equal(a.view(np.uint8), w.view(np.uint8)), k
+        assert ex.vt is None and ex.count is None
+    for k, w in want.items():
+        a = packed[k][:n].cpu().numpy()
+        assert packed[k].dtype == getattr(dev, k).dtype and np.array_equal(a.view(np.uint8), w.view(np.uint8)), k
+
+
+def test_one_engine_with_every_extra_on_two_rounds():
+    """surprise, search_value and ownership together: examples() / device_examples() pack the rows once and attach all four
+    columns; tic-tac-toe, 5 games, two rounds with restart"""
+    eng = SelfPlayEngine("ttt", 5, 8, "uniform", rounds=2, temp_moves=4, seed=3, game_id_base=70, surprise=True, search_value=True,
+                         ownership=True)
+    eng.reset_games()
+    for _ in range(2 * 9 + 2):
+        eng.search()
+        eng.play(True)
+        if eng.status()[0] == 0:
+            break
+    assert (eng.winners()[1] > 0).all()
+    eng.pack_examples()
+    fown, fopp = eng.pack_ownership()
+    _check_extras(eng, [eng], {"kl": eng.pack_surprise(), "q": eng.pack_search_value(), "fown": fown, "fopp": fopp})
+
+
+def test_ragged_pipelines_with_every_extra_on():
+    """3 pipelines over 7 games (3 + 2 + 2 slots): append chains of three for the block and for every extra column"""
+    sp = PipelinedSelfPlay("ttt", 7, 8, "uniform", pipelines=3, temp_moves=4, seed=3, game_id_base=20, surprise=True, search_value=True,
+                           ownership=True)
+    assert sp.sizes == [3, 2, 2]
+    sp.run_iteration()
+    sp.sync()
+    blk_kl, kl = sp.pack_examples_with_surprise()
+    blk_q, q = sp.pack_examples_with_search_value()
+    blk_own, fown, fopp = sp.pack_examples_with_ownership()
+    _check_extras(sp, sp.engines, {"kl": kl, "q": q, "fown": fown, "fopp": fopp})
+    raw = concat_examples([unpack_example_block(e.example_block()) for e in sp.engines])
+    for blk in (blk_kl, blk_q, blk_own):
+        _same_examples(unpack_packed_block(blk), raw)

@@ -1,4 +1,4 @@
-"""Policy surprise weighting on the GPU: k_surp_save / k_surp_note / k_surp_kl / k_pack_kl and the resampler
+"""Policy surprise weighting on the GPU: k_surp_save / k_surp_note / k_surp_kl / k_pack_f32 and the resampler
 (csrc/bz_surprise.hip) against the twins of tests/test_surprise_cpu.py.  "Equal" = bit for bit.  The feature observes: with it
 on, every byte the engine wrote without it is the same byte."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Search-value targets on the GPU: k_root_q / k_pack_q against the twins of tests/test_value_targets_cpu.py
+"""Search-value targets on the GPU: k_root_q / k_pack_f32 against the twins of tests/test_value_targets_cpu.py
 and the engine's own root statistics, bz_value_targets against the numpy twin, k_train_heads_vt against k_train_heads, the fp64
 reference and autograd.  "Equal" = bit for bit unless a tolerance is named.  The feature observes: with it on, every byte the
 engine wrote without it is the same byte."""

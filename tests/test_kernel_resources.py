@@ -100,9 +100,8 @@ TABLE = {
         *[row("k_surp_save", g, vgpr=("<=", 32), zero=Z3) for g in GAMES],          # 3.17
         *[row("k_surp_kl", g, vgpr=("<=", 32), zero=Z3) for g in GAMES],
         row("k_surp_note", vgpr=("<=", 32), zero=Z3),                  # shares the row rule with k_root_q
-        row("k_pack_kl", vgpr=("<=", 32), zero=Z3),
         row("k_root_q", vgpr=("<=", 32), zero=Z3),                     # 3.18
-        row("k_pack_q", vgpr=("<=", 32), zero=Z3),
+        row("k_pack_f32", vgpr=("<=", 32), zero=Z3),                   # 3.17's kl and 3.18's q into the packed block's row order
     ],
     "bz_net.hip": [
         # -- the bf16 towers: one workgroup per CU (<= 512); each plain tower keeps the count it had before the

@@ -1,5 +1,5 @@
 """The packed example block (bz_abi.h "Packed examples") without a GPU: pack_twin, a sequential numpy restatement of what
-k_pack_scan / k_pack_rows / k_pack_kl / k_pack_q (csrc/bz_mcts.hip) own of a block -- tests/test_gpu_pack.py pins the kernels
+k_pack_scan / k_pack_rows / k_pack_f32 (csrc/bz_mcts.hip) own of a block -- tests/test_gpu_pack.py pins the kernels
 to it byte for byte -- and the host-side constructors and unpackers of betazero_amd/engine.py against it and against a direct
 loop over (round, slot, ply).  The twin calls neither the library nor the functions of engine.py it is used to check."""
 import numpy as np
@@ -36,7 +36,7 @@ class Packed:
 
 
 def pack_vec_twin(out, src, lens, pack_off, cap):
-    """k_pack_kl / k_pack_q: the per-row source [rounds, B, t_max] of the games with pack_off >= 0 into `out` at off + t,
+    """k_pack_f32: the per-row source [rounds, B, t_max] of the games with pack_off >= 0 into `out` at off + t,
     t < len and off + t < cap; every other element of `out` keeps its bits"""
     out = np.array(out, np.float32).view(np.uint32).copy()
     src = np.asarray(src, np.float32).view(np.uint32).reshape(len(pack_off), -1)

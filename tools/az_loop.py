@@ -199,9 +199,8 @@ def build_parser():
 def window_rows(ex):
     """DeviceExamples -> {column: CPU tensor} (+ the board size), every column the rows carry: what a checkpoint keeps of a
     window slot"""
-    cols = {k: getattr(ex, k).cpu() for k in ("own", "opp", "pi", "z", "mover", "act", "game", "ply", "kl", "q", "vt", "fown", "fopp")
-            if getattr(ex, k) is not None}
-    return {"size": int(ex.size), **cols}
+    from betazero_amd.examples import columns
+    return {"size": int(ex.size), **{k: t.cpu() for k, t in columns(ex).items()}}
 
 
 def to_host(x):
@@ -216,7 +215,7 @@ def to_host(x):
 
 
 def rows_to_device(rows, device="cuda:0"):
-    from betazero_amd.engine import DeviceExamples
+    from betazero_amd.examples import DeviceExamples
     return DeviceExamples(**{k: (v if k == "size" else v.to(device)) for k, v in rows.items()})
 
 
