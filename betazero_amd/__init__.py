@@ -12,14 +12,14 @@ from .players import (Player, ReversiPlayer, RandomPlayer, ReversiRandomPlayer, 
 __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadless", "process_game_positions",
            "Player", "ReversiPlayer", "RandomPlayer", "ReversiRandomPlayer", "MCTSPlayer",
            "OptimalPlayer", "ReversiOptimalPlayer", "NetPlayer", "AIPlayer",
-           "TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model",
+           "TicTacToeNet", "TicTacToePVNet", "DeviceMLP", "MLPTrainer", "PVTrainer", "load_reference_model",
            "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
            "check_early_stop", "merge_positions", "merged_repeats", "save_checkpoint", "load_checkpoint",
            "Reanalyser", "reanalyse", "reanalyse_rows"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
-    if name in ("TicTacToeNet", "DeviceMLP", "MLPTrainer", "load_reference_model"):
+    if name in ("TicTacToeNet", "TicTacToePVNet", "DeviceMLP", "MLPTrainer", "PVTrainer", "load_reference_model"):
         from . import mlp
         return getattr(mlp, name)
     if name in ("MatchPlayer", "MatchResult", "play_match"):  # head-to-head matches

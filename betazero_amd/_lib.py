@@ -151,6 +151,16 @@ _SIGS = {
     "bz_mlp_forward_states_bf16": (i32, [vp, vp, i32, vp, vp]),
     "bz_mlp_train_workspace_bytes": (i64, [i32, i32]),
     "bz_mlp_train_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(MlpAdam), vp, i64, vp, vp, vp, vp]),
+    "bz_mlp_pv_param_count": (i64, [i32]),
+    "bz_mlp_pv_workspace_bytes": (i64, [i32, i32]),
+    "bz_mlp_create_pv": (i32, [i32, i32, vp, vp, i64, vp, C.POINTER(vp)]),
+    "bz_mlp_has_value": (i32, [vp]),
+    "bz_mlp_forward_pv_f32": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "bz_mlp_forward_pv_bf16": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "bz_mlp_forward_pv_states_f32": (i32, [vp, vp, i32, vp, vp, vp]),
+    "bz_mlp_forward_pv_states_bf16": (i32, [vp, vp, i32, vp, vp, vp]),
+    "bz_mlp_train_pv_workspace_bytes": (i64, [i32, i32]),
+    "bz_mlp_train_step_pv": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, C.POINTER(MlpAdam), vp, i64, vp, vp, vp, vp, vp]),
     "bz_engine_workspace_bytes": (i64, [C.POINTER(EngineCfg)]),
     "bz_engine_create": (i32, [C.POINTER(EngineCfg), vp, i64, C.POINTER(vp)]),
     "bz_engine_destroy": (i32, [vp]),

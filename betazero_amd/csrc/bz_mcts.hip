@@ -3548,7 +3548,7 @@ BZ_EXPORT int32_t bz_engine_evaluate(bz_engine* e, void* stream) {
         return BZ_OK;
     }
     if (ek == BZ_EVAL_EXTERNAL) return BZ_OK;
-    if (mlp_eval(ek)) {  // (cfg_ok: tic-tac-toe only) the packed leaves, value 0 -- the reference's net has no value head
+    if (mlp_eval(ek)) {  // (cfg_ok: tic-tac-toe only) the packed leaves; value 0 from the reference's net, which has no value head, the net's own from a PV handle
         BZ_REQUIRE(e->mlp, "bz_engine_evaluate: eval_kind needs an MLP (bz_engine_set_mlp)");
         return bz_mlp_forward_dev(e->mlp, ek == BZ_EVAL_MLP_BF16 ? 1 : 0, e->dev.c_own, e->dev.c_opp, nullptr, e->dev.B * e->dev.K,
                                   e->dev.flags + FLAG_NEVAL + e->pack_parity, e->dev.logits, e->dev.value, stream);

@@ -1,6 +1,8 @@
 // bz_mlp.hip -- the reference's tic-tac-toe policy MLP (SL/neural_networks.py: Linear(9,H)-ReLU-Linear(H,H)-ReLU-
 // Linear(H,H)-ReLU-Linear(H,9), logits only) on gfx950: forward in an fp32 parity mode and a bf16 MFMA mode, and the
 // supervised training step of SL/train.py (softmax cross-entropy on the argmax target, Adam).  DESIGN.md 11.
+// The same net with a value head (TicTacToePVNet: fc4 has a tenth row, v = tanh of it) goes through the same kernels with
+// NO = 10 outputs, and has a training step of its own (soft policy targets, a value loss).
 //
 // Weight forms kept in the workspace (written by bz_mlp_create / bz_mlp_update, and by the training step's Adam kernel):
 //  - wT: fp32, every weight matrix transposed ([in][out], out contiguous) so that the f32 kernels' lanes -- one per
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "bz_common.h"
+#include "bz_math.h"
 
 using namespace bz;
 
@@ -20,19 +23,20 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 m_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float m_f32x4;
 
-constexpr int kIn = 9, kOut = 9;
+constexpr int kIn = 9, kOut = 9, kOutPV = 10;
 constexpr int kF32Rows = 16;   // positions per workgroup of the f32 forward
 constexpr int kTrainRows = 4;  // ... of the training step's forward/backward kernel (batch 128 -> 32 workgroups)
 constexpr int kThreads = 256;
 
 inline bool h_ok(int H) { return H >= 32 && H <= 512 && H % 32 == 0; }
 
-// flat torch order: fc1.w[H][9] fc1.b[H] fc2.w[H][H] fc2.b[H] fc3.w[H][H] fc3.b[H] fc4.w[9][H] fc4.b[9]
+// flat torch order: fc1.w[H][9] fc1.b[H] fc2.w[H][H] fc2.b[H] fc3.w[H][H] fc3.b[H] fc4.w[NO][H] fc4.b[NO]
+// NO = 9 (TicTacToeNet, policy only) or 10 (TicTacToePVNet: row 9 of fc4 is the value pre-activation u, v = tanh(u))
 struct Layout {
     int64_t w[4], b[4], total;
     int K[4], N[4];
-    __host__ __device__ explicit Layout(int H) {
-        const int Ks[4] = {kIn, H, H, H}, Ns[4] = {H, H, H, kOut};
+    __host__ __device__ Layout(int H, int NO) {
+        const int Ks[4] = {kIn, H, H, H}, Ns[4] = {H, H, H, NO};
         int64_t o = 0;
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
@@ -62,7 +66,7 @@ __host__ __device__ inline int frag_k(int l, int kb, int q, int i) {
 }  // namespace
 
 struct bz_mlp {
-    int H, max_batch;
+    int H, max_batch, NO;
     float* wT;      // device, Layout(H).total floats
     uint4* frag;    // device, bf16 fragments
     bool frag_stale;
@@ -71,8 +75,8 @@ struct bz_mlp {
 namespace {
 struct MlpNeed {
     int64_t wT, frag, total;
-    explicit MlpNeed(int H) {
-        Layout L(H);
+    MlpNeed(int H, int NO) {
+        Layout L(H, NO);
         wT = 0;
         frag = (L.total * 4 + 255) & ~int64_t(255);
         total = frag + frag_off(4, H) * 16;
@@ -121,7 +125,7 @@ __device__ __forceinline__ void f32_layer(const float* __restrict__ wT, const fl
     }
 }
 
-__global__ void __launch_bounds__(kThreads) k_mlp_f32(const float* __restrict__ wT, int H, MlpIn in, int max_n,
+__global__ void __launch_bounds__(kThreads) k_mlp_f32(const float* __restrict__ wT, int H, int NO, MlpIn in, int max_n,
                                                       const uint32_t* n_dev, float* __restrict__ logits, float* __restrict__ value) {
     extern __shared__ float4 s_dyn4[];
     float* bufA = reinterpret_cast<float*>(s_dyn4);
@@ -130,7 +134,7 @@ __global__ void __launch_bounds__(kThreads) k_mlp_f32(const float* __restrict__ 
     const int cnt = row_count(max_n, n_dev);
     const int r0 = blockIdx.x * R;
     if (r0 >= cnt) return;
-    const Layout L(H);
+    const Layout L(H, NO);
     for (int t = threadIdx.x; t < kIn * R; t += kThreads) {
         const int k = t / R, r = t % R;
         bufB[t] = r0 + r < cnt ? in.at(r0 + r, k) : 0.0f;
@@ -139,19 +143,21 @@ __global__ void __launch_bounds__(kThreads) k_mlp_f32(const float* __restrict__ 
     f32_layer<R>(wT + L.w[0], wT + L.b[0], kIn, H, bufB, bufA, true); __syncthreads();
     f32_layer<R>(wT + L.w[1], wT + L.b[1], H, H, bufA, bufB, true); __syncthreads();
     f32_layer<R>(wT + L.w[2], wT + L.b[2], H, H, bufB, bufA, true); __syncthreads();
-    f32_layer<R>(wT + L.w[3], wT + L.b[3], H, kOut, bufA, bufB, false); __syncthreads();
+    f32_layer<R>(wT + L.w[3], wT + L.b[3], H, NO, bufA, bufB, false); __syncthreads();
     for (int t = threadIdx.x; t < kOut * R; t += kThreads) {
         const int r = t / kOut, o = t % kOut;
         if (r0 + r < cnt) logits[(size_t)(r0 + r) * kOut + o] = bufB[o * R + r];
     }
-    if (value && threadIdx.x < R && r0 + (int)threadIdx.x < cnt) value[r0 + threadIdx.x] = 0.0f;
+    // unit 9 of a PV net went through the same chain as the logits: v = tanh(u); a policy-only net has no value, 0
+    if (value && threadIdx.x < R && r0 + (int)threadIdx.x < cnt)
+        value[r0 + threadIdx.x] = NO > kOut ? tanhf_spec(bufB[kOut * R + threadIdx.x]) : 0.0f;
 }
 
 // ---- bf16: one wave per 16 positions, every layer as out^T = W . act^T on v_mfma_f32_16x16x32_bf16 (A = weights,
 // row = output unit; B = activations, column = position).  The accumulators of layer l are, after bias + ReLU + the
 // bf16 rounding, the B operand of layer l + 1 as they lie (frag_k); activations never leave the registers.
 template <int H>
-__global__ void __launch_bounds__(64) k_mlp_bf16(const uint4* __restrict__ frag, const float* __restrict__ wT, MlpIn in,
+__global__ void __launch_bounds__(64) k_mlp_bf16(const uint4* __restrict__ frag, const float* __restrict__ wT, int NO, MlpIn in,
                                                  int max_n, const uint32_t* n_dev, float* __restrict__ logits,
                                                  float* __restrict__ value) {
     constexpr int KB = H / 32;
@@ -160,7 +166,7 @@ __global__ void __launch_bounds__(64) k_mlp_bf16(const uint4* __restrict__ frag,
     const int r = blockIdx.x * 16 + col;
     if (blockIdx.x * 16 >= cnt) return;
     const bool ok = r < cnt;
-    const Layout L(H);
+    const Layout L(H, NO);
     m_bf16x8 x0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -209,7 +215,8 @@ __global__ void __launch_bounds__(64) k_mlp_bf16(const uint4* __restrict__ frag,
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) act[kb] = nxt[kb];
     }
-    // layer 3: 9 outputs (one tile of 16, rows 9..15 zero weights)
+    // layer 3: NO outputs (one tile of 16, rows NO..15 zero weights); row 9 of a PV net is the value pre-activation, which
+    // the MFMA leaves in c[1] of lane group 2
     {
         const uint4* f = frag + frag_off(3, H);
         m_f32x4 c = {0.f, 0.f, 0.f, 0.f};
@@ -223,18 +230,21 @@ __global__ void __launch_bounds__(64) k_mlp_bf16(const uint4* __restrict__ frag,
                 const int o = 4 * q + i;
                 if (o < kOut) logits[(size_t)r * kOut + o] = c[i] + b[o];
             }
-            if (value && q == 0) value[r] = 0.0f;
+            if (value) {
+                if (NO > kOut) { if (q == 2) value[r] = tanhf_spec(c[1] + b[kOut]); }
+                else if (q == 0) value[r] = 0.0f;
+            }
         }
     }
 }
 
 // wT (fp32, [in][out]) -> bf16 fragments; one thread per (fragment, lane)
-__global__ void k_mlp_pack_bf16(const float* __restrict__ wT, int H, uint4* __restrict__ frag) {
+__global__ void k_mlp_pack_bf16(const float* __restrict__ wT, int H, int NO, uint4* __restrict__ frag) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= frag_off(4, H)) return;
     const int l = t >= frag_off(3, H) ? 3 : (t >= frag_off(2, H) ? 2 : (t >= frag_off(1, H) ? 1 : 0));
-    const Layout L(H);
-    const int K = l == 0 ? kIn : H, N = l == 3 ? kOut : H;
+    const Layout L(H, NO);
+    const int K = l == 0 ? kIn : H, N = l == 3 ? NO : H;
     const int64_t w0 = l == 0 ? L.w[0] : (l == 1 ? L.w[1] : (l == 2 ? L.w[2] : L.w[3]));
     const int64_t u = t - frag_off(l, H);
     const int lane = (int)(u % 64), fidx = (int)(u / 64);
@@ -252,7 +262,7 @@ __global__ void k_mlp_pack_bf16(const float* __restrict__ wT, int H, uint4* __re
 
 int32_t pack_bf16(bz_mlp* m, hipStream_t s) {
     const int64_t n = frag_off(4, m->H);
-    hipLaunchKernelGGL(k_mlp_pack_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->wT, m->H, m->frag);
+    hipLaunchKernelGGL(k_mlp_pack_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->wT, m->H, m->NO, m->frag);
     BZ_LAUNCH_CHECK("k_mlp_pack_bf16");
     m->frag_stale = false;
     return BZ_OK;
@@ -260,7 +270,7 @@ int32_t pack_bf16(bz_mlp* m, hipStream_t s) {
 
 // torch layout (host) -> wT (host), then upload and rebuild the fragments
 int32_t upload(bz_mlp* m, const float* p, hipStream_t s) {
-    const Layout L(m->H);
+    const Layout L(m->H, m->NO);
     std::vector<float> t((size_t)L.total);
     for (int l = 0; l < 4; ++l) {
         const int K = L.K[l], N = L.N[l];
@@ -276,27 +286,18 @@ int32_t upload(bz_mlp* m, const float* p, hipStream_t s) {
 }
 }  // namespace
 
-BZ_EXPORT int64_t bz_mlp_param_count(int32_t H) {
-    if (!h_ok(H)) { set_error("bz_mlp_param_count: H must be a multiple of 32 in 32..512"); return -1; }
-    return Layout(H).total;
-}
-
-BZ_EXPORT int64_t bz_mlp_workspace_bytes(int32_t H, int32_t max_batch) {
-    if (!h_ok(H) || max_batch < 1) { set_error("bz_mlp_workspace_bytes: H must be a multiple of 32 in 32..512, max_batch >= 1"); return -1; }
-    return MlpNeed(H).total;
-}
-
-BZ_EXPORT int32_t bz_mlp_create(int32_t H, int32_t max_batch, const float* params_host, void* ws, int64_t bytes, void* stream,
-                                bz_mlp** out) {
-    BZ_REQUIRE(h_ok(H) && max_batch >= 1, "bz_mlp_create: H must be a multiple of 32 in 32..512, max_batch >= 1");
-    BZ_REQUIRE(params_host && ws && out, "bz_mlp_create: null pointer");
-    const MlpNeed need(H);
-    if (bytes < need.total) { set_error("bz_mlp_create: workspace too small (%lld < %lld)", (long long)bytes, (long long)need.total); return BZ_ENOMEM; }
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "bz_mlp_create: workspace must be 256-byte aligned");
-    if (bz_device_count() <= 0) { set_error("bz_mlp_create: no HIP device (the MLP has no CPU path)"); return BZ_ENOGPU; }
+namespace {
+int32_t create(const char* who, int32_t H, int NO, int32_t max_batch, const float* params_host, void* ws, int64_t bytes, void* stream,
+               bz_mlp** out) {
+    if (!(h_ok(H) && max_batch >= 1)) { set_error("%s: H must be a multiple of 32 in 32..512, max_batch >= 1", who); return BZ_EINVAL; }
+    if (!(params_host && ws && out)) { set_error("%s: null pointer", who); return BZ_EINVAL; }
+    const MlpNeed need(H, NO);
+    if (bytes < need.total) { set_error("%s: workspace too small (%lld < %lld)", who, (long long)bytes, (long long)need.total); return BZ_ENOMEM; }
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) { set_error("%s: workspace must be 256-byte aligned", who); return BZ_EINVAL; }
+    if (bz_device_count() <= 0) { set_error("%s: no HIP device (the MLP has no CPU path)", who); return BZ_ENOGPU; }
     bz_mlp* m = new (std::nothrow) bz_mlp();
     if (!m) { set_error("out of host memory"); return BZ_ENOMEM; }
-    m->H = H; m->max_batch = max_batch;
+    m->H = H; m->max_batch = max_batch; m->NO = NO;
     m->wT = reinterpret_cast<float*>(static_cast<char*>(ws) + need.wT);
     m->frag = reinterpret_cast<uint4*>(static_cast<char*>(ws) + need.frag);
     int32_t rc = upload(m, params_host, (hipStream_t)stream);
@@ -309,6 +310,39 @@ BZ_EXPORT int32_t bz_mlp_create(int32_t H, int32_t max_batch, const float* param
     *out = m;
     return BZ_OK;
 }
+}  // namespace
+
+BZ_EXPORT int64_t bz_mlp_param_count(int32_t H) {
+    if (!h_ok(H)) { set_error("bz_mlp_param_count: H must be a multiple of 32 in 32..512"); return -1; }
+    return Layout(H, kOut).total;
+}
+
+BZ_EXPORT int64_t bz_mlp_pv_param_count(int32_t H) {
+    if (!h_ok(H)) { set_error("bz_mlp_pv_param_count: H must be a multiple of 32 in 32..512"); return -1; }
+    return Layout(H, kOutPV).total;
+}
+
+BZ_EXPORT int64_t bz_mlp_workspace_bytes(int32_t H, int32_t max_batch) {
+    if (!h_ok(H) || max_batch < 1) { set_error("bz_mlp_workspace_bytes: H must be a multiple of 32 in 32..512, max_batch >= 1"); return -1; }
+    return MlpNeed(H, kOut).total;
+}
+
+BZ_EXPORT int64_t bz_mlp_pv_workspace_bytes(int32_t H, int32_t max_batch) {
+    if (!h_ok(H) || max_batch < 1) { set_error("bz_mlp_pv_workspace_bytes: H must be a multiple of 32 in 32..512, max_batch >= 1"); return -1; }
+    return MlpNeed(H, kOutPV).total;
+}
+
+BZ_EXPORT int32_t bz_mlp_create(int32_t H, int32_t max_batch, const float* params_host, void* ws, int64_t bytes, void* stream,
+                                bz_mlp** out) {
+    return create("bz_mlp_create", H, kOut, max_batch, params_host, ws, bytes, stream, out);
+}
+
+BZ_EXPORT int32_t bz_mlp_create_pv(int32_t H, int32_t max_batch, const float* params_host, void* ws, int64_t bytes, void* stream,
+                                   bz_mlp** out) {
+    return create("bz_mlp_create_pv", H, kOutPV, max_batch, params_host, ws, bytes, stream, out);
+}
+
+BZ_EXPORT int32_t bz_mlp_has_value(const bz_mlp* m) { return m && m->NO > kOut ? 1 : 0; }
 
 BZ_EXPORT int32_t bz_mlp_destroy(bz_mlp* m) {
     delete m;
@@ -333,7 +367,7 @@ int32_t bz_mlp_forward_dev(bz_mlp* m, int bf16, const uint64_t* own, const uint6
     MlpIn in; in.own = own; in.opp = opp; in.x = x;
     if (!bf16) {
         hipLaunchKernelGGL(k_mlp_f32, dim3((max_n + kF32Rows - 1) / kF32Rows), dim3(kThreads), (size_t)m->H * kF32Rows * 2 * 4, s,
-                           m->wT, m->H, in, max_n, n_dev, logits, value);
+                           m->wT, m->H, m->NO, in, max_n, n_dev, logits, value);
         BZ_LAUNCH_CHECK("k_mlp_f32");
         return BZ_OK;
     }
@@ -343,7 +377,7 @@ int32_t bz_mlp_forward_dev(bz_mlp* m, int bf16, const uint64_t* own, const uint6
     }
     const dim3 grid((max_n + 15) / 16);
     switch (m->H) {
-#define BZ_MLP_H(HH) case HH: hipLaunchKernelGGL(k_mlp_bf16<HH>, grid, dim3(64), 0, s, m->frag, m->wT, in, max_n, n_dev, logits, value); break;
+#define BZ_MLP_H(HH) case HH: hipLaunchKernelGGL(k_mlp_bf16<HH>, grid, dim3(64), 0, s, m->frag, m->wT, m->NO, in, max_n, n_dev, logits, value); break;
         BZ_MLP_H(32) BZ_MLP_H(64) BZ_MLP_H(96) BZ_MLP_H(128) BZ_MLP_H(160) BZ_MLP_H(192) BZ_MLP_H(224) BZ_MLP_H(256)
         BZ_MLP_H(288) BZ_MLP_H(320) BZ_MLP_H(352) BZ_MLP_H(384) BZ_MLP_H(416) BZ_MLP_H(448) BZ_MLP_H(480) BZ_MLP_H(512)
 #undef BZ_MLP_H
@@ -370,21 +404,52 @@ BZ_EXPORT int32_t bz_mlp_forward_states_bf16(bz_mlp* m, const float* x, int32_t 
     return bz_mlp_forward_dev(m, 1, nullptr, nullptr, x, n, nullptr, logits, nullptr, stream);
 }
 
+
+// logits and value of a PV handle (bz_mlp_create_pv); a policy-only handle has no value to give
+#define BZ_MLP_PV(who) \
+    BZ_REQUIRE(m && value, who ": null pointer"); \
+    BZ_REQUIRE(m->NO > kOut, who ": the net has no value head (bz_mlp_create_pv makes one that has)")
+BZ_EXPORT int32_t bz_mlp_forward_pv_f32(bz_mlp* m, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, float* value,
+                                        void* stream) {
+    BZ_MLP_PV("bz_mlp_forward_pv_f32");
+    BZ_REQUIRE(own && opp, "bz_mlp_forward_pv_f32: null pointer");
+    return bz_mlp_forward_dev(m, 0, own, opp, nullptr, n, nullptr, logits, value, stream);
+}
+BZ_EXPORT int32_t bz_mlp_forward_pv_bf16(bz_mlp* m, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, float* value,
+                                         void* stream) {
+    BZ_MLP_PV("bz_mlp_forward_pv_bf16");
+    BZ_REQUIRE(own && opp, "bz_mlp_forward_pv_bf16: null pointer");
+    return bz_mlp_forward_dev(m, 1, own, opp, nullptr, n, nullptr, logits, value, stream);
+}
+BZ_EXPORT int32_t bz_mlp_forward_pv_states_f32(bz_mlp* m, const float* x, int32_t n, float* logits, float* value, void* stream) {
+    BZ_MLP_PV("bz_mlp_forward_pv_states_f32");
+    BZ_REQUIRE(x, "bz_mlp_forward_pv_states_f32: null pointer");
+    return bz_mlp_forward_dev(m, 0, nullptr, nullptr, x, n, nullptr, logits, value, stream);
+}
+BZ_EXPORT int32_t bz_mlp_forward_pv_states_bf16(bz_mlp* m, const float* x, int32_t n, float* logits, float* value, void* stream) {
+    BZ_MLP_PV("bz_mlp_forward_pv_states_bf16");
+    BZ_REQUIRE(x, "bz_mlp_forward_pv_states_bf16: null pointer");
+    return bz_mlp_forward_dev(m, 1, nullptr, nullptr, x, n, nullptr, logits, value, stream);
+}
+#undef BZ_MLP_PV
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Training step (SL/train.py: CrossEntropyLoss(logits, argmax action), mean over the batch, then Adam).  Two launches:
 //  1. k_mlp_train_fb: per kTrainRows rows -- the f32 forward (saving the post-ReLU activations), softmax-CE gradient,
 //     backward-data through fc4..fc2 (ReLU masks from the saved activations); writes a1..a3, d1..d3, g4 and the rows' loss.
 //  2. k_mlp_train_adam: one thread per parameter -- its gradient summed over the rows in ascending order (deterministic),
 //     then Adam on (p, m, v) and the transposed copy the forward reads.  Block 0 also sums the loss (ascending rows).
+// The PV step (k_mlp_train_fb_pv, bz_mlp_train_step_pv) is the same two launches on a PV net: soft policy targets pi and a
+// value target vt per row, loss = sum_o pi_o (lse(z) - z_o) + c (v - vt)^2, fc4 and g4 ten outputs wide.
 namespace {
 struct TrainNeed {
     int64_t a[3], d[3], g4, rl, total;
-    TrainNeed(int H, int B) {
+    TrainNeed(int H, int B, int NO) {
         int64_t o = 0;
         auto take = [&](int64_t bytes) { int64_t r = o; o += (bytes + 255) & ~int64_t(255); return r; };
         for (int i = 0; i < 3; ++i) a[i] = take((int64_t)B * H * 4);
         for (int i = 0; i < 3; ++i) d[i] = take((int64_t)B * H * 4);
-        g4 = take((int64_t)B * kOut * 4);
+        g4 = take((int64_t)B * NO * 4);
         rl = take((int64_t)B * 4);
         total = o;
     }
@@ -417,17 +482,23 @@ __device__ __forceinline__ void bwd_layer(const float* __restrict__ W, int K, in
     }
 }
 
-__global__ void __launch_bounds__(kThreads) k_mlp_train_fb(const float* __restrict__ wT, const float* __restrict__ p, int H,
-                                                           const float* __restrict__ x, const int32_t* __restrict__ target,
-                                                           const float* __restrict__ row_w, int n, TrainPtrs T,
-                                                           float* __restrict__ logits_out, uint32_t* err) {
+// what a row is trained towards: the supervised step's class index, or the PV step's (pi, vt) with the value weight c
+struct TrainTarget {
+    const int32_t* target;                   // [n], 0..8                         (NO = 9)
+    const float* pi; const float* vt; float c;  // [n][9] >= 0, [n] in [-1, 1]    (NO = 10)
+};
+
+template <int NO>
+__device__ __forceinline__ void train_fb(const float* __restrict__ wT, const float* __restrict__ p, int H, const float* __restrict__ x,
+                                         const TrainTarget G, const float* __restrict__ row_w, int n, TrainPtrs T,
+                                         float* __restrict__ logits_out, float* __restrict__ value_out, uint32_t* err) {
     constexpr int R = kTrainRows;
     extern __shared__ float4 s_dyn4[];
     float* bufA = reinterpret_cast<float*>(s_dyn4);
     float* bufB = bufA + (size_t)H * R;
     __shared__ float s_red[kThreads];
     const int r0 = blockIdx.x * R;
-    const Layout L(H);
+    const Layout L(H, NO);
     // sum of the row weights, in a fixed order (every workgroup computes the same bits)
     float sw = 0.0f;
     for (int r = threadIdx.x; r < n; r += kThreads) sw += row_w ? row_w[r] : 1.0f;
@@ -455,15 +526,14 @@ __global__ void __launch_bounds__(kThreads) k_mlp_train_fb(const float* __restri
                     if (r0 + r < n) T.a[l][(size_t)(r0 + r) * H + j] = dst[j * R + r];
         float* t = const_cast<float*>(src); src = dst; dst = t;
     }
-    // src = logits [9][R]; softmax-CE gradient, scaled by w_r / sum w
-    float* g4l = dst;  // [9][R]
+    // src = fc4's outputs [NO][R]; the loss gradient on them, scaled by w_r / sum w
+    float* g4l = dst;  // [NO][R]
     if ((int)threadIdx.x < R) {
         const int r = threadIdx.x, row = r0 + r;
-        float g[kOut];
-        for (int o = 0; o < kOut; ++o) g[o] = 0.0f;
+        float g[NO];
+        for (int o = 0; o < NO; ++o) g[o] = 0.0f;
         if (row < n) {
             const float w = row_w ? row_w[row] : 1.0f;
-            const int t = target[row];
             float z[kOut], mx = -INFINITY;
             for (int o = 0; o < kOut; ++o) { z[o] = src[o * R + r]; mx = fmaxf(mx, z[o]); }
             if (logits_out)
@@ -473,33 +543,79 @@ __global__ void __launch_bounds__(kThreads) k_mlp_train_fb(const float* __restri
             const float scale = w / sumw;
             float loss = 0.0f;
             if (!(sumw > 0.0f)) atomicOr(err, 4u);
-            if (t < 0 || t >= kOut) { if (w != 0.0f) atomicOr(err, 1u); }
-            else if (w != 0.0f) {
-                const float ce = (mx + logf(s)) - z[t];
-                if (!isfinite(ce)) atomicOr(err, 2u);
-                loss = scale * ce;
-                for (int o = 0; o < kOut; ++o) g[o] = scale * (expf(z[o] - mx) / s - (o == t ? 1.0f : 0.0f));
+            if constexpr (NO == kOut) {
+                const int t = G.target[row];
+                if (t < 0 || t >= kOut) { if (w != 0.0f) atomicOr(err, 1u); }
+                else if (w != 0.0f) {
+                    const float ce = (mx + logf(s)) - z[t];
+                    if (!isfinite(ce)) atomicOr(err, 2u);
+                    loss = scale * ce;
+                    for (int o = 0; o < kOut; ++o) g[o] = scale * (expf(z[o] - mx) / s - (o == t ? 1.0f : 0.0f));
+                }
+            } else {
+                const float v = tanhf_spec(src[kOut * R + r]);  // the inference forward's value, bit for bit
+                if (value_out) value_out[row] = v;
+                if (w != 0.0f) {
+                    float pi[kOut], sp = 0.0f;
+                    bool bad = false;
+                    for (int o = 0; o < kOut; ++o) {
+                        pi[o] = G.pi[(size_t)row * kOut + o];
+                        if (!(pi[o] >= 0.0f) || !isfinite(pi[o])) bad = true;
+                        sp += pi[o];
+                    }
+                    const float vt = G.vt[row];
+                    if (!(sp > 0.0f) || !(vt >= -1.0f && vt <= 1.0f)) bad = true;
+                    if (bad) atomicOr(err, 1u);
+                    else {
+                        const float lse = mx + logf(s);
+                        float ce = 0.0f;
+                        for (int o = 0; o < kOut; ++o) ce += pi[o] * (lse - z[o]);
+                        const float dv = v - vt;
+                        const float rl = ce + G.c * (dv * dv);
+                        if (!isfinite(rl)) atomicOr(err, 2u);
+                        loss = scale * rl;
+                        for (int o = 0; o < kOut; ++o) g[o] = scale * (sp * (expf(z[o] - mx) / s) - pi[o]);
+                        g[kOut] = ((scale * G.c) * (2.0f * dv)) * (1.0f - v * v);
+                    }
+                }
             }
             T.rl[row] = loss;
-            for (int o = 0; o < kOut; ++o) T.g4[(size_t)row * kOut + o] = g[o];
+            for (int o = 0; o < NO; ++o) T.g4[(size_t)row * NO + o] = g[o];
         }
-        for (int o = 0; o < kOut; ++o) g4l[o * R + r] = g[o];
+        for (int o = 0; o < NO; ++o) g4l[o * R + r] = g[o];
     }
     __syncthreads();
     // backward-data: d3 = W4^T g4 * mask3, d2 = W3^T d3 * mask2, d1 = W2^T d2 * mask1
     float* other = const_cast<float*>(src);
-    bwd_layer<R>(p + L.w[3], H, kOut, g4l, T.a[2], r0, n, other, T.d[2]); __syncthreads();
+    bwd_layer<R>(p + L.w[3], H, NO, g4l, T.a[2], r0, n, other, T.d[2]); __syncthreads();
     bwd_layer<R>(p + L.w[2], H, H, other, T.a[1], r0, n, g4l, T.d[1]); __syncthreads();
     bwd_layer<R>(p + L.w[1], H, H, g4l, T.a[0], r0, n, other, T.d[0]);
 }
 
+__global__ void __launch_bounds__(kThreads) k_mlp_train_fb(const float* __restrict__ wT, const float* __restrict__ p, int H,
+                                                           const float* __restrict__ x, const int32_t* __restrict__ target,
+                                                           const float* __restrict__ row_w, int n, TrainPtrs T,
+                                                           float* __restrict__ logits_out, uint32_t* err) {
+    TrainTarget G; G.target = target; G.pi = nullptr; G.vt = nullptr; G.c = 0.0f;
+    train_fb<kOut>(wT, p, H, x, G, row_w, n, T, logits_out, nullptr, err);
+}
+
+__global__ void __launch_bounds__(kThreads) k_mlp_train_fb_pv(const float* __restrict__ wT, const float* __restrict__ p, int H,
+                                                              const float* __restrict__ x, const float* __restrict__ pi,
+                                                              const float* __restrict__ vt, float c, const float* __restrict__ row_w,
+                                                              int n, TrainPtrs T, float* __restrict__ logits_out,
+                                                              float* __restrict__ value_out, uint32_t* err) {
+    TrainTarget G; G.target = nullptr; G.pi = pi; G.vt = vt; G.c = c;
+    train_fb<kOutPV>(wT, p, H, x, G, row_w, n, T, logits_out, value_out, err);
+}
+
 struct AdamArgs { float lr, beta1, beta2, eps, step_size, bc2_sqrt; };
 
-__global__ void __launch_bounds__(256) k_mlp_train_adam(int H, int n, const float* __restrict__ x, TrainPtrs T,
+__global__ void __launch_bounds__(256) k_mlp_train_adam(int H, int NO, int n, const float* __restrict__ x, TrainPtrs T,
                                                         float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                         float* __restrict__ grad, float* __restrict__ wT, AdamArgs A,
                                                         const uint32_t* __restrict__ err, float* __restrict__ loss) {
-    const Layout L(H);
+    const Layout L(H, NO);
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0 && loss) {
         float s = 0.0f;
@@ -508,7 +624,7 @@ __global__ void __launch_bounds__(256) k_mlp_train_adam(int H, int n, const floa
     }
     if (t >= L.total) return;
     const int l = t >= L.w[3] ? 3 : (t >= L.w[2] ? 2 : (t >= L.w[1] ? 1 : 0));
-    const int K = l == 0 ? kIn : H, N = l == 3 ? kOut : H;
+    const int K = l == 0 ? kIn : H, N = l == 3 ? NO : H;
     const int64_t wl = l == 0 ? L.w[0] : (l == 1 ? L.w[1] : (l == 2 ? L.w[2] : L.w[3]));
     const int64_t bl = wl + (int64_t)K * N;
     const float* dl = l == 3 ? T.g4 : (l == 2 ? T.d[2] : (l == 1 ? T.d[1] : T.d[0]));  // [n][N]
@@ -536,29 +652,62 @@ __global__ void __launch_bounds__(256) k_mlp_train_adam(int H, int n, const floa
     const float pt = p[t] - A.step_size * (mt / denom);
     m[t] = mt; v[t] = vt; p[t] = pt; wT[tw] = pt;
 }
+
+// the arguments both steps share, checked; then the workspace carved and the Adam scalars made
+int32_t train_prepare(const char* who, const bz_mlp* mlp, int NO, int32_t n, const bz_mlp_adam* adam, void* ws, int64_t ws_bytes,
+                      TrainPtrs* T, AdamArgs* A) {
+    if (mlp->NO != NO) {
+        set_error(NO == kOut ? "%s: the net has a value head (bz_mlp_train_step_pv trains it)"
+                             : "%s: the net has no value head (bz_mlp_create_pv makes one that has)", who);
+        return BZ_EINVAL;
+    }
+    if (!(n >= 1 && n <= mlp->max_batch)) { set_error("%s: need 1 <= n <= max_batch", who); return BZ_EINVAL; }
+    if (!(adam->step >= 1 && adam->lr >= 0.0f && adam->beta1 >= 0.0f && adam->beta1 < 1.0f && adam->beta2 >= 0.0f &&
+          adam->beta2 < 1.0f && adam->eps >= 0.0f)) { set_error("%s: bad Adam hyper-parameters", who); return BZ_EINVAL; }
+    const TrainNeed need(mlp->H, n, NO);
+    if (ws_bytes < need.total) { set_error("%s: workspace too small (bz_mlp_train_workspace_bytes)", who); return BZ_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) { set_error("%s: workspace must be 256-byte aligned", who); return BZ_EINVAL; }
+    char* base = static_cast<char*>(ws);
+    for (int i = 0; i < 3; ++i) { T->a[i] = reinterpret_cast<float*>(base + need.a[i]); T->d[i] = reinterpret_cast<float*>(base + need.d[i]); }
+    T->g4 = reinterpret_cast<float*>(base + need.g4); T->rl = reinterpret_cast<float*>(base + need.rl);
+    A->lr = adam->lr; A->beta1 = adam->beta1; A->beta2 = adam->beta2; A->eps = adam->eps;
+    // torch computes the bias corrections in double on the host (capturable=False), then uses them as scalars
+    const double bc1 = 1.0 - pow((double)adam->beta1, adam->step), bc2 = 1.0 - pow((double)adam->beta2, adam->step);
+    A->step_size = (float)((double)adam->lr / bc1);
+    A->bc2_sqrt = (float)sqrt(bc2);
+    return BZ_OK;
+}
+
+int32_t train_adam(bz_mlp* mlp, int32_t n, const float* x, const TrainPtrs& T, float* params, float* m, float* v, float* grad,
+                   const AdamArgs& A, const uint32_t* err, float* loss, hipStream_t s) {
+    const int64_t P = Layout(mlp->H, mlp->NO).total;
+    hipLaunchKernelGGL(k_mlp_train_adam, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, mlp->H, mlp->NO, n, x, T, params, m, v,
+                       grad, mlp->wT, A, err, loss);
+    BZ_LAUNCH_CHECK("k_mlp_train_adam");
+    mlp->frag_stale = true;
+    return BZ_OK;
+}
 }  // namespace
 
 BZ_EXPORT int64_t bz_mlp_train_workspace_bytes(int32_t H, int32_t max_batch) {
     if (!h_ok(H) || max_batch < 1) { set_error("bz_mlp_train_workspace_bytes: H must be a multiple of 32 in 32..512, max_batch >= 1"); return -1; }
-    return TrainNeed(H, max_batch).total;
+    return TrainNeed(H, max_batch, kOut).total;
+}
+
+BZ_EXPORT int64_t bz_mlp_train_pv_workspace_bytes(int32_t H, int32_t max_batch) {
+    if (!h_ok(H) || max_batch < 1) { set_error("bz_mlp_train_pv_workspace_bytes: H must be a multiple of 32 in 32..512, max_batch >= 1"); return -1; }
+    return TrainNeed(H, max_batch, kOutPV).total;
 }
 
 BZ_EXPORT int32_t bz_mlp_train_step(bz_mlp* mlp, float* params, float* m, float* v, float* grad, const float* x,
                                     const int32_t* target, const float* row_w, int32_t n, const bz_mlp_adam* adam,
                                     void* ws, int64_t ws_bytes, float* loss, float* logits, uint32_t* err, void* stream) {
     BZ_REQUIRE(mlp && params && m && v && x && target && adam && ws && err, "bz_mlp_train_step: null pointer");
-    BZ_REQUIRE(n >= 1 && n <= mlp->max_batch, "bz_mlp_train_step: need 1 <= n <= max_batch");
-    BZ_REQUIRE(adam->step >= 1 && adam->lr >= 0.0f && adam->beta1 >= 0.0f && adam->beta1 < 1.0f && adam->beta2 >= 0.0f &&
-               adam->beta2 < 1.0f && adam->eps >= 0.0f, "bz_mlp_train_step: bad Adam hyper-parameters");
-    const TrainNeed need(mlp->H, n);
-    BZ_REQUIRE(ws_bytes >= need.total, "bz_mlp_train_step: workspace too small (bz_mlp_train_workspace_bytes)");
-    BZ_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "bz_mlp_train_step: workspace must be 256-byte aligned");
+    TrainPtrs T; AdamArgs A;
+    int32_t rc = train_prepare("bz_mlp_train_step", mlp, kOut, n, adam, ws, ws_bytes, &T, &A);
+    if (rc != BZ_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int H = mlp->H;
-    TrainPtrs T;
-    char* base = static_cast<char*>(ws);
-    for (int i = 0; i < 3; ++i) { T.a[i] = reinterpret_cast<float*>(base + need.a[i]); T.d[i] = reinterpret_cast<float*>(base + need.d[i]); }
-    T.g4 = reinterpret_cast<float*>(base + need.g4); T.rl = reinterpret_cast<float*>(base + need.rl);
     {
         static unsigned done = 0;
         const int lds = H * kTrainRows * 2 * 4;
@@ -568,16 +717,28 @@ BZ_EXPORT int32_t bz_mlp_train_step(bz_mlp* mlp, float* params, float* m, float*
                            mlp->wT, params, H, x, target, row_w, n, T, logits, err);
         BZ_LAUNCH_CHECK("k_mlp_train_fb");
     }
-    AdamArgs A;
-    A.lr = adam->lr; A.beta1 = adam->beta1; A.beta2 = adam->beta2; A.eps = adam->eps;
-    // torch computes the bias corrections in double on the host (capturable=False), then uses them as scalars
-    const double bc1 = 1.0 - pow((double)adam->beta1, adam->step), bc2 = 1.0 - pow((double)adam->beta2, adam->step);
-    A.step_size = (float)((double)adam->lr / bc1);
-    A.bc2_sqrt = (float)sqrt(bc2);
-    const int64_t P = Layout(H).total;
-    hipLaunchKernelGGL(k_mlp_train_adam, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, H, n, x, T, params, m, v, grad,
-                       mlp->wT, A, err, loss);
-    BZ_LAUNCH_CHECK("k_mlp_train_adam");
-    mlp->frag_stale = true;
-    return BZ_OK;
+    return train_adam(mlp, n, x, T, params, m, v, grad, A, err, loss, s);
+}
+
+BZ_EXPORT int32_t bz_mlp_train_step_pv(bz_mlp* mlp, float* params, float* m, float* v, float* grad, const float* x,
+                                       const float* pi, const float* vt, const float* row_w, int32_t n, float value_weight,
+                                       const bz_mlp_adam* adam, void* ws, int64_t ws_bytes, float* loss, float* logits, float* value,
+                                       uint32_t* err, void* stream) {
+    BZ_REQUIRE(mlp && params && m && v && x && pi && vt && adam && ws && err, "bz_mlp_train_step_pv: null pointer");
+    BZ_REQUIRE(value_weight >= 0.0f && isfinite(value_weight), "bz_mlp_train_step_pv: value_weight must be finite and >= 0");
+    TrainPtrs T; AdamArgs A;
+    int32_t rc = train_prepare("bz_mlp_train_step_pv", mlp, kOutPV, n, adam, ws, ws_bytes, &T, &A);
+    if (rc != BZ_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int H = mlp->H;
+    {
+        static unsigned done = 0;
+        const int lds = H * kTrainRows * 2 * 4;
+        hipError_t e = lds_attr_per_device(reinterpret_cast<const void*>(k_mlp_train_fb_pv), lds, &done);
+        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_mlp_train_fb_pv)");
+        hipLaunchKernelGGL(k_mlp_train_fb_pv, dim3((n + kTrainRows - 1) / kTrainRows), dim3(kThreads), (size_t)lds, s,
+                           mlp->wT, params, H, x, pi, vt, value_weight, row_w, n, T, logits, value, err);
+        BZ_LAUNCH_CHECK("k_mlp_train_fb_pv");
+    }
+    return train_adam(mlp, n, x, T, params, m, v, grad, A, err, loss, s);
 }

@@ -19,7 +19,7 @@ from .examples import (_EX_FIELDS, _GAMES, _PK_FIELDS, _SIZES, COLUMN, EX_MAGIC,
 
 _EVALS = {"uniform": EVAL_UNIFORM, "hash": EVAL_HASH, "net_f32": EVAL_NET_F32, "net_bf16": EVAL_NET_BF16,
           "external": EVAL_EXTERNAL, "net_fp8": EVAL_NET_FP8,
-          # the reference's tic-tac-toe MLP (betazero_amd.mlp.DeviceMLP as `net`): policy logits, value 0
+          # the reference's tic-tac-toe MLP (betazero_amd.mlp.DeviceMLP as `net`): policy logits; value 0, or the net's own with a value head
           "mlp_f32": _lib.EVAL_MLP_F32, "mlp_bf16": _lib.EVAL_MLP_BF16}
 
 

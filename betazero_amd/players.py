@@ -114,7 +114,7 @@ class NetPlayer(ReversiPlayer):
 class AIPlayer(Player):
     """The reference's AIPlayer (src/tic_tac_toe/players.py:76-104) on the device MLP: AIPlayer(path_to_model, symbol)
     loads the reference's checkpoint (mlp.load_reference_model: weights_only=True, never a pickle's code); path_to_model
-    may also be a TicTacToeNet or a DeviceMLP.  get_move runs one forward of symbol * board and plays the best LEGAL move
+    may also be a TicTacToeNet, a TicTacToePVNet (its logits alone are used) or a DeviceMLP.  get_move runs one forward of symbol * board and plays the best LEGAL move
     in descending-logit order; ties go to the lowest cell (torch.sort leaves their order unspecified).  Unlike the
     reference it prints nothing (its three debug print lines, :100-102); the logits of the last call are in last_logits.
     precision: "f32" (parity) or "bf16" (MFMA)."""
@@ -147,7 +147,8 @@ class MCTSPlayer(Player):
     from `board` with `symbol` to move; plays argmax visit count (ties -> lowest
     action).  Works for TicTacToeBoard and 8x8 ReversiBoard; evaluator "net_bf16"
     / "net_f32" need a betazero_amd.net.DeviceNet (Reversi, any of the reference's board sizes); "mlp_f32" (the default
-    with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0).
+    with a betazero_amd.mlp.DeviceMLP) / "mlp_bf16" the reference's tic-tac-toe MLP (policy only: leaf value 0; a
+    DeviceMLP of a TicTacToePVNet gives the leaves its own value).
     gumbel (True or an engine.GumbelConfig): Gumbel root search -- the move is the one the Gumbel search
     plays (SelfPlayEngine.root_policy) and last_policy its improved policy; the player draws no Gumbel noise (temp_moves 0),
     so it is deterministic.  eval_symmetry (True or a symmetry.EvalSymmetry): every leaf is evaluated under a hashed board

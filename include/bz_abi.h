@@ -48,8 +48,9 @@ enum { BZ_GAME_TTT = 0, BZ_GAME_REVERSI = 1, BZ_GAME_REVERSI6 = 2, BZ_GAME_REVER
 enum { BZ_EVAL_UNIFORM = 0, BZ_EVAL_HASH = 1, BZ_EVAL_NET_F32 = 2, BZ_EVAL_NET_BF16 = 3,
        BZ_EVAL_EXTERNAL = 4, BZ_EVAL_NET_FP8 = 5,
        /* the reference's tic-tac-toe policy MLP (bz_mlp below, set by bz_engine_set_mlp), BZ_GAME_TTT only:
-        * the f32 parity forward or the bf16 MFMA forward.  The net has no value head: value = 0 for every
-        * evaluated leaf (terminal leaves keep the rules' value). */
+        * the f32 parity forward or the bf16 MFMA forward.  The reference's net has no value head: value = 0 for
+        * every evaluated leaf; a PV handle (bz_mlp_create_pv) gives its own value.  Terminal leaves keep the
+        * rules' value either way. */
        BZ_EVAL_MLP_F32 = 6, BZ_EVAL_MLP_BF16 = 7 };
 #define BZ_PASS_ACTION 64
 
@@ -303,6 +304,36 @@ int64_t bz_mlp_train_workspace_bytes(int32_t H, int32_t max_batch);
 int32_t bz_mlp_train_step(bz_mlp* mlp, float* params, float* m, float* v, float* grad, const float* x,
                           const int32_t* target, const float* row_w, int32_t n, const bz_mlp_adam* adam,
                           void* ws, int64_t ws_bytes, float* loss, float* logits, uint32_t* err, void* stream);
+
+/* The MLP with a value head, TicTacToePVNet (betazero_amd/mlp.py): fc1..fc3 are the reference's, fc4 = Linear(H, 10); rows
+ * 0..8 are the policy logits, row 9 is the value pre-activation u and v = tanh(u).  Flat order as above with fc4.w[10][H]
+ * fc4.b[10]: 2 H^2 + 22 H + 10 floats.  A PV handle is a bz_mlp: destroy, update (its own parameter count), the engine
+ * (bz_engine_set_mlp: BZ_EVAL_MLP_* then put v on the evaluated leaves) and the four forwards above (logits alone) take it.
+ * _pv_ forwards: value f32 [n] as well; BZ_EINVAL on a handle of bz_mlp_create.
+ *   _f32: unit 9 runs through the same fmaf chain as the logits, then tanhf_spec (the conv net's value head's);
+ *   _bf16: row 9 of fc4's one MFMA tile, + bias, tanhf_spec -- no instruction more than the policy-only forward's tile. */
+int64_t bz_mlp_pv_param_count(int32_t H);
+int64_t bz_mlp_pv_workspace_bytes(int32_t H, int32_t max_batch);
+int32_t bz_mlp_create_pv(int32_t H, int32_t max_batch, const float* params_host, void* workspace, int64_t workspace_bytes,
+                         void* stream, bz_mlp** out);
+int32_t bz_mlp_has_value(const bz_mlp* mlp);   /* 1 = a handle of bz_mlp_create_pv */
+int32_t bz_mlp_forward_pv_f32(bz_mlp* mlp, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, float* value,
+                              void* stream);
+int32_t bz_mlp_forward_pv_bf16(bz_mlp* mlp, const uint64_t* own, const uint64_t* opp, int32_t n, float* logits, float* value,
+                               void* stream);
+int32_t bz_mlp_forward_pv_states_f32(bz_mlp* mlp, const float* x, int32_t n, float* logits, float* value, void* stream);
+int32_t bz_mlp_forward_pv_states_bf16(bz_mlp* mlp, const float* x, int32_t n, float* logits, float* value, void* stream);
+/* One AlphaZero step on a PV handle: loss = sum_r (w_r / sum w) [ sum_o pi_o (lse(z) - z_o) + value_weight (v - vt)^2 ], the
+ * logits unmasked; then Adam exactly as bz_mlp_train_step.  Two launches.  Buffers as there, with
+ *   params/m/v/grad: fp32 [bz_mlp_pv_param_count]; pi f32 [n][9] >= 0 (need not sum to 1: the gradient on logit o is
+ *     scale (S p_o - pi_o), S = sum_o pi_o in ascending o); vt f32 [n] in [-1, 1]; value f32 [n] (optional, forward output);
+ *   gradient on u: scale value_weight 2 (v - vt) (1 - v^2);  ws: bz_mlp_train_pv_workspace_bytes(H, n) bytes.
+ * err: 1 = on a row of non-zero weight a negative or non-finite pi entry, sum pi <= 0, or vt non-finite / outside [-1, 1];
+ * 2 = a non-finite loss; 4 = the row weights sum to <= 0.  While *err != 0 the step changes no parameter or moment. */
+int64_t bz_mlp_train_pv_workspace_bytes(int32_t H, int32_t max_batch);
+int32_t bz_mlp_train_step_pv(bz_mlp* mlp, float* params, float* m, float* v, float* grad, const float* x, const float* pi,
+                             const float* vt, const float* row_w, int32_t n, float value_weight, const bz_mlp_adam* adam,
+                             void* ws, int64_t ws_bytes, float* loss, float* logits, float* value, uint32_t* err, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Batched MCTS self-play engine.  The plug-in point it fills is             */
