@@ -15,7 +15,7 @@ __all__ = ["ReversiBoard", "ReversiHeadless", "TicTacToeBoard", "TicTacToeHeadle
            "TicTacToeNet", "TicTacToePVNet", "DeviceMLP", "MLPTrainer", "PVTrainer", "load_reference_model",
            "MatchPlayer", "MatchResult", "play_match", "Resign", "check_resign", "EarlyStop",
            "check_early_stop", "merge_positions", "merged_repeats", "save_checkpoint", "load_checkpoint",
-           "Reanalyser", "reanalyse", "reanalyse_rows"]
+           "Reanalyser", "reanalyse", "reanalyse_rows", "transform_rows"]
 
 
 def __getattr__(name):  # the MLP names load torch: only when asked for
@@ -41,4 +41,7 @@ def __getattr__(name):  # the MLP names load torch: only when asked for
         import importlib
         mod = importlib.import_module(".reanalyse", __name__)   # (`reanalyse` is the MODULE; its one-shot function is betazero_amd.reanalyse.reanalyse)
         return mod if name == "reanalyse" else getattr(mod, name)
+    if name == "transform_rows":  # a board symmetry per row of a training batch
+        from . import train_symmetry
+        return train_symmetry.transform_rows
     raise AttributeError(f"module 'betazero_amd' has no attribute {name!r}")

@@ -96,6 +96,14 @@ class TrainOwnAdam(C.Structure):      # bz_train_own_adam
                [(n, vp) for n in ("pw", "pb", "mw", "mb", "vw", "vb")]
 
 
+class TrainSymCols(C.Structure):     # bz_train_sym_cols (the kernel reads it from DEVICE memory)
+    _fields_ = [("vt", vp), ("fown", vp), ("fopp", vp), ("sym", vp)]
+
+
+class TrainSymStage(C.Structure):    # bz_train_sym_stage
+    _fields_ = [(n, vp) for n in ("own", "opp", "pi", "z", "vt", "fown", "fopp")]
+
+
 class MergeRows(C.Structure):         # bz_merge_rows: the columns of the rows going into / coming out of a merge
     _fields_ = [(n, vp) for n in ("own", "opp", "pi", "z", "mover", "act", "game", "ply", "vt", "q", "kl")]
 
@@ -290,6 +298,9 @@ _SIGS = {
     "bz_train_qat_pack_weights": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "bz_train_qat_tower_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "bz_train_qat_stem_fwd": (i32, [vp, i32, vp, vp, i32, vp, vp]),
+    "bz_train_sym_rows_per_workgroup": (i32, []),
+    "bz_train_sym_batch": (i32, [vp, vp, i32, i32, C.POINTER(TrainSymStage), vp, vp]),
+    "bz_train_sym_row": (i32, [u64, u64, vp, u64, u64, i32, i32, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64), C.POINTER(u64)]),
     "bz_profile_enable": (i32, [i32]),
     "bz_profile_reserve": (i32, [i32, i64]),
     "bz_profile_read": (i32, [i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]),

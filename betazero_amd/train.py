@@ -41,7 +41,7 @@ def ownership_targets(fown, fopp):
 
 
 def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, value_targets=False, ownership=None, own_weight=1.0,
-               fp8_qat=False):
+               fp8_qat=False, sym=None):
     """one Adam step on the rows `idx` of ex (Reversi 8x8 net).  ex: DeviceExamples (stays on the GPU; idx a device
     index tensor or None = all rows) or host Examples (uploaded first).  Returns (loss, policy CE, value MSE) as
     detached device scalars.  value_targets: the value MSE is against ex.vt (fp32) instead of z.
@@ -49,10 +49,16 @@ def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, 
     own_weight * L_own, L_own = the mean over positions and all 64 cells of (o - t)^2, and a fourth value, L_own, is returned.
     The optimizer must then hold the head's parameters too.
     fp8_qat: the forward is quant.qat_forward -- the fp8 net's arithmetic in fp32 torch, straight-through
-    gradients -- instead of the module's under autocast (128 channels only)."""
+    gradients -- instead of the module's under autocast (128 channels only).
+    sym: a uint8 tensor of board symmetries 0..7, one per trained row -- row p is trained under sym[p]: boards,
+    pi and the ownership targets go through train_symmetry.torch_sym_rows (symmetry.sym_action_map's cell permutation, the one
+    symmetry.sym_board moves the stones by) in front of the code below; what StepPlan(symmetry=True) does in its staging kernel."""
     from .train_kernels import check_fp8_qat, check_own_weight
     own_weight = check_own_weight(own_weight)
     check_fp8_qat(fp8_qat, module)
+    if sym is not None:
+        from .train_symmetry import check_size
+        check_size(ex.size)
     if isinstance(ex, Examples):
         ex = DeviceExamples.from_host(ex, device)
     if value_targets and ex.vt is None:
@@ -68,6 +74,10 @@ def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, 
     else:
         idx = torch.as_tensor(idx, device=dev)
         own, opp, pi, z = ex.own[idx], ex.opp[idx], ex.pi[idx], (ex.vt if value_targets else ex.z)[idx]
+    fown, fopp = (None, None) if ownership is None else (ex.fown, ex.fopp) if idx is None else (ex.fown[idx], ex.fopp[idx])
+    if sym is not None:
+        from .train_symmetry import check_sym, torch_sym_rows
+        own, opp, pi, fown, fopp = torch_sym_rows(own, opp, pi, check_sym(sym, int(own.shape[0]), dev), ex.size, fown, fopp)
     if fp8_qat:
         from .quant import qat_forward
         logits, v, saved = qat_forward(module, own, opp, acts=True)
@@ -86,7 +96,7 @@ def train_step(module, optimizer, ex, idx=None, device="cuda:0", autocast=True, 
     mse = F.mse_loss(v, z.to(torch.float32))
     loss = ce + mse
     if ownership is not None:
-        t = ownership_targets(ex.fown, ex.fopp) if idx is None else ownership_targets(ex.fown[idx], ex.fopp[idx])
+        t = ownership_targets(fown, fopp)
         l_own = F.mse_loss(o.float(), t)
         loss = loss + own_weight * l_own
     optimizer.zero_grad(set_to_none=True)
@@ -152,7 +162,14 @@ class GraphedTrainStep:
 
     def __init__(self, module, lr=1e-4, batch=1024, na=65, device="cuda:0", autocast=True, tower_kernels=None, lr_warmup_steps=0,
                  step_kernels=None, fused_adam=None, capture_autograd=False, value_targets=False, weight_decay=0.0, clip_norm=0.0,
-                 ema_decay=None, decay_biases=False, ownership=None, own_weight=1.0, fp8_qat=False):
+                 ema_decay=None, decay_biases=False, ownership=None, own_weight=1.0, fp8_qat=False, symmetry=False):
+        # symmetry: every batch position is trained under a board symmetry of its own, step(ex, idx, sym) -- inside
+        # the all-kernel step (StepPlan(symmetry=True): one launch more, k_train_sym_batch, in the same graph; the board size is
+        # the examples').  Any other form of the step refuses it.
+        self.symmetry = bool(symmetry)
+        if self.symmetry and (step_kernels is False or not getattr(module, "fused_tower", False) or not autocast or na != 65 or
+                              getattr(module, "VH", 65) > 64):
+            raise ValueError("symmetry=True needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels)")
         # fp8_qat: quantisation-aware training for the fp8 net, inside the all-kernel step (StepPlan(fp8_qat=True):
         # the four k_qat_* kernels in place of stem / pack / tower forward, one launch more in the same graph).  128 channels
         # only, and any other form of the step refuses it.
@@ -199,14 +216,17 @@ class GraphedTrainStep:
                 if ownership is not None:
                     ownership.to(device)
                 self.step_plan = self.plan = StepPlan(self.module, batch, device, value_targets=self.value_targets, ownership=ownership,
-                                                      own_weight=self.own_weight, fp8_qat=self.fp8_qat)
+                                                      own_weight=self.own_weight, fp8_qat=self.fp8_qat, symmetry=self.symmetry)
                 self.idx = torch.zeros(batch, dtype=torch.int64, device=self.dev)   # the batch's rows: the kernels gather them themselves
+                self.sym = torch.zeros(batch, dtype=torch.uint8, device=self.dev) if self.symmetry else None   # and their symmetries
             else:
                 self.plan = TowerPlan(module.C, 2 * module.NB, batch, device)
         if ownership is not None and self.step_plan is None:
             raise ValueError("ownership= needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels, fused_adam)")
         if self.fp8_qat and self.step_plan is None:
             raise ValueError("fp8_qat=True needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels)")
+        if self.symmetry and self.step_plan is None:
+            raise ValueError("symmetry=True needs the all-kernel step (PolicyValueNet(fused_tower=True), step_kernels)")
         # lr_warmup_steps > 0: the learning rate ramps linearly from lr / warmup to lr over the first steps.  Adam's first
         # updates move every weight by ~lr whatever the gradient's size; at the loop demo's lr = 2e-3 that kills the
         # single-channel value head's ReLU (and in 2 of 4 seeds every head ReLU, i.e. the whole net) within the first
@@ -293,8 +313,23 @@ class GraphedTrainStep:
         with torch.cuda.graph(self.graph):
             self.out = self._step()
 
-    def __call__(self, ex, idx):
+    def step(self, ex, idx, sym=None):
+        """__call__ under its name: one step on rows idx of ex; with symmetry=True, row p under the board symmetry sym[p]"""
+        return self(ex, idx, sym)
+
+    def __call__(self, ex, idx, sym=None):
         assert idx.numel() == self.batch, "GraphedTrainStep replays a fixed batch size"
+        if self.symmetry:   # (refused before anything is written)
+            from .train_symmetry import check_size, check_sym
+            check_sym(sym, self.batch, self.dev)
+            stage = self.step_plan.sym_stage
+            if check_size(ex.size) != stage.size:
+                if self.graph is not None:
+                    raise ValueError(f"GraphedTrainStep(symmetry=True): the graph was captured for {stage.size} x {stage.size} boards, "
+                                     f"these examples are {ex.size} x {ex.size}")
+                stage.size = int(ex.size)
+        elif sym is not None:
+            raise ValueError("GraphedTrainStep: sym given, but the step was built without symmetry=True")
         if self.value_targets and ex.vt is None:
             raise ValueError("GraphedTrainStep(value_targets=True) needs examples with vt (betazero_amd.value_targets.value_targets)")
         if self.ownership is not None and (ex.fown is None or ex.fopp is None):
@@ -302,6 +337,9 @@ class GraphedTrainStep:
         if self.step_plan is not None:   # the kernels read rows idx of the data set themselves: one 8-byte-per-row copy, no gathers
             self.idx.copy_(idx)
             own_kw = dict(fown=ex.fown, fopp=ex.fopp) if self.ownership is not None else {}
+            if self.symmetry:
+                self.sym.copy_(sym)
+                own_kw["sym"] = self.sym
             self.step_plan.set_batch(ex.own, ex.opp, ex.pi, ex.z, self.idx, vt=ex.vt if self.value_targets else None, **own_kw)
         else:
             torch.index_select(ex.own, 0, idx, out=self.own)

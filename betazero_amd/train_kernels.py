@@ -170,8 +170,15 @@ class StepPlan(TowerPlan):
                 "val_w": module.val.weight, "val_b": module.val.bias, "v1_w": module.v1.weight, "v1_b": module.v1.bias,
                 "v2_w": module.v2.weight, "v2_b": module.v2.bias}
 
-    def __init__(self, module, batch, device="cuda:0", value_targets=False, ownership=None, own_weight=1.0, fp8_qat=False):
-        """fp8_qat: quantisation-aware training for the fp8 net -- the step's forward is bz_net_forward_fp8's
+    def __init__(self, module, batch, device="cuda:0", value_targets=False, ownership=None, own_weight=1.0, fp8_qat=False,
+                 symmetry=False, size=8):
+        """symmetry: batch position p trains on row idx[p] under the board symmetry sym[p] (set_batch(..., sym=),
+        uint8 0..7, symmetry.SYM_NAMES) of the size x size board -- one launch more, k_train_sym_batch, in front of the stem: it
+        gathers and transforms the batch's rows into a staging batch this plan owns (train_symmetry.SymStaging), and the step's own
+        descriptor, its vt slot and its ownership slot point at the staged columns for good.  Every other kernel runs as it is, so the
+        option composes with all of the below; off (the default), the step is launch for launch the one it was.
+
+        fp8_qat: quantisation-aware training for the fp8 net -- the step's forward is bz_net_forward_fp8's
         arithmetic (k_qat_stem, k_qat_scales, k_qat_pack, k_qat_fwd in place of the stem, the weight packing and the tower
         forward: one launch more), the backward the straight-through estimator: the gradients with respect to the quantised
         weights land in the fp32 masters' .grad.  128 channels only (the fp8 tower's); composes with every option below.
@@ -193,6 +200,10 @@ class StepPlan(TowerPlan):
         if module.VH > 64:
             raise ValueError("the head kernels hold the value head's hidden layer in one wavefront: value_hidden <= 64")
         check_fp8_qat(fp8_qat, module)
+        self.symmetry = bool(symmetry)
+        if self.symmetry:
+            from .train_symmetry import check_size
+            size = check_size(size)
         super().__init__(module.C, 2 * module.NB, batch, device)
         L, dev = _lib.lib(), self.device
         self.module, self.VH = module, module.VH
@@ -240,13 +251,26 @@ class StepPlan(TowerPlan):
             self._own = _lib.TrainOwn(w=self.own_params["w"].data_ptr(), b=self.own_params["b"].data_ptr(), targets=self.own_slot.data_ptr(),
                                       weight=own_weight, partial=self.own_partial.data_ptr())
         self._optim, self.ema, self.stats, self.optim_partials = None, None, None, None   # the extended optimiser (enable_adam)
+        # symmetry: the staging batch, and the step's descriptor and slots pointed at it once (rows 0..batch-1 of the staged rows)
+        self.sym_stage = None
+        if self.symmetry:
+            from .train_symmetry import SymStaging
+            g = self.sym_stage = SymStaging(batch, size, dev, vt=self.value_targets, ownership=ownership is not None)
+            d = _lib.TrainBatch(own=g.own.data_ptr(), opp=g.opp.data_ptr(), pi=g.pi.data_ptr(), z=g.z.data_ptr(), idx=None, n_rows=batch)
+            with torch.cuda.device(dev):
+                self.batch_desc.copy_(torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8))
+                if self.value_targets:
+                    self.vt_slot.copy_(torch.tensor([g.vt.data_ptr()], dtype=torch.int64))
+                if ownership is not None:
+                    self.own_slot.copy_(torch.tensor([g.fown.data_ptr(), g.fopp.data_ptr()], dtype=torch.int64))
 
     # ---- the batch
-    def set_batch(self, own, opp, pi, z, idx=None, vt=None, fown=None, fopp=None):
+    def set_batch(self, own, opp, pi, z, idx=None, vt=None, fown=None, fopp=None, sym=None):
         """point the step at rows `idx` (int64 [batch], on the device; None: rows 0..batch-1) of the data set (own, opp, pi,
         z).  Asynchronous on the current stream; the tensors are kept alive until the next call.  vt: the data set's value
         targets, fp32 [rows] (a plan built with value_targets=True needs them; they are gathered by the same idx).  fown /
-        fopp: the data set's ownership targets, int64 [rows] (a plan built with ownership= needs them; gathered by idx too)."""
+        fopp: the data set's ownership targets, int64 [rows] (a plan built with ownership= needs them; gathered by idx too).
+        sym: the batch positions' board symmetries, uint8 [batch] on the device (a plan built with symmetry=True needs them)."""
         n, dev = self.n, self.device
         rows = int(own.shape[0])
         if rows < 1:
@@ -272,6 +296,13 @@ class StepPlan(TowerPlan):
                 raise ValueError(f"set_batch: the data set has {rows} rows, the batch needs {n}")
         elif not (idx.dtype == torch.int64 and idx.shape == (n,) and idx.is_contiguous() and idx.device == dev):
             raise ValueError(f"set_batch: idx must be a contiguous int64 tensor of {n} row numbers on the plan's device")
+        if self.symmetry:   # the staging kernel reads the data set; the step's own descriptor and slots stay on the staged rows
+            from .train_symmetry import check_sym
+            self.sym_stage.set_source(own, opp, pi, z, idx, check_sym(sym, n, dev), vt=vt, fown=fown, fopp=fopp)
+            self._batch_refs, self._vt_ref, self._own_ref = ("staged",), vt, ((fown, fopp) if self._own is not None else None)
+            return
+        if sym is not None:
+            raise ValueError("set_batch: sym given, but the plan was built without symmetry=True")
         d = _lib.TrainBatch(own=own.data_ptr(), opp=opp.data_ptr(), pi=pi.data_ptr(), z=z.data_ptr(),
                             idx=idx.data_ptr() if idx is not None else None, n_rows=rows)
         key = bytes(d)
@@ -477,7 +508,7 @@ class StepPlan(TowerPlan):
     def launch(self, adam=False):
         """the 9 (adam: 10, or 11 with the extended optimiser) launches of one step on the current stream (no host work besides:
         this is what a HIP graph captures); with the ownership head one more, k_train_own_finish, at the end; with fp8_qat one
-        more, k_qat_scales, in front of the weight packing"""
+        more, k_qat_scales, in front of the weight packing; with symmetry one more, k_train_sym_batch, in front of everything"""
         L, p, n, Cc, Ly = _lib.lib(), self.params, self.n, self.C, self.L
         if self._batch_refs is None:
             raise RuntimeError("StepPlan: set_batch() first")
@@ -488,6 +519,8 @@ class StepPlan(TowerPlan):
         with torch.cuda.device(self.device):
             st, bd = self._stream(), self.batch_desc.data_ptr()
             chk = _lib.check
+            if self.symmetry:
+                self.sym_stage.launch()
             if self.fp8_qat:
                 chk(L.bz_train_qat_stem_fwd(bd, n, p["stem_w"].data_ptr(), p["stem_b"].data_ptr(), Cc, self.acts[0].data_ptr(), st))
                 chk(L.bz_train_qat_scales(p["tower_w"].data_ptr(), p["pol_w"].data_ptr(), p["val_w"].data_ptr(), Cc, Ly,
@@ -542,11 +575,15 @@ class StepPlan(TowerPlan):
 
     def bad_rows(self, reset=True):
         """the step's error word (bz_abi.h, bz_train_finish): how many batch positions since the last reset had a row index
-        outside the data set -- the kernels clamped them, i.e. trained on row 0 / the last row instead.  Reads the device
-        (synchronises); call it where the losses are looked at."""
+        outside the data set -- the kernels clamped them, i.e. trained on row 0 / the last row instead.  With symmetry=True the
+        staged step sees no index any more: the staging kernel's own count (an index outside the data set, or a symmetry outside
+        0..7, which it takes & 7) is added here and reset along.  Reads the device (synchronises); call it where the losses are
+        looked at."""
         n = int(self.losses[3].item())
         if n and reset:
             self.losses[3:4].zero_()
+        if self.symmetry:
+            n += self.sym_stage.bad_rows(reset=reset)
         return n
 
     def check_rows(self):
@@ -554,15 +591,16 @@ class StepPlan(TowerPlan):
         the loop shape of SL/train.py:102-108, would have raised at once)"""
         n = self.bad_rows()
         if n:
-            raise IndexError(f"StepPlan: {n} batch position(s) had a row index outside the data set since the last check; "
+            raise IndexError(f"StepPlan: {n} batch position(s) had a row index outside the data set"
+                             f"{' or a symmetry outside 0..7' if self.symmetry else ''} since the last check; "
                              "the kernels clamp instead of faulting, so those steps trained on the wrong rows")
 
-    def grads(self, own=None, opp=None, pi=None, z=None, idx=None, vt=None, fown=None, fopp=None):
+    def grads(self, own=None, opp=None, pi=None, z=None, idx=None, vt=None, fown=None, fopp=None, sym=None):
         """forward, losses, backward: every parameter's .grad is set; returns the static [loss, CE, MSE, error word] tensor.
         (own, opp, pi, z[, idx][, vt][, fown, fopp]) given: set_batch() first.  With the ownership head the loss includes
         own_weight * L_own, and own_loss[0] is L_own."""
         if own is not None:
-            self.set_batch(own, opp, pi, z, idx, vt=vt, fown=fown, fopp=fopp)
+            self.set_batch(own, opp, pi, z, idx, vt=vt, fown=fown, fopp=fopp, sym=sym)
         return self.launch(adam=False)
 
     def step(self):

@@ -1289,6 +1289,50 @@ int32_t bz_train_qat_stem_fwd(const bz_train_batch* batch_dev, int32_t n, const 
                               void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* A board symmetry per row inside the training step (the     */
+/* per-position rotation / reflection of AlphaGo Zero's minibatches): batch   */
+/* position p trains on row idx[p] of the data set under the element sym[p]   */
+/* of the evaluation symmetries above (0..6 = bz_augment_d4_batch's           */
+/* transforms 0..6, 7 = the anti-transpose).  ONE staging kernel in front of  */
+/* the stem, k_train_sym_batch, writes the n transformed rows into a staging  */
+/* batch; the step's own bz_train_batch points at that batch with idx = NULL, */
+/* its vt slot and its ownership slot at the staged columns, and every other  */
+/* kernel of the step runs as it is.  Per row (csrc/bz_train_sym.h):          */
+/*   own, opp, fown, fopp -> T_s on the size x size corner (bz_sym_board)     */
+/*   pi'[tau_s(j)] = pi[j]; the pass entry 64 and cells outside the corner    */
+/*     stay; the 65 entries are moved as 32-bit patterns                      */
+/*   z, vt copied                                                             */
+/* ------------------------------------------------------------------------ */
+/* the data set's optional columns and the batch's symmetries: DEVICE memory, read at launch time like bz_train_batch and
+ * for the same reason (a captured step survives a new data set) */
+typedef struct bz_train_sym_cols {
+    const float* vt;                    /* [n_rows] or NULL */
+    const uint64_t *fown, *fopp;        /* [n_rows] or NULL */
+    const uint8_t* sym;                 /* [n]: the symmetry of batch position p */
+} bz_train_sym_cols;
+/* the staging batch (host struct of device pointers, all [n]; pi [n][65]); vt, and fown / fopp together, may be NULL */
+typedef struct bz_train_sym_stage {
+    uint64_t *own, *opp;
+    float* pi;
+    int8_t* z;
+    float* vt;
+    uint64_t *fown, *fopp;
+} bz_train_sym_stage;
+/* rows a workgroup of k_train_sym_batch stages (64): bad_dev below holds ceil(n / this) words */
+int32_t bz_train_sym_rows_per_workgroup(void);
+/* src_dev: the data set and the batch's idx (idx NULL: rows 0..n-1); n: 1 .. 2^24; size: 1..8.  An index outside [0, n_rows) is
+ * clamped as bz_train_batch says, a symmetry outside 0..7 is taken & 7; either is an ERROR of the caller that the staged
+ * step can no longer see: each such batch position is ADDED to its workgroup's word of bad_dev (uint32 per workgroup, owned by
+ * that workgroup alone: no atomics, no memset), which the caller sums into the step's error word and zeroes with it.  A
+ * staged optional column whose source address is NULL is left as it is. */
+int32_t bz_train_sym_batch(const bz_train_batch* src_dev, const bz_train_sym_cols* cols_dev, int32_t n, int32_t size,
+                           const bz_train_sym_stage* stage, uint32_t* bad_dev, void* stream);
+/* host: one row through the code the kernel runs.  s 0..7, size 1..8; pi / pi_out [65], distinct; fown_out / fopp_out may be
+ * NULL */
+int32_t bz_train_sym_row(uint64_t own, uint64_t opp, const float* pi, uint64_t fown, uint64_t fopp, int32_t size, int32_t s,
+                         uint64_t* own_out, uint64_t* opp_out, float* pi_out, uint64_t* fown_out, uint64_t* fopp_out);
+
+/* ------------------------------------------------------------------------ */
 /* In-library kernel timers: HIP events recorded on the launch stream around  */
 /* each launch of the named kernel (off by default; bench.py turns them on).  */
 /* ------------------------------------------------------------------------ */

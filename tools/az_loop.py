@@ -9,6 +9,8 @@
          (and kl); the slot is augmented again
       -> with --merge-positions: position averaging of the training window (merge_positions): the rows of one
          position become one row with the mean pi and the mean value target
+      -> with --train-symmetry: no augmentation at all: the window holds the rows as they were played and every
+         step draws a board symmetry per batch position, applied by a staging kernel inside the fused step
       -> policy cross-entropy + value MSE steps on the hand-written training kernels replayed as one HIP graph
          (GraphedTrainStep: stem, tower, heads, losses, every gradient and Adam as ten launches; --miopen-train /
          --eager-train / --fp32-train fall back to stock PyTorch autograd, run eagerly)
@@ -174,6 +176,12 @@ def build_parser():
                     "searched again with the net self-play just used and self-play's search options (no noise, no playout cap, no "
                     "resignation), and gets that search's pi (and kl under --surprise); the value targets stay, the held-out rows are "
                     "never touched; 0 = off")
+    ap.add_argument("--train-symmetry", action="store_true", help="a board symmetry per row inside the training step (DESIGN.md 12.5; "
+                    "AlphaGo Zero's per-position rotation / reflection): the window holds the training rows as played -- no eightfold "
+                    "copy, no dedupe, no re-augmentation after reanalysis -- and every step draws one of the eight symmetries per batch "
+                    "position from the generator that draws the rows; an epoch is 8 * rows / batch steps, so --epochs keeps its meaning.  "
+                    "--merge-positions then merges exact repeats only (symmetric copies of a position no longer meet).  Needs the "
+                    "all-kernel training step")
     ap.add_argument("--reanalyse-sims", type=int, default=None, help="simulations of a reanalysis search (default: --sims)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32-train", action="store_true", help="train without bf16 autocast (A/B of the loss curve)")
@@ -255,6 +263,8 @@ def main():
         ap.error("--weight-decay / --clip-norm / --ema-decay / --lr-decay need the all-kernel training step")
     if args.ownership and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
         ap.error("--ownership needs the all-kernel training step")
+    if args.train_symmetry and (args.miopen_train or args.eager_train or args.fp32_train or args.channels == 256):
+        ap.error("--train-symmetry needs the all-kernel training step")
     if args.resign_threshold is not None and args.ownership:
         ap.error("--resign-threshold does not combine with --ownership: a resigned game has no final board")
     if args.merge_positions and args.ownership:
@@ -290,7 +300,7 @@ def main():
     graphed = None if args.eager_train else GraphedTrainStep(module, lr=args.lr, batch=args.batch, autocast=not args.fp32_train, lr_warmup_steps=args.lr_warmup,
                                                                   value_targets=train_vt, weight_decay=args.weight_decay, clip_norm=args.clip_norm,
                                                                   ema_decay=args.ema_decay, ownership=own_head, own_weight=args.own_weight,
-                                                                  fp8_qat=fp8_qat)
+                                                                  fp8_qat=fp8_qat, symmetry=args.train_symmetry)
     bmax = max(args.games, args.arena_games, args.gate_games)
     if ckpt is not None:  # the trained state: the step's (parameters, optimiser, EMA, ownership head), or torch's where it trained
         with torch.no_grad():
@@ -347,6 +357,9 @@ def main():
         emit({"what": "arena, untrained net", "iter": 0, "evaluator": net_eval, **arena(net_eval, dnet)})
 
     window, val_window = [], []
+    # --train-symmetry: the rows as played ARE the window (the symmetries are drawn per step); otherwise the eightfold copy, deduped
+    augment = (lambda rows: rows) if args.train_symmetry else (lambda rows: augment_examples(rows, dedupe=True))
+    sym_fold = 8 if args.train_symmetry else 1   # steps per row of the window, so that an epoch is what it is without the flag
     # what a checkpoint keeps of the window: every slot's rows BEFORE augmentation (an eighth of the augmented rows), on the host
     keep_rows = bool(args.checkpoint) and not args.no_checkpoint_window
     raw_window = []
@@ -356,9 +369,9 @@ def main():
     rean = None
     if ckpt is not None and ckpt.get("window") is not None:   # augmentation and dedupe are deterministic: the same window again
         raw_window = list(ckpt["window"]) if keep_rows else []
-        if reanalysing:
-            raw_dev = [rows_to_device(w["train"]) for w in ckpt["window"]]
-        window = [augment_examples(rows_to_device(w["train"]), dedupe=True) for w in ckpt["window"]]
+        window = [augment(rows_to_device(w["train"])) for w in ckpt["window"]]
+        if reanalysing:   # (under --train-symmetry the very tensors of the window: reanalysis rewrites them in place)
+            raw_dev = list(window) if args.train_symmetry else [rows_to_device(w["train"]) for w in ckpt["window"]]
         val_window = [rows_to_device(w["val"]) for w in ckpt["window"]]
 
     def write_checkpoint(it):
@@ -417,7 +430,7 @@ def main():
                 rean.run(raw, idx, update_q=False)   # the slot's value targets were computed over whole games and stay
                 n_moved += (raw.pi[idx].argmax(1) != top).sum()
                 n_re += len(idx)
-                window[j] = augment_examples(raw, dedupe=True)
+                window[j] = augment(raw)
                 if keep_rows:
                     raw_window[j] = {"train": window_rows(raw), "val": raw_window[j]["val"]}
             torch.cuda.synchronize()
@@ -427,7 +440,7 @@ def main():
         # hold-out split of this iteration's rows BEFORE augmentation (a row's symmetric copies must not sit on both sides)
         tr_idx, va_idx = holdout_split(len(ex), args.val_split, gen, ex.own.device)
         tr_rows, va_rows = select_rows(ex, tr_idx), select_rows(ex, va_idx)
-        aug = augment_examples(tr_rows, dedupe=True)
+        aug = augment(tr_rows)
         del sp
         window = (window + [aug])[-args.window:]
         if reanalysing:
@@ -437,7 +450,7 @@ def main():
             raw_window = (raw_window + [{"train": window_rows(tr_rows), "val": window_rows(va_rows)}])[-args.window:]
         data, val = concat_device_examples(window), concat_device_examples(val_window)
         val_before = validate(dnet, val, fp8=args.fp8)   # the net that just played, on rows it has not been trained on
-        steps = max(1, int(args.epochs * len(data) / args.batch))
+        steps = max(1, int(args.epochs * sym_fold * len(data) / args.batch))
         losses = []
         surprise = {}
         res = None
@@ -445,7 +458,7 @@ def main():
         if args.merge_positions:  # once per iteration, over the window; the held-out rows stay unmerged
             rows_before = len(data)
             data, counts = merge_positions(data, return_counts=True)
-            steps = max(1, int(args.epochs * len(data) / args.batch))   # an epoch is a pass over the merged rows
+            steps = max(1, int(args.epochs * sym_fold * len(data) / args.batch))   # an epoch is a pass over the merged rows
             if args.merge_weight == "log":
                 res = merged_repeats(counts, "log")
             merge_info = {"merge": {"rows_before": rows_before, "rows_after": len(data), "largest_group": int(counts.max()),
@@ -460,7 +473,10 @@ def main():
             idx = torch.randint(0, len(data) if res is None else len(res), (args.batch,), device=data.own.device, generator=gen)
             if res is not None:
                 idx = res[idx]
-            if graphed is not None:
+            if args.train_symmetry:   # the same generator as the rows: a resumed run draws what the uninterrupted one draws
+                sym = torch.randint(0, 8, (args.batch,), dtype=torch.uint8, device=data.own.device, generator=gen)
+                losses.append(graphed(data, idx, sym))
+            elif graphed is not None:
                 losses.append(graphed(data, idx))
             else:
                 losses.append(torch.stack(train_step(module, opt, data, idx, autocast=not args.fp32_train, value_targets=train_vt)))
@@ -525,7 +541,7 @@ def main():
               **({"eval_symmetry_seed": args.seed + it} if args.eval_symmetry else {}),
               "mean_walk_nodes": round(cnt["n_path_nodes"] / max(1, cnt["n_sims"]), 2),
               "evaluations_shared": round(cnt["n_cache_hits"] / max(1, cnt["n_cache_hits"] + cnt["n_net_leaves"]), 3),
-              **({"fp8": True, "fp8_qat": fp8_qat} if args.fp8 else {}),
+              **({"fp8": True, "fp8_qat": fp8_qat} if args.fp8 else {}), **({"train_symmetry": True} if args.train_symmetry else {}),
               "arena": arena(net_eval, cand), **gate})
         if args.checkpoint and (it % args.checkpoint_every == 0 or it == args.iters):
             write_checkpoint(it)
